@@ -14,7 +14,11 @@ primary + shadow + reflect + refract).
   renders its own frame per step (independent frames: no data-path
   collective, "scaling": "weak"), so the line's workload per GPU is the same
   at every N and `value` is the whole job's rays / time.
-* The default run then also measures the north star's image-tile split, at
+* A plain run does only that: it sets up, warms up, times the K steps, writes
+  the last step's frame if --dump-outputs DIR is given, and prints the line
+  (metric, value, unit, ms_per_step, the workload and the first frame's
+  phases).  Everything below is measured with --full only.
+* With --full the run then also measures the north star's image-tile split, at
   every N (N = 1 included): BASELINE configs[3] and configs[4],
   scenes/cover.yaml and scenes/table.yaml at 3840x2160, every frame
   split across the N GPUs in cyclic row blocks by librtc's own multi-GPU
@@ -26,10 +30,12 @@ primary + shadow + reflect + refract).
   (`single_gpu_ms_per_step`, `speedup_vs_1gpu`).  `--mode tiled` makes the
   split the line itself ("scaling": "strong"); `--mode frames` skips it.
 
-Prints ONE JSON line on rank 0 with the roofline of the tracer kernel (FP32
-VALU roof, algorithmic FLOPs of SURVEY.md §8d) and, on one GPU, the CPU
-baseline (the f64 oracle = C++ restatement of the reference's rayon
-render_parallel, timed on this host's cores over a bounded sample).
+Prints ONE JSON line on rank 0; with --full it holds the roofline of the
+tracer kernel (FP32 VALU roof, algorithmic FLOPs of SURVEY.md §8d; one
+frame's own duration takes a run of K frames of its own) and, on one GPU,
+the host-frame and one-shot latencies and the CPU baseline (the f64 oracle =
+C++ restatement of the reference's rayon render_parallel, timed on this
+host's cores over a bounded sample).
 """
 from __future__ import annotations
 
@@ -59,7 +65,8 @@ def parse():
                     help="keep warming up (untimed) until at least this much wall time of frames has run, "
                          "whatever --warmup: a few 25 us frames leave the GPU below its steady clocks")
     ap.add_argument("--mode", choices=["auto", "frames", "tiled"], default="auto",
-                    help="auto: a frame per GPU per step, plus the configs[3]/[4] tile splits as 'tile_split'; "
+                    help="auto: a frame per GPU per step, with --full plus the configs[3]/[4] tile splits as "
+                         "'tile_split'; "
                          "frames: without it; tiled: the tile split is the line")
     ap.add_argument("--scene", default=None,
                     help="default three_sphere_scene (configs[1]) on one GPU / in frames mode, cover (configs[3]) "
@@ -73,14 +80,15 @@ def parse():
     ap.add_argument("--precision", choices=["f32", "f64"], default="f32")
     ap.add_argument("--out", choices=["real", "u8"], default=None,
                     help="framebuffer format: default real (f32) on one GPU, u8 (the quantized canvas) when tiled")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="bounded CPU-baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="bounded CPU-baseline sample (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--flags", type=int, default=0, help="RT_FLAG_* diagnostic ablations (profiling only)")
     ap.add_argument("--gather", choices=["rccl", "peer"], default="rccl",
                     help="tiled: how rank 0 gets the shards (rtc.h rt_context_set_gather); the other mode is "
                          "measured too and reported under gather_variants")
     ap.add_argument("--ab", action="store_true",
-                    help="A/B runs: skip the one-shot child, the host-frame latency and the per-generation frame")
+                    help="A/B runs with --full: skip the one-shot child, the host-frame latency and the "
+                         "per-generation frame")
     ap.add_argument("--inflight", type=int, default=None,
                     help="frames in flight: consecutive steps alternate between this many contexts, each on a "
                          "stream of its own, so one frame's launch tail overlaps the next frame's start (1 = "
@@ -88,6 +96,16 @@ def parse():
                          "(each a group context with its own RCCL communicator)")
     ap.add_argument("--stream", choices=["side", "null"], default="side",
                     help="the launch stream: a stream of the bench's own (default) or HIP's null stream")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the roofline's frame latency, the "
+                         "tile splits (auto mode), gather variants and one-GPU comparison (tiled), the host-frame "
+                         "and one-shot latencies, cold launches, rays per generation, the device state and the CPU "
+                         "baselines; without it the run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy: frame.npy (the "
+                         "frame as float32, or float64 with --precision f64; of a frame above 48 MB a fixed, seeded "
+                         "choice of rows, listed in frame_rows.npy) and rays_by_kind.npy (that frame's primary, "
+                         "shadow, reflect and refract rays)")
     ap.add_argument("--one-shot-child", action="store_true", help=argparse.SUPPRESS)
     return ap.parse_args()
 
@@ -375,9 +393,9 @@ def main():
     # "tile_split"; --mode tiled makes that split the line itself.
     tiled = args.mode == "tiled"
     # the device state before anything runs (measure: why not next to the region)
-    state0 = device_state(local)
-    line = measure(resolve(args, tiled), tiled, world, rank, local, state0)
-    if args.mode == "auto":
+    state0 = device_state(local) if args.full else None
+    line = measure(resolve(args, tiled), tiled, world, rank, local, state0, args.dump_outputs)
+    if args.mode == "auto" and args.full:
         # The north star's strong-scaling series, at every N (N = 1 included,
         # so a scaling curve compares one workload): configs[3] and configs[4],
         # each 4K frame split across the N GPUs by librtc's group context.
@@ -417,9 +435,63 @@ def args_for_split(args, scene):
     return a
 
 
-def measure(args, tiled, world, rank, local, state_before=None):
+def roofline(args, tiled, world, workload, flops_per_launch, kernel_ms):
+    """The line's roofline object from one launch's duration (`kernel_ms`),
+    its algorithmic FLOPs and the committed PMC figures of the workload."""
+    if tiled:
+        # the tile split's PMC figures (scripts/shard_pmc.sh): the whole frame at
+        # N = 1, one of the eight shards a rank renders at N = 8, none otherwise
+        split_prof = load_profile("tile_split_pmc.json", workload + (f",shard_of_{world}" if world > 1 else ""))
+        traffic = (split_prof or {}).get("traffic")
+        issue = split_prof or {}
+    else:
+        traffic = load_profile("traffic.json", workload)
+        issue = load_profile("issue.json", workload) or {}
+    peak = PEAK_FP32_TFLOPS if args.precision == "f32" else PEAK_FP64_TFLOPS
+    achieved = flops_per_launch / (kernel_ms * 1e-3) / 1e12
+    # the path is FP32-VALU bound (SURVEY.md §8d): no MFMA, the compute roof is the vector ALU's
+    out = {"bound": "valu", "pipe": f"valu-{args.precision}", "achieved": achieved, "peak": peak,
+           "unit": "TFLOP/s", "frac": achieved / peak, "traffic": traffic,
+           "kernel_ms": kernel_ms, "flops_per_launch": flops_per_launch,
+           # the north star's HBM view: PMC bytes per launch over the launch time,
+           # against the ~8 TB/s memory roof (a diagnostic: the path is compute-bound)
+           "hbm_gbs": traffic / (kernel_ms * 1e-3) / 1e9 if traffic else None,
+           "hbm_frac": traffic / (kernel_ms * 1e-3) / 1e9 / PEAK_HBM_GBS if traffic else None,
+           # the issue side (PMC, same launches): `frac` charges every ray brute force
+           # over all shapes (SURVEY.md §8d), so culls count as achieved FLOPs; these
+           # say how busy the VALU really was and how long waves waited
+           "valu_issue_frac": issue.get("valu_issue_frac"), "wait_frac": issue.get("wait_frac")}
+    if tiled:
+        out["kernel"] = "rank 0's shard launch (median of 5 instrumented frames)"
+    return out
+
+
+def write_outputs(dump_dir, frame, by_kind, limit=48 << 20):
+    """--dump-outputs: the last timed step's frame (what render_device left
+    in the caller's buffer) and its rays by kind, as .npy files.  A frame
+    above `limit` bytes (48 MB) is cut to a fixed, seeded choice of whole rows
+    (frame_rows.npy lists them), so two builds write the same pixels."""
+    import numpy as np
+    os.makedirs(dump_dir, exist_ok=True)
+    dtype = np.float64 if frame.dtype == np.float64 else np.float32
+    row_bytes = frame.shape[1] * frame.shape[2] * np.dtype(dtype).itemsize
+    keep = max(1, limit // row_bytes)
+    if keep < frame.shape[0]:
+        rows = np.sort(np.random.default_rng(20261019).choice(frame.shape[0], size=keep, replace=False))
+        frame = frame[rows]
+        np.save(os.path.join(dump_dir, "frame_rows.npy"), rows.astype(np.float64))
+    elif os.path.exists(os.path.join(dump_dir, "frame_rows.npy")):  # (an earlier, larger run's)
+        os.remove(os.path.join(dump_dir, "frame_rows.npy"))
+    np.save(os.path.join(dump_dir, "frame.npy"), np.ascontiguousarray(frame, dtype=dtype))
+    np.save(os.path.join(dump_dir, "rays_by_kind.npy"),
+            np.array([by_kind[k] for k in ("primary", "shadow", "reflect", "refract")], dtype=np.float64))
+
+
+def measure(args, tiled, world, rank, local, state_before=None, dump_dir=None):
     """One workload on this rank's GPU (frames) or split across the group
-    (tiled); returns rank 0's JSON line (None elsewhere)."""
+    (tiled); returns rank 0's JSON line (None elsewhere).  Without --full
+    only what `value` and `ms_per_step` need runs; `dump_dir`: where rank 0
+    writes the last timed step's outputs (--dump-outputs)."""
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -433,7 +505,8 @@ def measure(args, tiled, world, rank, local, state_before=None):
     # before the region), so the samples are taken before the
     # context, the first frame and the >= 200 ms warm-up, and after the
     # region's clock has stopped.
-    if state_before is None:
+    full_run = args.full
+    if state_before is None and full_run:
         state_before = device_state(local)
     # Only rank 0 holds the world, as the reference's single caller does
     t_first = time.perf_counter()
@@ -525,7 +598,7 @@ def measure(args, tiled, world, rank, local, state_before=None):
     torch.cuda.synchronize()
     phase["first_render_ms"] = (time.perf_counter() - t) * 1e3
     first_frame_ms = (time.perf_counter() - t_first) * 1e3
-    if rank == 0:  # the frame into host memory (the rest of a one-shot Camera::render)
+    if rank == 0 and full_run:  # the frame into host memory (the rest of a one-shot Camera::render)
         t = time.perf_counter()
         image.cpu()
         phase["d2h_ms"] = (time.perf_counter() - t) * 1e3
@@ -601,10 +674,13 @@ def measure(args, tiled, world, rank, local, state_before=None):
     # region) and the max over ranks is taken below (rdist.job_totals).  In
     # tiled mode rank 0's stream holds the gather, which waits for every shard.
     elapsed = time.perf_counter() - t0
-    state_after = device_state(local)
+    state_after = device_state(local) if full_run else None
     if world > 1:
         dist.barrier()
     after = counters_sum()
+    # the frame of the last timed step, before anything else renders into its buffer
+    last = images[(args.steps - 1) % inflight]
+    last_frame = last.cpu().numpy() if dump_dir and last is not None and args.steps > 0 else None
 
     rays = after["rays"] - before["rays"]
     flops = after["algorithmic_flops"] - before["algorithmic_flops"]
@@ -612,7 +688,8 @@ def measure(args, tiled, world, rank, local, state_before=None):
     by_kind = {k: (after[k] - before[k]) // args.steps for k in ("primary", "shadow", "reflect", "refract")}
     elapsed, total_rays = rdist.job_totals(elapsed, rays, "cpu")
     extra = {}
-    if tiled:
+    kernel_ms = None  # (one launch's duration: the roofline's; without --full only where the region gives it)
+    if tiled and full_run:
         # per-shard render, gather + de-interleave and end-to-end device ms of
         # one frame (rt_render's events; median of 5), every rank collective
         host = np.empty((cam.height, cam.width, 3), dtype=image.cpu().numpy().dtype) if rank == 0 else None
@@ -719,7 +796,7 @@ def measure(args, tiled, world, rank, local, state_before=None):
                     o_.close()
         if world > 1:
             dist.barrier()
-    elif inflight > 1:
+    elif not tiled and inflight > 1 and full_run:
         # The roofline's per-launch duration: the same frames one after
         # another on one stream (the K-frame bracket above overlaps frames in
         # flight, so bracket / K is the throughput, not a launch's duration;
@@ -733,25 +810,13 @@ def measure(args, tiled, world, rank, local, state_before=None):
         torch.cuda.synchronize()
         kernel_ms = lat() / args.steps
         ctx.set_frames_in_flight(inflight)
-    else:
+    elif bracket_ms is not None:
         kernel_ms = bracket_ms / args.steps
     line = None
     if rank == 0:
-        flops_per_launch = flops / args.steps
-        peak = PEAK_FP32_TFLOPS if args.precision == "f32" else PEAK_FP64_TFLOPS
-        achieved = flops_per_launch / (kernel_ms * 1e-3) / 1e12
         workload = f"{args.scene}@{cam.width}x{cam.height},depth={args.depth},{args.precision}"
         if args.out == "u8":
             workload += ",u8"
-        if tiled:
-            # the tile split's PMC figures (scripts/shard_pmc.sh): the whole frame at
-            # N = 1, one of the eight shards a rank renders at N = 8, none otherwise
-            split_prof = load_profile("tile_split_pmc.json", workload + (f",shard_of_{world}" if world > 1 else ""))
-            traffic = (split_prof or {}).get("traffic")
-            issue = split_prof or {}
-        else:
-            traffic = load_profile("traffic.json", workload)
-            issue = load_profile("issue.json", workload) or {}
         line = {
             "metric": "Mray/s (primary+secondary) and ms/frame at 1920x1080",
             "value": total_rays / elapsed / 1e6,
@@ -761,9 +826,6 @@ def measure(args, tiled, world, rank, local, state_before=None):
             "warmup": args.warmup,
             "warmup_frames_run": warm_run,
             "frames_in_flight": inflight,
-            # one frame's device time on its own (frames: one launch after another on
-            # one stream; tiled: rank 0's render + gather + de-interleave of one frame)
-            "frame_latency_ms": extra.get("frame_ms", kernel_ms) if tiled else kernel_ms,
             "rewarm_frames": burst,
             "ms_per_step": elapsed * 1e3 / args.steps,
             "higher_is_better": True,
@@ -777,28 +839,22 @@ def measure(args, tiled, world, rank, local, state_before=None):
                        "rays_per_frame": int(total_rays // args.steps) if tiled else int(rays // args.steps),
                        "stream": args.stream,
                        "mode": "tiled" if tiled else "frames"},
-            # the path is FP32-VALU bound: no MFMA, the compute roof is the vector ALU's
-            "roofline": {"bound": "valu", "pipe": f"valu-{args.precision}", "achieved": achieved, "peak": peak,
-                         "unit": "TFLOP/s", "frac": achieved / peak, "traffic": traffic,
-                         "kernel_ms": kernel_ms, "flops_per_launch": flops_per_launch,
-                         # the north star's HBM view: PMC bytes per launch over the launch time,
-                         # against the ~8 TB/s memory roof (a diagnostic: the path is compute-bound)
-                         "hbm_gbs": traffic / (kernel_ms * 1e-3) / 1e9 if traffic else None,
-                         "hbm_frac": traffic / (kernel_ms * 1e-3) / 1e9 / PEAK_HBM_GBS if traffic else None,
-                         # the issue side (PMC, same launches): `frac` charges every ray brute force
-                         # over all shapes, so culls count as achieved FLOPs; these
-                         # say how busy the VALU really was and how long waves waited
-                         "valu_issue_frac": issue.get("valu_issue_frac"), "wait_frac": issue.get("wait_frac")},
         }
-        if tiled:
-            line["roofline"]["kernel"] = "rank 0's shard launch (median of 5 instrumented frames)"
+        if kernel_ms is not None:  # (--full, or one frame in flight: the region's own bracket)
+            # one frame's device time on its own (frames: one launch after another on
+            # one stream; tiled: rank 0's render + gather + de-interleave of one frame)
+            line["frame_latency_ms"] = extra.get("frame_ms", kernel_ms) if tiled else kernel_ms
+            line["roofline"] = roofline(args, tiled, world, workload, flops / args.steps, kernel_ms)
         line.update(extra)
-        # clocks, power and temperature just before and just after the timed
-        # region (tell a slower box from a box-sensitive build)
-        line["device_state"] = {"before": state_before, "after": state_after,
-                                "note": "before: ahead of the warm-up (an amdsmi query right before the "
-                                        "region slows it); after: once the region's clock has stopped"}
+        if full_run:
+            # clocks, power and temperature just before and just after the timed
+            # region (tell a slower box from a box-sensitive build)
+            line["device_state"] = {"before": state_before, "after": state_after,
+                                    "note": "before: ahead of the warm-up (an amdsmi query right before the "
+                                            "region slows it); after: once the region's clock has stopped"}
         line["rays_by_kind"] = by_kind
+        if last_frame is not None:
+            write_outputs(dump_dir, last_frame, by_kind)
         line["first_frame_ms"] = first_frame_ms
         line["first_frame_breakdown"] = phase
         try:  # per-scene build (hipRTC, or a load from RTC_JIT_CACHE) on its host thread, after the first frame
@@ -809,7 +865,7 @@ def measure(args, tiled, world, rank, local, state_before=None):
             line["jit_pending"] = jit_pending
         except Exception:  # noqa: BLE001  (group contexts may not report it)
             pass
-        if not tiled and world == 1:
+        if not tiled and world == 1 and full_run:
             if ctx.scene.has_secondary() and args.depth > 0:
                 # cold launch: the first frame after an upload has no recorded
                 # tile costs; its tiles are handed out centre-out
@@ -818,7 +874,7 @@ def measure(args, tiled, world, rank, local, state_before=None):
                     ctx.upload(scene)
                     cold.append(timed_launches(step0, stream, 1)())
                 line["cold_kernel_ms"] = float(np.median(cold))
-        if not tiled and world == 1 and not args.ab:
+        if not tiled and world == 1 and full_run and not args.ab:
             # a drop-in Camera::render: synchronous rt_render into host memory,
             # PCIe copy included, into a canvas kept across frames (median of
             # 10; never `value`).  A canvas allocated per call adds its first-
@@ -862,11 +918,11 @@ def measure(args, tiled, world, rank, local, state_before=None):
                                           "shadow": [light_n * v for v in gen["shaded"]],
                                           "note": "generation g = bounce g (0 = camera rays); traced = radiance "
                                                   "rays (the wavefront), shadow = L per shaded hit"}
-        if world == 1 and not tiled and not args.ab:
+        if world == 1 and not tiled and full_run and not args.ab:
             line["one_shot"] = one_shot(args)
             # the same with the runtime's default copy engine (SDMA) for the frame copy
             line["one_shot_sdma_copy"] = one_shot(args, {"GPU_FORCE_BLIT_COPY_SIZE": "0"})
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and full_run and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(scene, cam, args.depth, args.cpu_seconds)
             line["cpu_baseline"]["configs0_serial"] = cpu_serial_configs0(min(3.0, args.cpu_seconds / 4))
     for c in ctxs:

@@ -6,7 +6,7 @@ set -u
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd $R; mkdir -p gpurun_out; rm -f gpurun_out/ab.log
 source scripts/ab_lib.sh
-B="python bench.py --steps 300 --warmup 20 --no-cpu-baseline"
+B="python bench.py --full --steps 300 --warmup 20 --no-cpu-baseline"
 for sc in ${SCENES:-three_sphere_scene shadow_puppets}; do
   for v in ${VARIANTS:-default}; do
     lib=$R/ray-tracer-challenge-rs_amd/rtc_amd/_lib/librtc.so

@@ -10,7 +10,8 @@ for sc in $SCENES; do
   for r in $(seq $ROUNDS); do
     for tree in new old; do
       dir=$R; [ $tree = old ] && dir=$OLD
-      out=$(cd $dir && timeout -k 10 120 python bench.py --scene $name --width ${size%x*} --height ${size#*x} --precision $PREC --steps ${AB_STEPS:-200} --warmup 20 --no-cpu-baseline 2>/dev/null | grep '^{') || { echo "$tree $name FAILED"; exit 1; }
+      full=--full; grep -q -e --full $dir/bench.py || full=  # (a tree from before the option measures all of it anyway)
+      out=$(cd $dir && timeout -k 10 120 python bench.py $full --scene $name --width ${size%x*} --height ${size#*x} --precision $PREC --steps ${AB_STEPS:-200} --warmup 20 --no-cpu-baseline 2>/dev/null | grep '^{') || { echo "$tree $name FAILED"; exit 1; }
       echo "$out" | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('$tree', '$name', '$size', 'kernel_ms %.4f' % d['roofline']['kernel_ms'], 'frac %.3f' % d['roofline']['frac'])"
     done
   done

@@ -16,7 +16,8 @@ for sc in $SCENES; do
   for r in $(seq $ROUNDS); do
     for tree in new old; do
       dir=$R; [ $tree = old ] && dir=$OLD
-      out=$(cd $dir && timeout -k 10 120 python bench.py --scene $name --width $w --height $h --steps $STEPS --warmup 20 --no-cpu-baseline 2>/dev/null | grep '^{')
+      full=--full; grep -q -e --full $dir/bench.py || full=  # (a tree from before the option measures all of it anyway)
+      out=$(cd $dir && timeout -k 10 120 python bench.py $full --scene $name --width $w --height $h --steps $STEPS --warmup 20 --no-cpu-baseline 2>/dev/null | grep '^{')
       rc=$?
       if [ $rc -ne 0 ]; then echo "$tree $name FAILED rc=$rc"; exit 1; fi
       echo "$out" | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('$tree', '$name', '$size', 'kernel_ms %.4f' % d['roofline']['kernel_ms'], 'ms_per_step %.4f' % d['ms_per_step'], 'cold', d.get('cold_kernel_ms'))"

@@ -6,7 +6,7 @@ set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 OUT=gpurun_out/steps_probe.jsonl; : > $OUT
-b() { timeout -k 10 120 python bench.py --no-cpu-baseline "$@" 2>/dev/null | grep '^{' >> $OUT || exit 1
+b() { timeout -k 10 120 python bench.py --full --no-cpu-baseline "$@" 2>/dev/null | grep '^{' >> $OUT || exit 1
       python -c "import json,sys; d=json.loads(open('$OUT').readlines()[-1]); print('$*', round(d['value']), round(d['ms_per_step']*1e3,2), round(d['roofline']['kernel_ms']*1e3,2))"; }
 b --steps 20 --warmup 5 --warmup-ms 0
 b --steps 20 --warmup 5

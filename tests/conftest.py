@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "ray-tracer-challenge-rs_amd")
 ORACLE = os.path.join(ROOT, "oracle")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-REFERENCE = "/root/reference"
+SCENES_YAML = os.path.join(GOLDEN, "scenes_yaml")  # the reference's scenes/*.yaml, as they are
 for p in (PKG, ORACLE):
     if p not in sys.path:
         sys.path.insert(0, p)

@@ -1,6 +1,9 @@
 """Generate the committed fixtures under tests/golden/ from the reference
 checkout (/root/reference, build container only).
 
+  scenes_yaml/<name>.yaml
+                       the reference's scenes/<name>.yaml as they are (input
+                       data of the loader tests and the sanitizer runs).
   scenes/<name>.json   the reference's scenes/<name>.yaml flattened by OUR
                        loader (rt_scene_load_yaml, scene_loader.rs semantics)
                        into the rt_* descriptor tables + camera.  The loader
@@ -17,6 +20,7 @@ from __future__ import annotations
 
 import argparse
 import os
+import shutil
 import sys
 
 import numpy as np
@@ -44,9 +48,11 @@ def main() -> None:
     from PIL import Image
 
     os.makedirs(os.path.join(HERE, "scenes"), exist_ok=True)
+    os.makedirs(os.path.join(HERE, "scenes_yaml"), exist_ok=True)
     bands = {}
     for name in SCENES:
         src = os.path.join(args.reference, "scenes", f"{name}.yaml")
+        shutil.copyfile(src, os.path.join(HERE, "scenes_yaml", f"{name}.yaml"))
         scene = rtc_amd.load_scene(src)
         scene_io.save(scene, os.path.join(HERE, "scenes", f"{name}.json"), source=f"scenes/{name}.yaml")
         png = np.asarray(Image.open(os.path.join(args.reference, "rendered_images", f"{name}.png")).convert("RGB"))

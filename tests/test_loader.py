@@ -9,7 +9,7 @@ the reference's ray-tracer-cli/src/scene_loader.rs.
   kinds ignored (scene_loader.rs:330), cylinder/cone min/max/closed
   (scene_loader.rs:293-328), defaults (material.rs:157-161);
 * the committed fixtures tests/golden/scenes/*.json are what the loader makes
-  of the reference's scenes/*.yaml (skipped where /root/reference is absent).
+  of the reference's scenes/*.yaml (kept as tests/golden/scenes_yaml/*.yaml).
   Those fixtures feed the oracle that reproduces the reference's PNGs
   bit-exactly (test_oracle_images.py), which pins this loader end to end.
 """
@@ -20,7 +20,7 @@ import os
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, REFERENCE, scene_fixture
+from conftest import GOLDEN, SCENES_YAML, scene_fixture
 
 CAMERA = """
 - add: camera
@@ -162,10 +162,7 @@ FIXTURES = sorted(f[:-5] for f in os.listdir(os.path.join(GOLDEN, "scenes")) if 
 
 @pytest.mark.parametrize("name", FIXTURES)
 def test_loader_reproduces_committed_fixtures(rtc, name):
-    src = os.path.join(REFERENCE, "scenes", f"{name}.yaml")
-    if not os.path.exists(src):
-        pytest.skip("reference scenes not mounted here")
-    got = rtc.load_scene(src)
+    got = rtc.load_scene(os.path.join(SCENES_YAML, f"{name}.yaml"))
     want = scene_fixture(name)
     for field in ("shapes", "materials", "patterns", "lights"):
         a, b = getattr(got, field), getattr(want, field)

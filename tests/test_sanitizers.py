@@ -8,7 +8,7 @@ per-scene build cache files (csrc/rtc_jit_cache.hpp) and the f64 oracle
 
 * the oracle's KAT runner: its output equals the optimised build's, byte for byte;
 * scenes: a feature-complete YAML scene plus the loader tests' documents (and
-  the reference's own scenes/*.yaml where /root/reference is mounted) are
+  the reference's own scenes/*.yaml, tests/golden/scenes_yaml/) are
   loaded, rendered by the oracle, quantized and written as PNG, P3 and P6;
 * fuzzing: seeded byte mutations of those documents (deletions, insertions,
   bit flips, duplicated spans, truncations) through the loader and the oracle;
@@ -170,7 +170,7 @@ def _scene_files(tmp_path):
         p = tmp_path / f"doc{i}.yaml"
         p.write_text(text)
         paths.append(str(p))
-    paths += sorted(glob.glob("/root/reference/scenes/*.yaml"))  # input data, where mounted
+    paths += sorted(glob.glob(os.path.join(HERE, "golden", "scenes_yaml", "*.yaml")))  # the reference's scenes
     return paths
 
 
