@@ -311,8 +311,19 @@ __device__ inline void quadratic(R a, R b, R c, bool ok, F&& emit2) {
     const R da = (R)2 * a;
     const R root = Real<R>::sqrt(disc);
     if constexpr (sizeof(R) == 4) {
+        // The callers decide on these roots (ymin < o.y + t d.y < ymax), so a
+        // quotient that f32 can hold must come out as the division gives it:
+        // n * rcp(da) alone is an ulp short of 7 / 3.5 = 2, which put a side
+        // hit at y = ymax - 3e-8 inside the cone where the reference's y =
+        // ymax is outside (exact-boundary parity).  One Newton
+        // step on the quotient: the residual n - q da is exact in an fma, and
+        // q + residual * rcp(da) rounds to n / da whenever that is an f32.
         const R ri = __builtin_amdgcn_rcpf(da);
-        emit2((-b - root) * ri, (-b + root) * ri, v);
+        auto quot = [&](R n) {
+            const R q = n * ri;
+            return __builtin_fmaf(__builtin_fmaf(-q, da, n), ri, q);
+        };
+        emit2(quot(-b - root), quot(-b + root), v);
     } else {
         emit2((-b - root) / da, (-b + root) / da, v);
     }

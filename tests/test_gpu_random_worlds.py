@@ -153,6 +153,11 @@ def test_random_world_parity(gpu_ctx, oracle, seed):
     assert agree >= F32_PIX_FRAC, f"seed {seed}: f32 {agree:.4f}"
 
 
+PER_SCENE_USED = {}  # (seed, plain) -> the per-scene build was accepted and ran (filled by the test below)
+PER_SCENE_CASES = 32
+PER_SCENE_MIN_USED = 16  # round 6 recorded 21 of 32
+
+
 @pytest.mark.parametrize("plain", [False, True], ids=["pool", "direct"])
 @pytest.mark.parametrize("seed", list(range(16)))
 def test_random_world_per_scene_kernel_equals_generic(rtc, seed, plain):
@@ -170,6 +175,7 @@ def test_random_world_per_scene_kernel_equals_generic(rtc, seed, plain):
         a, sa = gen.render(cam, depth, precision="f32")
         b, sb = jit.render(cam, depth, precision="f32")
         js = jit.jit_status()
+        PER_SCENE_USED[(seed, plain)] = js["used"]
         if not js["used"]:
             # a build that spills or loses occupancy is refused (rtc_jit.cpp
             # jit_variant), with its reason in the log, and the frame falls
@@ -177,6 +183,19 @@ def test_random_world_per_scene_kernel_equals_generic(rtc, seed, plain):
             assert "not used" in js["log"] and ("scratch" in js["log"] or "workgroups/CU" in js["log"]), js
         assert np.array_equal(a, b), f"seed {seed}: {int((a != b).any(axis=2).sum())} pixels differ"
         assert _counts(sa) == _counts(sb)
+
+
+def test_random_world_per_scene_kernels_were_used():
+    """The comparison above also passes when a build is refused and the frame
+    falls back to the generic kernel.  Were every build refused it would
+    compare the generic kernel with itself: at least half of the 32 builds
+    must have been accepted and run (a condition against that vacuous pass,
+    not a target).  Needs all 32 cases of the test above in this session."""
+    if len(PER_SCENE_USED) < PER_SCENE_CASES:
+        pytest.skip(f"only {len(PER_SCENE_USED)} of the {PER_SCENE_CASES} per-scene cases ran in this session")
+    used = sum(PER_SCENE_USED.values())
+    print(f"per-scene builds used: {used} of {PER_SCENE_CASES}")
+    assert used >= PER_SCENE_MIN_USED, sorted(k for k, v in PER_SCENE_USED.items() if not v)
 
 
 @pytest.mark.parametrize("seed", list(range(16)))
