@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cstdint>
 #include <map>
@@ -14,6 +15,7 @@
 #include <vector>
 
 #include "../../include/rtc.h"
+#include "device_memory.hpp"
 #include "flop_model.hpp"
 #include "rtc_internal.hpp"
 
@@ -26,31 +28,39 @@ namespace rtc {
 // with one contiguous copy (scene_view).
 template <typename R>
 struct DeviceWorld {
-    void* image = nullptr;  // the allocation holding the four tables
+    DeviceBuffer<unsigned char> image;  // the allocation holding the four tables
     ShapeRec<R>* shapes = nullptr;
     MaterialRec<R>* materials = nullptr;
     PatternRec<R>* patterns = nullptr;
-    LightRec<R>* lights = nullptr;
+    DeviceBuffer<LightRec<R>> lights;
     int32_t* world_slot = nullptr;
     DevScene<R> scene{};
     // Point the tables into `image` for ns shapes, nm materials, np patterns.
     void carve(size_t ns, size_t nm, size_t np) {
-        unsigned char* b = static_cast<unsigned char*>(image);
+        unsigned char* b = image.get();
         shapes = reinterpret_cast<ShapeRec<R>*>(b);
         materials = reinterpret_cast<MaterialRec<R>*>(b + ns * sizeof(ShapeRec<R>));
         patterns = reinterpret_cast<PatternRec<R>*>(b + ns * sizeof(ShapeRec<R>) + nm * sizeof(MaterialRec<R>));
         world_slot = reinterpret_cast<int32_t*>(b + ns * sizeof(ShapeRec<R>) + nm * sizeof(MaterialRec<R>) +
                                                 np * sizeof(PatternRec<R>));
     }
-    void release() {
-        (void)hipFree(image);
-        (void)hipFree(lights);
-        image = nullptr;
-        shapes = nullptr;
-        materials = nullptr;
-        patterns = nullptr;
-        world_slot = nullptr;
-        lights = nullptr;
+    // Room for the tables of ns shapes, nm materials and np patterns (an empty
+    // world still gets a buffer) and for nl lights; what the buffers held is
+    // gone if they grew.  Points the tables and the scene's view at them.
+    int allocate(size_t ns, size_t nm, size_t np, size_t nl) {
+        int rc;
+        if ((rc = image.reserve(std::max<size_t>(world_lds_bytes<R>(ns, nm, np), 16))) || (rc = lights.reserve(nl)))
+            return rc;
+        carve(ns, nm, np);
+        scene.shapes = shapes;
+        scene.materials = materials;
+        scene.patterns = patterns;
+        scene.lights = nl ? lights.get() : nullptr;
+        scene.world_slot = world_slot;
+        scene.n_materials = (int32_t)nm;
+        scene.n_patterns = (int32_t)np;
+        scene.n_lights = (int32_t)nl;
+        return RT_OK;
     }
 };
 
@@ -60,135 +70,168 @@ struct CodeBuild;  // rtc_jit.cpp: one hipRTC build of a per-scene kernel, possi
 
 // One device's render state.  A single-device context is one of these; a
 // multi-GPU context (rtc_group.cpp) is the rank-0 member, holding the other
-// devices of the process as `peers`, each member with its own communicator.
+// devices of the process as `group.peers`, each member with its own
+// communicator.  Buffers, events and the stream are owning members
+// (device_memory.hpp): ~rt_context does what needs an order, they do the rest.
 struct rt_context {
+    // A/B and diagnostic switches (debug_knobs.hpp: RTC_DEBUG=key=value,...)
+    struct Knobs {
+        // Defaults from A/B on MI355X (scripts/ab_sched.sh, scripts/stamps2.sh):
+        // uniform-cost direct tiles -> static stride; high-variance pool tiles ->
+        // per-XCD atomic queues; per-lane stores beat LDS-staged ones (the
+        // staging barriers wait for store completion).
+        // (RTC_DEBUG=sched_direct=grid|static; the pool kernel always takes the
+        // per-XCD queues)
+        uint32_t sched_direct = rtc::kSchedStatic;
+        // f32 direct kernel's resident-grid multiple, in tenths (RTC_DEBUG=direct_oversub=T)
+        uint32_t direct_oversub10 = 25;
+        bool lds_world = true;      // RTC_DEBUG=lds_world=0 gathers shade data from global memory
+        bool cull = true;  // RTC_DEBUG=cull=0 uploads every shape as unbounded (no wave cull; exactness tests)
+        bool kind_variants = true;  // RTC_DEBUG=kind_variants=0: always the all-kinds kernels
+        uint32_t pool_lds_rays = 0;  // RTC_DEBUG=pool_lds_rays=N: LDS-resident pool slots (0 = sized for occupancy)
+        bool tile_order = true;      // RTC_DEBUG=tile_order=0: raster order always
+        // Tiles costing more than split_factor x the mean workgroup load are
+        // handed out in parts (order_tiles); RTC_DEBUG=split=0 never splits.  Round-3
+        // sweep (per-scene kernels, slowest of 8 shards at 4K / 1-GPU frame):
+        // 1.5: cover 0.239 / 1.132 ms, table 0.244 / 1.389; 1.0: 0.217 / 1.142,
+        // 0.226 / 1.369; 0.75: 0.206 / 1.128, 0.233 / 1.384; 0.5: 0.205 / 1.128,
+        // 0.245 / 1.414; reflect_refract 1080p, slowest of 4: 0.146 / 0.129 /
+        // 0.126 / 0.131 with whole frames unchanged (0.385-0.403).
+        double split_factor = 1.0;
+        // RTC_DEBUG=split_max=L: log2 of the most parts a tile is split into.  Same-box
+        // sweep (profiles/ab/r03_split16_sweep.txt, r03_shard_floor.txt), slowest
+        // shard ms at 2 / 3 / 4: cover 4K of 8 0.198 / 0.202 / 0.207, of 32
+        // 0.130 / 0.096 / 0.115; reflect_refract 1080p of 4 0.127 / 0.128 /
+        // 0.121, of 16 0.112 / 0.092 / 0.097; whole frames split nothing.
+        uint32_t split_max = 3;
+        // Items (tiles or parts) costing more than urgent_factor x the mean
+        // workgroup load run at raised wave priority, graded 1/2/3 above 1x/2x/4x
+        // that cost (RTC_DEBUG=urgent=F, 0 = none; one level for all measured no better).  Same-box sweep, kernel ms, none / flat 0.25 / flat 0.125 /
+        // graded 0.125: reflect_refract 0.367 / 0.310 / 0.306 / 0.310, cylinders
+        // 0.124 / 0.117 / 0.117 / 0.117, cover 4K 1.014 / 1.023 / 1.011 / 1.011,
+        // table 4K, refraction, metal within 1 %; slowest of 8 shards at 4K: cover
+        // 0.215 / 0.201 / 0.215 / 0.201, table 0.229 / 0.266 / 0.230 / 0.231.
+        double urgent_factor = 0.125;
+    };
+    // Heaviest-first tile order for repeated pool launches of the same frame
+    // (order_tiles): per-tile costs of the last launch and its signature.
+    struct TileOrder {
+        rtc::DeviceBuffer<uint32_t> d_cost;   // one per tile
+        rtc::DeviceBuffer<uint32_t> d_order;  // up to 2^kMaxSplitLog2 items per tile, then the item count
+        uint64_t sig = 0;
+        uint64_t geometry = 0;  // sig without the camera
+        bool valid = false;
+        bool built = false;     // d_order holds an order for `geometry`
+        int builds = 0;         // order_tiles runs for the current signature so far
+        // First launch of a frame geometry (no recorded costs): tiles handed out
+        // centre-out instead of in raster order (full frames; shards keep raster).
+        rtc::DeviceBuffer<uint32_t> d_cold;  // centre-out order + item count, for cold_w x cold_h
+        uint32_t cold_w = 0, cold_h = 0;
+    };
+    // Per-scene f32 kernels (rtc_jit.cpp): the f32 shape table of the last
+    // upload, the kernels built for it (direct/pool x global/LDS world), and
+    // RTC_JIT / rt_context_set_jit = RT_JIT_OFF | RT_JIT_SYNC | RT_JIT_AUTO
+    // (default) | RT_JIT_EAGER (rtc.h).
+    struct Jit {
+        std::vector<rtc::ShapeRec<float>> shapes;
+        std::vector<rtc::LightRec<float>> lights;  // per-scene builds unroll the lights as constants
+        std::vector<rtc::MaterialRec<float>> materials;  // ... and the direct kernel reads materials as constants
+        std::vector<rtc::PatternRec<float>> pattern_recs;  // (pattern kinds present)
+        bool patterns = true;                      // some material has a pattern (else pattern code is dropped)
+        uint32_t pattern_kinds = ~0u;              // pattern kinds in the world's table (bit per RT_PATTERN_*)
+        bool transparent = true;                   // some material is transparent (else no refraction code)
+        int32_t begin[rtc::kNumKinds + 1] = {};
+        // variants: pool x LDS world x RT_FLAG_NO_SKIPS x (pool) 7 waves/SIMD (rtc_jit.cpp jit_function)
+        static constexpr int kVariants = 16;
+        hipFunction_t fn[kVariants] = {};
+        std::shared_ptr<rtc::CodeBuild> build[kVariants];  // the build each variant waits for (host thread)
+        bool rejected[kVariants] = {};   // built, but refused for occupancy or scratch (that variant only)
+        bool owner[kVariants] = {};      // this context started the build: its time goes into compile_ms
+        uint32_t frames = 0;     // large f32 frames of this upload so far (RT_JIT_AUTO starts at the 2nd)
+        std::string arch;            // the device's gfx target (gcnArchName), for hipRTC; read lazily (device_arch)
+        int mode = 2;
+        bool failed = false, used = false;  // failed: the world's build failed (compile or load)
+        double compile_ms = 0;  // compile (or disk-cache load) time of this context's per-scene builds
+        int cache_hits = 0;     // builds loaded from the on-disk cache
+        std::string log;
+        // A new upload: no kernel, build or verdict of the previous world is kept.
+        void reset() {
+            for (int v = 0; v < kVariants; ++v) {
+                fn[v] = nullptr;
+                build[v].reset();
+                rejected[v] = owner[v] = false;
+            }
+            frames = 0;
+            failed = false;
+            log.clear();
+        }
+    };
+    // Multi-GPU group (rtc_group.cpp, SURVEY.md §8b/§8e).  A frame is split
+    // into n_ranks shards of cyclic RT_TILE_H-row blocks; this member renders
+    // shard `rank` into d_strip, RCCL gathers the strips onto rank 0, which
+    // de-interleaves them into the image.  Single-device contexts: comm null.
+    struct Group {
+        ncclComm_t comm = nullptr;
+        int n_ranks = 1, rank = 0;
+        std::vector<rt_context*> peers;  // rank 0 of a one-process group: the other devices' members
+        rtc::DeviceBuffer<int32_t> d_status;  // agree_status's word, allocated with the member so a rank can always join
+        rtc::DeviceBuffer<unsigned char> d_strip;     // this member's shard strip
+        rtc::DeviceBuffer<unsigned char> d_gathered;  // rank 0: every strip, shard-major
+        rtc::Event ev_render0, ev_render1, ev_gather1;  // frame timing
+        // RT_GATHER_PEER groups: the shared canvas (rank 0's allocation; mapped or
+        // peer-accessed on the others) and the frame sequence number.
+        int gather_mode = RT_GATHER_RCCL;
+        void* canvas = nullptr;
+        uint64_t canvas_bytes = 0, canvas_seq = 0;
+    };
+
+    rt_context() = default;
+    rt_context(const rt_context&) = delete;
+    rt_context& operator=(const rt_context&) = delete;
+    // In this order: hipSetDevice, hipDeviceSynchronize (launches on caller
+    // streams too), close the canvases, ncclCommDestroy; then the members.
+    ~rt_context();
+
     int device = 0;
     int cu_count = 0;
     size_t lds_per_block = 64 * 1024;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev_start = nullptr, ev_stop = nullptr;
+    size_t occ_lds[8] = {};     // occupancy cache: {direct,pool} x {f32,f64} x {global,LDS world}
+    int occ_blocks[8] = {};
+    Knobs knobs;
+    rtc::Stream stream;
+    rtc::Event ev_start, ev_stop;
     // Stream order across entry points: every launch shares the queue heads,
     // tile costs/order and pool spill.  rt_render_device runs on the caller's
     // stream, rt_render/rt_color_at on `stream`; a launch on a stream other
     // than the previous launch's first makes its stream wait on all work
     // submitted so far to that one (ev_order recorded at the switch).
-    hipEvent_t ev_order = nullptr;
+    rtc::Event ev_order;
     hipStream_t last_stream = nullptr;
     bool launched = false;
-    unsigned long long* d_tile_counter = nullptr;  // two sets of queue heads (launch: dynamic schedule)
+    rtc::DeviceBuffer<unsigned long long> d_tile_counter;  // two sets of queue heads (launch: dynamic schedule)
     int head_set = 0;                              // the set the next dynamic launch uses
-    unsigned long long* d_counters = nullptr;  // kNumCounters cumulative
-    unsigned long long* d_gen_counts = nullptr;  // RT_FLAG_GENERATIONS: traced, shaded x kGenSlots, cumulative
-    int32_t* d_error = nullptr;
+    rtc::DeviceBuffer<unsigned long long> d_counters;  // kNumCounters cumulative
+    rtc::DeviceBuffer<unsigned long long> d_gen_counts;  // RT_FLAG_GENERATIONS: traced, shaded x kGenSlots, cumulative
+    rtc::DeviceBuffer<int32_t> d_error;
+    // rt_render: counters before/after and the error flag come back pinned,
+    // on the stream, so a frame needs one host sync
+    rtc::PinnedBuffer<unsigned long long> h_counters;  // 2 x kCounterShards x kNumCounters + the error flag
     bool have_scene = false;
     rtc::DeviceWorld<float> w32;
     rtc::DeviceWorld<double> w64;
     rtc::FlopScene flops;  // per-kind shape counts for the algorithmic FLOP model
     double bright_hit = 1.0, bright_w = 0.0;  // brightness bound of the world (acc_shift_f32)
-    // Defaults from A/B on MI355X (scripts/ab_sched.sh, scripts/stamps2.sh):
-    // uniform-cost direct tiles -> static stride; high-variance pool tiles ->
-    // per-XCD atomic queues; per-lane stores beat LDS-staged ones (the
-    // staging barriers wait for store completion).
-    // (RTC_DEBUG=sched_direct=grid|static; the pool kernel always takes the
-    // per-XCD queues)
-    uint32_t sched_direct = rtc::kSchedStatic;
-    // f32 direct kernel's resident-grid multiple, in tenths (RTC_DEBUG=direct_oversub=T)
-    uint32_t direct_oversub10 = 25;
-    bool lds_world = true;      // RTC_DEBUG=lds_world=0 gathers shade data from global memory
-    bool cull = true;  // RTC_DEBUG=cull=0 uploads every shape as unbounded (no wave cull; exactness tests)
-    bool kind_variants = true;  // RTC_DEBUG=kind_variants=0: always the all-kinds kernels
-    size_t occ_lds[8] = {};     // occupancy cache: {direct,pool} x {f32,f64} x {global,LDS world}
-    int occ_blocks[8] = {};
-    uint32_t pool_lds_rays = 0;  // RTC_DEBUG=pool_lds_rays=N: LDS-resident pool slots (0 = sized for occupancy)
-    void* d_spill = nullptr;     // ray-pool overflow regions, one per resident workgroup
-    // Heaviest-first tile order for repeated pool launches of the same frame
-    // (order_tiles): per-tile costs of the last launch and its signature.
-    bool tile_order = true;      // RTC_DEBUG=tile_order=0: raster order always
-    uint32_t* d_tile_cost = nullptr;
-    uint32_t* d_tile_order = nullptr;
-    uint32_t order_capacity = 0;
-    uint64_t order_sig = 0;
-    uint64_t order_geometry = 0;  // order_sig without the camera
-    bool order_valid = false;
-    bool order_built = false;     // d_tile_order holds an order for order_geometry
-    // First launch of a frame geometry (no recorded costs): tiles handed out
-    // centre-out instead of in raster order (full frames; shards keep raster).
-    uint32_t* d_cold_order = nullptr;  // centre-out order + item count, for cold_w x cold_h
-    uint32_t cold_w = 0, cold_h = 0;
-    // Tiles costing more than split_factor x the mean workgroup load are
-    // handed out in parts (order_tiles); RTC_DEBUG=split=0 never splits.  Round-3
-    // sweep (per-scene kernels, slowest of 8 shards at 4K / 1-GPU frame):
-    // 1.5: cover 0.239 / 1.132 ms, table 0.244 / 1.389; 1.0: 0.217 / 1.142,
-    // 0.226 / 1.369; 0.75: 0.206 / 1.128, 0.233 / 1.384; 0.5: 0.205 / 1.128,
-    // 0.245 / 1.414; reflect_refract 1080p, slowest of 4: 0.146 / 0.129 /
-    // 0.126 / 0.131 with whole frames unchanged (0.385-0.403).
-    double split_factor = 1.0;
-    // RTC_DEBUG=split_max=L: log2 of the most parts a tile is split into.  Same-box
-    // sweep (profiles/ab/r03_split16_sweep.txt, r03_shard_floor.txt), slowest
-    // shard ms at 2 / 3 / 4: cover 4K of 8 0.198 / 0.202 / 0.207, of 32
-    // 0.130 / 0.096 / 0.115; reflect_refract 1080p of 4 0.127 / 0.128 /
-    // 0.121, of 16 0.112 / 0.092 / 0.097; whole frames split nothing.
-    uint32_t split_max = 3;
-    // Items (tiles or parts) costing more than urgent_factor x the mean
-    // workgroup load run at raised wave priority, graded 1/2/3 above 1x/2x/4x
-    // that cost (RTC_DEBUG=urgent=F, 0 = none; one level for all measured no better).  Same-box sweep, kernel ms, none / flat 0.25 / flat 0.125 /
-    // graded 0.125: reflect_refract 0.367 / 0.310 / 0.306 / 0.310, cylinders
-    // 0.124 / 0.117 / 0.117 / 0.117, cover 4K 1.014 / 1.023 / 1.011 / 1.011,
-    // table 4K, refraction, metal within 1 %; slowest of 8 shards at 4K: cover
-    // 0.215 / 0.201 / 0.215 / 0.201, table 0.229 / 0.266 / 0.230 / 0.231.
-    double urgent_factor = 0.125;
-    int order_builds = 0;        // order_tiles runs for the current signature so far
     uint64_t scene_gen = 0;      // bumped by every rt_scene_upload
     uint32_t duplicate_shapes = 0;  // shapes value-equal to an earlier one (one identity class)
     std::vector<int32_t> world_slot;  // world index -> slot | kind << 24 of the uploaded table
-    size_t spill_bytes = 0;
-    unsigned long long* d_stamps = nullptr;  // RT_FLAG_STAMPS diagnostics
-    uint32_t stamp_capacity = 0, stamp_count = 0;
-    unsigned long long* d_item_log = nullptr;  // RT_FLAG_STAMPS pool launches: item spans
-    size_t item_log_capacity = 0;  // items
-    void* d_scratch = nullptr;  // host-buffer renders / color_at staging
-    size_t scratch_bytes = 0;
-    // Per-scene f32 kernels (rtc_jit.cpp): the f32 shape table of the last
-    // upload, the kernels built for it (direct/pool x global/LDS world), and
-    // RTC_JIT / rt_context_set_jit = RT_JIT_OFF | RT_JIT_SYNC | RT_JIT_AUTO
-    // (default) | RT_JIT_EAGER (rtc.h).
-    std::vector<rtc::ShapeRec<float>> jit_shapes;
-    std::vector<rtc::LightRec<float>> jit_lights;  // per-scene builds unroll the lights as constants
-    std::vector<rtc::MaterialRec<float>> jit_materials;  // ... and the direct kernel reads materials as constants
-    std::vector<rtc::PatternRec<float>> jit_pattern_recs;  // (pattern kinds present)
-    bool jit_patterns = true;                      // some material has a pattern (else pattern code is dropped)
-    uint32_t jit_pattern_kinds = ~0u;              // pattern kinds in the world's table (bit per RT_PATTERN_*)
-    bool jit_transparent = true;                   // some material is transparent (else no refraction code)
-    int32_t jit_begin[rtc::kNumKinds + 1] = {};
-    // variants: pool x LDS world x RT_FLAG_NO_SKIPS x (pool) 7 waves/SIMD (rtc_jit.cpp jit_function)
-    static constexpr int kJitVariants = 16;
-    hipFunction_t jit_fn[kJitVariants] = {};
-    std::shared_ptr<rtc::CodeBuild> jit_build[kJitVariants];  // the build each variant waits for (host thread)
-    bool jit_rejected[kJitVariants] = {};   // built, but refused for occupancy or scratch (that variant only)
-    bool jit_owner[kJitVariants] = {};      // this context started the build: its time goes into jit_compile_ms
-    uint32_t jit_frames = 0;     // large f32 frames of this upload so far (RT_JIT_AUTO starts at the 2nd)
-    std::string arch;            // the device's gfx target (gcnArchName), for hipRTC; read lazily (device_arch)
-    int jit_mode = 2;
-    bool jit_failed = false, jit_used = false;  // jit_failed: the world's build failed (compile or load)
-    double jit_compile_ms = 0;  // compile (or disk-cache load) time of this context's per-scene builds
-    int jit_cache_hits = 0;     // builds loaded from the on-disk cache
-    std::string jit_log;
-    // rt_render: counters before/after and the error flag come back pinned,
-    // on the stream, so a frame needs one host sync
-    unsigned long long* h_counters = nullptr;  // 2 x kCounterShards x kNumCounters + the error flag
-    // Multi-GPU group (rtc_group.cpp, SURVEY.md §8b/§8e).  A frame is split
-    // into n_ranks shards of cyclic RT_TILE_H-row blocks; this member renders
-    // shard `rank` into d_strip, RCCL gathers the strips onto rank 0, which
-    // de-interleaves them into the image.  Single-device contexts: comm null.
-    ncclComm_t comm = nullptr;
-    int n_ranks = 1, rank = 0;
-    std::vector<rt_context*> peers;  // rank 0 of a one-process group: the other devices' members
-    int32_t* d_status = nullptr;     // agree_status's word, allocated with the member so a rank can always join
-    void* d_strip = nullptr;         // this member's shard strip
-    size_t strip_bytes = 0;
-    void* d_gathered = nullptr;      // rank 0: every strip, shard-major
-    size_t gathered_bytes = 0;
-    hipEvent_t ev_render0 = nullptr, ev_render1 = nullptr, ev_gather1 = nullptr;  // frame timing
+    rtc::DeviceBuffer<unsigned char> d_spill;  // ray-pool overflow regions, one per resident workgroup
+    TileOrder order;
+    Jit jit;
+    rtc::DeviceBuffer<unsigned char> d_scratch;  // host-buffer renders / color_at staging
+    rtc::DeviceBuffer<unsigned long long> d_stamps;  // RT_FLAG_STAMPS diagnostics: two per workgroup
+    uint32_t stamp_count = 0;
+    rtc::DeviceBuffer<unsigned long long> d_item_log;  // RT_FLAG_STAMPS pool launches: a count, then item spans
+    Group group;
     // Peer canvases this context created or mapped (rt_canvas_*): image
     // bytes and flag count per base pointer.
     struct Canvas {
@@ -197,15 +240,20 @@ struct rt_context {
         bool owned = false;  // created here (hipFree) or mapped (hipIpcCloseMemHandle / peer pointer)
     };
     std::map<void*, Canvas> canvases;
-    // RT_GATHER_PEER groups: the shared canvas (rank 0's allocation; mapped or
-    // peer-accessed on the others) and the frame sequence number.
-    int gather_mode = RT_GATHER_RCCL;
-    void* group_canvas = nullptr;
-    uint64_t group_canvas_bytes = 0;
-    uint64_t canvas_seq = 0;
 };
 
 namespace rtc {
+
+// The context and the other devices' members of a one-process group.
+inline std::vector<rt_context*> members(rt_context* ctx) {
+    std::vector<rt_context*> m{ctx};
+    m.insert(m.end(), ctx->group.peers.begin(), ctx->group.peers.end());
+    return m;
+}
+inline size_t element_bytes(uint32_t out_format, uint32_t precision) {
+    return out_format == RT_OUT_U8 ? 1 : (precision == RT_PRECISION_F32 ? 4 : 8);
+}
+inline size_t pixel_bytes(const rt_render_options* o) { return 3 * element_bytes(o->out_format, o->precision); }
 
 // rtc_host.cpp
 // RTC_DEBUG=trace_init=1: per-step milliseconds of context creation, upload and
@@ -220,16 +268,16 @@ private:
     std::chrono::steady_clock::time_point t0_, t_;
 };
 int create_device_context(int device, rt_context** out);
-void destroy_device_context(rt_context* ctx);
+void destroy_device_context(rt_context* ctx);  // null is fine
 int check_ready(rt_context* ctx);
 int check_options(const rt_render_options* o);
-int ensure_scratch(rt_context* ctx, size_t bytes);
+// kCounterShards x kNumCounters as the kernels keep them -> their sums
+void sum_counter_shards(const unsigned long long* shards, unsigned long long out[kNumCounters]);
 int read_counters(rt_context* ctx, unsigned long long out[kNumCounters]);
 void fill_stats(rt_context* ctx, const unsigned long long before[kNumCounters],
                 const unsigned long long after[kNumCounters], float ms, rt_stats* s);
 int check_pool_error(rt_context* ctx);
 int order_after_last(rt_context* ctx, hipStream_t stream);  // cross-stream launch order (rtc.h)
-int ensure_host_counters(rt_context* ctx);
 int copy_to_host(rt_context* ctx, void* out, size_t bytes);  // d_scratch -> caller host buffer, on ctx->stream
 uint32_t tile_rows_for(uint32_t height, uint32_t shards, uint32_t shard);
 int validate_scene(const rt_shape_desc* shapes, uint32_t ns, const rt_material_desc* mats, uint32_t nm,
@@ -275,11 +323,9 @@ int group_read_counters(rt_context* ctx, rt_stats* totals);
 hipError_t launch_assemble(const void* gathered, void* image, uint32_t width, uint32_t height, uint32_t shards,
                            uint32_t strip_rows, uint32_t bpp, hipStream_t stream);
 
-#define RT_HIP(call)                                                                               \
-    do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess)                                                                      \
-            return set_error(RT_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));       \
+#define RT_HIP(call)                                        \
+    do {                                                    \
+        if (int rc_ = hip_status((call), #call)) return rc_; \
     } while (0)
 
 }  // namespace rtc

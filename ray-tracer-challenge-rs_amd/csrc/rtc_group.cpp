@@ -44,12 +44,6 @@ namespace {
         if (r_ != ncclSuccess) return set_error(RT_ERR_COMM, std::string(#call) + ": " + ncclGetErrorString(r_)); \
     } while (0)
 
-std::vector<rt_context*> members(rt_context* ctx) {
-    std::vector<rt_context*> m{ctx};
-    m.insert(m.end(), ctx->peers.begin(), ctx->peers.end());
-    return m;
-}
-
 // The flattened world's shape, broadcast ahead of the tables so the other
 // ranks can allocate them.
 struct SceneHeader {
@@ -62,61 +56,46 @@ struct SceneHeader {
     double bright_hit, bright_w;  // acc_shift_f32's bound
 };
 
-template <typename R>
-int alloc_world(DeviceWorld<R>& w, const SceneHeader& h) {
-    w.release();
-    RT_HIP(hipMalloc(&w.image, std::max<size_t>(world_lds_bytes<R>(h.ns, h.nm, h.np), 16)));
-    w.carve(h.ns, h.nm, h.np);
-    if (h.nl) RT_HIP(hipMalloc(reinterpret_cast<void**>(&w.lights), h.nl * sizeof(LightRec<R>)));
-    return RT_OK;
-}
-
-template <typename R>
-void describe_world(DeviceWorld<R>& w, const SceneHeader& h) {
-    w.scene.shapes = w.shapes;
-    w.scene.materials = w.materials;
-    w.scene.patterns = w.patterns;
-    w.scene.lights = w.lights;
-    w.scene.world_slot = w.world_slot;
-    for (int k = 0; k <= kNumKinds; ++k) w.scene.kind_begin[k] = h.kind_begin[k];
-    w.scene.n_materials = (int32_t)h.nm;
-    w.scene.n_patterns = (int32_t)h.np;
-    w.scene.n_lights = (int32_t)h.nl;
-    w.scene.any_secondary = h.any_secondary;
-}
-
 // (device pointer, bytes) of every table of a member's world, in one order
 // on every rank.
 template <typename R>
 void world_buffers(DeviceWorld<R>& w, const SceneHeader& h, std::vector<std::pair<void*, size_t>>& out) {
-    out.push_back({w.image, world_lds_bytes<R>(h.ns, h.nm, h.np)});  // shapes, materials, patterns, world_slot
-    out.push_back({w.lights, h.nl * sizeof(LightRec<R>)});
+    out.push_back({w.image.get(), world_lds_bytes<R>(h.ns, h.nm, h.np)});  // shapes, materials, patterns, world_slot
+    out.push_back({w.lights.get(), h.nl * sizeof(LightRec<R>)});
 }
 
-int ensure(void** p, size_t* have, size_t need) {
-    if (*have >= need) return RT_OK;
-    (void)hipFree(*p);
-    *p = nullptr;
-    *have = 0;
-    RT_HIP(hipMalloc(p, need));
-    *have = need;
+// Rank 0's `value` to every member of every rank, over RCCL (collective):
+// got[i] is what ms[i] received.
+template <typename T>
+int broadcast_value(const std::vector<rt_context*>& ms, const T& value, std::vector<T>& got) {
+    std::vector<DeviceBuffer<T>> d(ms.size());
+    for (size_t i = 0; i < ms.size(); ++i) {
+        RT_HIP(hipSetDevice(ms[i]->device));
+        if (int rc = d[i].reserve(1)) return rc;
+        if (ms[i]->group.rank == 0) RT_HIP(hipMemcpy(d[i].get(), &value, sizeof(T), hipMemcpyHostToDevice));
+    }
+    RT_NCCL(ncclGroupStart());
+    for (size_t i = 0; i < ms.size(); ++i)
+        RT_NCCL(ncclBroadcast(d[i].get(), d[i].get(), sizeof(T), ncclUint8, 0, ms[i]->group.comm, ms[i]->stream));
+    RT_NCCL(ncclGroupEnd());
+    got.resize(ms.size());
+    for (size_t i = 0; i < ms.size(); ++i) {
+        RT_HIP(hipSetDevice(ms[i]->device));
+        RT_HIP(hipStreamSynchronize(ms[i]->stream));
+        RT_HIP(hipMemcpy(&got[i], d[i].get(), sizeof(T), hipMemcpyDeviceToHost));
+    }
     return RT_OK;
 }
 
 int init_member(rt_context* m, ncclComm_t comm, int n_ranks, int rank) {
-    m->comm = comm;
-    m->n_ranks = n_ranks;
-    m->rank = rank;
+    rt_context::Group& g = m->group;
+    g.comm = comm;  // (the member owns it from here on: ~rt_context)
+    g.n_ranks = n_ranks;
+    g.rank = rank;
     RT_HIP(hipSetDevice(m->device));
-    RT_HIP(hipEventCreate(&m->ev_render0));
-    RT_HIP(hipEventCreate(&m->ev_render1));
-    RT_HIP(hipEventCreate(&m->ev_gather1));
-    RT_HIP(hipMalloc(reinterpret_cast<void**>(&m->d_status), sizeof(int32_t)));
-    return RT_OK;
-}
-
-size_t pixel_bytes(const rt_render_options* o) {
-    return 3 * (o->out_format == RT_OUT_U8 ? 1 : (o->precision == RT_PRECISION_F32 ? 4 : 8));
+    int rc;
+    if ((rc = g.ev_render0.create()) || (rc = g.ev_render1.create()) || (rc = g.ev_gather1.create())) return rc;
+    return g.d_status.reserve(1);
 }
 
 // The shards of one frame: every local member renders its strip on its
@@ -128,39 +107,39 @@ int render_shards_peer(rt_context* ctx, const rt_camera_desc* cam, const rt_rend
 
 int render_shards(rt_context* ctx, const rt_camera_desc* cam, const rt_render_options* o, void* image,
                   hipStream_t root_stream, bool timed) {
-    if (ctx->gather_mode == RT_GATHER_PEER) return render_shards_peer(ctx, cam, o, image, root_stream, timed);
+    if (ctx->group.gather_mode == RT_GATHER_PEER) return render_shards_peer(ctx, cam, o, image, root_stream, timed);
     const std::vector<rt_context*> ms = members(ctx);
-    const uint32_t G = (uint32_t)ctx->n_ranks;
+    const uint32_t G = (uint32_t)ctx->group.n_ranks;
     const uint32_t rows = tile_rows_for(cam->height, G, 0) * RT_TILE_H;  // shard 0 has the most rows
     const size_t strip = (size_t)rows * cam->width * pixel_bytes(o);
     int rc;
-    auto stream_of = [&](rt_context* m) { return m->rank == 0 ? root_stream : m->stream; };
+    auto stream_of = [&](rt_context* m) { return m->group.rank == 0 ? root_stream : m->stream; };
     for (rt_context* m : ms) {
         RT_HIP(hipSetDevice(m->device));
-        if (m->rank != 0 && (rc = ensure(&m->d_strip, &m->strip_bytes, strip))) return rc;
-        if (m->rank == 0 && (rc = ensure(&m->d_gathered, &m->gathered_bytes, strip * G))) return rc;
+        rt_context::Group& g = m->group;
+        if ((rc = g.rank ? g.d_strip.reserve(strip) : g.d_gathered.reserve(strip * G))) return rc;
     }
     // Rank 0 renders its strip straight into its slot of the gather buffer
     // (slot 0), and gathers in place: RCCL then copies only the other ranks'.
-    auto strip_of = [&](rt_context* m) { return m->rank == 0 ? m->d_gathered : m->d_strip; };
+    auto strip_of = [&](rt_context* m) { return m->group.rank ? m->group.d_strip.get() : m->group.d_gathered.get(); };
     for (rt_context* m : ms) {
         hipStream_t s = stream_of(m);
         RT_HIP(hipSetDevice(m->device));
-        if (timed) RT_HIP(hipEventRecord(m->ev_render0, s));
-        if ((rc = launch_frame(m, cam, o, (uint32_t)m->rank, G, strip_of(m), s))) return rc;
-        if (timed) RT_HIP(hipEventRecord(m->ev_render1, s));
+        if (timed) RT_HIP(hipEventRecord(m->group.ev_render0, s));
+        if ((rc = launch_frame(m, cam, o, (uint32_t)m->group.rank, G, strip_of(m), s))) return rc;
+        if (timed) RT_HIP(hipEventRecord(m->group.ev_render1, s));
     }
     RT_NCCL(ncclGroupStart());
     for (rt_context* m : ms)
-        RT_NCCL(ncclGather(strip_of(m), m->rank == 0 ? m->d_gathered : nullptr, strip, ncclUint8, 0, m->comm,
-                           stream_of(m)));
+        RT_NCCL(ncclGather(strip_of(m), m->group.rank ? nullptr : m->group.d_gathered.get(), strip, ncclUint8, 0,
+                           m->group.comm, stream_of(m)));
     RT_NCCL(ncclGroupEnd());
     for (rt_context* m : ms) {
-        if (m->rank != 0) continue;
+        if (m->group.rank != 0) continue;
         RT_HIP(hipSetDevice(m->device));
-        RT_HIP(launch_assemble(m->d_gathered, image, cam->width, cam->height, G, rows, (uint32_t)pixel_bytes(o),
+        RT_HIP(launch_assemble(m->group.d_gathered.get(), image, cam->width, cam->height, G, rows, (uint32_t)pixel_bytes(o),
                                root_stream));
-        if (timed) RT_HIP(hipEventRecord(m->ev_gather1, root_stream));
+        if (timed) RT_HIP(hipEventRecord(m->group.ev_gather1, root_stream));
     }
     return RT_OK;
 }
@@ -172,22 +151,22 @@ int render_shards(rt_context* ctx, const rt_camera_desc* cam, const rt_render_op
 // access to rank 0's pointer.
 int ensure_group_canvas(rt_context* ctx, uint64_t bytes) {
     const std::vector<rt_context*> ms = members(ctx);
-    if (ctx->group_canvas && ctx->group_canvas_bytes >= bytes) return RT_OK;
-    const uint32_t G = (uint32_t)ctx->n_ranks;
-    const bool remote = (int)ms.size() < ctx->n_ranks;  // ranks in other processes
+    if (ctx->group.canvas && ctx->group.canvas_bytes >= bytes) return RT_OK;
+    const uint32_t G = (uint32_t)ctx->group.n_ranks;
+    const bool remote = (int)ms.size() < ctx->group.n_ranks;  // ranks in other processes
     int rc;
     for (rt_context* m : ms) {  // drop the old canvas (rank 0's allocation, a mapping, or a peer pointer)
-        if (m->group_canvas && m->canvases.count(m->group_canvas) && (rc = canvas_close(m, m->group_canvas))) return rc;
-        m->group_canvas = nullptr;
-        m->group_canvas_bytes = 0;
-        m->canvas_seq = 0;  // a new canvas's flags start at 0: its first frame is seq 1 on every rank
+        if (m->group.canvas && m->canvases.count(m->group.canvas) && (rc = canvas_close(m, m->group.canvas))) return rc;
+        m->group.canvas = nullptr;
+        m->group.canvas_bytes = 0;
+        m->group.canvas_seq = 0;  // a new canvas's flags start at 0: its first frame is seq 1 on every rank
     }
     void* root = nullptr;
     for (rt_context* m : ms)
-        if (m->rank == 0) {
+        if (m->group.rank == 0) {
             if ((rc = canvas_create(m, bytes, G, &root))) return rc;
-            m->group_canvas = root;
-            m->group_canvas_bytes = bytes;
+            m->group.canvas = root;
+            m->group.canvas_bytes = bytes;
         }
     if (remote) {  // the IPC handle from rank 0 to every rank, over RCCL
         hipIpcMemHandle_t h{};
@@ -195,32 +174,20 @@ int ensure_group_canvas(rt_context* ctx, uint64_t bytes) {
             RT_HIP(hipSetDevice(ctx->device));
             RT_HIP(hipIpcGetMemHandle(&h, root));
         }
-        std::vector<void*> d_h(ms.size(), nullptr);
+        std::vector<hipIpcMemHandle_t> got;
+        if ((rc = broadcast_value(ms, h, got))) return rc;
         for (size_t i = 0; i < ms.size(); ++i) {
+            if (ms[i]->group.rank == 0) continue;
             RT_HIP(hipSetDevice(ms[i]->device));
-            RT_HIP(hipMalloc(&d_h[i], sizeof h));
-            if (ms[i]->rank == 0) RT_HIP(hipMemcpy(d_h[i], &h, sizeof h, hipMemcpyHostToDevice));
-        }
-        RT_NCCL(ncclGroupStart());
-        for (size_t i = 0; i < ms.size(); ++i)
-            RT_NCCL(ncclBroadcast(d_h[i], d_h[i], sizeof h, ncclUint8, 0, ms[i]->comm, ms[i]->stream));
-        RT_NCCL(ncclGroupEnd());
-        for (size_t i = 0; i < ms.size(); ++i) {
-            RT_HIP(hipSetDevice(ms[i]->device));
-            RT_HIP(hipStreamSynchronize(ms[i]->stream));
-            hipIpcMemHandle_t got;
-            RT_HIP(hipMemcpy(&got, d_h[i], sizeof got, hipMemcpyDeviceToHost));
-            (void)hipFree(d_h[i]);
-            if (ms[i]->rank == 0) continue;
             void* p = nullptr;
-            RT_HIP(hipIpcOpenMemHandle(&p, got, hipIpcMemLazyEnablePeerAccess));
+            RT_HIP(hipIpcOpenMemHandle(&p, got[i], hipIpcMemLazyEnablePeerAccess));
             ms[i]->canvases[p] = {bytes, G, false};
-            ms[i]->group_canvas = p;
-            ms[i]->group_canvas_bytes = bytes;
+            ms[i]->group.canvas = p;
+            ms[i]->group.canvas_bytes = bytes;
         }
     } else {  // every rank in this process: peer access to rank 0's device
         for (rt_context* m : ms) {
-            if (m->rank == 0) continue;
+            if (m->group.rank == 0) continue;
             RT_HIP(hipSetDevice(m->device));
             if (m->device != ctx->device) {
                 hipError_t e = hipDeviceEnablePeerAccess(ctx->device, 0);
@@ -228,8 +195,8 @@ int ensure_group_canvas(rt_context* ctx, uint64_t bytes) {
                     return set_error(RT_ERR_HIP, std::string("hipDeviceEnablePeerAccess: ") + hipGetErrorString(e));
                 (void)hipGetLastError();
             }
-            m->group_canvas = root;
-            m->group_canvas_bytes = bytes;
+            m->group.canvas = root;
+            m->group.canvas_bytes = bytes;
         }
     }
     return RT_OK;
@@ -243,32 +210,46 @@ constexpr double kPeerTimeoutMs = 10000.0;
 int render_shards_peer(rt_context* ctx, const rt_camera_desc* cam, const rt_render_options* o, void* image,
                        hipStream_t root_stream, bool timed) {
     const std::vector<rt_context*> ms = members(ctx);
-    const uint32_t G = (uint32_t)ctx->n_ranks;
+    const uint32_t G = (uint32_t)ctx->group.n_ranks;
     const uint64_t bytes = (uint64_t)cam->width * cam->height * pixel_bytes(o);
     int rc;
     if ((rc = ensure_group_canvas(ctx, bytes))) return rc;
-    auto stream_of = [&](rt_context* m) { return m->rank == 0 ? root_stream : m->stream; };
+    auto stream_of = [&](rt_context* m) { return m->group.rank == 0 ? root_stream : m->stream; };
     for (rt_context* m : ms) {
         hipStream_t s = stream_of(m);
         RT_HIP(hipSetDevice(m->device));
-        const uint64_t seq = ++m->canvas_seq;  // every rank renders the same frames: the same number
-        unsigned long long* flags = canvas_flags(m->group_canvas, m->group_canvas_bytes);
-        if (seq > 1) RT_HIP(launch_canvas_wait(flags + G, 1, seq - 1, timeout_ticks(kPeerTimeoutMs), m->d_error, s));
-        if (timed) RT_HIP(hipEventRecord(m->ev_render0, s));
-        if ((rc = launch_frame(m, cam, o, (uint32_t)m->rank, G, m->group_canvas, s, true))) return rc;
-        if (timed) RT_HIP(hipEventRecord(m->ev_render1, s));
-        RT_HIP(launch_canvas_signal(flags + m->rank, seq, s));
+        const uint64_t seq = ++m->group.canvas_seq;  // every rank renders the same frames: the same number
+        unsigned long long* flags = canvas_flags(m->group.canvas, m->group.canvas_bytes);
+        if (seq > 1) RT_HIP(launch_canvas_wait(flags + G, 1, seq - 1, timeout_ticks(kPeerTimeoutMs), m->d_error.get(), s));
+        if (timed) RT_HIP(hipEventRecord(m->group.ev_render0, s));
+        if ((rc = launch_frame(m, cam, o, (uint32_t)m->group.rank, G, m->group.canvas, s, true))) return rc;
+        if (timed) RT_HIP(hipEventRecord(m->group.ev_render1, s));
+        RT_HIP(launch_canvas_signal(flags + m->group.rank, seq, s));
     }
     for (rt_context* m : ms) {
-        if (m->rank != 0) continue;
+        if (m->group.rank != 0) continue;
         RT_HIP(hipSetDevice(m->device));
-        unsigned long long* flags = canvas_flags(m->group_canvas, m->group_canvas_bytes);
-        RT_HIP(launch_canvas_wait(flags, G, m->canvas_seq, timeout_ticks(kPeerTimeoutMs), m->d_error, root_stream));
-        if (image) RT_HIP(hipMemcpyAsync(image, m->group_canvas, bytes, hipMemcpyDeviceToDevice, root_stream));
-        RT_HIP(launch_canvas_signal(flags + G, m->canvas_seq, root_stream));
-        if (timed) RT_HIP(hipEventRecord(m->ev_gather1, root_stream));
+        unsigned long long* flags = canvas_flags(m->group.canvas, m->group.canvas_bytes);
+        RT_HIP(launch_canvas_wait(flags, G, m->group.canvas_seq, timeout_ticks(kPeerTimeoutMs), m->d_error.get(),
+                                  root_stream));
+        if (image) RT_HIP(hipMemcpyAsync(image, m->group.canvas, bytes, hipMemcpyDeviceToDevice, root_stream));
+        RT_HIP(launch_canvas_signal(flags + G, m->group.canvas_seq, root_stream));
+        if (timed) RT_HIP(hipEventRecord(m->group.ev_gather1, root_stream));
     }
     return RT_OK;
+}
+
+// One member's ray counts and FLOPs into the group's.
+void add_rays(rt_stats& t, const rt_stats& s) {
+    t.primary += s.primary;
+    t.shadow += s.shadow;
+    t.reflect += s.reflect;
+    t.refract += s.refract;
+    t.shaded += s.shaded;
+    t.lit_patterned += s.lit_patterned;
+    t.refract_evals += s.refract_evals;
+    t.schlick_evals += s.schlick_evals;
+    t.algorithmic_flops += s.algorithmic_flops;
 }
 
 int check_group_options(rt_context* ctx, const rt_render_options* o) {
@@ -276,7 +257,6 @@ int check_group_options(rt_context* ctx, const rt_render_options* o) {
         return set_error(RT_ERR_INVALID, "a multi-GPU context shards frames itself: shard_index/shard_count must be 0/1");
     for (rt_context* m : members(ctx))
         if (!m->have_scene) return set_error(RT_ERR_NO_SCENE, "render before rt_scene_upload");
-    (void)ctx;
     return RT_OK;
 }
 
@@ -295,18 +275,19 @@ int agree_status(const std::vector<rt_context*>& ms, int local) {
     const int32_t mine = local ? -local : 0;
     std::vector<int32_t> got(ms.size(), 0);
     int rc = RT_OK;
+    auto word = [&](size_t i) { return ms[i]->group.d_status.get(); };
     for (size_t i = 0; i < ms.size(); ++i) {
         if (hipSetDevice(ms[i]->device) != hipSuccess ||
-            hipMemcpyAsync(ms[i]->d_status, &mine, sizeof mine, hipMemcpyHostToDevice, ms[i]->stream) != hipSuccess)
+            hipMemcpyAsync(word(i), &mine, sizeof mine, hipMemcpyHostToDevice, ms[i]->stream) != hipSuccess)
             if (!rc) rc = set_error(RT_ERR_HIP, "status exchange: writing the status word");
     }
     ncclResult_t r = ncclGroupStart();
     for (size_t i = 0; i < ms.size() && r == ncclSuccess; ++i)
-        r = ncclAllReduce(ms[i]->d_status, ms[i]->d_status, 1, ncclInt32, ncclMax, ms[i]->comm, ms[i]->stream);
+        r = ncclAllReduce(word(i), word(i), 1, ncclInt32, ncclMax, ms[i]->group.comm, ms[i]->stream);
     if (r == ncclSuccess) r = ncclGroupEnd();
     for (size_t i = 0; i < ms.size() && r == ncclSuccess; ++i) {
         if (hipSetDevice(ms[i]->device) != hipSuccess || hipStreamSynchronize(ms[i]->stream) != hipSuccess ||
-            hipMemcpy(&got[i], ms[i]->d_status, sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
+            hipMemcpy(&got[i], word(i), sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
             if (!rc) rc = set_error(RT_ERR_HIP, "status exchange: read back");
     }
     if (r != ncclSuccess) return set_error(RT_ERR_COMM, std::string("status exchange: ") + ncclGetErrorString(r));
@@ -329,7 +310,7 @@ int group_scene_upload(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns
     }
     int root_rc = RT_OK;
     std::string root_err;
-    if (ctx->rank == 0) {  // only rank 0's tables are used (rtc.h)
+    if (ctx->group.rank == 0) {  // only rank 0's tables are used (rtc.h)
         // a failure here still takes part in the header broadcast, so the
         // other ranks return it instead of waiting in the table broadcast
         root_rc = validate_scene(shapes, ns, mats, nm, pats, np, lights, nl);
@@ -349,34 +330,8 @@ int group_scene_upload(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns
         root_h.bright_w = ctx->bright_w;
     }
     // 1. the header
-    std::vector<SceneHeader*> d_hdr(ms.size(), nullptr);
-    std::vector<SceneHeader> hdr(ms.size(), root_h);
-    for (size_t i = 0; i < ms.size(); ++i) {
-        RT_HIP(hipSetDevice(ms[i]->device));
-        RT_HIP(hipMalloc(reinterpret_cast<void**>(&d_hdr[i]), sizeof(SceneHeader)));
-        if (ms[i]->rank == 0) RT_HIP(hipMemcpy(d_hdr[i], &root_h, sizeof(SceneHeader), hipMemcpyHostToDevice));
-    }
-    auto free_hdr = [&]() {
-        for (size_t i = 0; i < ms.size(); ++i) {
-            (void)hipSetDevice(ms[i]->device);
-            (void)hipFree(d_hdr[i]);
-        }
-    };
-    auto bcast_header = [&]() -> int {
-        RT_NCCL(ncclGroupStart());
-        for (size_t i = 0; i < ms.size(); ++i)
-            RT_NCCL(ncclBroadcast(d_hdr[i], d_hdr[i], sizeof(SceneHeader), ncclUint8, 0, ms[i]->comm, ms[i]->stream));
-        RT_NCCL(ncclGroupEnd());
-        for (size_t i = 0; i < ms.size(); ++i) {
-            RT_HIP(hipSetDevice(ms[i]->device));
-            RT_HIP(hipStreamSynchronize(ms[i]->stream));
-            RT_HIP(hipMemcpy(&hdr[i], d_hdr[i], sizeof(SceneHeader), hipMemcpyDeviceToHost));
-        }
-        return RT_OK;
-    };
-    rc = bcast_header();
-    free_hdr();
-    if (rc) return rc;
+    std::vector<SceneHeader> hdr;
+    if ((rc = broadcast_value(ms, root_h, hdr))) return rc;
     if (root_rc) return set_error(root_rc, root_err);
     for (const SceneHeader& h : hdr)
         if (h.status) return set_error(h.status, "rt_scene_upload failed on rank 0");
@@ -385,36 +340,37 @@ int group_scene_upload(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns
     // rank first allocates its copies, then the ranks agree on the outcome
     // (one all-reduce of a status word): a rank whose allocation failed still
     // takes part, so no other rank is left waiting in the table broadcast.
-    std::vector<std::vector<std::pair<void*, size_t>>> bufs(ms.size());
     int local_rc = RT_OK;
     std::string local_err;
     for (size_t i = 0; i < ms.size() && !local_rc; ++i) {
         rt_context* m = ms[i];
         if (hipSetDevice(m->device) != hipSuccess) local_rc = set_error(RT_ERR_HIP, "hipSetDevice");
-        else if (m->rank != 0) {
-            if ((local_rc = alloc_world(m->w32, hdr[i])) == RT_OK) local_rc = alloc_world(m->w64, hdr[i]);
+        else if (m->group.rank != 0) {
+            const SceneHeader& h = hdr[i];
+            if ((local_rc = m->w32.allocate(h.ns, h.nm, h.np, h.nl)) == RT_OK)
+                local_rc = m->w64.allocate(h.ns, h.nm, h.np, h.nl);
         }
         if (local_rc) local_err = rt_last_error();
     }
     if ((rc = agree_status(ms, local_rc))) return rc;
     if (local_rc) return set_error(local_rc, local_err);
-    for (size_t i = 0; i < ms.size(); ++i) {
-        world_buffers(ms[i]->w32, hdr[i], bufs[i]);
-        world_buffers(ms[i]->w64, hdr[i], bufs[i]);
-    }
     RT_NCCL(ncclGroupStart());
-    for (size_t i = 0; i < ms.size(); ++i)
-        for (auto& b : bufs[i])
-            if (b.second) RT_NCCL(ncclBroadcast(b.first, b.first, b.second, ncclUint8, 0, ms[i]->comm, ms[i]->stream));
+    for (size_t i = 0; i < ms.size(); ++i) {
+        std::vector<std::pair<void*, size_t>> bufs;
+        world_buffers(ms[i]->w32, hdr[i], bufs);
+        world_buffers(ms[i]->w64, hdr[i], bufs);
+        for (auto& b : bufs)
+            if (b.second) RT_NCCL(ncclBroadcast(b.first, b.first, b.second, ncclUint8, 0, ms[i]->group.comm, ms[i]->stream));
+    }
     RT_NCCL(ncclGroupEnd());
     for (size_t i = 0; i < ms.size(); ++i) {
         rt_context* m = ms[i];
         RT_HIP(hipSetDevice(m->device));
         RT_HIP(hipStreamSynchronize(m->stream));
-        if (m->rank == 0) continue;
+        if (m->group.rank == 0) continue;
         const SceneHeader& h = hdr[i];
-        describe_world(m->w32, h);
-        describe_world(m->w64, h);
+        for (int k = 0; k <= kNumKinds; ++k) m->w32.scene.kind_begin[k] = m->w64.scene.kind_begin[k] = h.kind_begin[k];
+        m->w32.scene.any_secondary = m->w64.scene.any_secondary = h.any_secondary;
         m->world_slot.assign(h.ns, 0);
         if (h.ns)
             RT_HIP(hipMemcpy(m->world_slot.data(), m->w32.world_slot, h.ns * sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -442,7 +398,7 @@ int group_render(rt_context* ctx, const rt_camera_desc* cam, const rt_render_opt
                  rt_stats* stats) {
     int rc = check_group_options(ctx, o);
     if (rc) return rc;
-    if (ctx->rank == 0 && !out_host) return set_error(RT_ERR_INVALID, "null output on rank 0");
+    if (ctx->group.rank == 0 && !out_host) return set_error(RT_ERR_INVALID, "null output on rank 0");
     const std::vector<rt_context*> ms = members(ctx);
     const size_t bytes = (size_t)cam->width * cam->height * pixel_bytes(o);
     if (bytes == 0) {
@@ -454,12 +410,13 @@ int group_render(rt_context* ctx, const rt_camera_desc* cam, const rt_render_opt
         RT_HIP(hipSetDevice(ms[i]->device));
         if ((rc = read_counters(ms[i], before[i].data()))) return rc;
     }
-    if (ctx->rank == 0) {
+    if (ctx->group.rank == 0) {
         RT_HIP(hipSetDevice(ctx->device));
-        if ((rc = ensure_scratch(ctx, bytes))) return rc;
+        if ((rc = ctx->d_scratch.reserve(bytes))) return rc;
     }
-    if ((rc = render_shards(ctx, cam, o, ctx->rank == 0 ? ctx->d_scratch : nullptr, ctx->stream, true))) return rc;
-    if (ctx->rank == 0) {  // enqueued behind the de-interleave on rank 0's stream
+    void* image = ctx->group.rank == 0 ? ctx->d_scratch.get() : nullptr;
+    if ((rc = render_shards(ctx, cam, o, image, ctx->stream, true))) return rc;
+    if (ctx->group.rank == 0) {  // enqueued behind the de-interleave on rank 0's stream
         RT_HIP(hipSetDevice(ctx->device));
         if ((rc = copy_to_host(ctx, out_host, bytes))) return rc;
     }
@@ -476,30 +433,22 @@ int group_render(rt_context* ctx, const rt_camera_desc* cam, const rt_render_opt
         unsigned long long after[kNumCounters];
         if ((rc = read_counters(m, after))) return rc;
         float r = 0.f;
-        RT_HIP(hipEventElapsedTime(&r, m->ev_render0, m->ev_render1));
+        RT_HIP(hipEventElapsedTime(&r, m->group.ev_render0, m->group.ev_render1));
         render_ms = std::max(render_ms, r);
-        if (m->rank == 0) {
-            RT_HIP(hipEventElapsedTime(&gather_ms, m->ev_render1, m->ev_gather1));
-            RT_HIP(hipEventElapsedTime(&frame_ms, m->ev_render0, m->ev_gather1));
+        if (m->group.rank == 0) {
+            RT_HIP(hipEventElapsedTime(&gather_ms, m->group.ev_render1, m->group.ev_gather1));
+            RT_HIP(hipEventElapsedTime(&frame_ms, m->group.ev_render0, m->group.ev_gather1));
         }
         rt_stats s{};
         fill_stats(m, before[i].data(), after, r, &s);
-        total.primary += s.primary;
-        total.shadow += s.shadow;
-        total.reflect += s.reflect;
-        total.refract += s.refract;
-        total.shaded += s.shaded;
-        total.lit_patterned += s.lit_patterned;
-        total.refract_evals += s.refract_evals;
-        total.schlick_evals += s.schlick_evals;
-        total.algorithmic_flops += s.algorithmic_flops;
+        add_rays(total, s);
     }
     if (stats) {
         *stats = total;
         stats->kernel_ms = render_ms;
         stats->gather_ms = gather_ms;
         stats->frame_ms = frame_ms;
-        stats->n_shards = (uint32_t)ctx->n_ranks;
+        stats->n_shards = (uint32_t)ctx->group.n_ranks;
     }
     return RT_OK;
 }
@@ -514,18 +463,10 @@ int group_read_counters(rt_context* ctx, rt_stats* totals) {
         if ((rc = read_counters(m, now))) return rc;
         rt_stats s{};
         fill_stats(m, zero, now, 0.f, &s);
-        t.primary += s.primary;
-        t.shadow += s.shadow;
-        t.reflect += s.reflect;
-        t.refract += s.refract;
-        t.shaded += s.shaded;
-        t.lit_patterned += s.lit_patterned;
-        t.refract_evals += s.refract_evals;
-        t.schlick_evals += s.schlick_evals;
-        t.algorithmic_flops += s.algorithmic_flops;
+        add_rays(t, s);
         if ((rc = check_pool_error(m))) return rc;
     }
-    t.n_shards = (uint32_t)ctx->n_ranks;
+    t.n_shards = (uint32_t)ctx->group.n_ranks;
     *totals = t;
     return RT_OK;
 }
@@ -547,27 +488,20 @@ int rt_context_create_multi(const int* devices, int n, rt_context** out) {
         for (int j = 0; j < i; ++j)
             if (devices[j] == devices[i]) return set_error(RT_ERR_INVALID, "a device appears twice");
     }
-    std::vector<rt_context*> ms(n, nullptr);
-    auto cleanup = [&]() {
-        for (rt_context* m : ms) destroy_device_context(m);
-    };
-    for (int i = 0; i < n; ++i)
-        if (int rc = create_device_context(devices[i], &ms[i])) {
-            cleanup();
-            return rc;
-        }
-    std::vector<ncclComm_t> comms(n, nullptr);
-    if (ncclResult_t r = ncclCommInitAll(comms.data(), n, devices); r != ncclSuccess) {
-        cleanup();
-        return set_error(RT_ERR_COMM, std::string("ncclCommInitAll: ") + ncclGetErrorString(r));
+    std::vector<std::unique_ptr<rt_context>> ms(n);
+    for (int i = 0; i < n; ++i) {
+        rt_context* m = nullptr;
+        if (int rc = create_device_context(devices[i], &m)) return rc;
+        ms[i].reset(m);
     }
+    std::vector<ncclComm_t> comms(n, nullptr);
+    if (ncclResult_t r = ncclCommInitAll(comms.data(), n, devices); r != ncclSuccess)
+        return set_error(RT_ERR_COMM, std::string("ncclCommInitAll: ") + ncclGetErrorString(r));
+    for (int i = 0; i < n; ++i) ms[i]->group.comm = comms[i];  // owned before any step can fail
     for (int i = 0; i < n; ++i)
-        if (int rc = init_member(ms[i], comms[i], n, i)) {
-            cleanup();
-            return rc;
-        }
-    ms[0]->peers.assign(ms.begin() + 1, ms.end());
-    *out = ms[0];
+        if (int rc = init_member(ms[i].get(), comms[i], n, i)) return rc;
+    for (int i = 1; i < n; ++i) ms[0]->group.peers.push_back(ms[i].release());
+    *out = ms[0].release();
     return RT_OK;
 }
 
@@ -586,35 +520,31 @@ int rt_context_create_rank(int device, int n_ranks, int rank, const uint8_t id[R
     if (!id || !out || n_ranks < 1 || rank < 0 || rank >= n_ranks)
         return set_error(RT_ERR_INVALID, "rt_context_create_rank: bad arguments");
     *out = nullptr;
-    rt_context* m = nullptr;
-    if (int rc = create_device_context(device, &m)) return rc;
+    rt_context* created = nullptr;
+    if (int rc = create_device_context(device, &created)) return rc;
+    std::unique_ptr<rt_context> m(created);
     ncclUniqueId u;
     std::memcpy(&u, id, sizeof(u));
     ncclComm_t comm = nullptr;
     (void)hipSetDevice(device);
-    if (ncclResult_t r = ncclCommInitRank(&comm, n_ranks, u, rank); r != ncclSuccess) {
-        destroy_device_context(m);
+    if (ncclResult_t r = ncclCommInitRank(&comm, n_ranks, u, rank); r != ncclSuccess)
         return set_error(RT_ERR_COMM, std::string("ncclCommInitRank: ") + ncclGetErrorString(r));
-    }
-    if (int rc = init_member(m, comm, n_ranks, rank)) {
-        destroy_device_context(m);
-        return rc;
-    }
-    *out = m;
+    if (int rc = init_member(m.get(), comm, n_ranks, rank)) return rc;
+    *out = m.release();
     return RT_OK;
 }
 
 int rt_context_set_gather(rt_context* ctx, int mode) {
     if (!ctx || (mode != RT_GATHER_RCCL && mode != RT_GATHER_PEER)) return set_error(RT_ERR_INVALID, "bad arguments");
-    for (rt_context* m : members(ctx)) m->gather_mode = mode;
+    for (rt_context* m : members(ctx)) m->group.gather_mode = mode;
     return RT_OK;
 }
 
 int rt_context_group(rt_context* ctx, int* n_ranks, int* rank, int* local_devices) {
     if (!ctx) return set_error(RT_ERR_INVALID, "null context");
-    if (n_ranks) *n_ranks = ctx->n_ranks;
-    if (rank) *rank = ctx->rank;
-    if (local_devices) *local_devices = 1 + (int)ctx->peers.size();
+    if (n_ranks) *n_ranks = ctx->group.n_ranks;
+    if (rank) *rank = ctx->group.rank;
+    if (local_devices) *local_devices = 1 + (int)ctx->group.peers.size();
     return RT_OK;
 }
 

@@ -49,8 +49,6 @@ hipError_t launch_order_tiles(uint32_t* cost, uint32_t* order, uint32_t n, uint3
 template <typename R>
 hipError_t launch_debug_shape(const ShapeRec<R>* shapes, int slot, int kind, uint32_t mode, uint32_t world_space,
                               const double* in, uint32_t n, double* out, hipStream_t stream);
-hipError_t launch_assemble(const void* gathered, void* image, uint32_t width, uint32_t height, uint32_t shards,
-                           uint32_t strip_rows, uint32_t bpp, hipStream_t stream);
 
 namespace {
 thread_local std::string g_error;
@@ -60,29 +58,6 @@ int set_error(int code, const std::string& msg) {
     g_error = msg;
     return code;
 }
-
-
-}  // namespace rtc
-
-namespace rtc {
-namespace {
-
-// Copies run on the context's stream, never the null stream: HIP creates a
-// hardware queue for the null stream at its first use, ~8 ms that a one-shot
-// render would pay.  The caller synchronizes the stream before
-// the host vector goes away.
-template <typename T>
-int upload(T** dst, const std::vector<T>& v, hipStream_t s) {
-    if (v.empty()) {
-        *dst = nullptr;
-        return RT_OK;
-    }
-    RT_HIP(hipMalloc(reinterpret_cast<void**>(dst), v.size() * sizeof(T)));
-    RT_HIP(hipMemcpyAsync(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s));
-    return RT_OK;
-}
-
-}  // namespace
 
 // World-space bounding sphere of a shape's intersection set, for the
 // kernels' wave-level cull (wave_may_hit).  Acceleration only: a shape is
@@ -223,7 +198,6 @@ template <typename R>
 int build_world(rt_context* ctx, DeviceWorld<R>& w, const rt_shape_desc* shapes, uint32_t ns,
                 const rt_material_desc* mats, uint32_t nm, const rt_pattern_desc* pats, uint32_t np,
                 const rt_light_desc* lights, uint32_t nl, const std::vector<uint32_t>& cls) {
-    w.release();
     std::vector<ShapeRec<R>> sh;
     std::vector<int32_t> begin(kNumKinds + 1, 0);
     const std::vector<uint32_t> order = table_order(shapes, ns, cls);
@@ -241,7 +215,7 @@ int build_world(rt_context* ctx, DeviceWorld<R>& w, const rt_shape_desc* shapes,
             // the device keeps r^2; unbounded is +inf for spheres and cubes
             // (their test has no branch), -1 for the other kinds (wave_may_hit)
             const bool branchless = d.kind == RT_SHAPE_SPHERE || d.kind == RT_SHAPE_CUBE;
-            r.bound[3] = ctx->cull && bs[3] >= 0.0 ? (R)(bs[3] * bs[3])
+            r.bound[3] = ctx->knobs.cull && bs[3] >= 0.0 ? (R)(bs[3] * bs[3])
                                                    : (branchless ? std::numeric_limits<R>::infinity() : (R)-1);
             r.ymin = (R)d.minimum;
             r.ymax = (R)d.maximum;
@@ -329,30 +303,25 @@ int build_world(rt_context* ctx, DeviceWorld<R>& w, const rt_shape_desc* shapes,
     put(mt.data(), mt.size() * sizeof(MaterialRec<R>));
     put(pt.data(), pt.size() * sizeof(PatternRec<R>));
     put(ws.data(), ws.size() * sizeof(int32_t));
-    RT_HIP(hipMalloc(&w.image, std::max<size_t>(image_bytes, 16)));  // (an empty world still gets a buffer)
-    if (image_bytes) RT_HIP(hipMemcpyAsync(w.image, img.data(), image_bytes, hipMemcpyHostToDevice, ctx->stream));
-    w.carve(sh.size(), nm, np);
-    if ((rc = upload(&w.lights, lt, ctx->stream))) {
+    // Copies run on the context's stream, never the null stream: HIP creates a
+    // hardware queue for the null stream at its first use, ~8 ms that a one-shot
+    // render would pay.
+    if ((rc = w.allocate(sh.size(), nm, np, nl))) return rc;
+    if (image_bytes) RT_HIP(hipMemcpyAsync(w.image.get(), img.data(), image_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (nl && (rc = hip_status(hipMemcpyAsync(w.lights.get(), lt.data(), nl * sizeof(LightRec<R>),
+                                              hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync"))) {
         (void)hipStreamSynchronize(ctx->stream);  // the image copy may still read `img`
         return rc;
     }
     RT_HIP(hipStreamSynchronize(ctx->stream));  // (img and lt are host temporaries)
     if constexpr (sizeof(R) == 4) {  // the per-scene build's tables (capture_jit_table), from the host copies
-        ctx->jit_shapes = sh;
-        ctx->jit_lights = lt;
-        ctx->jit_materials = mt;
-        ctx->jit_pattern_recs = pt;
+        ctx->jit.shapes = sh;
+        ctx->jit.lights = lt;
+        ctx->jit.materials = mt;
+        ctx->jit.pattern_recs = pt;
     }
     ctx->world_slot.assign(ws.begin(), ws.begin() + ns);
-    w.scene.shapes = w.shapes;
-    w.scene.materials = w.materials;
-    w.scene.patterns = w.patterns;
-    w.scene.lights = w.lights;
-    w.scene.world_slot = w.world_slot;
     for (int k = 0; k <= kNumKinds; ++k) w.scene.kind_begin[k] = begin[k];
-    w.scene.n_materials = (int32_t)nm;
-    w.scene.n_patterns = (int32_t)np;
-    w.scene.n_lights = (int32_t)nl;
     w.scene.any_secondary = any_secondary ? 1 : 0;
     return RT_OK;
 }
@@ -454,9 +423,16 @@ struct LaunchShape {
     uint32_t grid_tiles;        // the launch's tiles (the grid's upper bound)
 };
 
+// Workgroups per CU at `lds` dynamic bytes: the occupancy API's register/wave
+// limit `api`, capped by the LDS limit from static + dynamic bytes (512-byte
+// granules).
+int cap_by_lds(int api, size_t lds) {
+    const size_t per_block = (kStaticLds + lds + 511) / 512 * 512;
+    return std::min(api, (int)(kLdsPerCu / per_block));
+}
+
 // Cached occupancy (workgroups per CU) of one kernel instantiation at a
-// given dynamic LDS size: the occupancy API's register/wave limit, and the
-// LDS limit computed here from static + dynamic bytes (512-byte granules).
+// given dynamic LDS size (cap_by_lds).
 template <typename R>
 int blocks_per_cu(rt_context* ctx, bool pool, bool lds_world, size_t lds, int* per_cu) {
     const int key = (pool ? 1 : 0) + (sizeof(R) == 8 ? 2 : 0) + (lds_world ? 4 : 0);
@@ -466,9 +442,7 @@ int blocks_per_cu(rt_context* ctx, bool pool, bool lds_world, size_t lds, int* p
     }
     int api = 0;
     RT_HIP(occupancy<R>(pool, lds_world, lds, &api));
-    const size_t per_block = (kStaticLds + lds + 511) / 512 * 512;
-    const int by_lds = per_block ? (int)((size_t)kLdsPerCu / per_block) : api;
-    *per_cu = std::min(api, by_lds);
+    *per_cu = cap_by_lds(api, lds);
     ctx->occ_lds[key] = lds;
     ctx->occ_blocks[key] = *per_cu;
     return RT_OK;
@@ -507,8 +481,8 @@ int pool_lds_plan(rt_context* ctx, uint32_t world_lds, uint32_t cap, Occ&& occ, 
 // RTC_DEBUG=pool_lds_rays=N overrides (A/B).
 template <typename R>
 int pool_lds_rays(rt_context* ctx, uint32_t world_lds, uint32_t cap, uint32_t* lcap) {
-    if (ctx->pool_lds_rays > 0) {
-        *lcap = std::min<uint32_t>(cap, std::max<uint32_t>(kBlock, ctx->pool_lds_rays & ~7u));
+    if (ctx->knobs.pool_lds_rays > 0) {
+        *lcap = std::min<uint32_t>(cap, std::max<uint32_t>(kBlock, ctx->knobs.pool_lds_rays & ~7u));
         return RT_OK;
     }
     const bool lw = world_lds != 0;
@@ -538,8 +512,7 @@ int plan_pool_for(rt_context* ctx, hipFunction_t fn, LaunchShape& ls) {
     auto blocks = [&](size_t lds, int* per_cu) -> int {  // (blocks_per_cu's rule, for this function)
         int api = 0;
         RT_HIP(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&api, fn, kBlock, lds));
-        const size_t per_block = (kStaticLds + lds + 511) / 512 * 512;
-        *per_cu = std::min(api, (int)((size_t)kLdsPerCu / per_block));
+        *per_cu = cap_by_lds(api, lds);
         return RT_OK;
     };
     uint32_t n = 0;
@@ -563,10 +536,10 @@ int plan_launch(rt_context* ctx, const DevScene<R>& sc, uint32_t depth, uint32_t
                                   : world_lds_bytes<R>(sc.kind_begin[kNumKinds], sc.n_materials, sc.n_patterns);
     // (a per-scene direct kernel takes its materials from constants too and
     // stages no world at all: rtc_kernels.hip kJitConstMaterials)
-    ls.world_lds = (ctx->lds_world && wb <= kMaxWorldLds && !(jit_records && !ls.pool)) ? (uint32_t)wb : 0;
+    ls.world_lds = (ctx->knobs.lds_world && wb <= kMaxWorldLds && !(jit_records && !ls.pool)) ? (uint32_t)wb : 0;
     ls.lds = ls.world_lds;
     ls.cap = ls.lcap = ls.batch = 0;
-    ls.sched = ls.pool ? kSchedDynamic : ctx->sched_direct;
+    ls.sched = ls.pool ? kSchedDynamic : ctx->knobs.sched_direct;
     int rc;
     if (ls.pool) {
         // (the pool kernel takes its items from the per-XCD queues only)
@@ -588,7 +561,7 @@ int plan_launch(rt_context* ctx, const DevScene<R>& sc, uint32_t depth, uint32_t
     // 8160 (one tile each) 34.1 / 39.8; three_sphere 4K 115.6 -> 107.0 us.
     // The f64 kernel (3 waves/SIMD) measured 3.7% slower that way.
     const bool oversub = !ls.pool && ls.sched == kSchedStatic && sizeof(R) == 4;
-    const uint64_t grid_cap = oversub ? std::max<uint64_t>(1, resident * ctx->direct_oversub10 / 10) : resident;
+    const uint64_t grid_cap = oversub ? std::max<uint64_t>(1, resident * ctx->knobs.direct_oversub10 / 10) : resident;
     ls.grid = ls.sched != kSchedGrid ? (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_tiles, grid_cap)) : n_tiles;
     ls.grid_tiles = n_tiles;
     return RT_OK;
@@ -623,41 +596,36 @@ int plan_tile_order(rt_context* ctx, LaunchParams<R>& P, const rt_camera_desc* c
     mix(fields, sizeof(fields));
     const uint64_t geometry = h;
     if (cam) mix(cam, sizeof(*cam));
-    if (ctx->order_capacity < P.n_tiles) {
-        (void)hipFree(ctx->d_tile_cost);
-        (void)hipFree(ctx->d_tile_order);
-        ctx->d_tile_cost = ctx->d_tile_order = nullptr;
-        ctx->order_capacity = 0;
-        ctx->order_valid = ctx->order_built = false;
-        RT_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->d_tile_cost), P.n_tiles * sizeof(uint32_t)));
-        // (the kernel records a tile's cost as the maximum over its parts)
-        RT_HIP(hipMemsetAsync(ctx->d_tile_cost, 0, P.n_tiles * sizeof(uint32_t), stream));
-        // up to 2^kMaxSplitLog2 items per tile, then the item count
-        RT_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->d_tile_order),
-                         (((size_t)P.n_tiles << kMaxSplitLog2) + 1) * sizeof(uint32_t)));
-        ctx->order_capacity = P.n_tiles;
-    }
-    const bool same = ctx->order_valid && ctx->order_sig == h;
-    const bool moved = !same && ctx->order_valid && ctx->order_geometry == geometry;
-    if (!same) ctx->order_builds = 0;
-    if (!ctx->order_valid || ctx->order_geometry != geometry) ctx->order_built = false;
-    uint32_t* n_items = ctx->d_tile_order + ((size_t)ctx->order_capacity << kMaxSplitLog2);
-    if ((same || moved) && ctx->order_builds < kOrderBuilds) {
-        const float split = ctx->split_factor > 0 ? (float)(ctx->split_factor / grid) : 0.0f;
-        const float urgent = ctx->urgent_factor > 0 ? (float)(ctx->urgent_factor / grid) : 0.0f;
-        RT_HIP(launch_order_tiles(ctx->d_tile_cost, ctx->d_tile_order, P.n_tiles, n_items, split, ctx->split_max,
+    rt_context::TileOrder& to = ctx->order;
+    bool grew_cost = false, grew_order = false;
+    int rc = to.d_cost.reserve(P.n_tiles, &grew_cost);
+    // up to 2^kMaxSplitLog2 items per tile, then the item count
+    if (!rc) rc = to.d_order.reserve(((size_t)P.n_tiles << kMaxSplitLog2) + 1, &grew_order);
+    if (rc || grew_cost || grew_order) to.valid = to.built = false;
+    if (rc) return rc;
+    if (grew_cost || grew_order)  // (the kernel records a tile's cost as the maximum over its parts)
+        RT_HIP(hipMemsetAsync(to.d_cost.get(), 0, to.d_cost.capacity() * sizeof(uint32_t), stream));
+    const bool same = to.valid && to.sig == h;
+    const bool moved = !same && to.valid && to.geometry == geometry;
+    if (!same) to.builds = 0;
+    if (!to.valid || to.geometry != geometry) to.built = false;
+    uint32_t* n_items = to.d_order.get() + to.d_order.capacity() - 1;
+    if ((same || moved) && to.builds < kOrderBuilds) {
+        const float split = ctx->knobs.split_factor > 0 ? (float)(ctx->knobs.split_factor / grid) : 0.0f;
+        const float urgent = ctx->knobs.urgent_factor > 0 ? (float)(ctx->knobs.urgent_factor / grid) : 0.0f;
+        RT_HIP(launch_order_tiles(to.d_cost.get(), to.d_order.get(), P.n_tiles, n_items, split, ctx->knobs.split_max,
                                   urgent, 1u, 0u, stream));
-        ++ctx->order_builds;
-        ctx->order_built = true;
+        ++to.builds;
+        to.built = true;
     }
-    if (ctx->order_built) {  // built from this frame's costs, or from the previous camera's frame
-        P.tile_order = ctx->d_tile_order;
+    if (to.built) {  // built from this frame's costs, or from the previous camera's frame
+        P.tile_order = to.d_order.get();
         P.item_count = n_items;
     } else if (P.shard_count == 1) {
         // No costs yet: tiles nearest the image centre first.  The order
         // depends on the canvas only, so it is built and uploaded once per
-        // canvas size into its own buffer (order_tiles reuses d_tile_order).
-        if (!ctx->d_cold_order || ctx->cold_w != P.width || ctx->cold_h != P.height) {
+        // canvas size into its own buffer (order_tiles reuses d_order).
+        if (!to.d_cold.get() || to.cold_w != P.width || to.cold_h != P.height) {
             const uint32_t n = P.n_tiles, tx = P.tiles_x;
             std::vector<std::pair<uint64_t, uint32_t>> key(n);
             const int64_t cx = (int64_t)P.width, cy = (int64_t)P.height;  // doubled centre
@@ -670,23 +638,22 @@ int plan_tile_order(rt_context* ctx, LaunchParams<R>& P, const rt_camera_desc* c
             std::vector<uint32_t> v(n + 1);
             for (uint32_t i = 0; i < n; ++i) v[i] = key[i].second;
             v[n] = n;
-            (void)hipFree(ctx->d_cold_order);
-            ctx->d_cold_order = nullptr;
-            RT_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->d_cold_order), v.size() * sizeof(uint32_t)));
+            to.cold_w = to.cold_h = 0;  // (nothing valid until the copy below is done)
+            if ((rc = to.d_cold.reserve(v.size()))) return rc;
             // (the launch's stream, not the null stream; v is a host temporary)
-            RT_HIP(hipMemcpyAsync(ctx->d_cold_order, v.data(), v.size() * sizeof(uint32_t), hipMemcpyHostToDevice,
+            RT_HIP(hipMemcpyAsync(to.d_cold.get(), v.data(), v.size() * sizeof(uint32_t), hipMemcpyHostToDevice,
                                   stream));
             RT_HIP(hipStreamSynchronize(stream));
-            ctx->cold_w = P.width;
-            ctx->cold_h = P.height;
+            to.cold_w = P.width;
+            to.cold_h = P.height;
         }
-        P.tile_order = ctx->d_cold_order;
-        P.item_count = ctx->d_cold_order + P.n_tiles;
+        P.tile_order = to.d_cold.get();
+        P.item_count = to.d_cold.get() + P.n_tiles;
     }
-    P.tile_cost = ctx->d_tile_cost;
-    ctx->order_sig = h;
-    ctx->order_geometry = geometry;
-    ctx->order_valid = true;
+    P.tile_cost = to.d_cost.get();
+    to.sig = h;
+    to.geometry = geometry;
+    to.valid = true;
     return RT_OK;
 }
 
@@ -700,13 +667,27 @@ int order_after_last(rt_context* ctx, hipStream_t stream) {
     return RT_OK;
 }
 
+// One tracer launch: a frame or shard strip of `cam` (launch_frame), or a batch of rays (rt_color_at).
+struct LaunchRequest {
+    const rt_camera_desc* cam = nullptr;  // a frame, or ...
+    const double* d_rays = nullptr;       // ... n_rays rays of 6 doubles on the device
+    uint64_t n_rays = 0;
+    uint32_t depth = 0, out_format = RT_OUT_REAL;
+    uint32_t shard_index = 0, shard_count = 1;
+    void* out_device = nullptr;
+    hipStream_t stream = nullptr;
+    uint32_t flags = 0;
+    bool image_rows = false;
+};
+
 template <typename R>
-int launch(rt_context* ctx, DeviceWorld<R>& w, const rt_camera_desc* cam, const double* d_rays, uint64_t n_rays,
-           uint32_t depth, uint32_t out_format, uint32_t shard_index, uint32_t shard_count, void* out_device,
-           hipStream_t stream, uint32_t flags = 0, bool image_rows = false) {
+int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
+    const rt_camera_desc* cam = q.cam;
+    const uint32_t depth = q.depth, flags = q.flags, shard_index = q.shard_index, shard_count = q.shard_count;
+    hipStream_t stream = q.stream;
     int rc;
     LaunchParams<R> P{};
-    P.image_rows = image_rows ? 1u : 0u;
+    P.image_rows = q.image_rows ? 1u : 0u;
     P.scene = w.scene;
     if (cam) {
         for (int q = 0; q < 12; ++q) P.cam.inv[q] = (R)cam->inverse[q];
@@ -721,19 +702,19 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const rt_camera_desc* cam, const 
         P.n_tiles = P.tiles_x * P.tile_rows;
         P.tiles_x_magic = div_magic(P.tiles_x, P.n_tiles);
     } else {
-        P.rays = d_rays;
-        P.n_rays = n_rays;
-        P.n_tiles = (uint32_t)((n_rays + kBlock - 1) / kBlock);
+        P.rays = q.d_rays;
+        P.n_rays = q.n_rays;
+        P.n_tiles = (uint32_t)((q.n_rays + kBlock - 1) / kBlock);
     }
-    P.out = out_device;
-    P.out_format = out_format;
+    P.out = q.out_device;
+    P.out_format = q.out_format;
     P.shard_index = shard_index;
     P.shard_count = shard_count;
     P.max_depth = depth;
-    P.tile_counter = ctx->d_tile_counter;
-    P.counters = ctx->d_counters;
-    P.error_flag = ctx->d_error;
-    if (flags & RT_FLAG_GENERATIONS) P.gen_counts = ctx->d_gen_counts;
+    P.tile_counter = ctx->d_tile_counter.get();
+    P.counters = ctx->d_counters.get();
+    P.error_flag = ctx->d_error.get();
+    if (flags & RT_FLAG_GENERATIONS) P.gen_counts = ctx->d_gen_counts.get();
     if (P.n_tiles == 0) return RT_OK;
     if ((rc = order_after_last(ctx, stream))) return rc;
     LaunchShape ls;
@@ -753,11 +734,11 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const rt_camera_desc* cam, const 
         const uint32_t generic_only =
             RT_FLAG_NO_SHADE | RT_FLAG_NO_TRACE | RT_FLAG_GENERATIONS | (ls.pool ? 0u : RT_FLAG_STAMPS);
         const bool want = cam && !dup && !(flags & generic_only) &&
-                          (ctx->jit_mode == RT_JIT_SYNC || (ctx->jit_mode >= RT_JIT_AUTO && P.n_tiles >= kJitMinTiles));
+                          (ctx->jit.mode == RT_JIT_SYNC || (ctx->jit.mode >= RT_JIT_AUTO && P.n_tiles >= kJitMinTiles));
         if (want) {
-            ++ctx->jit_frames;
+            ++ctx->jit.frames;
             LaunchShape lj = ls;
-            if (ctx->lds_world && !ls.pool && w.scene.kind_begin[kNumKinds] <= kJitRecordsMaxShapes &&
+            if (ctx->knobs.lds_world && !ls.pool && w.scene.kind_begin[kNumKinds] <= kJitRecordsMaxShapes &&
                 (rc = plan_launch<R>(ctx, w.scene, depth, P.n_tiles, lj, true)))
                 return rc;
             int waves = 0;
@@ -768,23 +749,17 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const rt_camera_desc* cam, const 
             if (jf) ls = lj;
         }
     }
-    ctx->jit_used = jf != nullptr;
+    ctx->jit.used = jf != nullptr;
     P.pool_capacity = ls.cap;
     P.pool_lds_capacity = ls.lcap;
     P.pop_batch = ls.batch;
     if (ls.pool && (rc = check_pixel_range(ctx, depth, sizeof(R) == 4))) return rc;
     P.acc_log2 = acc_shift_f32(ctx->bright_hit, ctx->bright_w, depth);
     if (ls.cap > ls.lcap) {
-        const size_t need = (size_t)ls.grid * 8 * (ls.cap - ls.lcap) * sizeof(R);
-        if (ctx->spill_bytes < need) {
-            (void)hipFree(ctx->d_spill);
-            ctx->d_spill = nullptr;
-            ctx->spill_bytes = 0;
-            RT_HIP(hipMalloc(&ctx->d_spill, need));
-            ctx->spill_bytes = need;
-        }
-        P.spill = ctx->d_spill;
-        P.spill_blocks = (uint32_t)(ctx->spill_bytes / ((size_t)8 * (ls.cap - ls.lcap) * sizeof(R)));
+        const size_t per_block = (size_t)8 * (ls.cap - ls.lcap) * sizeof(R);
+        if ((rc = ctx->d_spill.reserve((size_t)ls.grid * per_block))) return rc;
+        P.spill = ctx->d_spill.get();
+        P.spill_blocks = (uint32_t)(ctx->d_spill.capacity() / per_block);  // (of a buffer an earlier launch may have sized)
     }
     P.persistent = ls.sched;
     P.flags = flags;
@@ -799,33 +774,21 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const rt_camera_desc* cam, const 
     const bool dynamic = ls.pool;
     if (dynamic) {
         const size_t set = (size_t)kTileQueues * kQueueStride;
-        P.tile_counter = ctx->d_tile_counter + (ctx->head_set ? set : 0);
-        P.next_tile_counter = ctx->d_tile_counter + (ctx->head_set ? 0 : set);
-        if (ls.pool && ctx->tile_order && cam) {  // frames only: a ray batch's content is not in the signature
+        P.tile_counter = ctx->d_tile_counter.get() + (ctx->head_set ? set : 0);
+        P.next_tile_counter = ctx->d_tile_counter.get() + (ctx->head_set ? 0 : set);
+        if (ls.pool && ctx->knobs.tile_order && cam) {  // frames only: a ray batch's content is not in the signature
             if ((rc = plan_tile_order<R>(ctx, P, cam, depth, ls.grid, stream))) return rc;
         }
     }
     if (flags & RT_FLAG_STAMPS) {
-        if (ctx->stamp_capacity < ls.grid) {
-            (void)hipFree(ctx->d_stamps);
-            ctx->d_stamps = nullptr;
-            ctx->stamp_capacity = 0;
-            RT_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->d_stamps), 2 * sizeof(unsigned long long) * ls.grid));
-            ctx->stamp_capacity = ls.grid;
-        }
-        P.stamps = ctx->d_stamps;
+        if ((rc = ctx->d_stamps.reserve((size_t)2 * ls.grid))) return rc;
+        P.stamps = ctx->d_stamps.get();
         ctx->stamp_count = ls.grid;
         if (ls.pool) {  // every item of the launch: up to 2^kMaxSplitLog2 per tile
             const size_t items = (size_t)P.n_tiles << kMaxSplitLog2;
-            if (ctx->item_log_capacity < items) {
-                (void)hipFree(ctx->d_item_log);
-                ctx->d_item_log = nullptr;
-                ctx->item_log_capacity = 0;
-                RT_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->d_item_log), (1 + 3 * items) * sizeof(uint64_t)));
-                ctx->item_log_capacity = items;
-            }
-            RT_HIP(hipMemsetAsync(ctx->d_item_log, 0, sizeof(uint64_t), stream));
-            P.item_log = ctx->d_item_log;
+            if ((rc = ctx->d_item_log.reserve(1 + 3 * items))) return rc;
+            RT_HIP(hipMemsetAsync(ctx->d_item_log.get(), 0, sizeof(uint64_t), stream));
+            P.item_log = ctx->d_item_log.get();
         }
     }
     // Worlds of spheres and planes only run the pool kernel built without the
@@ -837,7 +800,7 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const rt_camera_desc* cam, const 
     uint32_t kinds = 0;
     for (int k = 0; k < kNumKinds; ++k)
         if (w.scene.kind_begin[k + 1] > w.scene.kind_begin[k]) kinds |= 1u << k;
-    const bool sp = sizeof(R) == 4 && ls.pool && ctx->kind_variants && (kinds & ~kKindsSp) == 0 && !dup;
+    const bool sp = sizeof(R) == 4 && ls.pool && ctx->knobs.kind_variants && (kinds & ~kKindsSp) == 0 && !dup;
     if (flags & RT_FLAG_FAIL_LAUNCH) return set_error(RT_ERR_HIP, "launch refused (RT_FLAG_FAIL_LAUNCH)");
     if (jf) {
         const ShapeRec<R>* sh = P.scene.shapes;
@@ -847,12 +810,9 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const rt_camera_desc* cam, const 
         void* args[] = {&P, &sh, &mt, &pt, &lt};
         (void)hipGetLastError();
         RT_HIP(hipModuleLaunchKernel(jf, ls.grid, 1, 1, kBlock, 1, 1, (unsigned)ls.lds, stream, args, nullptr));
-        if (dynamic) ctx->head_set ^= 1;
-        return RT_OK;
-    }
-    if (hipError_t e = sp ? sp::launch_trace<R>(P, ls.pool, dup, ls.grid, ls.lds, stream)
-                          : launch_trace<R>(P, ls.pool, dup, ls.grid, ls.lds, stream);
-        e != hipSuccess)
+    } else if (hipError_t e = sp ? sp::launch_trace<R>(P, ls.pool, dup, ls.grid, ls.lds, stream)
+                                 : launch_trace<R>(P, ls.pool, dup, ls.grid, ls.lds, stream);
+               e != hipSuccess)
         return set_error(RT_ERR_HIP, std::string("launch of the ") + (ls.pool ? "pool" : "direct") + " kernel (grid " +
                                          std::to_string(ls.grid) + ", dynamic LDS " + std::to_string(ls.lds) +
                                          " B, pool " + std::to_string(ls.lcap) + "/" + std::to_string(ls.cap) +
@@ -888,23 +848,17 @@ int check_options(const rt_render_options* o) {
     return RT_OK;
 }
 
-int ensure_scratch(rt_context* ctx, size_t bytes) {
-    if (ctx->scratch_bytes >= bytes) return RT_OK;
-    if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
-    ctx->d_scratch = nullptr;
-    ctx->scratch_bytes = 0;
-    RT_HIP(hipMalloc(&ctx->d_scratch, bytes));
-    ctx->scratch_bytes = bytes;
-    return RT_OK;
+void sum_counter_shards(const unsigned long long* shards, unsigned long long out[kNumCounters]) {
+    for (int i = 0; i < kNumCounters; ++i) out[i] = 0;
+    for (int s = 0; s < kCounterShards; ++s)
+        for (int i = 0; i < kNumCounters; ++i) out[i] += shards[(size_t)s * kNumCounters + i];
 }
 
 int read_counters(rt_context* ctx, unsigned long long out[kNumCounters]) {
     std::vector<unsigned long long> shards((size_t)kCounterShards * kNumCounters);
-    RT_HIP(hipMemcpy(shards.data(), ctx->d_counters, shards.size() * sizeof(unsigned long long),
+    RT_HIP(hipMemcpy(shards.data(), ctx->d_counters.get(), shards.size() * sizeof(unsigned long long),
                      hipMemcpyDeviceToHost));
-    for (int i = 0; i < kNumCounters; ++i) out[i] = 0;
-    for (int s = 0; s < kCounterShards; ++s)
-        for (int i = 0; i < kNumCounters; ++i) out[i] += shards[(size_t)s * kNumCounters + i];
+    sum_counter_shards(shards.data(), out);
     return RT_OK;
 }
 
@@ -928,13 +882,6 @@ void fill_stats(rt_context* ctx, const unsigned long long before[kNumCounters],
     s->reserved = 0;
 }
 
-int ensure_host_counters(rt_context* ctx) {
-    if (ctx->h_counters) return RT_OK;
-    const size_t cbytes = 2 * (size_t)kCounterShards * kNumCounters * sizeof(unsigned long long) + 64;
-    RT_HIP(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_counters), cbytes, hipHostMallocDefault));
-    return RT_OK;
-}
-
 // Device scratch -> the caller's host buffer, enqueued on ctx->stream after
 // the render.  A pageable hipMemcpyAsync runs at the PCIe rate here (the
 // runtime pipelines its own pinned staging): measured on MI355X for a 1080p
@@ -943,16 +890,16 @@ int ensure_host_counters(rt_context* ctx) {
 // each of 8 DMA chunks landed took 0.71 ms (scripts/host_frame_probe.py).
 // A canvas allocated per call pays its page faults on top (~0.3 ms at 1080p).
 int copy_to_host(rt_context* ctx, void* out, size_t bytes) {
-    RT_HIP(hipMemcpyAsync(out, ctx->d_scratch, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    RT_HIP(hipMemcpyAsync(out, ctx->d_scratch.get(), bytes, hipMemcpyDeviceToHost, ctx->stream));
     return RT_OK;
 }
 
 int check_pool_error(rt_context* ctx) {
     int32_t err = 0;
-    RT_HIP(hipMemcpyAsync(&err, ctx->d_error, sizeof(err), hipMemcpyDeviceToHost, ctx->stream));
+    RT_HIP(hipMemcpyAsync(&err, ctx->d_error.get(), sizeof(err), hipMemcpyDeviceToHost, ctx->stream));
     RT_HIP(hipStreamSynchronize(ctx->stream));
     if (err) {
-        RT_HIP(hipMemsetAsync(ctx->d_error, 0, sizeof(int32_t), ctx->stream));
+        RT_HIP(hipMemsetAsync(ctx->d_error.get(), 0, sizeof(int32_t), ctx->stream));
         return set_error(RT_ERR_POOL, device_error_text(err));
     }
     return RT_OK;
@@ -980,8 +927,7 @@ int rt_context_create(int device_ordinal, rt_context** out) { return create_devi
 
 int rt_context_destroy(rt_context* ctx) {
     if (!ctx) return RT_OK;
-    for (rt_context* p : ctx->peers) destroy_device_context(p);
-    ctx->peers.clear();
+    for (rt_context* p : ctx->group.peers) destroy_device_context(p);
     destroy_device_context(ctx);
     return RT_OK;
 }
@@ -989,6 +935,29 @@ int rt_context_destroy(rt_context* ctx) {
 }  // extern "C"
 
 namespace rtc {
+
+// A/B and diagnostic switches (debug_knobs.hpp: RTC_DEBUG=key=value,...)
+rt_context::Knobs read_knobs() {
+    rt_context::Knobs k;
+    std::string v;
+    // direct-kernel tile scheduling: "grid" (one workgroup per tile, the
+    // hardware dispatcher balances) or "static" (resident grid, fixed stride)
+    if (debug_knob("sched_direct", &v)) {
+        if (v == "grid") k.sched_direct = kSchedGrid;
+        else if (v == "static") k.sched_direct = kSchedStatic;
+    }
+    if (debug_knob("lds_world", &v)) k.lds_world = v != "0";
+    if (debug_knob("cull", &v)) k.cull = v != "0";
+    if (debug_knob("kind_variants", &v)) k.kind_variants = v != "0";
+    if (debug_knob("pool_lds_rays", &v)) k.pool_lds_rays = (uint32_t)std::atoi(v.c_str());
+    if (debug_knob("tile_order", &v)) k.tile_order = v != "0";
+    if (debug_knob("split", &v)) k.split_factor = std::atof(v.c_str());
+    if (debug_knob("split_max", &v))
+        k.split_max = (uint32_t)std::min<int>((int)kMaxSplitLog2, std::max(0, std::atoi(v.c_str())));
+    if (debug_knob("urgent", &v)) k.urgent_factor = std::atof(v.c_str());
+    if (debug_knob("direct_oversub", &v)) k.direct_oversub10 = (uint32_t)std::max(1, std::atoi(v.c_str()));
+    return k;
+}
 
 int create_device_context(int device_ordinal, rt_context** out) {
     if (!out) return set_error(RT_ERR_INVALID, "null out");
@@ -1013,90 +982,49 @@ int create_device_context(int device_ordinal, rt_context** out) {
     tr.step("hipDeviceGetAttribute x2");
     ctx->cu_count = cus;
     ctx->lds_per_block = (size_t)lds;  // launch limit of static + dynamic LDS
-    // A/B and diagnostic switches (debug_knobs.hpp: RTC_DEBUG=key=value,...)
-    std::string v;
-    // direct-kernel tile scheduling: "grid" (one workgroup per tile, the
-    // hardware dispatcher balances) or "static" (resident grid, fixed stride)
-    if (debug_knob("sched_direct", &v)) {
-        if (v == "grid") ctx->sched_direct = kSchedGrid;
-        else if (v == "static") ctx->sched_direct = kSchedStatic;
-    }
-    if (debug_knob("lds_world", &v)) ctx->lds_world = v != "0";
-    if (debug_knob("cull", &v)) ctx->cull = v != "0";
-    if (debug_knob("kind_variants", &v)) ctx->kind_variants = v != "0";
-    if (debug_knob("pool_lds_rays", &v)) ctx->pool_lds_rays = (uint32_t)std::atoi(v.c_str());
-    if (debug_knob("tile_order", &v)) ctx->tile_order = v != "0";
-    if (debug_knob("split", &v)) ctx->split_factor = std::atof(v.c_str());
-    if (debug_knob("split_max", &v))
-        ctx->split_max = (uint32_t)std::min<int>((int)kMaxSplitLog2, std::max(0, std::atoi(v.c_str())));
-    if (debug_knob("urgent", &v)) ctx->urgent_factor = std::atof(v.c_str());
-    if (debug_knob("direct_oversub", &v)) ctx->direct_oversub10 = (uint32_t)std::max(1, std::atoi(v.c_str()));
+    ctx->knobs = read_knobs();
     // RTC_JIT: the per-scene build mode (rt_context_set_jit's values), a user setting
     if (const char* e = std::getenv("RTC_JIT"))
-        ctx->jit_mode = (e[0] >= '0' && e[0] <= '3' && !e[1]) ? e[0] - '0' : RT_JIT_AUTO;
-    RT_HIP(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
+        ctx->jit.mode = (e[0] >= '0' && e[0] <= '3' && !e[1]) ? e[0] - '0' : RT_JIT_AUTO;
+    int rc;
+    if ((rc = ctx->stream.create(hipStreamNonBlocking))) return rc;
     tr.step("hipStreamCreate");
-    RT_HIP(hipEventCreate(&ctx->ev_start));
-    RT_HIP(hipEventCreate(&ctx->ev_stop));
-    RT_HIP(hipEventCreateWithFlags(&ctx->ev_order, hipEventDisableTiming));
+    if ((rc = ctx->ev_start.create()) || (rc = ctx->ev_stop.create()) ||
+        (rc = ctx->ev_order.create(hipEventDisableTiming)))
+        return rc;
     tr.step("hipEventCreate x3");
-    const size_t qbytes = 2 * (size_t)kTileQueues * kQueueStride * sizeof(unsigned long long);  // two sets
-    RT_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->d_tile_counter), qbytes));
+    const size_t heads = 2 * (size_t)kTileQueues * kQueueStride;  // two sets
+    if ((rc = ctx->d_tile_counter.reserve(heads))) return rc;
     tr.step("hipMalloc");
     // (on the context's stream: the null stream's queue would cost ~8 ms more)
-    RT_HIP(hipMemsetAsync(ctx->d_tile_counter, 0, qbytes, ctx->stream));
+    RT_HIP(hipMemsetAsync(ctx->d_tile_counter.get(), 0, heads * sizeof(unsigned long long), ctx->stream));
     tr.step("hipMemsetAsync (first)");
-    const size_t counter_bytes = (size_t)kCounterShards * kNumCounters * sizeof(unsigned long long);
-    RT_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->d_counters), counter_bytes));
-    RT_HIP(hipMemsetAsync(ctx->d_counters, 0, counter_bytes, ctx->stream));
-    RT_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->d_error), sizeof(int32_t)));
-    RT_HIP(hipMemsetAsync(ctx->d_error, 0, sizeof(int32_t), ctx->stream));
-    const size_t gen_bytes = 2 * (size_t)kGenSlots * sizeof(unsigned long long);
-    RT_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->d_gen_counts), gen_bytes));
-    RT_HIP(hipMemsetAsync(ctx->d_gen_counts, 0, gen_bytes, ctx->stream));
+    const size_t n_counters = (size_t)kCounterShards * kNumCounters, n_gen = 2 * (size_t)kGenSlots;
+    if ((rc = ctx->d_counters.reserve(n_counters)) || (rc = ctx->d_error.reserve(1)) ||
+        (rc = ctx->d_gen_counts.reserve(n_gen)))
+        return rc;
+    RT_HIP(hipMemsetAsync(ctx->d_counters.get(), 0, n_counters * sizeof(unsigned long long), ctx->stream));
+    RT_HIP(hipMemsetAsync(ctx->d_error.get(), 0, sizeof(int32_t), ctx->stream));
+    RT_HIP(hipMemsetAsync(ctx->d_gen_counts.get(), 0, n_gen * sizeof(unsigned long long), ctx->stream));
     RT_HIP(hipStreamSynchronize(ctx->stream));
     tr.step("hipMalloc+hipMemsetAsync x3, sync");
     *out = ctx.release();
     return RT_OK;
 }
 
-void destroy_device_context(rt_context* ctx) {
-    if (!ctx) return;
-    (void)hipSetDevice(ctx->device);
+void destroy_device_context(rt_context* ctx) { delete ctx; }
+
+}  // namespace rtc
+
+rt_context::~rt_context() {
+    (void)hipSetDevice(device);
     (void)hipDeviceSynchronize();  // launches on caller streams too
-    for (auto& c : ctx->canvases) {
+    for (auto& c : canvases) {
         if (c.second.owned) (void)hipFree(c.first);
         else (void)hipIpcCloseMemHandle(c.first);
     }
-    ctx->canvases.clear();
-    ctx->w32.release();
-    ctx->w64.release();
-    (void)hipFree(ctx->d_tile_counter);
-    (void)hipFree(ctx->d_counters);
-    (void)hipFree(ctx->d_error);
-    (void)hipFree(ctx->d_gen_counts);
-    (void)hipFree(ctx->d_scratch);
-    (void)hipFree(ctx->d_stamps);
-    (void)hipFree(ctx->d_item_log);
-    (void)hipFree(ctx->d_spill);
-    (void)hipFree(ctx->d_tile_cost);
-    (void)hipFree(ctx->d_tile_order);
-    (void)hipFree(ctx->d_cold_order);
-    if (ctx->ev_start) (void)hipEventDestroy(ctx->ev_start);
-    if (ctx->ev_stop) (void)hipEventDestroy(ctx->ev_stop);
-    if (ctx->ev_order) (void)hipEventDestroy(ctx->ev_order);
-    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    if (ctx->comm) (void)ncclCommDestroy(ctx->comm);
-    (void)hipFree(ctx->d_strip);
-    (void)hipFree(ctx->d_gathered);
-    (void)hipFree(ctx->d_status);
-    if (ctx->h_counters) (void)hipHostFree(ctx->h_counters);
-    for (hipEvent_t e : {ctx->ev_render0, ctx->ev_render1, ctx->ev_gather1})
-        if (e) (void)hipEventDestroy(e);
-    delete ctx;
+    if (group.comm) (void)ncclCommDestroy(group.comm);
 }
-
-}  // namespace rtc
 
 extern "C" {
 
@@ -1104,7 +1032,7 @@ int rt_scene_upload(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns, c
                     uint32_t nm, const rt_pattern_desc* pats, uint32_t np, const rt_light_desc* lights,
                     uint32_t nl) {
     if (!ctx) return set_error(RT_ERR_INVALID, "null context");
-    if (ctx->comm) return group_scene_upload(ctx, shapes, ns, mats, nm, pats, np, lights, nl);
+    if (ctx->group.comm) return group_scene_upload(ctx, shapes, ns, mats, nm, pats, np, lights, nl);
     int rc = validate_scene(shapes, ns, mats, nm, pats, np, lights, nl);
     if (rc) return rc;
     RT_HIP(hipSetDevice(ctx->device));
@@ -1232,51 +1160,49 @@ int build_scene(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns, const
 
 int fetch_jit_tables(rt_context* ctx) {
     const DevScene<float>& sc = ctx->w32.scene;
-    ctx->jit_shapes.assign(sc.kind_begin[kNumKinds], ShapeRec<float>{});
-    ctx->jit_lights.assign(sc.n_lights, LightRec<float>{});
-    ctx->jit_materials.assign(sc.n_materials, MaterialRec<float>{});
-    ctx->jit_pattern_recs.assign(sc.n_patterns, PatternRec<float>{});
+    ctx->jit.shapes.assign(sc.kind_begin[kNumKinds], ShapeRec<float>{});
+    ctx->jit.lights.assign(sc.n_lights, LightRec<float>{});
+    ctx->jit.materials.assign(sc.n_materials, MaterialRec<float>{});
+    ctx->jit.pattern_recs.assign(sc.n_patterns, PatternRec<float>{});
     auto get = [&](auto& v, const void* src) -> hipError_t {
         return v.empty() ? hipSuccess
                          : hipMemcpyAsync(v.data(), src, v.size() * sizeof(v[0]), hipMemcpyDeviceToHost, ctx->stream);
     };
-    RT_HIP(get(ctx->jit_shapes, ctx->w32.shapes));
-    RT_HIP(get(ctx->jit_lights, ctx->w32.lights));
-    RT_HIP(get(ctx->jit_materials, ctx->w32.materials));
-    RT_HIP(get(ctx->jit_pattern_recs, ctx->w32.patterns));
+    RT_HIP(get(ctx->jit.shapes, ctx->w32.shapes));
+    RT_HIP(get(ctx->jit.lights, ctx->w32.lights.get()));
+    RT_HIP(get(ctx->jit.materials, ctx->w32.materials));
+    RT_HIP(get(ctx->jit.pattern_recs, ctx->w32.patterns));
     RT_HIP(hipStreamSynchronize(ctx->stream));
     return RT_OK;
 }
 
 int capture_jit_table(rt_context* ctx) {
-    // (jit_shapes, jit_lights, jit_materials, jit_pattern_recs: build_world<float>'s host tables)
-    for (int k = 0; k <= kNumKinds; ++k) ctx->jit_begin[k] = ctx->w32.scene.kind_begin[k];
-    const std::vector<MaterialRec<float>>& mats = ctx->jit_materials;
-    ctx->jit_patterns = std::any_of(mats.begin(), mats.end(), [](const MaterialRec<float>& m) { return m.pattern >= 0; });
-    ctx->jit_transparent =
+    // (jit.shapes, lights, materials, pattern_recs: build_world<float>'s host tables)
+    rt_context::Jit& j = ctx->jit;
+    for (int k = 0; k <= kNumKinds; ++k) j.begin[k] = ctx->w32.scene.kind_begin[k];
+    const std::vector<MaterialRec<float>>& mats = j.materials;
+    j.patterns = std::any_of(mats.begin(), mats.end(), [](const MaterialRec<float>& m) { return m.pattern >= 0; });
+    j.transparent =
         std::any_of(mats.begin(), mats.end(), [](const MaterialRec<float>& m) { return m.transparency != 0.0f; });
-    ctx->jit_pattern_kinds = 0;
-    for (const PatternRec<float>& q : ctx->jit_pattern_recs)  // every kind a pattern_color walk can meet (complex sub-patterns included)
-        ctx->jit_pattern_kinds |= 1u << std::min<uint32_t>((uint32_t)q.kind, RT_PATTERN_TEST);
-    for (int v = 0; v < rt_context::kJitVariants; ++v) {
-        ctx->jit_fn[v] = nullptr;
-        ctx->jit_build[v].reset();
-        ctx->jit_rejected[v] = ctx->jit_owner[v] = false;
-    }
-    ctx->jit_frames = 0;
-    ctx->jit_failed = false;
-    ctx->jit_log.clear();
+    j.pattern_kinds = 0;
+    for (const PatternRec<float>& q : j.pattern_recs)  // every kind a pattern_color walk can meet (complex sub-patterns included)
+        j.pattern_kinds |= 1u << std::min<uint32_t>((uint32_t)q.kind, RT_PATTERN_TEST);
+    j.reset();
     return RT_OK;
+}
+
+// A launch for whichever precision's world the request asks for.
+int launch_precision(rt_context* ctx, uint32_t precision, const LaunchRequest& q) {
+    return precision == RT_PRECISION_F32 ? launch<float>(ctx, ctx->w32, q) : launch<double>(ctx, ctx->w64, q);
 }
 
 int launch_frame(rt_context* ctx, const rt_camera_desc* cam, const rt_render_options* o, uint32_t shard_index,
                  uint32_t shard_count, void* out_device, hipStream_t s, bool image_rows) {
     RT_HIP(hipSetDevice(ctx->device));
-    if (o->precision == RT_PRECISION_F32)
-        return launch<float>(ctx, ctx->w32, cam, nullptr, 0, o->max_depth, o->out_format, shard_index, shard_count,
-                             out_device, s, o->flags, image_rows);
-    return launch<double>(ctx, ctx->w64, cam, nullptr, 0, o->max_depth, o->out_format, shard_index, shard_count,
-                          out_device, s, o->flags, image_rows);
+    return launch_precision(ctx, o->precision,
+                            {.cam = cam, .depth = o->max_depth, .out_format = o->out_format, .shard_index = shard_index,
+                             .shard_count = shard_count, .out_device = out_device, .stream = s, .flags = o->flags,
+                             .image_rows = image_rows});
 }
 
 // ------------------------------------------------------------ peer canvas
@@ -1387,18 +1313,17 @@ int rt_render_to_canvas(rt_context* ctx, const rt_camera_desc* cam, const rt_ren
     int rc = check_ready(ctx);
     if (rc) return rc;
     if ((rc = check_options(o))) return rc;
-    if (ctx->comm) return set_error(RT_ERR_INVALID, "rt_render_to_canvas takes a single-GPU context");
+    if (ctx->group.comm) return set_error(RT_ERR_INVALID, "rt_render_to_canvas takes a single-GPU context");
     auto it = ctx->canvases.find(canvas);
     if (!cam || it == ctx->canvases.end()) return set_error(RT_ERR_INVALID, "null camera or unknown canvas");
     const rt_context::Canvas& c = it->second;
-    const size_t elem = o->out_format == RT_OUT_U8 ? 1 : (o->precision == RT_PRECISION_F32 ? 4 : 8);
-    if ((uint64_t)cam->width * cam->height * 3 * elem > c.bytes || o->shard_index >= c.n_flags || seq == 0)
+    if ((uint64_t)cam->width * cam->height * pixel_bytes(o) > c.bytes || o->shard_index >= c.n_flags || seq == 0)
         return set_error(RT_ERR_INVALID, "rt_render_to_canvas: canvas too small, shard without a flag, or seq 0");
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     RT_HIP(hipSetDevice(ctx->device));
     unsigned long long* flags = canvas_flags(canvas, c.bytes);
     // the owner has released the previous frame (its readers are done)
-    if (seq > 1) RT_HIP(launch_canvas_wait(flags + c.n_flags, 1, seq - 1, timeout_ticks(timeout_ms), ctx->d_error, s));
+    if (seq > 1) RT_HIP(launch_canvas_wait(flags + c.n_flags, 1, seq - 1, timeout_ticks(timeout_ms), ctx->d_error.get(), s));
     if (cam->width && cam->height &&
         (rc = launch_frame(ctx, cam, o, o->shard_index, o->shard_count, canvas, s, true)))
         return rc;
@@ -1412,7 +1337,7 @@ int rt_canvas_wait(rt_context* ctx, void* canvas, uint64_t seq, double timeout_m
     if (it == ctx->canvases.end()) return set_error(RT_ERR_INVALID, "unknown canvas");
     RT_HIP(hipSetDevice(ctx->device));
     RT_HIP(launch_canvas_wait(canvas_flags(canvas, it->second.bytes), it->second.n_flags, seq, timeout_ticks(timeout_ms),
-                              ctx->d_error, static_cast<hipStream_t>(hip_stream)));
+                              ctx->d_error.get(), static_cast<hipStream_t>(hip_stream)));
     return RT_OK;
 }
 
@@ -1436,14 +1361,6 @@ int rt_canvas_release(rt_context* ctx, void* canvas, uint64_t seq, void* hip_str
     return RT_OK;
 }
 
-}  // extern "C"
-
-namespace rtc {
-
-}  // namespace rtc
-
-extern "C" {
-
 int rt_shard_rows(uint32_t height, uint32_t shard_count, uint32_t* rows) {
     if (!rows || shard_count == 0) return set_error(RT_ERR_INVALID, "bad arguments");
     *rows = tile_rows_for(height, shard_count, 0) * RT_TILE_H;
@@ -1462,11 +1379,11 @@ int rt_render_device(rt_context* ctx, const rt_camera_desc* cam, const rt_render
     int rc = check_ready(ctx);
     if (rc) return rc;
     if ((rc = check_options(o))) return rc;
-    if (!cam || (!out_device && !(ctx->comm && ctx->rank != 0)))  // a group's other ranks write no image
+    if (!cam || (!out_device && !(ctx->group.comm && ctx->group.rank != 0)))  // a group's other ranks write no image
         return set_error(RT_ERR_INVALID, "null camera or output");
     if (cam->width == 0 || cam->height == 0) return RT_OK;  // empty canvas (canvas.rs:27-35)
     hipStream_t s = static_cast<hipStream_t>(hip_stream);  // NULL = HIP's default stream
-    if (ctx->comm) return group_render_device(ctx, cam, o, out_device, s);
+    if (ctx->group.comm) return group_render_device(ctx, cam, o, out_device, s);
     return launch_frame(ctx, cam, o, o->shard_index, o->shard_count, out_device, s);
 }
 
@@ -1476,40 +1393,40 @@ int rt_render(rt_context* ctx, const rt_camera_desc* cam, const rt_render_option
     if (rc) return rc;
     if ((rc = check_options(o))) return rc;
     if (!cam) return set_error(RT_ERR_INVALID, "null camera");
-    if (ctx->comm) return group_render(ctx, cam, o, out_host, stats);
+    if (ctx->group.comm) return group_render(ctx, cam, o, out_host, stats);
     if (!out_host) return set_error(RT_ERR_INVALID, "null output");
     RT_HIP(hipSetDevice(ctx->device));
-    const size_t elem = o->out_format == RT_OUT_U8 ? 1 : (o->precision == RT_PRECISION_F32 ? 4 : 8);
     const uint32_t rows = tile_rows_for(cam->height, o->shard_count, o->shard_index) * RT_TILE_H;
     const uint32_t valid_rows = o->shard_count == 1 ? cam->height : rows;
-    const size_t bytes = (size_t)rows * cam->width * 3 * elem;
-    const size_t out_bytes = (size_t)valid_rows * cam->width * 3 * elem;
+    const size_t bytes = (size_t)rows * cam->width * pixel_bytes(o);
+    const size_t out_bytes = (size_t)valid_rows * cam->width * pixel_bytes(o);
     if (bytes == 0) {
         if (stats) std::memset(stats, 0, sizeof(*stats));
         return RT_OK;
     }
     InitTrace tr("rt_render");
-    if ((rc = ensure_scratch(ctx, bytes))) return rc;
+    if ((rc = ctx->d_scratch.reserve(bytes))) return rc;
     tr.step("scratch");
-    if ((rc = ensure_host_counters(ctx))) return rc;
+    // (before and after: kCounterShards x kNumCounters each; the error flag in the 64 bytes behind them)
+    if ((rc = ctx->h_counters.reserve(2 * (size_t)kCounterShards * kNumCounters + 8))) return rc;
     tr.step("pinned counters");
     hipStream_t s = ctx->stream;
     // counters before and after, and the error flag, come back in pinned
     // memory on the stream: one host sync for the whole frame
     if ((rc = order_after_last(ctx, s))) return rc;
     const size_t cbytes = (size_t)kCounterShards * kNumCounters * sizeof(unsigned long long);
-    unsigned long long* h_before = ctx->h_counters;
-    unsigned long long* h_after = ctx->h_counters + (size_t)kCounterShards * kNumCounters;
+    unsigned long long* h_before = ctx->h_counters.get();
+    unsigned long long* h_after = h_before + (size_t)kCounterShards * kNumCounters;
     int32_t* h_err = reinterpret_cast<int32_t*>(h_after + (size_t)kCounterShards * kNumCounters);
-    RT_HIP(hipMemcpyAsync(h_before, ctx->d_counters, cbytes, hipMemcpyDeviceToHost, s));
-    if (o->shard_count > 1) RT_HIP(hipMemsetAsync(ctx->d_scratch, 0, bytes, s));  // strip rows past the canvas
+    RT_HIP(hipMemcpyAsync(h_before, ctx->d_counters.get(), cbytes, hipMemcpyDeviceToHost, s));
+    if (o->shard_count > 1) RT_HIP(hipMemsetAsync(ctx->d_scratch.get(), 0, bytes, s));  // strip rows past the canvas
     RT_HIP(hipEventRecord(ctx->ev_start, s));
     tr.step("enqueue before launch");
-    if ((rc = launch_frame(ctx, cam, o, o->shard_index, o->shard_count, ctx->d_scratch, s))) return rc;
+    if ((rc = launch_frame(ctx, cam, o, o->shard_index, o->shard_count, ctx->d_scratch.get(), s))) return rc;
     tr.step("launch");
     RT_HIP(hipEventRecord(ctx->ev_stop, s));
-    RT_HIP(hipMemcpyAsync(h_after, ctx->d_counters, cbytes, hipMemcpyDeviceToHost, s));
-    RT_HIP(hipMemcpyAsync(h_err, ctx->d_error, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    RT_HIP(hipMemcpyAsync(h_after, ctx->d_counters.get(), cbytes, hipMemcpyDeviceToHost, s));
+    RT_HIP(hipMemcpyAsync(h_err, ctx->d_error.get(), sizeof(int32_t), hipMemcpyDeviceToHost, s));
     if ((rc = copy_to_host(ctx, out_host, out_bytes))) return rc;
     tr.step("enqueue copies");
     RT_HIP(hipStreamSynchronize(s));
@@ -1517,17 +1434,14 @@ int rt_render(rt_context* ctx, const rt_camera_desc* cam, const rt_render_option
     float ms = 0.f;
     RT_HIP(hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop));
     if (*h_err) {
-        RT_HIP(hipMemsetAsync(ctx->d_error, 0, sizeof(int32_t), s));
+        RT_HIP(hipMemsetAsync(ctx->d_error.get(), 0, sizeof(int32_t), s));
         RT_HIP(hipStreamSynchronize(s));
         return set_error(RT_ERR_POOL, device_error_text(*h_err));
     }
     if (stats) {
-        unsigned long long before[kNumCounters] = {}, after[kNumCounters] = {};
-        for (int sh = 0; sh < kCounterShards; ++sh)
-            for (int i = 0; i < kNumCounters; ++i) {
-                before[i] += h_before[(size_t)sh * kNumCounters + i];
-                after[i] += h_after[(size_t)sh * kNumCounters + i];
-            }
+        unsigned long long before[kNumCounters], after[kNumCounters];
+        sum_counter_shards(h_before, before);
+        sum_counter_shards(h_after, after);
         fill_stats(ctx, before, after, ms, stats);
     }
     return RT_OK;
@@ -1561,20 +1475,17 @@ int rt_color_at(rt_context* ctx, const double* rays, uint64_t n, uint32_t depth,
         }
     }
     RT_HIP(hipSetDevice(ctx->device));
-    const size_t elem = precision == RT_PRECISION_F32 ? 4 : 8;
-    const size_t in_bytes = n * 6 * sizeof(double), out_bytes = n * 3 * elem;
-    if ((rc = ensure_scratch(ctx, in_bytes + out_bytes))) return rc;
-    double* d_rays = static_cast<double*>(ctx->d_scratch);
-    void* d_out = static_cast<char*>(ctx->d_scratch) + in_bytes;
+    const size_t in_bytes = n * 6 * sizeof(double), out_bytes = n * 3 * element_bytes(RT_OUT_REAL, precision);
+    if ((rc = ctx->d_scratch.reserve(in_bytes + out_bytes))) return rc;
+    double* d_rays = reinterpret_cast<double*>(ctx->d_scratch.get());
+    void* d_out = ctx->d_scratch.get() + in_bytes;
     RT_HIP(hipMemcpy(d_rays, rays, in_bytes, hipMemcpyHostToDevice));
     unsigned long long before[kNumCounters], after[kNumCounters];
     if ((rc = read_counters(ctx, before))) return rc;
     RT_HIP(hipEventRecord(ctx->ev_start, ctx->stream));
-    if (precision == RT_PRECISION_F32)
-        rc = launch<float>(ctx, ctx->w32, nullptr, d_rays, n, depth, RT_OUT_REAL, 0, 1, d_out, ctx->stream);
-    else
-        rc = launch<double>(ctx, ctx->w64, nullptr, d_rays, n, depth, RT_OUT_REAL, 0, 1, d_out, ctx->stream);
-    if (rc) return rc;
+    if ((rc = launch_precision(ctx, precision,
+                               {.d_rays = d_rays, .n_rays = n, .depth = depth, .out_device = d_out, .stream = ctx->stream})))
+        return rc;
     RT_HIP(hipEventRecord(ctx->ev_stop, ctx->stream));
     RT_HIP(hipStreamSynchronize(ctx->stream));
     float ms = 0.f;
@@ -1607,8 +1518,8 @@ int debug_shape(rt_context* ctx, uint32_t shape, uint32_t mode, const double* in
     if (n > 0xFFFFFFFFull) return set_error(RT_ERR_INVALID, "too many rays");
     RT_HIP(hipSetDevice(ctx->device));
     const size_t in_bytes = n * in_stride * sizeof(double), out_bytes = n * out_stride * sizeof(double);
-    if ((rc = ensure_scratch(ctx, in_bytes + out_bytes))) return rc;
-    double* d_in = static_cast<double*>(ctx->d_scratch);
+    if ((rc = ctx->d_scratch.reserve(in_bytes + out_bytes))) return rc;
+    double* d_in = reinterpret_cast<double*>(ctx->d_scratch.get());
     double* d_out = d_in + n * in_stride;
     RT_HIP(hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
     const int32_t ws = ctx->world_slot[shape];
@@ -1641,18 +1552,16 @@ int rt_context_set_frames_in_flight(rt_context* ctx, uint32_t frames) {
     // (an A/B setting of RTC_DEBUG wins over the hint)
     std::string v;
     const bool grid_knob = debug_knob("direct_oversub", &v), split_knob = debug_knob("split", &v);
-    std::vector<rt_context*> ms{ctx};
-    ms.insert(ms.end(), ctx->peers.begin(), ctx->peers.end());
-    for (rt_context* m : ms) {
-        if (!grid_knob) m->direct_oversub10 = frames > 1 ? 15u : 25u;
+    for (rt_context* m : members(ctx)) {
+        if (!grid_knob) m->knobs.direct_oversub10 = frames > 1 ? 15u : 25u;
         // pool kernels: with the next frame filling a launch's tail, tiles
         // split only above 1.5x the mean workgroup load (a 4K shard of 8 with
         // two in flight, round 6: cover 0.104 -> 0.094 ms per frame, table
         // 0.115 -> 0.113; a frame alone keeps 1.0x)
         const double split = frames > 1 ? 1.5 : 1.0;
-        if (!split_knob && m->split_factor != split) {
-            m->split_factor = split;
-            m->order_valid = false;  // the next launches rebuild the tile order with it
+        if (!split_knob && m->knobs.split_factor != split) {
+            m->knobs.split_factor = split;
+            m->order.valid = false;  // the next launches rebuild the tile order with it
         }
     }
     return RT_OK;
@@ -1660,17 +1569,16 @@ int rt_context_set_frames_in_flight(rt_context* ctx, uint32_t frames) {
 
 int rt_context_set_jit(rt_context* ctx, int mode) {
     if (!ctx || mode < RT_JIT_OFF || mode > RT_JIT_EAGER) return set_error(RT_ERR_INVALID, "bad arguments");
-    ctx->jit_mode = mode;
-    for (rt_context* p : ctx->peers) p->jit_mode = mode;
+    for (rt_context* m : members(ctx)) m->jit.mode = mode;
     return RT_OK;
 }
 
 int rt_jit_status(rt_context* ctx, int* used_last_launch, double* compile_ms, char* log, size_t log_len) {
     if (!ctx) return set_error(RT_ERR_INVALID, "null context");
-    if (used_last_launch) *used_last_launch = ctx->jit_used ? 1 : 0;
-    if (compile_ms) *compile_ms = ctx->jit_compile_ms;
+    if (used_last_launch) *used_last_launch = ctx->jit.used ? 1 : 0;
+    if (compile_ms) *compile_ms = ctx->jit.compile_ms;
     if (log && log_len) {
-        std::strncpy(log, ctx->jit_log.c_str(), log_len - 1);
+        std::strncpy(log, ctx->jit.log.c_str(), log_len - 1);
         log[log_len - 1] = '\0';
     }
     return RT_OK;
@@ -1686,12 +1594,11 @@ int rt_jit_wait(rt_context* ctx, double timeout_ms, int* pending) {
         return std::max(0.0, timeout_ms - spent);
     };
     int total = 0, left = 0;
-    for (rt_context* c : ctx->peers) {
+    for (rt_context* c : members(ctx)) {
         jit_wait(c, remaining(), &left);
         total += left;
     }
-    jit_wait(ctx, remaining(), &left);
-    if (pending) *pending = total + left;
+    if (pending) *pending = total;
     return RT_OK;
 }
 
@@ -1702,7 +1609,7 @@ int rt_debug_stamps(rt_context* ctx, uint64_t* out, uint32_t max_wg, uint32_t* n
     *n = ctx->stamp_count;
     const uint32_t copy = std::min(max_wg, ctx->stamp_count);
     if (out && copy)
-        RT_HIP(hipMemcpy(out, ctx->d_stamps, 2 * sizeof(uint64_t) * copy, hipMemcpyDeviceToHost));
+        RT_HIP(hipMemcpy(out, ctx->d_stamps.get(), 2 * sizeof(uint64_t) * copy, hipMemcpyDeviceToHost));
     return RT_OK;
 }
 
@@ -1711,11 +1618,12 @@ int rt_debug_item_log(rt_context* ctx, uint64_t* out, uint32_t max_items, uint32
     RT_HIP(hipSetDevice(ctx->device));
     RT_HIP(hipDeviceSynchronize());
     uint64_t count = 0;
-    if (ctx->d_item_log) RT_HIP(hipMemcpy(&count, ctx->d_item_log, sizeof count, hipMemcpyDeviceToHost));
-    *n = (uint32_t)std::min<uint64_t>(count, ctx->item_log_capacity);
+    const unsigned long long* log = ctx->d_item_log.get();  // a count, then 3 words per item
+    if (log) RT_HIP(hipMemcpy(&count, log, sizeof count, hipMemcpyDeviceToHost));
+    *n = (uint32_t)std::min<uint64_t>(count, log ? (ctx->d_item_log.capacity() - 1) / 3 : 0);
     const uint32_t copy = std::min(max_items, *n);
     if (out && copy)
-        RT_HIP(hipMemcpy(out, ctx->d_item_log + 1, 3 * sizeof(uint64_t) * copy, hipMemcpyDeviceToHost));
+        RT_HIP(hipMemcpy(out, log + 1, 3 * sizeof(uint64_t) * copy, hipMemcpyDeviceToHost));
     return RT_OK;
 }
 
@@ -1723,15 +1631,15 @@ int rt_debug_tile_costs(rt_context* ctx, uint32_t* out, uint32_t max_tiles, uint
     if (!ctx || !n) return set_error(RT_ERR_INVALID, "null argument");
     RT_HIP(hipSetDevice(ctx->device));
     RT_HIP(hipDeviceSynchronize());
-    *n = ctx->order_valid ? ctx->order_capacity : 0;
+    *n = ctx->order.valid ? (uint32_t)ctx->order.d_cost.capacity() : 0;
     const uint32_t copy = std::min(max_tiles, *n);
-    if (out && copy) RT_HIP(hipMemcpy(out, ctx->d_tile_cost, copy * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (out && copy) RT_HIP(hipMemcpy(out, ctx->order.d_cost.get(), copy * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return RT_OK;
 }
 
 int rt_read_counters(rt_context* ctx, rt_stats* totals) {
     if (!ctx || !totals) return set_error(RT_ERR_INVALID, "null argument");
-    if (!ctx->peers.empty()) return group_read_counters(ctx, totals);
+    if (!ctx->group.peers.empty()) return group_read_counters(ctx, totals);
     RT_HIP(hipSetDevice(ctx->device));
     RT_HIP(hipDeviceSynchronize());
     unsigned long long zero[kNumCounters] = {}, now[kNumCounters];
@@ -1744,13 +1652,11 @@ int rt_read_counters(rt_context* ctx, rt_stats* totals) {
 int rt_read_generation_counts(rt_context* ctx, rt_generation_counts* out) {
     if (!ctx || !out) return set_error(RT_ERR_INVALID, "null argument");
     std::memset(out, 0, sizeof(*out));
-    std::vector<rt_context*> members = {ctx};
-    members.insert(members.end(), ctx->peers.begin(), ctx->peers.end());
-    for (rt_context* m : members) {
+    for (rt_context* m : members(ctx)) {
         unsigned long long buf[2 * kGenSlots];
         RT_HIP(hipSetDevice(m->device));
         RT_HIP(hipDeviceSynchronize());
-        RT_HIP(hipMemcpy(buf, m->d_gen_counts, sizeof buf, hipMemcpyDeviceToHost));
+        RT_HIP(hipMemcpy(buf, m->d_gen_counts.get(), sizeof buf, hipMemcpyDeviceToHost));
         for (int i = 0; i < kGenSlots; ++i) {
             out->traced[i] += buf[i];
             out->shaded[i] += buf[kGenSlots + i];

@@ -556,16 +556,16 @@ void start_build(const std::shared_ptr<CodeBuild>& b, const jitfile::Request& rq
 // per-scene builds' --offload-arch: read at the first build, not at context
 // creation (hipGetDeviceProperties fills the whole struct).
 const std::string& device_arch(rt_context* ctx) {
-    if (ctx->arch.empty()) {
+    if (ctx->jit.arch.empty()) {
         hipDeviceProp_t prop;
         if (hipSetDevice(ctx->device) == hipSuccess && hipGetDeviceProperties(&prop, ctx->device) == hipSuccess) {
             const std::string a(prop.gcnArchName);
-            ctx->arch = a.empty() ? std::string("gfx950") : a.substr(0, a.find(':'));
+            ctx->jit.arch = a.empty() ? std::string("gfx950") : a.substr(0, a.find(':'));
         } else {
-            ctx->arch = "gfx950";
+            ctx->jit.arch = "gfx950";
         }
     }
-    return ctx->arch;
+    return ctx->jit.arch;
 }
 
 // The per-scene kernel for this context's uploaded world, or null (use the
@@ -580,39 +580,39 @@ constexpr int kPool7ScratchMax = 40;
 
 namespace {
 // One variant's build: *fn stays null while it compiles, if it failed or if
-// it was refused (jit_rejected[variant]).
+// it was refused (jit.rejected[variant]).
 // start_only: make sure the build runs (in the background even in
 // RT_JIT_SYNC mode) and return without waiting for it or taking it.
 // scratch_max: the B/lane of scratch a pool build may use (direct: none).
 int jit_variant(rt_context* ctx, int variant, bool pool, bool lds, size_t dyn_lds, int static_blocks,
                 hipFunction_t* fn, bool no_skips, int pool_waves, int scratch_max, bool start_only = false) {
     *fn = nullptr;
-    if (ctx->jit_fn[variant]) {
-        *fn = ctx->jit_fn[variant];
+    if (ctx->jit.fn[variant]) {
+        *fn = ctx->jit.fn[variant];
         return RT_OK;
     }
-    if (ctx->jit_rejected[variant]) return RT_OK;
-    const bool sync = ctx->jit_mode == RT_JIT_SYNC;
-    std::shared_ptr<CodeBuild>& b = ctx->jit_build[variant];
+    if (ctx->jit.rejected[variant]) return RT_OK;
+    const bool sync = ctx->jit.mode == RT_JIT_SYNC;
+    std::shared_ptr<CodeBuild>& b = ctx->jit.build[variant];
     if (!b) {
-        uint64_t table = fnv(ctx->jit_begin, sizeof ctx->jit_begin,
-                             fnv(ctx->jit_shapes.data(), ctx->jit_shapes.size() * sizeof(ShapeRec<float>)));
-        table = fnv(ctx->jit_lights.data(), ctx->jit_lights.size() * sizeof(LightRec<float>), table);
-        table = fnv(ctx->jit_materials.data(), ctx->jit_materials.size() * sizeof(MaterialRec<float>), table);
-        const uint32_t traits[3] = {ctx->jit_patterns, ctx->jit_pattern_kinds, ctx->jit_transparent};
+        uint64_t table = fnv(ctx->jit.begin, sizeof ctx->jit.begin,
+                             fnv(ctx->jit.shapes.data(), ctx->jit.shapes.size() * sizeof(ShapeRec<float>)));
+        table = fnv(ctx->jit.lights.data(), ctx->jit.lights.size() * sizeof(LightRec<float>), table);
+        table = fnv(ctx->jit.materials.data(), ctx->jit.materials.size() * sizeof(MaterialRec<float>), table);
+        const uint32_t traits[3] = {ctx->jit.patterns, ctx->jit.pattern_kinds, ctx->jit.transparent};
         table = fnv(traits, sizeof traits, table);
         // the device's gfx target: each build is compiled for one (make_request),
         // so devices of another target in the same process get builds of their own
         const std::string& arch = device_arch(ctx);
         table = fnv(arch.data(), arch.size() + 1, table);
-        const uint32_t start_at = ctx->jit_mode == RT_JIT_AUTO ? 2 : 1;
+        const uint32_t start_at = ctx->jit.mode == RT_JIT_AUTO ? 2 : 1;
         bool start = false;
         {
             std::lock_guard<std::mutex> lk(g_mu);
             auto it = g_code.find({table, variant});
             if (it != g_code.end()) {
                 b = it->second;  // built (or building, or failed) for another context or an earlier upload
-            } else if (sync || ctx->jit_frames >= start_at) {
+            } else if (sync || ctx->jit.frames >= start_at) {
                 b = std::make_shared<CodeBuild>();
                 g_code[{table, variant}] = b;
                 start = true;
@@ -620,12 +620,12 @@ int jit_variant(rt_context* ctx, int variant, bool pool, bool lds, size_t dyn_ld
         }
         if (!b) return RT_OK;
         if (start) {
-            ctx->jit_owner[variant] = true;
+            ctx->jit.owner[variant] = true;
             uint64_t key = 0;
             const jitfile::Request rq =
-                make_request(scene_header(ctx->jit_shapes, ctx->jit_begin, ctx->jit_lights, ctx->jit_materials,
-                                          ctx->jit_patterns,
-                                          ctx->jit_pattern_kinds, ctx->jit_transparent),
+                make_request(scene_header(ctx->jit.shapes, ctx->jit.begin, ctx->jit.lights, ctx->jit.materials,
+                                          ctx->jit.patterns,
+                                          ctx->jit.pattern_kinds, ctx->jit.transparent),
                              kernel_name(pool, lds), device_arch(ctx), &key, no_skips, pool_waves);
             start_build(b, rq, key, sync && !start_only);
         }
@@ -637,10 +637,10 @@ int jit_variant(rt_context* ctx, int variant, bool pool, bool lds, size_t dyn_ld
     }
     const int state = b->state.load(std::memory_order_acquire);
     if (state == 0) return RT_OK;  // still compiling: the generic kernel this frame
-    if (ctx->jit_owner[variant]) {
-        ctx->jit_compile_ms += b->ms;
-        if (b->from_disk) ++ctx->jit_cache_hits;
-        ctx->jit_owner[variant] = false;
+    if (ctx->jit.owner[variant]) {
+        ctx->jit.compile_ms += b->ms;
+        if (b->from_disk) ++ctx->jit.cache_hits;
+        ctx->jit.owner[variant] = false;
     }
     // A failed build of the optional 7-wave variant (variant >= 8) refuses
     // that variant only: jit_function falls back to the static-occupancy
@@ -648,8 +648,8 @@ int jit_variant(rt_context* ctx, int variant, bool pool, bool lds, size_t dyn_ld
     // for this world.
     const bool optional = variant >= 8;
     if (state == 2) {
-        (optional ? ctx->jit_rejected[variant] : ctx->jit_failed) = true;
-        ctx->jit_log = b->log;
+        (optional ? ctx->jit.rejected[variant] : ctx->jit.failed) = true;
+        ctx->jit.log = b->log;
         return RT_OK;
     }
     std::pair<hipModule_t, hipFunction_t> mf{};
@@ -672,8 +672,8 @@ int jit_variant(rt_context* ctx, int variant, bool pool, bool lds, size_t dyn_ld
         }
         if (e != hipSuccess) {
             (void)hipGetLastError();
-            (optional ? ctx->jit_rejected[variant] : ctx->jit_failed) = true;
-            ctx->jit_log = std::string("per-scene kernel not loaded (") + ctx->arch + "): " + hipGetErrorString(e);
+            (optional ? ctx->jit.rejected[variant] : ctx->jit.failed) = true;
+            ctx->jit.log = std::string("per-scene kernel not loaded (") + ctx->jit.arch + "): " + hipGetErrorString(e);
             return RT_OK;
         }
         std::lock_guard<std::mutex> lk(g_mu);
@@ -694,13 +694,13 @@ int jit_variant(rt_context* ctx, int variant, bool pool, bool lds, size_t dyn_ld
     RT_HIP(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, mf.second, kBlock, dyn_lds));
     RT_HIP(hipFuncGetAttribute(&scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, mf.second));
     if (blocks < static_blocks || scratch > (pool ? scratch_max : 0)) {
-        ctx->jit_rejected[variant] = true;
-        ctx->jit_log = std::string("per-scene ") + (pool ? "pool" : "direct") + " kernel not used: " +
+        ctx->jit.rejected[variant] = true;
+        ctx->jit.log = std::string("per-scene ") + (pool ? "pool" : "direct") + " kernel not used: " +
                        std::to_string(blocks) + " workgroups/CU (generic " + std::to_string(static_blocks) + "), " +
                        std::to_string(scratch) + " B/lane of scratch";
         return RT_OK;
     }
-    ctx->jit_fn[variant] = mf.second;
+    ctx->jit.fn[variant] = mf.second;
     *fn = mf.second;
     return RT_OK;
 }
@@ -710,7 +710,7 @@ int jit_function(rt_context* ctx, bool pool, bool lds, size_t dyn_lds, int stati
                  bool no_skips, int* pool_waves) {
     *fn = nullptr;
     if (pool_waves) *pool_waves = 0;
-    if (ctx->jit_failed || ctx->jit_shapes.empty()) return RT_OK;
+    if (ctx->jit.failed || ctx->jit.shapes.empty()) return RT_OK;
     const int variant = (no_skips ? 4 : 0) + (pool ? 2 : 0) + (lds ? 1 : 0);
     if (!pool) return jit_variant(ctx, variant, pool, lds, dyn_lds, static_blocks, fn, no_skips, 0, 0);
     // The pool kernel at 7 waves/SIMD (jit_options.hpp) and, compiled beside
@@ -724,7 +724,7 @@ int jit_function(rt_context* ctx, bool pool, bool lds, size_t dyn_lds, int stati
     int rc = jit_variant(ctx, variant, pool, lds, dyn_lds, static_blocks, fn, no_skips, 0, 16, true);
     if (rc) return rc;
     rc = jit_variant(ctx, variant + 8, pool, lds, dyn_lds, static_blocks, fn, no_skips, 7, kPool7ScratchMax);
-    if (rc || ctx->jit_failed) return rc;
+    if (rc || ctx->jit.failed) return rc;
     if (*fn) {
         if (pool_waves) *pool_waves = 7;
         return RT_OK;
@@ -739,7 +739,7 @@ int jit_wait(rt_context* ctx, double timeout_ms, int* pending) {
                           std::chrono::microseconds((int64_t)(timeout_ms < 0 ? 3.6e12 : timeout_ms * 1e3));
     auto left = [ctx] {
         int n = 0;
-        for (const auto& b : ctx->jit_build) n += b && b->state.load() == 0;
+        for (const auto& b : ctx->jit.build) n += b && b->state.load() == 0;
         return n;
     };
     std::unique_lock<std::mutex> lk(g_mu);
