@@ -286,6 +286,54 @@ int rt_color_at(rt_context* ctx, const double* rays, uint64_t n_rays,
                 uint32_t max_depth, uint32_t precision, double* out_rgb,
                 rt_stats* stats);
 
+/* Ray batches: World::color_at (world.rs:89-95) for ANY ray in ANY uploaded
+ * world.  rays[i] = {ox,oy,oz,dx,dy,dz}, rgb[i] = its colour.  Each ray's
+ * tree is walked by one GPU lane that sums its contributions in a fixed order
+ * (refraction subtree before reflection subtree), so there is no unit-length
+ * rule for directions and no brightness bound on the world (rt_color_at and
+ * rt_render* keep theirs), and results are bit-reproducible.  A zero or
+ * non-finite direction yields whatever the reference's arithmetic yields.
+ *   options.max_depth  `remaining` of the rays (<= RT_MAX_SUPPORTED_DEPTH);
+ *   options.precision  rt_precision: the element type of the device buffers;
+ *   options.flags      0, or RT_FLAG_NO_COUNTERS | RT_FLAG_NO_SKIPS |
+ *                      RT_FLAG_GENERATIONS | RT_FLAG_FAIL_LAUNCH;
+ *   options.reserved   0.
+ * Hits (optional): per ray, t of the PRIMARY ray's closest hit and the hit
+ * shape's index in the uploaded shape table; a miss is shape = -1 (t = +inf).
+ * At most 2^31 rays per call; n_rays = 0 is RT_OK.  Group contexts run the
+ * batch on rank 0. */
+typedef struct rt_ray_options {
+    uint32_t max_depth;
+    uint32_t precision;
+    uint32_t flags;
+    uint32_t reserved;
+} rt_ray_options;
+typedef struct rt_ray_hit_f32 {
+    float t;
+    int32_t shape;
+} rt_ray_hit_f32;
+typedef struct rt_ray_hit_f64 {
+    double t;
+    int32_t shape;
+    int32_t reserved;
+} rt_ray_hit_f64;
+
+/* Asynchronous, on `hip_stream` (NULL = HIP's default stream), no host sync,
+ * stream-ordered with the context's other launches as rt_render_device is.
+ * Caller-owned DEVICE buffers in the precision's own type: n_rays x 6 f32/f64
+ * in, n_rays x 3 out, and n_rays x rt_ray_hit_f32/_f64 (8/16-byte aligned) or
+ * NULL.  Counters accumulate into rt_read_counters; a device error is
+ * reported by the context's next synchronous call. */
+int rt_trace_rays_device(rt_context* ctx, const void* rays_device, uint64_t n_rays,
+                         const rt_ray_options* options, void* out_rgb_device,
+                         void* out_hit_device, void* hip_stream);
+/* Synchronous host convenience, like rt_color_at: f64 host arrays in and out
+ * for either precision (f32 rounds the rays once on the host and widens the
+ * results), out_hit = n_rays x rt_ray_hit_f64 or NULL, plus stats. */
+int rt_trace_rays(rt_context* ctx, const double* rays, uint64_t n_rays,
+                  const rt_ray_options* options, double* out_rgb, void* out_hit,
+                  rt_stats* stats);
+
 /* Diagnostics: the per-workgroup {start, end} s_memrealtime stamps (100 MHz)
  * of the last launch made with RT_FLAG_STAMPS; *n = number of workgroups. */
 int rt_debug_stamps(rt_context* ctx, uint64_t* out, uint32_t max_workgroups, uint32_t* n);

@@ -195,8 +195,8 @@ struct rt_context {
     int device = 0;
     int cu_count = 0;
     size_t lds_per_block = 64 * 1024;
-    size_t occ_lds[8] = {};     // occupancy cache: {direct,pool} x {f32,f64} x {global,LDS world}
-    int occ_blocks[8] = {};
+    size_t occ_lds[12] = {};    // occupancy cache: {direct,pool} x {f32,f64} x {global,LDS world},
+    int occ_blocks[12] = {};    // then the ray-batch kernel's {f32,f64} x {global,LDS world}
     Knobs knobs;
     rtc::Stream stream;
     rtc::Event ev_start, ev_stop;
@@ -224,7 +224,8 @@ struct rt_context {
     uint64_t scene_gen = 0;      // bumped by every rt_scene_upload
     uint32_t duplicate_shapes = 0;  // shapes value-equal to an earlier one (one identity class)
     std::vector<int32_t> world_slot;  // world index -> slot | kind << 24 of the uploaded table
-    rtc::DeviceBuffer<unsigned char> d_spill;  // ray-pool overflow regions, one per resident workgroup
+    // ray-pool overflow regions, one per resident workgroup; a ray batch's per-lane LIFOs (launch_rays)
+    rtc::DeviceBuffer<unsigned char> d_spill;
     TileOrder order;
     Jit jit;
     rtc::DeviceBuffer<unsigned char> d_scratch;  // host-buffer renders / color_at staging

@@ -35,6 +35,11 @@ hipError_t launch_trace(const LaunchParams<R>& P, bool pool, bool dup, uint32_t 
                         hipStream_t stream);
 template <typename R>
 hipError_t occupancy(bool pool, bool lds, size_t dyn_lds, int* blocks_per_cu);
+template <typename R>
+hipError_t launch_trace_rays(const LaunchParams<R>& P, bool dup, uint32_t grid, size_t dyn_lds, const void* rays,
+                             void* rgb, void* hits, hipStream_t stream);
+template <typename R>
+hipError_t occupancy_rays(bool lds, size_t dyn_lds, int* blocks_per_cu);
 
 namespace sp {  // rtc_kernels_sp.o: the f32 pool kernel for worlds of spheres and planes only
 template <typename R>
@@ -821,6 +826,99 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
     return RT_OK;
 }
 
+// Workgroups per CU of the ray-batch kernel (trace_rays) at `lds` dynamic
+// bytes, cached like blocks_per_cu's (keys 8..11 of the same table).
+template <typename R>
+int ray_blocks_per_cu(rt_context* ctx, bool lds_world, size_t lds, int* per_cu) {
+    const int key = 8 + (sizeof(R) == 8 ? 1 : 0) + (lds_world ? 2 : 0);
+    if (ctx->occ_lds[key] == lds && ctx->occ_blocks[key] > 0) {
+        *per_cu = ctx->occ_blocks[key];
+        return RT_OK;
+    }
+    int api = 0;
+    RT_HIP(occupancy_rays<R>(lds_world, lds, &api));
+    *per_cu = cap_by_lds(api, lds);
+    ctx->occ_lds[key] = lds;
+    ctx->occ_blocks[key] = *per_cu;
+    return RT_OK;
+}
+
+// A ray batch's launch: the world in LDS as for the other kernels, no pool
+// (cap = the per-lane LIFO's entries, none of them in LDS), a resident grid
+// striding over the batch's chunks of kBlock rays.
+template <typename R>
+int plan_rays(rt_context* ctx, const DevScene<R>& sc, uint32_t depth, uint32_t n_chunks, LaunchShape& ls) {
+    ls.pool = false;
+    const size_t wb = world_lds_bytes<R>(sc.kind_begin[kNumKinds], sc.n_materials, sc.n_patterns);
+    ls.world_lds = (ctx->knobs.lds_world && wb <= kMaxWorldLds) ? (uint32_t)wb : 0;
+    ls.lds = ls.world_lds;
+    ls.cap = ray_stack_entries(depth);
+    ls.lcap = ls.batch = 0;
+    ls.sched = kSchedStatic;
+    int per_cu = 0, rc;
+    if ((rc = ray_blocks_per_cu<R>(ctx, ls.world_lds != 0, ls.lds, &per_cu))) return rc;
+    ls.per_cu = std::max(per_cu, 1);
+    const uint64_t resident = (uint64_t)ls.per_cu * (uint64_t)ctx->cu_count;
+    ls.grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_chunks, resident));
+    ls.grid_tiles = n_chunks;
+    return RT_OK;
+}
+
+// One ray batch (rt_trace_rays*): n rays of R at d_rays -> RGB of R at d_rgb
+// and, if d_hits, the primary hits, on `stream`.  No range check of the
+// world and none of the directions: trace_rays sums per lane in plain R.
+template <typename R>
+int launch_rays(rt_context* ctx, DeviceWorld<R>& w, const void* d_rays, uint64_t n, const rt_ray_options* o,
+                void* d_rgb, void* d_hits, hipStream_t stream) {
+    int rc;
+    LaunchParams<R> P{};
+    P.scene = w.scene;
+    P.n_rays = n;
+    P.n_tiles = (uint32_t)((n + kBlock - 1) / kBlock);
+    P.max_depth = o->max_depth;
+    P.flags = o->flags;
+    P.counters = ctx->d_counters.get();
+    P.error_flag = ctx->d_error.get();
+    if (o->flags & RT_FLAG_GENERATIONS) P.gen_counts = ctx->d_gen_counts.get();
+    if ((rc = order_after_last(ctx, stream))) return rc;
+    LaunchShape ls;
+    if ((rc = plan_rays<R>(ctx, w.scene, o->max_depth, P.n_tiles, ls))) return rc;
+    P.pool_capacity = ls.cap;
+    P.persistent = ls.sched;
+    P.world_lds = ls.world_lds;
+    if (ls.cap) {
+        // the lanes' LIFOs share the pool's spill buffer: launches are ordered
+        // (order_after_last), so it has one user at a time
+        const size_t per_block = ray_stack_word(1, ls.cap, 0, 0) * sizeof(R);
+        if ((rc = ctx->d_spill.reserve((size_t)ls.grid * per_block))) return rc;
+        P.spill = ctx->d_spill.get();
+        P.spill_blocks = (uint32_t)std::min<size_t>(ctx->d_spill.capacity() / per_block, 0xFFFFFFFFu);
+    }
+    ctx->jit.used = false;
+    if (o->flags & RT_FLAG_FAIL_LAUNCH) return set_error(RT_ERR_HIP, "launch refused (RT_FLAG_FAIL_LAUNCH)");
+    if (hipError_t e = launch_trace_rays<R>(P, ctx->duplicate_shapes > 0, ls.grid, ls.lds, d_rays, d_rgb, d_hits, stream);
+        e != hipSuccess)
+        return set_error(RT_ERR_HIP, "launch of the ray-batch kernel (grid " + std::to_string(ls.grid) +
+                                         ", dynamic LDS " + std::to_string(ls.lds) + " B, " + std::to_string(ls.cap) +
+                                         " stack entries per lane): " + hipGetErrorString(e));
+    return RT_OK;
+}
+
+int check_ray_options(const rt_ray_options* o) {
+    if (!o) return set_error(RT_ERR_INVALID, "null options");
+    if (o->precision > RT_PRECISION_F64) return set_error(RT_ERR_INVALID, "unknown precision");
+    if (o->max_depth > RT_MAX_SUPPORTED_DEPTH) return set_error(RT_ERR_INVALID, "max_depth above RT_MAX_SUPPORTED_DEPTH");
+    constexpr uint32_t kRayFlags = RT_FLAG_NO_COUNTERS | RT_FLAG_FAIL_LAUNCH | RT_FLAG_GENERATIONS | RT_FLAG_NO_SKIPS;
+    if (o->flags & ~kRayFlags) return set_error(RT_ERR_INVALID, "flag not supported by ray batches");
+    return RT_OK;
+}
+
+int launch_rays_precision(rt_context* ctx, const void* d_rays, uint64_t n, const rt_ray_options* o, void* d_rgb,
+                          void* d_hits, hipStream_t stream) {
+    return o->precision == RT_PRECISION_F32 ? launch_rays<float>(ctx, ctx->w32, d_rays, n, o, d_rgb, d_hits, stream)
+                                            : launch_rays<double>(ctx, ctx->w64, d_rays, n, o, d_rgb, d_hits, stream);
+}
+
 InitTrace::InitTrace(const char* what) : what_(what), on_(debug_knob("trace_init", nullptr)) {
     t0_ = t_ = std::chrono::steady_clock::now();
 }
@@ -1496,6 +1594,81 @@ int rt_color_at(rt_context* ctx, const double* rays, uint64_t n, uint32_t depth,
         for (uint64_t i = 0; i < n * 3; ++i) out[i] = tmp[i];
     } else {
         RT_HIP(hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost));
+    }
+    if ((rc = check_pool_error(ctx))) return rc;
+    if (stats) {
+        if ((rc = read_counters(ctx, after))) return rc;
+        fill_stats(ctx, before, after, ms, stats);
+    }
+    return RT_OK;
+}
+
+int rt_trace_rays_device(rt_context* ctx, const void* rays_device, uint64_t n_rays, const rt_ray_options* o,
+                         void* out_rgb_device, void* out_hit_device, void* hip_stream) {
+    if (!ctx) return set_error(RT_ERR_INVALID, "null context");
+    if (!rays_device || !out_rgb_device) return set_error(RT_ERR_INVALID, "null rays or output");
+    int rc = check_ray_options(o);
+    if (rc) return rc;
+    if (n_rays > kMaxRayBatch) return set_error(RT_ERR_INVALID, "more than 2^31 rays in one batch");
+    if ((rc = check_ready(ctx))) return rc;
+    if (n_rays == 0) return RT_OK;
+    RT_HIP(hipSetDevice(ctx->device));
+    return launch_rays_precision(ctx, rays_device, n_rays, o, out_rgb_device, out_hit_device,
+                                 static_cast<hipStream_t>(hip_stream));
+}
+
+int rt_trace_rays(rt_context* ctx, const double* rays, uint64_t n, const rt_ray_options* o, double* out,
+                  void* out_hit_f64, rt_stats* stats) {
+    rt_ray_hit_f64* out_hit = static_cast<rt_ray_hit_f64*>(out_hit_f64);
+    if (!ctx) return set_error(RT_ERR_INVALID, "null context");
+    if (!rays || !out) return set_error(RT_ERR_INVALID, "null rays or output");
+    int rc = check_ray_options(o);
+    if (rc) return rc;
+    if (n > kMaxRayBatch) return set_error(RT_ERR_INVALID, "more than 2^31 rays in one batch");
+    if ((rc = check_ready(ctx))) return rc;
+    if (n == 0) {
+        if (stats) std::memset(stats, 0, sizeof(*stats));
+        return RT_OK;
+    }
+    RT_HIP(hipSetDevice(ctx->device));
+    // staging in the kernel's own real type: [rays][rgb][hits], each 16-byte aligned
+    const bool f32 = o->precision == RT_PRECISION_F32;
+    const size_t real = f32 ? sizeof(float) : sizeof(double);
+    auto align16 = [](size_t b) { return (b + 15) / 16 * 16; };
+    const size_t in_bytes = n * 6 * real, rgb_bytes = n * 3 * real;
+    const size_t hit_bytes = out_hit ? n * (f32 ? sizeof(rt_ray_hit_f32) : sizeof(rt_ray_hit_f64)) : 0;
+    const size_t rgb_at = align16(in_bytes), hit_at = rgb_at + align16(rgb_bytes);
+    if ((rc = ctx->d_scratch.reserve(hit_at + hit_bytes))) return rc;
+    unsigned char* d_rays = ctx->d_scratch.get();
+    unsigned char* d_rgb = d_rays + rgb_at;
+    unsigned char* d_hit = out_hit ? d_rays + hit_at : nullptr;
+    if (f32) {
+        std::vector<float> tmp(n * 6);
+        for (uint64_t i = 0; i < n * 6; ++i) tmp[i] = (float)rays[i];
+        RT_HIP(hipMemcpy(d_rays, tmp.data(), in_bytes, hipMemcpyHostToDevice));
+    } else {
+        RT_HIP(hipMemcpy(d_rays, rays, in_bytes, hipMemcpyHostToDevice));
+    }
+    unsigned long long before[kNumCounters], after[kNumCounters];
+    if ((rc = read_counters(ctx, before))) return rc;
+    RT_HIP(hipEventRecord(ctx->ev_start, ctx->stream));
+    if ((rc = launch_rays_precision(ctx, d_rays, n, o, d_rgb, d_hit, ctx->stream))) return rc;
+    RT_HIP(hipEventRecord(ctx->ev_stop, ctx->stream));
+    RT_HIP(hipStreamSynchronize(ctx->stream));
+    float ms = 0.f;
+    RT_HIP(hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop));
+    if (f32) {
+        std::vector<float> tmp(n * 3);
+        RT_HIP(hipMemcpy(tmp.data(), d_rgb, rgb_bytes, hipMemcpyDeviceToHost));
+        for (uint64_t i = 0; i < n * 3; ++i) out[i] = tmp[i];
+        if (out_hit) {
+            std::vector<rt_ray_hit_f32> h(n);
+            RT_HIP(hipMemcpy(h.data(), d_hit, hit_bytes, hipMemcpyDeviceToHost));
+            for (uint64_t i = 0; i < n; ++i) out_hit[i] = {h[i].t, h[i].shape, 0};
+        }
+    } else {
+        RT_HIP(hipMemcpy(out, d_rgb, rgb_bytes, hipMemcpyDeviceToHost));
+        if (out_hit) RT_HIP(hipMemcpy(out_hit, d_hit, hit_bytes, hipMemcpyDeviceToHost));
     }
     if ((rc = check_pool_error(ctx))) return rc;
     if (stats) {

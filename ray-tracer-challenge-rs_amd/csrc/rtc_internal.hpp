@@ -122,6 +122,32 @@ RTC_HD inline uint64_t spill_word(uint32_t block, uint32_t spill_cap, uint32_t s
     return ((uint64_t)block * spill_cap + (slot - lds_cap)) * 8u;
 }
 
+// Ray batches (rtc_kernels.hip trace_rays): one ray tree per lane, walked
+// depth first with a private LIFO of pending rays.  The lane holds the ray it
+// is shading in registers; shading pushes its children (at most two, each at
+// remaining - 1, none at remaining 0) and the lane then pops its next ray.
+// Entries the LIFO must hold for a tree of `max_depth`: by induction on the
+// walk, when the lane shades a ray at remaining r the LIFO holds at most one
+// pending sibling per ancestor, max_depth - r entries (the other sibling is
+// the ancestor's popped child on the path to this ray), and pushing two
+// children makes max_depth - r + 2.  Only rays at r >= 1 push, so the peak is
+// at r = 1: max_depth + 1 entries, reached by a path that spawns two children
+// at every level; a tree of depth 0 pushes nothing.
+// (Both children are stored and one is popped straight back: keeping it in
+// registers would save one entry and cost a second live ray through
+// shade_ray.)  tests/test_trace_rays_cpu.py models the walk against this.
+RTC_HD inline uint32_t ray_stack_entries(uint32_t max_depth) { return max_depth ? max_depth + 1u : 0u; }
+// Lane `tid` of workgroup `block` keeps entry e of its LIFO at this word (of
+// the launch's real type) of the stack buffer: 8 words per entry {o, d,
+// weight, remaining}, the 256 lanes of an entry adjacent, so a wave's push or
+// pop is one contiguous 2 KB (f32) run.
+RTC_HD inline uint64_t ray_stack_word(uint32_t block, uint32_t entries, uint32_t e, uint32_t tid) {
+    return (((uint64_t)block * entries + e) * 256u + tid) * 8u;
+}
+// Rays of one rt_trace_rays* call: chunks of 256 indexed in 32 bits with room
+// for the grid stride, element offsets in 64.
+constexpr uint64_t kMaxRayBatch = 1ull << 31;
+
 // RTC_BOUNDS_CHECK builds (debug variant, scripts/build_variant.sh): the pool
 // kernel checks every computed index against its buffer before the access,
 // skips a bad access and raises one of these bits of LaunchParams::error_flag

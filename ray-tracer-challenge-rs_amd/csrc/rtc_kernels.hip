@@ -2300,6 +2300,111 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(sizeof(R
     }
 }
 
+#ifndef RTC_JIT  // ray batches run the generic build only: per-scene sources stop here
+// Waves per SIMD the f32 ray-batch kernel is register-limited to.  Left to
+// itself it takes 82 VGPRs (5 waves, no scratch).  Same-box A/B, 1080p camera
+// rays, alternating builds (profiles/ab/ray_batch_waves_ab.jsonl), ms per
+// launch at 5 / 6 (80 VGPRs, no scratch) / 7 (72, 32 B/lane) / 8 (64, 64
+// B/lane): reflect_refract 0.844 / 0.877 / 1.076 / 0.934, cover 1.265 / 1.378
+// / 1.543 / 1.558, three_sphere 0.0377 / 0.0360 / 0.0371 / 0.0432.
+#ifndef RTC_RAYS_WAVES
+#define RTC_RAYS_WAVES 5
+#endif
+
+// A caller's ray batch (rt_trace_rays*), in the kernel's own real type.
+template <typename R>
+struct RayBatch {
+    const R* rays;  // n_rays x {o, d}
+    R* rgb;         // n_rays x 3
+    void* hits;     // n_rays x rt_ray_hit_f32 / rt_ray_hit_f64, or null
+};
+
+// trace_rays: one ray tree per lane, walked depth first.
+// The lane shades the ray it holds; shade_ray's push stores the children in
+// the lane's LIFO (ray_stack_word: a per-lane region of P.spill, the pool's
+// spill record per entry) and the lane pops its next ray, so the refraction
+// child's subtree (pushed last) is walked before the reflection child's.  The
+// colour is the plain sum of weight x surface in that order: one lane, one
+// order, no cross-lane sum, so results are bit-deterministic with no bound on
+// the world's brightness or on |d|.  Rays t * 256 + tid of chunk t; chunks
+// b, b + G, ... per workgroup (the LIFO regions are per resident workgroup).
+// The wave leaves the walk when none of its lanes holds a ray: the trip count
+// is bounded by the tree's size, 2^(max_depth + 1) - 1, whatever the rays hold.
+template <typename R, bool kLds, bool kDup>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(sizeof(R) == 4 ? RTC_RAYS_WAVES : 1))) void trace_rays(
+    LaunchParams<R> P, RTC_WORLD_PARAMS(R), RayBatch<R> B) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const DevScene<R> sc = scene_view<R, kLds>(P, shapes, materials, patterns, lights, smem, true);
+    Counts k = {};
+    const uint32_t tid = threadIdx.x;
+    // (a workgroup beyond the stack buffer's regions keeps no LIFO: its pushes raise the overflow bit)
+    const uint32_t cap = blockIdx.x < P.spill_blocks ? P.pool_capacity : 0u;
+    RTC_AS_GLOBAL R* const stack = (RTC_AS_GLOBAL R*)P.spill + ray_stack_word(blockIdx.x, cap, 0, tid);
+    constexpr uint32_t kEntryWords = 8u * kBlock;
+    // Chunks b, b + G, ...: no atomics and no barrier, so the four waves of a
+    // workgroup run on independently.  (Taking the chunks of worlds with
+    // secondary rays from the pool kernel's per-XCD queues instead, one
+    // barrier per chunk, measured 15 % slower on reflect_refract and 11 % on
+    // cover at 1080p: profiles/ab/ray_batch_queue_rejected.jsonl.)
+    for (uint32_t t = blockIdx.x; t < P.n_tiles; t += gridDim.x) {  // (n_tiles <= 2^23: no wrap)
+        const uint64_t r = (uint64_t)t * kBlock + tid;
+        const bool valid = r < P.n_rays;
+        V3<R> o = {(R)0, (R)0, (R)0}, d = o;
+        if (valid) {
+            const R* q = B.rays + 6 * r;
+            o = {q[0], q[1], q[2]};
+            d = {q[3], q[4], q[5]};
+        }
+        if (B.hits) {  // the primary ray's closest hit: t and the shape's world index
+            if (valid) {
+                const Hit<R> h = closest_hit(sc, o, d);
+                const int32_t shape = h.slot < 0 ? -1 : (int32_t)h.world;
+                const R ht = h.slot < 0 ? Real<R>::kInf : h.t;
+                if constexpr (sizeof(R) == 4) {
+                    typedef float f2 __attribute__((ext_vector_type(2)));
+                    static_cast<f2*>(B.hits)[r] = f2{ht, __int_as_float(shape)};
+                } else {
+                    typedef double d2 __attribute__((ext_vector_type(2)));
+                    static_cast<d2*>(B.hits)[r] = d2{ht, __longlong_as_double((long long)(uint32_t)shape)};
+                }
+            }
+        }
+        V3<R> acc = {(R)0, (R)0, (R)0};
+        R w = (R)1;
+        uint32_t rem = P.max_depth, top = 0;
+        bool active = valid, primary = valid;
+        while (wave_any(active)) {
+            Shaded<R> sh;
+            bool hit = false;
+            auto push = [&](V3<R> co, V3<R> cd, R cw) {
+                if (top < cap) {
+                    spill_store<R>(stack + (size_t)top * kEntryWords, co, cd, w * cw, rem - 1u);
+                    ++top;
+                } else {
+                    atomicOr(P.error_flag, kErrPoolOverflow);
+                }
+            };
+            if (active) hit = shade_ray<R, true, kDup>(sc, o, d, rem, sh, push);
+            count_events(k, primary, hit, sh, sc.n_lights);
+            if (P.gen_counts) count_generations(P.gen_counts, active, hit, rem);
+            if (hit) acc = {acc.x + w * sh.surface.x, acc.y + w * sh.surface.y, acc.z + w * sh.surface.z};
+            primary = false;
+            active = top > 0;
+            if (active) {
+                --top;
+                spill_load<R>(stack + (size_t)top * kEntryWords, o, d, w, rem);
+            }
+        }
+        if (valid) {
+            R* c = B.rgb + 3 * r;
+            __builtin_nontemporal_store(acc.x, c);
+            __builtin_nontemporal_store(acc.y, c + 1);
+            __builtin_nontemporal_store(acc.z, c + 2);
+        }
+    }
+    if (!(P.flags & RT_FLAG_NO_COUNTERS)) flush_counts(k, P.counters);
+}
+#endif  // !RTC_JIT
 
 #ifndef RTC_PRECISION
 #define RTC_PRECISION 0
@@ -2594,6 +2699,43 @@ template hipError_t occupancy<float>(bool, bool, size_t, int*);
 #if RTC_PRECISION != 1
 template hipError_t launch_trace<double>(const LaunchParams<double>&, bool, bool, uint32_t, size_t, hipStream_t);
 template hipError_t occupancy<double>(bool, bool, size_t, int*);
+#endif
+
+// The ray-batch kernel (trace_rays): `rays`, `rgb` and `hits` in R.
+template <typename R>
+hipError_t launch_trace_rays(const LaunchParams<R>& P, bool dup, uint32_t grid, size_t dyn_lds, const void* rays,
+                             void* rgb, void* hits, hipStream_t stream) {
+    (void)hipGetLastError();  // see launch_trace
+    const RayBatch<R> B{static_cast<const R*>(rays), static_cast<R*>(rgb), hits};
+#define RTC_LAUNCH(...)                                                                                      \
+    hipLaunchKernelGGL((trace_rays<R, __VA_ARGS__>), dim3(grid), dim3(kBlock), dyn_lds, stream, P, P.scene.shapes, \
+                       P.scene.materials, P.scene.patterns, P.scene.lights, B)
+    if (P.world_lds != 0) {
+        if (dup) RTC_LAUNCH(true, true);
+        else RTC_LAUNCH(true, false);
+    } else {
+        if (dup) RTC_LAUNCH(false, true);
+        else RTC_LAUNCH(false, false);
+    }
+#undef RTC_LAUNCH
+    return hipGetLastError();
+}
+
+template <typename R>
+hipError_t occupancy_rays(bool lds, size_t dyn_lds, int* blocks_per_cu) {
+    return lds ? hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, trace_rays<R, true, false>, kBlock, dyn_lds)
+               : hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, trace_rays<R, false, false>, kBlock,
+                                                              dyn_lds);
+}
+#if RTC_PRECISION != 2
+template hipError_t launch_trace_rays<float>(const LaunchParams<float>&, bool, uint32_t, size_t, const void*, void*,
+                                             void*, hipStream_t);
+template hipError_t occupancy_rays<float>(bool, size_t, int*);
+#endif
+#if RTC_PRECISION != 1
+template hipError_t launch_trace_rays<double>(const LaunchParams<double>&, bool, uint32_t, size_t, const void*, void*,
+                                              void*, hipStream_t);
+template hipError_t occupancy_rays<double>(bool, size_t, int*);
 #endif
 
 #if RTC_PRECISION != 2

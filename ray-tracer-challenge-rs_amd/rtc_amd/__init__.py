@@ -115,6 +115,16 @@ class Stats(C.Structure):
         return d
 
 
+class RayOptions(C.Structure):
+    _fields_ = [("max_depth", C.c_uint32), ("precision", C.c_uint32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+# rt_ray_hit_f64 / rt_ray_hit_f32 as numpy records
+RAY_HIT_F64 = np.dtype([("t", np.float64), ("shape", np.int32), ("reserved", np.int32)])
+RAY_HIT_F32 = np.dtype([("t", np.float32), ("shape", np.int32)])
+
+
 class GenerationCounts(C.Structure):
     _fields_ = [("traced", C.c_uint64 * (RT_MAX_SUPPORTED_DEPTH + 1)),
                 ("shaded", C.c_uint64 * (RT_MAX_SUPPORTED_DEPTH + 1))]
@@ -174,6 +184,10 @@ def _load() -> C.CDLL:
         "rt_render_device": (C.c_int, [C.c_void_p, P(CameraDesc), P(RenderOptions), C.c_void_p, C.c_void_p]),
         "rt_color_at": (C.c_int, [C.c_void_p, P(C.c_double), C.c_uint64, C.c_uint32, C.c_uint32, P(C.c_double),
                                   P(Stats)]),
+        "rt_trace_rays_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, P(RayOptions), C.c_void_p, C.c_void_p,
+                                           C.c_void_p]),
+        "rt_trace_rays": (C.c_int, [C.c_void_p, P(C.c_double), C.c_uint64, P(RayOptions), P(C.c_double), C.c_void_p,
+                                    P(Stats)]),
         "rt_read_counters": (C.c_int, [C.c_void_p, P(Stats)]),
         "rt_read_generation_counts": (C.c_int, [C.c_void_p, P(GenerationCounts)]),
         "rt_debug_stamps": (C.c_int, [C.c_void_p, P(C.c_uint64), C.c_uint32, P(C.c_uint32)]),
@@ -231,6 +245,7 @@ _lib = _load()
 EXPORTED_SYMBOLS = (
     "rt_abi_version", "rt_last_error", "rt_device_count", "rt_context_create", "rt_context_destroy",
     "rt_scene_upload", "rt_shard_rows", "rt_render", "rt_render_device", "rt_color_at", "rt_read_counters",
+    "rt_trace_rays", "rt_trace_rays_device",
     "rt_read_generation_counts",
     "rt_debug_stamps", "rt_debug_tile_costs", "rt_debug_item_log", "rt_debug_intersect", "rt_debug_normal", "rt_camera_set_transform",
     "rt_shard_row_map", "rt_context_create_multi", "rt_comm_unique_id", "rt_context_create_rank", "rt_context_group",
@@ -387,6 +402,35 @@ def load_scene_text(text: str) -> SceneTables:
     return _load_with(_lib.rt_scene_load_yaml_text, text.encode())
 
 
+def _ray_batch_kind(rays, precision, device):
+    """("torch" | "numpy", "f32" | "f64") of a ray batch for Context.trace_rays, or ValueError."""
+    if precision is not None and precision not in PRECISIONS:
+        raise ValueError(f"precision must be one of {sorted(PRECISIONS)} or None")
+    if isinstance(rays, np.ndarray):
+        kind, names = "numpy", {np.dtype(np.float32): "f32", np.dtype(np.float64): "f64"}
+        contiguous = rays.flags.c_contiguous
+    else:
+        import sys
+        torch = sys.modules.get("torch")  # (a tensor cannot exist unless torch is loaded)
+        if torch is None or not isinstance(rays, torch.Tensor):
+            raise ValueError("rays must be a numpy array or a torch tensor of shape (n, 6)")
+        kind, names = "torch", {torch.float32: "f32", torch.float64: "f64"}
+        contiguous = rays.is_contiguous()
+        if not rays.is_cuda or rays.device.index != device:
+            raise ValueError(f"rays are on {rays.device}, the context drives cuda:{device}")
+    if rays.ndim != 2 or rays.shape[1] != 6:
+        raise ValueError(f"rays must have shape (n, 6), not {tuple(rays.shape)}")
+    if rays.dtype not in names:
+        raise ValueError(f"rays must be float32 or float64, not {rays.dtype}")
+    if not contiguous:
+        raise ValueError("rays must be C-contiguous")
+    if kind == "numpy":  # host rays travel as f64 either way (rt_trace_rays): `precision` may choose the kernel
+        return kind, precision or names[rays.dtype]
+    if precision is not None and precision != names[rays.dtype]:
+        raise ValueError(f"precision {precision} does not match the tensor's dtype {rays.dtype}")
+    return kind, names[rays.dtype]
+
+
 class Context:
     """One GPU.  Mirrors the borrow in Camera::render(&self, world: &World)."""
 
@@ -521,6 +565,47 @@ class Context:
         _check(_lib.rt_color_at(self._h, r.ctypes.data_as(C.POINTER(C.c_double)), r.shape[0], depth,
                                 PRECISIONS[precision], out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(st)))
         return out, st.as_dict()
+
+    def trace_rays(self, rays, depth: int = RT_DEFAULT_MAX_DEPTH, precision: str | None = None, hits: bool = False,
+                   flags: int = 0):
+        """World::color_at for any rays in any uploaded world (rtc.h rt_trace_rays*): no unit-length rule, no
+        brightness bound.  rays (n, 6) = origin, direction, float32 or float64, C-contiguous; the dtype is the
+        precision (a tensor's must agree with `precision` if given; a numpy batch travels as f64 and
+        `precision` may pick the f32 kernel for it).
+          - a torch tensor on this context's device: rt_trace_rays_device on torch's current stream, no sync,
+            no host copy; returns colours (n, 3), with hits=True (colours, t (n,), shape (n,) int32);
+          - a numpy array: rt_trace_rays; returns (colours f64, stats), with hits=True (colours, t, shape, stats).
+        shape is the primary hit's index in the uploaded shape table, -1 on a miss (t = inf).
+        Raises ValueError for anything else before the library is called."""
+        kind, prec = _ray_batch_kind(rays, precision, self.device)
+        opts = RayOptions(int(depth), PRECISIONS[prec], int(flags), 0)
+        n = int(rays.shape[0])
+        if kind == "torch":
+            import torch
+            rgb = torch.empty((n, 3), dtype=rays.dtype, device=rays.device)
+            # rt_ray_hit_f32 = {f32, i32}, rt_ray_hit_f64 = {f64, i32, i32}: n x 2 words of the real's size
+            rec = torch.empty((n, 2), dtype=torch.int32 if prec == "f32" else torch.int64,
+                              device=rays.device) if hits else None
+            if n:
+                stream = torch.cuda.current_stream(rays.device).cuda_stream
+                _check(_lib.rt_trace_rays_device(self._h, C.c_void_p(rays.data_ptr()), n, C.byref(opts),
+                                                 C.c_void_p(rgb.data_ptr()),
+                                                 C.c_void_p(rec.data_ptr()) if hits else None, C.c_void_p(stream or 0)))
+            if not hits:
+                return rgb
+            t = rec[:, 0].view(rays.dtype).contiguous()
+            shape = (rec[:, 1] if prec == "f32" else rec.view(torch.int32).reshape(n, 4)[:, 2]).contiguous()
+            return rgb, t, shape
+        r = np.ascontiguousarray(rays, dtype=np.float64)
+        out = np.zeros((n, 3), dtype=np.float64)
+        rec = np.zeros(n, dtype=RAY_HIT_F64) if hits else None
+        st = Stats()
+        _check(_lib.rt_trace_rays(self._h, r.ctypes.data_as(C.POINTER(C.c_double)), n, C.byref(opts),
+                                  out.ctypes.data_as(C.POINTER(C.c_double)),
+                                  rec.ctypes.data_as(C.c_void_p) if hits else None, C.byref(st)))
+        if not hits:
+            return out, st.as_dict()
+        return out, rec["t"].copy(), rec["shape"].copy(), st.as_dict()
 
     def debug_stamps(self) -> np.ndarray:
         """(workgroups, 2) s_memrealtime {start, end} of the last RT_FLAG_STAMPS launch (100 MHz ticks)."""
