@@ -63,6 +63,15 @@ int rt_camera_resize(rt_camera_desc* camera, uint32_t width, uint32_t height);
  * row-major `transform` and update the origin (camera.rs:114-116). */
 int rt_camera_set_transform(rt_camera_desc* camera, const double transform[16]);
 
+/* The inclusive pixel rectangle {x0, y0, x1, y1} of `camera`'s canvas that
+ * holds every pixel whose f32 primary ray can pass the kernels' wave cull of
+ * a bounding ball `bound` = {centre, radius^2} as the f32 shape table holds
+ * it: what a frame's launch hands the per-scene direct kernel for each shape
+ * (its primary cull).  The whole canvas where no cull applies (the eye in or
+ * beside the ball, radius^2 negative or not finite, a camera transformation
+ * that is no similarity); x0 > x1 for a ball behind the camera.  Host only. */
+int rt_camera_bound_rect(const rt_camera_desc* camera, const float bound[4], uint32_t rect[4]);
+
 /* Matrix<4>::inverse, row-major 16 doubles. */
 int rt_matrix_inverse(const double m[16], double out[16]);
 

@@ -24,6 +24,7 @@
 #include "flop_model.hpp"
 #include "host_math.hpp"
 #include "debug_knobs.hpp"
+#include "primary_rect.hpp"
 #include "rtc_context.hpp"
 #include "rtc_internal.hpp"
 #include "shape_identity.hpp"
@@ -807,6 +808,29 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
         if (w.scene.kind_begin[k + 1] > w.scene.kind_begin[k]) kinds |= 1u << k;
     const bool sp = sizeof(R) == 4 && ls.pool && ctx->knobs.kind_variants && (kinds & ~kKindsSp) == 0 && !dup;
     if (flags & RT_FLAG_FAIL_LAUNCH) return set_error(RT_ERR_HIP, "launch refused (RT_FLAG_FAIL_LAUNCH)");
+    if constexpr (sizeof(R) == 4) {
+        // The per-scene direct kernel's primary cull: each slot's screen
+        // rectangle for this camera (primary_rect.hpp), from the f32 bounds
+        // the kernel's own ball test reads, as miss bits per block column and
+        // block row (rtc_internal.hpp).  Recomputed every launch (the camera
+        // is the call's argument); a few hundred ns for a small world.
+        const size_t ns = ctx->jit.shapes.size();
+        if (jf && !ls.pool && cam && ns <= (size_t)kPrimaryRectSlots && (int)ns == w.scene.kind_begin[kNumKinds] &&
+            P.width <= kCullCols * kCullCellW && P.height <= kCullRows * kCullCellH) {
+            const uint32_t nc = (P.width + kCullCellW - 1) / kCullCellW, nr = (P.height + kCullCellH - 1) / kCullCellH;
+            for (size_t s = 0; s < ns; ++s) {
+                uint32_t r[4];
+                primary_rect(P.cam, P.width, P.height, ctx->jit.shapes[s].bound, r);
+                const bool none = r[0] > r[2] || r[1] > r[3];  // empty: every block misses
+                const uint32_t c0 = none ? nc : r[0] / kCullCellW, c1 = none ? 0 : r[2] / kCullCellW + 1;
+                const uint32_t r0 = none ? nr : r[1] / kCullCellH, r1 = none ? 0 : r[3] / kCullCellH + 1;
+                for (uint32_t i = 0; i < nc; ++i)
+                    if (i < c0 || i >= c1) P.cull_cols[i] |= 1u << s;
+                for (uint32_t j = 0; j < nr; ++j)
+                    if (j < r0 || j >= r1) P.cull_rows[j] |= 1u << s;
+            }
+        }
+    }
     if (jf) {
         const ShapeRec<R>* sh = P.scene.shapes;
         const MaterialRec<R>* mt = P.scene.materials;

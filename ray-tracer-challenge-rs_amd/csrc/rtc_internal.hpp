@@ -351,6 +351,24 @@ struct DevScene {
     int32_t no_skips;       // RT_FLAG_NO_SKIPS launch (the generic kernels; per-scene builds: RTC_NO_SKIPS)
 };
 
+// Primary cull of the per-scene f32 direct kernel (rtc_kernels.hip
+// closest_hit): each launch of a camera frame works out, per shape slot, the
+// screen rectangle outside which no primary ray can pass the slot's wave cull
+// (primary_rect.hpp), and hands it over as two bit tables over the kernel's
+// wave blocks (kCullCellW x kCullCellH pixels): bit s of cull_cols[i] is set
+// when slot s's rectangle misses pixel columns [16 i, 16 i + 15], bit s of
+// cull_rows[j] when it misses rows [4 j, 4 j + 3].  A wave passes slot s by
+// when either bit of its block is set: two scalar loads and an OR per wave
+// and tile, whatever the number of slots (a compare of the block against each
+// rectangle cost ~14 SALU per slot and ate the gain: the scalar unit is as
+// busy as the vector units in this kernel).  All zero (no
+// cull) for every other launch, for worlds of more than kPrimaryRectSlots
+// slots (the same small-world limit as RTC_JIT_NORMAL_MAX) and for canvases
+// beyond the tables.
+constexpr int kPrimaryRectSlots = 8;
+constexpr uint32_t kCullCellW = 16, kCullCellH = 4;
+constexpr uint32_t kCullCols = 128, kCullRows = 512;  // canvases up to 2048 x 2048
+
 // One launch of the tracer.
 template <typename R>
 struct LaunchParams {
@@ -388,6 +406,8 @@ struct LaunchParams {
     unsigned long long* counters;      // kCounterShards x kNumCounters cumulative u64
     unsigned long long* gen_counts;    // RT_FLAG_GENERATIONS: traced[kGenSlots], shaded[kGenSlots]; else null
     int32_t* error_flag;               // set nonzero on pool overflow
+    uint32_t cull_cols[kCullCols];     // primary cull: slots whose rectangle misses a block column ...
+    uint32_t cull_rows[kCullRows];     // ... or a block row (above); zero = none
 };
 
 }  // namespace rtc

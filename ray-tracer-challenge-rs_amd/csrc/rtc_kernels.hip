@@ -647,6 +647,38 @@ __device__ inline bool wave_ball_may_hit(R cx, R cy, R cz, R r2, V3<R> o, V3<R> 
     return (front & __builtin_amdgcn_ballot_w64(Real<R>::madd(oo, kKeep, -r2) * dd <= tc * tc)) != 0;
 }
 
+// The same cull for shadow rays, from the light's side (the per-scene f32
+// direct build, any_hit): every shadow segment of a light ends at the light l, so the
+// half-line from l through the surface point holds the segment, and "can it
+// meet the ball" needs only tl = l - point and tt = |tl|^2, which shade_ray
+// has formed already.  With cl = c - l: the line passes within r of c iff
+// (|cl|^2 kKeep - r^2) tt <= (cl . tl)^2, and the centre is not behind the
+// light iff cl . tl <= 0 (the half-line runs along -tl) or the light is
+// inside the ball.  In a per-scene build c, r^2 and l are constants: cl,
+// |cl|^2 and the bracket fold, a light inside the ball (or r^2 = +inf:
+// RTC_DEBUG=cull=0) folds the whole test to "may hit", and a lane pays one dot
+// with constants, two multiplies and two compares where wave_ball_may_hit
+// pays oc, two dots, a multiply-add, two multiplies and three compares.
+// Conservative like the first form: DESIGN.md 3.3 (the margin holds for
+// segments up to kLightCullFar long; any_hit takes the first form for waves
+// with a longer one).  Unlike the first form it does not reject a ball that
+// lies beyond the point: the direct kernel's small worlds gain (three_sphere
+// -3.5 %), the pool kernel's do not all (same box: table 4K -5.5 %,
+// reflect_refract -1.8 %, but cover 4K +3.2 %: its piled cubes lie beyond
+// most lit points), so only the direct kernel takes it (any_hit kDirect).
+#ifndef RTC_SHADOW_LIGHT_CULL
+#define RTC_SHADOW_LIGHT_CULL 1  // (A/B builds: 0 keeps the first form for shadow rays)
+#endif
+template <typename R>
+__device__ inline bool wave_ball_may_hit_from(R cx, R cy, R cz, R r2, V3<R> l, V3<R> tl, R tt) {
+    constexpr R kKeep = sizeof(R) == 4 ? (R)(1 - 1e-5) : (R)(1 - 1e-12);
+    const V3<R> cl = {cx - l.x, cy - l.y, cz - l.z};
+    const R k = Real<R>::madd(dot(cl, cl), kKeep, -r2);
+    if (!(k > (R)0)) return true;  // the light inside the ball, or an unbounded one (wave-uniform; a constant)
+    const R tc = dot(cl, tl);
+    return (__builtin_amdgcn_ballot_w64(tc <= (R)0) & __builtin_amdgcn_ballot_w64(k * tt <= tc * tc)) != 0;
+}
+
 template <typename R, int K>
 __device__ inline bool wave_may_hit(const ShapeRec<R>& s, V3<R> o, V3<R> d, R dd) {
     if constexpr (K == RT_SHAPE_PLANE) return true;
@@ -734,34 +766,35 @@ constexpr bool jit_cluster_convex() {
     }
     return true;
 }
-template <bool kHalfLine, int C, typename F, typename S>
+template <bool kHalfLine, bool kBall, int C, typename F, typename S>
 __device__ inline void jit_clusters(V3<float>& o, V3<float>& d, float dd, F&& f, S&& skip) {
     if constexpr (C < jit::kNumClusters) {
         jit_fence(o, d);
         if (!skip(jit::kClusterBall[C][0], jit::kClusterBall[C][1], jit::kClusterBall[C][2], jit::kClusterBall[C][3],
                   jit_cluster_convex<C>()) &&
-            wave_ball_may_hit<float, kHalfLine>(jit::kClusterBall[C][0], jit::kClusterBall[C][1], jit::kClusterBall[C][2],
-                                                jit::kClusterBall[C][3], o, d, dd))
+            (!kBall || wave_ball_may_hit<float, kHalfLine>(jit::kClusterBall[C][0], jit::kClusterBall[C][1],
+                                                           jit::kClusterBall[C][2], jit::kClusterBall[C][3], o, d, dd)))
             jit_members<C, jit::kClusterBegin[C]>(f);
-        jit_clusters<kHalfLine, C + 1>(o, d, dd, f, skip);
+        jit_clusters<kHalfLine, kBall, C + 1>(o, d, dd, f, skip);
     }
 }
 #endif
 // `skip(centre, r^2, convex)`: a caller's wave-uniform reason to pass a
 // cluster by before its ball test (none by default); `convex`: every member
-// is a sphere or a cube.
+// is a sphere or a cube.  kBall = false: the caller's skip holds a ball test
+// of its own (any_hit's, from the light's side) and this one is left out.
 struct NoSkip {
     template <typename... A>
     __device__ bool operator()(A...) const {
         return false;
     }
 };
-template <typename R, bool kHalfLine, typename F, typename S = NoSkip>
+template <typename R, bool kHalfLine, bool kBall = true, typename F, typename S = NoSkip>
 __device__ inline void for_all_culled(const DevScene<R>& sc, V3<R>& o, V3<R>& d, R dd, F&& f, S&& skip = S{}) {
 #ifdef RTC_JIT
     if constexpr (sizeof(R) == 4 && jit::kNumClusters > 0) {
         jit_unclustered<0>(f);
-        jit_clusters<kHalfLine, 0>(o, d, dd, f, skip);
+        jit_clusters<kHalfLine, kBall, 0>(o, d, dd, f, skip);
         return;
     }
 #endif
@@ -878,22 +911,65 @@ __device__ inline bool skips_on(const DevScene<R>& sc) {
 #endif
 }
 
-template <typename R>
-__device__ inline Hit<R> closest_hit(const DevScene<R>& sc, V3<R> o, V3<R> d) {
+// Primary cull (per-scene f32 direct kernel, camera frames): every primary
+// ray starts at the camera, so whether a wave's pixel block can meet a shape's
+// bounding ball is a question about pixel rectangles.  The host hands each
+// launch the rectangle outside which no pixel's ray passes the shape's ball
+// test (primary_rect.hpp), as miss bits per block column and block row
+// (LaunchParams::cull_cols, cull_rows); a wave whose block
+// misses it passes the shape by on a scalar bit test, before the per-lane
+// test (wave_may_hit), which the blocks that overlap still run.  Acceleration
+// only, like the ball test it stands in front of.  PixelBlock: bit s set =
+// the wave's block misses slot s's rectangle, wave-uniform by construction
+// (trace_direct wave_pixel_block); NoBlock: every other caller, nothing changes.
+#ifndef RTC_PRIMARY_RECTS
+#define RTC_PRIMARY_RECTS 1  // (A/B builds: 0 keeps the per-lane test alone)
+#endif
+struct NoBlock {
+    static constexpr bool kOn = false;
+    __device__ bool misses(int) const { return false; }
+};
+struct PixelBlock {
+    static constexpr bool kOn = true;
+    uint32_t miss;
+    __device__ inline bool misses(int slot) const { return (miss >> slot) & 1u; }
+};
+
+template <typename R, typename B = NoBlock>
+__device__ inline Hit<R> closest_hit(const DevScene<R>& sc, V3<R> o, V3<R> d, B blk = B{}) {
     Nearest<R> best;
-    const R dd = dot(d, d), rdd = recip(dd);
-    const V3<R> rd = recip3(d);
-    for_all_culled<R, true>(sc, o, d, dd, [&]<int K>(const ShapeRec<R>& s, int slot) {
+#if defined(RTC_JIT) && !defined(RTC_NO_SKIPS) && RTC_PRIMARY_RECTS
+    constexpr bool kRects = B::kOn && sizeof(R) == 4 && jit::kBegin[kNumKinds] <= kPrimaryRectSlots;
+    // |d|^2 and the reciprocals are formed where a shape that uses them
+    // survives, so a wave that passes every bounded shape by pays for none
+    // (worlds without clusters: a cluster's ball test needs |d|^2 up front)
+    constexpr bool kLazy = kRects && jit::kNumClusters == 0;
+#else
+    constexpr bool kRects = false, kLazy = false;
+#endif
+    R dd0 = (R)0, rdd0 = (R)0;
+    V3<R> rd0 = {(R)0, (R)0, (R)0};
+    if constexpr (!kLazy) {
+        dd0 = dot(d, d);
+        rdd0 = recip(dd0);
+        rd0 = recip3(d);
+    }
+    for_all_culled<R, true>(sc, o, d, dd0, [&]<int K>(const ShapeRec<R>& s, int slot) {
         jit_fence(o, d, slot);
+        if constexpr (kRects && K != RT_SHAPE_PLANE)
+            if (blk.misses(slot)) return;  // wave-uniform, SALU
+        const R dd = kLazy ? dot(d, d) : dd0;
         if (!wave_may_hit<R, K>(s, o, d, dd)) return;
         // (per-scene records: the slot rides below the world index; world
         // indices are distinct, so the order is the world order)
         const int w = kJitRecords && sizeof(R) == 4 ? (s.world_index << 8) | slot : s.world_index;
         if (world_sphere<R, K>(s)) {
+            const R rdd = kLazy ? recip(dd) : rdd0;
             sphere_world<R, true>(s, o, d, dd, rdd, [&](R t, bool v) { best.offer(t, v, w); });
             return;
         }
         if (world_cube<R, K>(s)) {  // (an enclosing cube's exit too: tmin < 0 keeps tmax)
+            const V3<R> rd = kLazy ? recip3(d) : rd0;
             cube_world<R, true>(s, o, d, rd, [&](R t, bool v) { best.offer(t, v, w); });
             return;
         }
@@ -957,18 +1033,47 @@ struct Blocker {
 };
 
 // is_in_shadow (world.rs:98-112): any casting shape with 0 <= t < distance.
-// lpos: the light the ray runs to (o + dist d).
-template <typename R>
+// lpos: the light the ray runs to (o + dist d).  kDirect: called by the
+// direct kernel (its per-scene build culls from the light's side).
+template <typename R, bool kDirect = false>
 __device__ inline bool any_hit(const DevScene<R>& sc, V3<R> o, V3<R> d, R dist, V3<R> lpos) {
     Blocker<R> b;
-    const R dd = dot(d, d), rdd = recip(dd);
-    const V3<R> rd = recip3(d);
+#if defined(RTC_JIT) && !defined(RTC_NO_SKIPS) && RTC_SHADOW_LIGHT_CULL
+    // the per-scene f32 direct build culls from the light's side (wave_ball_may_hit_from)
+    constexpr bool kLight = sizeof(R) == 4 && kDirect;
+#else
+    constexpr bool kLight = false;
+#endif
+    // |d|^2 and the reciprocals: up front, or (kLight) where a shape that
+    // uses them survives its cull
+    R dd0 = (R)0, rdd0 = (R)0;
+    V3<R> rd0 = {(R)0, (R)0, (R)0};
+    if constexpr (!kLight) {
+        dd0 = dot(d, d);
+        rdd0 = recip(dd0);
+        rd0 = recip3(d);
+    }
+    // tl and tt as shade_ray forms them for the light's distance (the same
+    // expressions: one computation); a wave with a segment longer than
+    // kLightCullFar (or not a number) keeps the first form of the test
+    constexpr R kLightCullFar = (R)100;
+    const V3<R> tl = vsub(lpos, o);
+    const R tt = Real<R>::madd(tl.z, tl.z, Real<R>::madd(tl.y, tl.y, tl.x * tl.x));
+    const bool near = kLight && !wave_any(!(tt <= kLightCullFar * kLightCullFar));
+    auto ball_may_hit = [&](R cx, R cy, R cz, R r2) {
+        if (kLight && near) return wave_ball_may_hit_from<R>(cx, cy, cz, r2, lpos, tl, tt);
+        return wave_ball_may_hit<R, true>(cx, cy, cz, r2, o, d, kLight ? dot(d, d) : dd0);
+    };
     // once every active lane is blocked the remaining clusters cannot change
     // the answer (per cluster, not per shape: a per-shape check measured
     // slower in round 3; per cluster cover -2.5 %, cylinders -4 %, table +1 %)
     const bool skips = skips_on(sc);
-    auto skip = [&](R, R, R, R, bool) { return skips && !wave_any(!b.blocked(dist)); };
-    for_all_culled<R, true>(sc, o, d, dd, [&]<int K>(const ShapeRec<R>& s, int slot) {
+    auto skip = [&](R cx, R cy, R cz, R r2, bool) {
+        if (skips && !wave_any(!b.blocked(dist))) return true;
+        if constexpr (kLight) return !ball_may_hit(cx, cy, cz, r2);  // (stands in for for_all_culled's test)
+        return false;
+    };
+    for_all_culled<R, true, !kLight>(sc, o, d, dd0, [&]<int K>(const ShapeRec<R>& s, int slot) {
         if (!s.casts_shadow) return;  // wave-uniform
         jit_fence(o, d, slot);
         if (K == RT_SHAPE_CUBE && skips) {
@@ -997,13 +1102,21 @@ __device__ inline bool any_hit(const DevScene<R>& sc, V3<R> o, V3<R> d, R dist, 
                 clear = clear || (Real<R>::fabs(po.x) < (R)1 && Real<R>::fabs(po.y) < (R)1 && Real<R>::fabs(po.z) < (R)1);
             if (!wave_any(!clear)) return;
         }
-        if (!wave_may_hit<R, K>(s, o, d, dd)) return;
+        if constexpr (kLight) {  // wave_may_hit, with the ball test from the light's side
+            if constexpr (K != RT_SHAPE_PLANE) {
+                const bool bounded = K == RT_SHAPE_SPHERE || K == RT_SHAPE_CUBE || s.bound[3] >= (R)0;
+                if (bounded && !ball_may_hit(s.bound[0], s.bound[1], s.bound[2], s.bound[3])) return;
+            }
+        } else if (!wave_may_hit<R, K>(s, o, d, dd0)) {
+            return;
+        }
         if (world_sphere<R, K>(s)) {
-            sphere_world<R, false>(s, o, d, dd, rdd, [&](R t, bool v) { b.offer(t, v, dist); });
+            const R dd = kLight ? dot(d, d) : dd0;
+            sphere_world<R, false>(s, o, d, dd, kLight ? recip(dd) : rdd0, [&](R t, bool v) { b.offer(t, v, dist); });
             return;
         }
         if (world_cube<R, K>(s)) {
-            cube_world<R, false>(s, o, d, rd, [&](R t, bool v) { b.offer(t, v, dist); });
+            cube_world<R, false>(s, o, d, kLight ? recip3(d) : rd0, [&](R t, bool v) { b.offer(t, v, dist); });
             return;
         }
         const V3<R> lo = xform_point(s.inv, o);
@@ -1578,11 +1691,12 @@ __device__ inline V3<R> lighting_term(const LightRec<R>& L, const MaterialRec<R>
     return c;
 }
 
-template <typename R, bool kChildren, bool kDup = false, typename Push = NoPush>
+// blk: the wave's pixel block when (o, d) are a frame's primary rays (closest_hit's primary cull)
+template <typename R, bool kChildren, bool kDup = false, typename Push = NoPush, typename B = NoBlock>
 __device__ inline bool shade_ray(const DevScene<R>& sc, V3<R> o, V3<R> d, uint32_t remaining, Shaded<R>& out,
-                                 Push&& push = Push{}) {
+                                 Push&& push = Push{}, B blk = B{}) {
     using T = Real<R>;
-    const Hit<R> h = closest_hit(sc, o, d);
+    const Hit<R> h = closest_hit(sc, o, d, blk);
     if (h.slot < 0) return false;  // world.rs:85: miss -> BLACK
     Prepared<R> q;
 #ifdef RTC_JIT
@@ -1613,7 +1727,7 @@ __device__ inline bool shade_ray(const DevScene<R>& sc, V3<R> o, V3<R> d, uint32
         // counters still count one shadow ray per light.
         const R ldn = dot(ld, n);
         bool shadowed = false;
-        if (!(ldn < (R)0) || !skips_on(sc)) shadowed = any_hit(sc, over, ld, dist, lpos);
+        if (!(ldn < (R)0) || !skips_on(sc)) shadowed = any_hit<R, B::kOn>(sc, over, ld, dist, lpos);
         const V3<R> c = lighting_term(L, m, base, n, eye, ld, ldn, shadowed);
         surface = {surface.x + c.x, surface.y + c.y, surface.z + c.z};
     });
@@ -1736,6 +1850,30 @@ __device__ inline bool tile_pixel(const LaunchParams<R>& P, uint32_t t, uint32_t
     out_idx = (uint64_t)(P.image_rows ? y : local_y) * P.width + x;
     return x < P.width && y < P.height;
 }
+
+// The slots this thread's wave passes by in tile t: the launch's miss bits of
+// the wave's block column and block row (LaunchParams::cull_cols/cull_rows),
+// indexed from the uniform terms of tile_pixel alone (tile row and column,
+// the wave's index, the shard's row map), so the loads are scalar and the
+// test of a slot is one scalar bit test.  The tables are cut for the default
+// 16 x 4 block; other block shapes (RTC_WAVE_W builds) take no primary cull.
+#ifdef RTC_JIT
+template <typename R>
+__device__ inline PixelBlock wave_pixel_block(const LaunchParams<R>& P, uint32_t t) {
+    constexpr uint32_t kPerRow = RT_TILE_W / RTC_WAVE_W, kWaveH = 64 / RTC_WAVE_W;
+    if constexpr (RTC_WAVE_W != kCullCellW || kWaveH != kCullCellH || RT_TILE_H % kCullCellH != 0) return {0u};
+    const uint32_t lrow = div_by(t, P.tiles_x, P.tiles_x_magic), tcol = t - lrow * P.tiles_x;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x / 64);
+    const uint32_t row0 = lrow * RT_TILE_H + (wave / kPerRow) * kWaveH;  // the block's first row in the strip
+    const uint32_t cx = tcol * (RT_TILE_W / kCullCellW) + wave % kPerRow;
+    const uint32_t cy = shard_image_row(row0, P.shard_count, P.shard_index) / kCullCellH;
+    // (indices masked into the tables: a block with a pixel on a canvas the
+    // tables cover is in range as it is; a canvas beyond them has them all
+    // zero, and a ragged tile's blocks past the canvas have no pixels)
+    static_assert((kCullCols & (kCullCols - 1)) == 0 && (kCullRows & (kCullRows - 1)) == 0);
+    return {P.cull_cols[cx & (kCullCols - 1)] | P.cull_rows[cy & (kCullRows - 1)]};
+}
+#endif
 
 // kFramesOnly: the caller never runs in color_at mode (per-scene direct
 // kernels, rtc_host.cpp launch: camera frames only).  Same-box A/B: three_sphere
@@ -1949,7 +2087,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(sizeof(R
                     const Hit<R> h = closest_hit(sc, o, d);
                     c = {h.t * (R)0.01, (R)h.slot, (R)0};
                 }
+#ifdef RTC_JIT  // (camera frames only: load_primary above)
+            } else if (shade_ray<R, false>(sc, o, d, 0, sh, NoPush{}, wave_pixel_block(P, t))) {
+#else
             } else if (shade_ray<R, false>(sc, o, d, 0, sh)) {
+#endif
                 hit = true;
                 c = sh.surface;
             }

@@ -29,6 +29,7 @@
 
 #include "../../include/rtc_scene.h"
 #include "host_math.hpp"
+#include "primary_rect.hpp"
 #include "rtc_internal.hpp"
 #include "shape_identity.hpp"
 
@@ -813,6 +814,19 @@ int rt_camera_set_transform(rt_camera_desc* cam, const double t[16]) {
         for (int c = 0; c < 4; ++c) cam->inverse[4 * r + c] = inv.m[r][c];
     const double o[3] = {0, 0, 0};
     rtc::hm::mul_point(inv, o, cam->origin);  // update_origin, camera.rs:114-116
+    return RT_OK;
+}
+
+int rt_camera_bound_rect(const rt_camera_desc* cam, const float bound[4], uint32_t rect[4]) {
+    if (!cam || !bound || !rect) return rtc::set_error(RT_ERR_INVALID, "rt_camera_bound_rect: null argument");
+    if (cam->width == 0 || cam->height == 0) return rtc::set_error(RT_ERR_INVALID, "rt_camera_bound_rect: empty canvas");
+    rtc::CameraRec<float> c;  // as a launch casts it (rtc_host.cpp launch)
+    for (int q = 0; q < 12; ++q) c.inv[q] = (float)cam->inverse[q];
+    for (int q = 0; q < 3; ++q) c.origin[q] = (float)cam->origin[q];
+    c.half_width = (float)cam->half_width;
+    c.half_height = (float)cam->half_height;
+    c.pixel_size = (float)cam->pixel_size;
+    rtc::primary_rect(c, cam->width, cam->height, bound, rect);
     return RT_OK;
 }
 

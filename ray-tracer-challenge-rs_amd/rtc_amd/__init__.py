@@ -26,7 +26,7 @@ import numpy as np
 
 __all__ = [
     "RenderError", "lib_path", "abi_version", "device_count", "matrix_inverse", "camera_make",
-    "camera_resize", "camera_set_transform", "load_scene", "load_scene_text", "SceneTables", "Context", "shard_rows",
+    "camera_resize", "camera_set_transform", "camera_bound_rect", "load_scene", "load_scene_text", "SceneTables", "Context", "shard_rows",
     "RT_DEFAULT_MAX_DEPTH", "RT_TILE_H", "RT_TILE_W",
 ]
 
@@ -205,6 +205,7 @@ def _load() -> C.CDLL:
         "rt_camera_make": (C.c_int, [C.c_uint32, C.c_uint32, C.c_double, P(C.c_double), P(C.c_double),
                                      P(C.c_double), P(CameraDesc)]),
         "rt_camera_resize": (C.c_int, [P(CameraDesc), C.c_uint32, C.c_uint32]),
+        "rt_camera_bound_rect": (C.c_int, [P(CameraDesc), P(C.c_float), P(C.c_uint32)]),
         "rt_matrix_inverse": (C.c_int, [P(C.c_double), P(C.c_double)]),
         "rt_camera_set_transform": (C.c_int, [P(CameraDesc), P(C.c_double)]),
         "rt_shard_row_map": (C.c_int, [C.c_uint32, C.c_uint32, P(C.c_uint32), P(C.c_uint32)]),
@@ -252,7 +253,7 @@ EXPORTED_SYMBOLS = (
     "rt_context_set_jit", "rt_context_set_frames_in_flight", "rt_jit_status", "rt_jit_wait", "rt_canvas_create", "rt_canvas_open", "rt_canvas_close",
     "rt_render_to_canvas", "rt_canvas_wait", "rt_canvas_release", "rt_canvas_read", "rt_context_set_gather",
     "rt_assemble_shards", "rt_scene_load_yaml", "rt_scene_load_yaml_text", "rt_scene_view_get", "rt_scene_free",
-    "rt_camera_make", "rt_camera_resize", "rt_matrix_inverse", "rt_image_write", "rt_image_write_format",
+    "rt_camera_make", "rt_camera_resize", "rt_camera_bound_rect", "rt_matrix_inverse", "rt_image_write", "rt_image_write_format",
     "rt_canvas_quantize",
 )
 
@@ -301,6 +302,15 @@ def camera_resize(cam: CameraDesc, width: int, height: int) -> CameraDesc:
     c = cam.copy()
     _check(_lib.rt_camera_resize(C.byref(c), width, height))
     return c
+
+
+def camera_bound_rect(cam: CameraDesc, bound) -> tuple:
+    """(x0, y0, x1, y1), inclusive: the pixels of `cam` whose primary rays can pass the wave cull of the
+    bounding ball `bound` = (centre, radius^2) in f32; x0 > x1 = none (rt_camera_bound_rect)."""
+    b = (C.c_float * 4)(*np.asarray(bound, dtype=np.float32).reshape(4))
+    r = (C.c_uint32 * 4)()
+    _check(_lib.rt_camera_bound_rect(C.byref(cam), b, r))
+    return tuple(r[:])
 
 
 IMAGE_FORMATS = {"auto": 0, "png": 1, "ppm": 2, "ppm-binary": 3}
