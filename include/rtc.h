@@ -334,6 +334,30 @@ int rt_trace_rays(rt_context* ctx, const double* rays, uint64_t n_rays,
                   const rt_ray_options* options, double* out_rgb, void* out_hit,
                   rt_stats* stats);
 
+/* Supersampled frames: `grid` x `grid` samples per pixel, averaged in the
+ * frame kernel.  `camera` is the OUTPUT camera (W x H); the buffer is W x H x
+ * 3 in options.out_format (a shard's strip when shard_count > 1), exactly as
+ * for rt_render*.  The samples are the pixels of the sample camera Cn =
+ * rt_camera_resize(camera, grid W, grid H): sample (i, j) of pixel (x, y) is
+ * Cn's ray_for_pixel(grid x + i, grid y + j) (camera.rs:52-68), traced by
+ * World::color_at at max_depth, and the pixel is the mean of its grid^2
+ * sample colours; u8 output is quantized once, after the mean.  rt_stats
+ * counts what a frame of Cn counts (primary = grid^2 W H).  grid = 1 is
+ * rt_render* itself: the same bytes and counters.
+ * RT_ERR_INVALID for a grid outside 1..RT_MAX_SAMPLE_GRID, for grid W or
+ * grid H beyond uint32_t, for flags other than RT_FLAG_NO_SKIPS |
+ * RT_FLAG_NO_COUNTERS | RT_FLAG_FAIL_LAUNCH, for a world rt_render* refuses
+ * (the samples' weights sum to 1, so the brightness bound is the same) and
+ * for a group context of more than one rank (shard the frame yourself with
+ * shard_index / shard_count).  Stream order as for rt_render_device. */
+#define RT_MAX_SAMPLE_GRID 4
+int rt_render_supersampled(rt_context* ctx, const rt_camera_desc* camera,
+                           const rt_render_options* options, uint32_t grid,
+                           void* out_host, rt_stats* stats);
+int rt_render_supersampled_device(rt_context* ctx, const rt_camera_desc* camera,
+                                  const rt_render_options* options, uint32_t grid,
+                                  void* out_device, void* hip_stream);
+
 /* Diagnostics: the per-workgroup {start, end} s_memrealtime stamps (100 MHz)
  * of the last launch made with RT_FLAG_STAMPS; *n = number of workgroups. */
 int rt_debug_stamps(rt_context* ctx, uint64_t* out, uint32_t max_workgroups, uint32_t* n);

@@ -11,6 +11,7 @@
 //   tile_order=0 | split=F | split_max=L | urgent=F   pool item order (rtc_host.cpp)
 //   trace_init=1                  context-creation step times on stderr
 //   jit_clusters=N | jit_cluster_refine=0 | jit_flags=...   per-scene builds (rtc_jit.cpp)
+//   jit_ss_scratch=N              B/lane of scratch a per-scene supersampled pool build may use (rtc_jit.cpp)
 //   jit_dump=DIR                  per-scene header + code object per build (rtc_jitc)
 // Values may not contain ','.  The variable is read at each use (contexts
 // created after a change see it).

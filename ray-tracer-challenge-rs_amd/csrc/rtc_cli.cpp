@@ -9,8 +9,10 @@
 // Extra flags: --width/--height (same as editing the YAML camera size),
 // --depth (World::MAX_REFLECTION_ITERATIONS = 6 by default), --precision
 // f32|f64, --device N, --gpus N (split the frame across devices 0..N-1 of a
-// multi-GPU context).  Pixels are quantized on the device as
-// canvas.rs:117-123 does.
+// multi-GPU context), --samples N (N x N samples per pixel,
+// averaged on the device: rt_render_supersampled; 1, the
+// default, is the reference's one ray per pixel).  Pixels are quantized on the
+// device as canvas.rs:117-123 does.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -25,8 +27,12 @@ static int usage() {
     std::fprintf(stderr,
                  "usage: rtc <SCENE.yaml> <OUT.png|OUT.ppm> [-r serial|parallel|gpu] [-q] [--width W] [--height H]\n"
                  "           [--depth D] [--precision f32|f64] [--device N] [--gpus N] [--ppm-binary] [--timings]\n"
+                 "           [--samples N]\n"
+                 "  --samples N renders N x N samples per pixel (1..%d, default 1 = one ray per pixel centre) and\n"
+                 "  averages them on the GPU.\n"
                  "  -r serial|parallel are accepted for the reference's command lines but render on the GPU like\n"
-                 "  -r gpu: this build ships no CPU renderer (Camera::render / render_parallel are not in it).\n");
+                 "  -r gpu: this build ships no CPU renderer (Camera::render / render_parallel are not in it).\n",
+                 RT_MAX_SAMPLE_GRID);
     return 2;
 }
 
@@ -44,6 +50,7 @@ int main(int argc, char** argv) {
     bool quiet = false, ppm_binary = false, timings = false;
     uint32_t width = 0, height = 0, depth = RT_DEFAULT_MAX_DEPTH, precision = RT_PRECISION_F32;
     int device = 0, gpus = 1;
+    uint32_t samples = 1;
     for (int i = 3; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> const char* { return i + 1 < argc ? argv[++i] : nullptr; };
@@ -58,6 +65,16 @@ int main(int argc, char** argv) {
         else if (a == "--width") { const char* v = next(); if (!v) return usage(); width = (uint32_t)std::atoi(v); }
         else if (a == "--height") { const char* v = next(); if (!v) return usage(); height = (uint32_t)std::atoi(v); }
         else if (a == "--depth") { const char* v = next(); if (!v) return usage(); depth = (uint32_t)std::atoi(v); }
+        else if (a == "--samples") {
+            const char* v = next();
+            char* end = nullptr;
+            const long n = v ? std::strtol(v, &end, 10) : 0;
+            if (!v || *end || n < 1 || n > RT_MAX_SAMPLE_GRID) {
+                std::fprintf(stderr, "error: --samples takes a whole number from 1 to %d\n", RT_MAX_SAMPLE_GRID);
+                return usage();
+            }
+            samples = (uint32_t)n;
+        }
         else if (a == "--device") { const char* v = next(); if (!v) return usage(); device = std::atoi(v); }
         else if (a == "--precision") {
             const char* v = next();
@@ -100,7 +117,8 @@ int main(int argc, char** argv) {
     std::vector<uint8_t> img((size_t)cam.width * cam.height * 3);
     rt_stats st;
     auto t0 = std::chrono::steady_clock::now();
-    if (rt_render(ctx, &cam, &o, img.data(), &st) != RT_OK) {
+    if ((samples > 1 ? rt_render_supersampled(ctx, &cam, &o, samples, img.data(), &st)
+                     : rt_render(ctx, &cam, &o, img.data(), &st)) != RT_OK) {
         std::fprintf(stderr, "error: %s\n", rt_last_error());
         return 1;
     }

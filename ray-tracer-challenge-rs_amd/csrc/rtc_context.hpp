@@ -141,8 +141,8 @@ struct rt_context {
         uint32_t pattern_kinds = ~0u;              // pattern kinds in the world's table (bit per RT_PATTERN_*)
         bool transparent = true;                   // some material is transparent (else no refraction code)
         int32_t begin[rtc::kNumKinds + 1] = {};
-        // variants: pool x LDS world x RT_FLAG_NO_SKIPS x (pool) 7 waves/SIMD (rtc_jit.cpp jit_function)
-        static constexpr int kVariants = 16;
+        // variants: pool x LDS world x RT_FLAG_NO_SKIPS x (pool) 7 waves/SIMD x supersampled (rtc_jit.cpp jit_function)
+        static constexpr int kVariants = 32;
         hipFunction_t fn[kVariants] = {};
         std::shared_ptr<rtc::CodeBuild> build[kVariants];  // the build each variant waits for (host thread)
         bool rejected[kVariants] = {};   // built, but refused for occupancy or scratch (that variant only)
@@ -195,8 +195,9 @@ struct rt_context {
     int device = 0;
     int cu_count = 0;
     size_t lds_per_block = 64 * 1024;
-    size_t occ_lds[12] = {};    // occupancy cache: {direct,pool} x {f32,f64} x {global,LDS world},
-    int occ_blocks[12] = {};    // then the ray-batch kernel's {f32,f64} x {global,LDS world}
+    size_t occ_lds[20] = {};    // occupancy cache: {direct,pool} x {f32,f64} x {global,LDS world},
+    int occ_blocks[20] = {};    // then the ray-batch kernel's {f32,f64} x {global,LDS world},
+                                // then the supersampled kernels' (as the first eight)
     Knobs knobs;
     rtc::Stream stream;
     rtc::Event ev_start, ev_stop;
@@ -227,6 +228,7 @@ struct rt_context {
     // ray-pool overflow regions, one per resident workgroup; a ray batch's per-lane LIFOs (launch_rays)
     rtc::DeviceBuffer<unsigned char> d_spill;
     TileOrder order;
+    TileOrder order_ss;  // ... of the supersampled launches (rt_render_supersampled*): costs of n^2 samples per tile
     Jit jit;
     rtc::DeviceBuffer<unsigned char> d_scratch;  // host-buffer renders / color_at staging
     rtc::DeviceBuffer<unsigned long long> d_stamps;  // RT_FLAG_STAMPS diagnostics: two per workgroup
@@ -307,8 +309,11 @@ unsigned long long timeout_ticks(double timeout_ms);
 constexpr uint32_t kJitMinTiles = 256;  // 64K pixels
 // *pool_waves: the waves/SIMD the returned pool kernel was built for (7, or
 // 6 = the static build's), so the caller can plan its LDS for them.
+// ss: the supersampled kernel (trace_direct_ss / trace_pool_ss), a build of
+// its own that only worlds rendered supersampled ask for; its pool build is
+// made at the static occupancy alone.
 int jit_function(rt_context* ctx, bool pool, bool lds, size_t dyn_lds, int static_blocks, hipFunction_t* fn,
-                 bool no_skips = false, int* pool_waves = nullptr);
+                 bool no_skips = false, int* pool_waves = nullptr, bool ss = false);
 int jit_wait(rt_context* ctx, double timeout_ms, int* pending);
 const std::string& device_arch(rt_context* ctx);  // rtc_jit.cpp: the device's gfx target, read once
 

@@ -41,6 +41,12 @@ hipError_t launch_trace_rays(const LaunchParams<R>& P, bool dup, uint32_t grid, 
                              void* rgb, void* hits, hipStream_t stream);
 template <typename R>
 hipError_t occupancy_rays(bool lds, size_t dyn_lds, int* blocks_per_cu);
+// the supersampled frame kernels (trace_direct_ss, trace_pool_ss)
+template <typename R>
+hipError_t launch_trace_ss(const LaunchParams<R>& P, bool pool, bool dup, uint32_t grid, size_t dyn_lds,
+                           hipStream_t stream);
+template <typename R>
+hipError_t occupancy_ss(bool pool, bool lds, size_t dyn_lds, int* blocks_per_cu);
 
 namespace sp {  // rtc_kernels_sp.o: the f32 pool kernel for worlds of spheres and planes only
 template <typename R>
@@ -406,6 +412,11 @@ int check_pixel_range(const rt_context* ctx, uint32_t depth, bool f32) {
 // material.rs:83-114) and a hit's children carry at most bright_w of its
 // weight (reflectiveness + transparency, world.rs:54-66: Schlick's R and
 // 1 - R are in [0, 1]), so a pixel is below bright_hit x sum_{g<=depth} bright_w^g.
+// A supersampled pixel (trace_pool_ss) is the sum of n^2 such trees, each
+// seeded at weight 1/n^2: the weights sum to 1 (in R, n^2 x R(1)/R(n^2) <= 1
+// up to one rounding, far inside the factor of 2 between the bound and 2^30),
+// so its bound is the same, and so are this scale and check_pixel_range's
+// verdict, whatever the grid.
 uint32_t acc_shift_f32(double bright_hit, double bright_w, uint32_t depth) {
     const double bound = std::max(pixel_bound(bright_hit, bright_w, depth), 1e-30);
     const int s = 30 - (int)std::ceil(std::log2(bound));
@@ -438,16 +449,17 @@ int cap_by_lds(int api, size_t lds) {
 }
 
 // Cached occupancy (workgroups per CU) of one kernel instantiation at a
-// given dynamic LDS size (cap_by_lds).
+// given dynamic LDS size (cap_by_lds).  ss: the supersampled kernels (keys
+// 12..19 of the same table).
 template <typename R>
-int blocks_per_cu(rt_context* ctx, bool pool, bool lds_world, size_t lds, int* per_cu) {
-    const int key = (pool ? 1 : 0) + (sizeof(R) == 8 ? 2 : 0) + (lds_world ? 4 : 0);
+int blocks_per_cu(rt_context* ctx, bool pool, bool lds_world, size_t lds, int* per_cu, bool ss = false) {
+    const int key = (pool ? 1 : 0) + (sizeof(R) == 8 ? 2 : 0) + (lds_world ? 4 : 0) + (ss ? 12 : 0);
     if (ctx->occ_lds[key] == lds && ctx->occ_blocks[key] > 0) {
         *per_cu = ctx->occ_blocks[key];
         return RT_OK;
     }
     int api = 0;
-    RT_HIP(occupancy<R>(pool, lds_world, lds, &api));
+    RT_HIP(ss ? occupancy_ss<R>(pool, lds_world, lds, &api) : occupancy<R>(pool, lds_world, lds, &api));
     *per_cu = cap_by_lds(api, lds);
     ctx->occ_lds[key] = lds;
     ctx->occ_blocks[key] = *per_cu;
@@ -486,14 +498,14 @@ int pool_lds_plan(rt_context* ctx, uint32_t world_lds, uint32_t cap, Occ&& occ, 
 // ... for the static pool kernel (6 workgroups/CU for f32 at <= 80 VGPRs).
 // RTC_DEBUG=pool_lds_rays=N overrides (A/B).
 template <typename R>
-int pool_lds_rays(rt_context* ctx, uint32_t world_lds, uint32_t cap, uint32_t* lcap) {
+int pool_lds_rays(rt_context* ctx, uint32_t world_lds, uint32_t cap, uint32_t* lcap, bool ss = false) {
     if (ctx->knobs.pool_lds_rays > 0) {
         *lcap = std::min<uint32_t>(cap, std::max<uint32_t>(kBlock, ctx->knobs.pool_lds_rays & ~7u));
         return RT_OK;
     }
     const bool lw = world_lds != 0;
     return pool_lds_plan<R>(ctx, world_lds, cap,
-                            [&](size_t lds, int* b) { return blocks_per_cu<R>(ctx, true, lw, lds, b); }, lcap, nullptr);
+                            [&](size_t lds, int* b) { return blocks_per_cu<R>(ctx, true, lw, lds, b, ss); }, lcap, nullptr);
 }
 
 // LDS world of a per-scene kernel that takes the shape records from its
@@ -534,9 +546,12 @@ int plan_pool_for(rt_context* ctx, hipFunction_t fn, LaunchShape& ls) {
     return RT_OK;
 }
 
+// samples: the grid of a supersampled launch (its kernels, their occupancy
+// and their pool bound), 0 = a plain one.
 template <typename R>
 int plan_launch(rt_context* ctx, const DevScene<R>& sc, uint32_t depth, uint32_t n_tiles, LaunchShape& ls,
-                bool jit_records = false) {
+                bool jit_records = false, uint32_t samples = 0) {
+    const bool ss = samples != 0;
     ls.pool = sc.any_secondary && depth > 0;
     const size_t wb = jit_records ? std::max<size_t>(16, jit_world_lds_bytes(sc))
                                   : world_lds_bytes<R>(sc.kind_begin[kNumKinds], sc.n_materials, sc.n_patterns);
@@ -550,12 +565,12 @@ int plan_launch(rt_context* ctx, const DevScene<R>& sc, uint32_t depth, uint32_t
     if (ls.pool) {
         // (the pool kernel takes its items from the per-XCD queues only)
         ls.batch = kPoolBatch;
-        ls.cap = pool_capacity(depth, ls.batch);
-        if ((rc = pool_lds_rays<R>(ctx, ls.world_lds, ls.cap, &ls.lcap))) return rc;
+        ls.cap = ss ? pool_capacity_ss(depth, ls.batch, samples) : pool_capacity(depth, ls.batch);
+        if ((rc = pool_lds_rays<R>(ctx, ls.world_lds, ls.cap, &ls.lcap, ss))) return rc;
         ls.lds += pool_lds_bytes<R>(ls.lcap);
     }
     int per_cu = 0;
-    if ((rc = blocks_per_cu<R>(ctx, ls.pool, ls.world_lds != 0, ls.lds, &per_cu))) return rc;
+    if ((rc = blocks_per_cu<R>(ctx, ls.pool, ls.world_lds != 0, ls.lds, &per_cu, ss))) return rc;
     if (per_cu < 1) per_cu = 1;
     ls.per_cu = per_cu;
     const uint64_t resident = (uint64_t)per_cu * (uint64_t)ctx->cu_count;
@@ -588,9 +603,13 @@ int plan_launch(rt_context* ctx, const DevScene<R>& sc, uint32_t depth, uint32_t
 // from the previous frame's costs (scripts/camera_path.py), against 0.422
 // for a repeated camera; metal, whose 0.1 ms frames gain little from any
 // order, pays the 10 us sort (0.101 -> 0.107 ms).
+// A supersampled launch keeps an order and costs of its own (`to` =
+// ctx->order_ss, the sample grid in the signature): its tiles cost n^2
+// samples each, and it neither reuses nor overwrites what the plain launches
+// of the same camera recorded.
 template <typename R>
-int plan_tile_order(rt_context* ctx, LaunchParams<R>& P, const rt_camera_desc* cam, uint32_t depth, uint32_t grid,
-                    hipStream_t stream) {
+int plan_tile_order(rt_context* ctx, rt_context::TileOrder& to, LaunchParams<R>& P, const rt_camera_desc* cam,
+                    uint32_t depth, uint32_t grid, hipStream_t stream) {
     if (P.n_tiles > kItemTileMask + 1) return RT_OK;  // items carry 20 tile bits: raster order
     uint64_t h = 1469598103934665603ull;  // FNV-1a
     auto mix = [&h](const void* p, size_t n) {
@@ -598,11 +617,10 @@ int plan_tile_order(rt_context* ctx, LaunchParams<R>& P, const rt_camera_desc* c
         for (size_t i = 0; i < n; ++i) h = (h ^ b[i]) * 1099511628211ull;
     };
     const uint64_t fields[] = {ctx->scene_gen, P.n_tiles, P.width, P.height, P.shard_index, P.shard_count,
-                               depth, sizeof(R), grid};
+                               depth, sizeof(R), grid, P.ss_grid};
     mix(fields, sizeof(fields));
     const uint64_t geometry = h;
     if (cam) mix(cam, sizeof(*cam));
-    rt_context::TileOrder& to = ctx->order;
     bool grew_cost = false, grew_order = false;
     int rc = to.d_cost.reserve(P.n_tiles, &grew_cost);
     // up to 2^kMaxSplitLog2 items per tile, then the item count
@@ -684,6 +702,8 @@ struct LaunchRequest {
     hipStream_t stream = nullptr;
     uint32_t flags = 0;
     bool image_rows = false;
+    uint32_t samples = 0;  // a supersampled frame's grid (cam = the sample camera, out_w x out_h the output), 0 = plain
+    uint32_t out_w = 0, out_h = 0;
 };
 
 template <typename R>
@@ -701,10 +721,12 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
         P.cam.half_width = (R)cam->half_width;
         P.cam.half_height = (R)cam->half_height;
         P.cam.pixel_size = (R)cam->pixel_size;
-        P.width = cam->width;
-        P.height = cam->height;
-        P.tiles_x = (cam->width + RT_TILE_W - 1) / RT_TILE_W;
-        P.tile_rows = tile_rows_for(cam->height, shard_count, shard_index);
+        // (a supersampled frame: the canvas and its tiles are the output's)
+        P.ss_grid = q.samples;
+        P.width = q.samples ? q.out_w : cam->width;
+        P.height = q.samples ? q.out_h : cam->height;
+        P.tiles_x = (P.width + RT_TILE_W - 1) / RT_TILE_W;
+        P.tile_rows = tile_rows_for(P.height, shard_count, shard_index);
         P.n_tiles = P.tiles_x * P.tile_rows;
         P.tiles_x_magic = div_magic(P.tiles_x, P.n_tiles);
     } else {
@@ -724,7 +746,8 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
     if (P.n_tiles == 0) return RT_OK;
     if ((rc = order_after_last(ctx, stream))) return rc;
     LaunchShape ls;
-    rc = plan_launch<R>(ctx, w.scene, depth, P.n_tiles, ls);
+    const bool ss = q.samples != 0;
+    rc = plan_launch<R>(ctx, w.scene, depth, P.n_tiles, ls, false, q.samples);
     if (rc) return rc;
     // value-equal shapes (rt_scene_upload's identity classes) take the pool
     // kernel whose containers walk aggregates per class
@@ -745,11 +768,11 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
             ++ctx->jit.frames;
             LaunchShape lj = ls;
             if (ctx->knobs.lds_world && !ls.pool && w.scene.kind_begin[kNumKinds] <= kJitRecordsMaxShapes &&
-                (rc = plan_launch<R>(ctx, w.scene, depth, P.n_tiles, lj, true)))
+                (rc = plan_launch<R>(ctx, w.scene, depth, P.n_tiles, lj, true, q.samples)))
                 return rc;
             int waves = 0;
             if ((rc = jit_function(ctx, lj.pool, lj.world_lds != 0, lj.lds, lj.per_cu, &jf,
-                                   (flags & RT_FLAG_NO_SKIPS) != 0, &waves)))
+                                   (flags & RT_FLAG_NO_SKIPS) != 0, &waves, ss)))
                 return rc;
             if (jf && waves > 0 && (rc = plan_pool_for<R>(ctx, jf, lj))) return rc;
             if (jf) ls = lj;
@@ -783,7 +806,8 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
         P.tile_counter = ctx->d_tile_counter.get() + (ctx->head_set ? set : 0);
         P.next_tile_counter = ctx->d_tile_counter.get() + (ctx->head_set ? 0 : set);
         if (ls.pool && ctx->knobs.tile_order && cam) {  // frames only: a ray batch's content is not in the signature
-            if ((rc = plan_tile_order<R>(ctx, P, cam, depth, ls.grid, stream))) return rc;
+            if ((rc = plan_tile_order<R>(ctx, ss ? ctx->order_ss : ctx->order, P, cam, depth, ls.grid, stream)))
+                return rc;
         }
     }
     if (flags & RT_FLAG_STAMPS) {
@@ -806,7 +830,8 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
     uint32_t kinds = 0;
     for (int k = 0; k < kNumKinds; ++k)
         if (w.scene.kind_begin[k + 1] > w.scene.kind_begin[k]) kinds |= 1u << k;
-    const bool sp = sizeof(R) == 4 && ls.pool && ctx->knobs.kind_variants && (kinds & ~kKindsSp) == 0 && !dup;
+    // (supersampled launches: the all-kinds build only)
+    const bool sp = sizeof(R) == 4 && ls.pool && ctx->knobs.kind_variants && (kinds & ~kKindsSp) == 0 && !dup && !ss;
     if (flags & RT_FLAG_FAIL_LAUNCH) return set_error(RT_ERR_HIP, "launch refused (RT_FLAG_FAIL_LAUNCH)");
     if constexpr (sizeof(R) == 4) {
         // The per-scene direct kernel's primary cull: each slot's screen
@@ -815,7 +840,8 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
         // block row (rtc_internal.hpp).  Recomputed every launch (the camera
         // is the call's argument); a few hundred ns for a small world.
         const size_t ns = ctx->jit.shapes.size();
-        if (jf && !ls.pool && cam && ns <= (size_t)kPrimaryRectSlots && (int)ns == w.scene.kind_begin[kNumKinds] &&
+        // (a supersampled launch takes no primary cull: the tables stay zero)
+        if (jf && !ls.pool && cam && !ss && ns <= (size_t)kPrimaryRectSlots && (int)ns == w.scene.kind_begin[kNumKinds] &&
             P.width <= kCullCols * kCullCellW && P.height <= kCullRows * kCullCellH) {
             const uint32_t nc = (P.width + kCullCellW - 1) / kCullCellW, nr = (P.height + kCullCellH - 1) / kCullCellH;
             for (size_t s = 0; s < ns; ++s) {
@@ -839,10 +865,12 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
         void* args[] = {&P, &sh, &mt, &pt, &lt};
         (void)hipGetLastError();
         RT_HIP(hipModuleLaunchKernel(jf, ls.grid, 1, 1, kBlock, 1, 1, (unsigned)ls.lds, stream, args, nullptr));
-    } else if (hipError_t e = sp ? sp::launch_trace<R>(P, ls.pool, dup, ls.grid, ls.lds, stream)
-                                 : launch_trace<R>(P, ls.pool, dup, ls.grid, ls.lds, stream);
+    } else if (hipError_t e = ss   ? launch_trace_ss<R>(P, ls.pool, dup, ls.grid, ls.lds, stream)
+                              : sp ? sp::launch_trace<R>(P, ls.pool, dup, ls.grid, ls.lds, stream)
+                                   : launch_trace<R>(P, ls.pool, dup, ls.grid, ls.lds, stream);
                e != hipSuccess)
-        return set_error(RT_ERR_HIP, std::string("launch of the ") + (ls.pool ? "pool" : "direct") + " kernel (grid " +
+        return set_error(RT_ERR_HIP, std::string("launch of the ") + (ss ? "supersampled " : "") +
+                                         (ls.pool ? "pool" : "direct") + " kernel (grid " +
                                          std::to_string(ls.grid) + ", dynamic LDS " + std::to_string(ls.lds) +
                                          " B, pool " + std::to_string(ls.lcap) + "/" + std::to_string(ls.cap) +
                                          " rays in LDS): " + hipGetErrorString(e));
@@ -1509,13 +1537,73 @@ int rt_render_device(rt_context* ctx, const rt_camera_desc* cam, const rt_render
     return launch_frame(ctx, cam, o, o->shard_index, o->shard_count, out_device, s);
 }
 
-int rt_render(rt_context* ctx, const rt_camera_desc* cam, const rt_render_options* o, void* out_host,
-              rt_stats* stats) {
+}  // extern "C"
+
+namespace {
+
+// What a supersampled call may ask for (rtc.h), checked before any work; the
+// sample camera Cn of `cam` into *cn.
+int check_supersampled(rt_context* ctx, const rt_camera_desc* cam, const rt_render_options* o, uint32_t samples,
+                       rt_camera_desc* cn) {
     int rc = check_ready(ctx);
     if (rc) return rc;
     if ((rc = check_options(o))) return rc;
     if (!cam) return set_error(RT_ERR_INVALID, "null camera");
-    if (ctx->group.comm) return group_render(ctx, cam, o, out_host, stats);
+    if (samples < 1 || samples > RT_MAX_SAMPLE_GRID)
+        return set_error(RT_ERR_INVALID, "sample grid " + std::to_string(samples) + " outside 1.." +
+                                             std::to_string(RT_MAX_SAMPLE_GRID));
+    if ((uint64_t)samples * cam->width > 0xFFFFFFFFull || (uint64_t)samples * cam->height > 0xFFFFFFFFull)
+        return set_error(RT_ERR_INVALID, "sample grid " + std::to_string(samples) + " x the canvas is beyond 2^32 - 1 "
+                                         "sample columns or rows (the grid's range is 1.." +
+                                             std::to_string(RT_MAX_SAMPLE_GRID) + ")");
+    if (o->flags & ~(RT_FLAG_NO_SKIPS | RT_FLAG_NO_COUNTERS | RT_FLAG_FAIL_LAUNCH))
+        return set_error(RT_ERR_INVALID, "supersampled frames take RT_FLAG_NO_SKIPS, RT_FLAG_NO_COUNTERS and "
+                                         "RT_FLAG_FAIL_LAUNCH only (the diagnostic launches are rt_render's)");
+    if (ctx->group.comm && ctx->group.n_ranks > 1)
+        return set_error(RT_ERR_INVALID, "supersampled frames are not split across a group of " +
+                                             std::to_string(ctx->group.n_ranks) +
+                                             " ranks: render shards per context (shard_index, shard_count)");
+    // rt_camera_resize(cam, n W, n H), rtc_scene.h
+    auto resized = [](const rt_camera_desc& c, uint32_t w, uint32_t h) {
+        rt_camera_desc r = c;
+        const hm::CameraSize z = hm::camera_size(w, h, c.field_of_view);
+        r.width = w;
+        r.height = h;
+        r.half_width = z.half_width;
+        r.half_height = z.half_height;
+        r.pixel_size = z.pixel_size;
+        return r;
+    };
+    *cn = resized(*cam, samples * cam->width, samples * cam->height);
+    // The sample camera keeps the output camera's half extents bit for bit
+    // (n W / n H and W / H round to the same f64; tests/test_supersample_cpu.py):
+    // the premise of "a pixel is the mean of Cn's pixels".  A size where it
+    // failed would be refused here.
+    const rt_camera_desc c1 = resized(*cam, cam->width, cam->height);
+    if (cam->width && cam->height && (c1.half_width != cn->half_width || c1.half_height != cn->half_height))
+        return set_error(RT_ERR_INVALID, "sample grid " + std::to_string(samples) +
+                                             ": the sample camera's half extents differ from the output camera's");
+    return RT_OK;
+}
+
+// One supersampled frame (or shard strip) of output camera `cam`, sample
+// camera `cn`, into `out_device` on `s`.  A grid of 1 is the plain frame.
+int launch_frame_ss(rt_context* ctx, const rt_camera_desc* cam, const rt_camera_desc* cn, const rt_render_options* o,
+                    uint32_t samples, void* out_device, hipStream_t s) {
+    if (samples == 1) return launch_frame(ctx, cam, o, o->shard_index, o->shard_count, out_device, s);
+    RT_HIP(hipSetDevice(ctx->device));
+    return launch_precision(ctx, o->precision,
+                            {.cam = cn, .depth = o->max_depth, .out_format = o->out_format,
+                             .shard_index = o->shard_index, .shard_count = o->shard_count, .out_device = out_device,
+                             .stream = s, .flags = o->flags, .samples = samples, .out_w = cam->width,
+                             .out_h = cam->height});
+}
+
+// rt_render's frame into a host buffer; samples != 0: rt_render_supersampled's
+// (cn = the sample camera).
+int render_to_host(rt_context* ctx, const rt_camera_desc* cam, const rt_render_options* o, void* out_host,
+                   rt_stats* stats, uint32_t samples, const rt_camera_desc* cn) {
+    int rc;
     if (!out_host) return set_error(RT_ERR_INVALID, "null output");
     RT_HIP(hipSetDevice(ctx->device));
     const uint32_t rows = tile_rows_for(cam->height, o->shard_count, o->shard_index) * RT_TILE_H;
@@ -1544,7 +1632,9 @@ int rt_render(rt_context* ctx, const rt_camera_desc* cam, const rt_render_option
     if (o->shard_count > 1) RT_HIP(hipMemsetAsync(ctx->d_scratch.get(), 0, bytes, s));  // strip rows past the canvas
     RT_HIP(hipEventRecord(ctx->ev_start, s));
     tr.step("enqueue before launch");
-    if ((rc = launch_frame(ctx, cam, o, o->shard_index, o->shard_count, ctx->d_scratch.get(), s))) return rc;
+    if ((rc = samples ? launch_frame_ss(ctx, cam, cn, o, samples, ctx->d_scratch.get(), s)
+                      : launch_frame(ctx, cam, o, o->shard_index, o->shard_count, ctx->d_scratch.get(), s)))
+        return rc;
     tr.step("launch");
     RT_HIP(hipEventRecord(ctx->ev_stop, s));
     RT_HIP(hipMemcpyAsync(h_after, ctx->d_counters.get(), cbytes, hipMemcpyDeviceToHost, s));
@@ -1567,6 +1657,36 @@ int rt_render(rt_context* ctx, const rt_camera_desc* cam, const rt_render_option
         fill_stats(ctx, before, after, ms, stats);
     }
     return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_render(rt_context* ctx, const rt_camera_desc* cam, const rt_render_options* o, void* out_host,
+              rt_stats* stats) {
+    int rc = check_ready(ctx);
+    if (rc) return rc;
+    if ((rc = check_options(o))) return rc;
+    if (!cam) return set_error(RT_ERR_INVALID, "null camera");
+    if (ctx->group.comm) return group_render(ctx, cam, o, out_host, stats);
+    return render_to_host(ctx, cam, o, out_host, stats, 0, nullptr);
+}
+
+int rt_render_supersampled(rt_context* ctx, const rt_camera_desc* cam, const rt_render_options* o, uint32_t samples,
+                           void* out_host, rt_stats* stats) {
+    rt_camera_desc cn;
+    if (int rc = check_supersampled(ctx, cam, o, samples, &cn)) return rc;
+    return render_to_host(ctx, cam, o, out_host, stats, samples, &cn);
+}
+
+int rt_render_supersampled_device(rt_context* ctx, const rt_camera_desc* cam, const rt_render_options* o,
+                                  uint32_t samples, void* out_device, void* hip_stream) {
+    rt_camera_desc cn;
+    if (int rc = check_supersampled(ctx, cam, o, samples, &cn)) return rc;
+    if (!out_device) return set_error(RT_ERR_INVALID, "null camera or output");
+    if (cam->width == 0 || cam->height == 0) return RT_OK;  // empty canvas, as rt_render_device
+    return launch_frame_ss(ctx, cam, &cn, o, samples, out_device, static_cast<hipStream_t>(hip_stream));
 }
 
 int rt_color_at(rt_context* ctx, const double* rays, uint64_t n, uint32_t depth, uint32_t precision, double* out,
@@ -1758,7 +1878,7 @@ int rt_context_set_frames_in_flight(rt_context* ctx, uint32_t frames) {
         const double split = frames > 1 ? 1.5 : 1.0;
         if (!split_knob && m->knobs.split_factor != split) {
             m->knobs.split_factor = split;
-            m->order.valid = false;  // the next launches rebuild the tile order with it
+            m->order.valid = m->order_ss.valid = false;  // the next launches rebuild the tile order with it
         }
     }
     return RT_OK;

@@ -122,6 +122,31 @@ RTC_HD inline uint64_t spill_word(uint32_t block, uint32_t spill_cap, uint32_t s
     return ((uint64_t)block * spill_cap + (slot - lds_cap)) * 8u;
 }
 
+// LIFO bound (rays) of a workgroup's pool in a supersampled launch
+// (rtc_kernels.hip trace_pool_ss).  Seeding rule: the seeds of sample s + 1
+// (at most kBlock rays, each at remaining = depth) enter only when the pool
+// has drained, i.e. holds no ray of sample s.  So at every moment the pool
+// holds rays of one sample only, and what one sample can pile up is what a
+// plain frame's single seeding can.  A generation pops min(size, batch) rays
+// off the top and pushes at most two children per popped ray, each at its
+// parent's remaining - 1, none from remaining 0.  Call the rays one
+// generation pushed a segment (the seeds are the first).  Children lie above
+// every ray that stayed and have less remaining than any of them (the popped
+// rays were on top of those), so from the bottom up the segments' largest
+// remaining strictly falls from `depth`: at most depth + 1 segments.  A
+// segment is born with at most 2 x batch rays; a later segment exists only
+// after a full batch was popped off it (a pop that reaches below a segment
+// removes it), so every segment but the top one holds at most `batch`, and
+// the seeds' at most kBlock - batch.  Size <= (kBlock - batch) + (depth - 1)
+// x batch + 2 x batch = kBlock + depth x batch, whatever the grid: the bound
+// of a plain frame (rtc_host.cpp pool_capacity; batch = kPoolBatch = kBlock).
+// tests/pool_seed_model.cpp walks the rule for grids 1..RT_MAX_SAMPLE_GRID
+// and depths 0..16 with two children everywhere against this function.
+RTC_HD inline uint32_t pool_capacity_ss(uint32_t depth, uint32_t batch, uint32_t grid) {
+    (void)grid;  // a drained pool forgets the samples before
+    return (uint32_t)kBlock + depth * batch;
+}
+
 // Ray batches (rtc_kernels.hip trace_rays): one ray tree per lane, walked
 // depth first with a private LIFO of pending rays.  The lane holds the ray it
 // is shading in registers; shading pushes its children (at most two, each at
@@ -408,6 +433,12 @@ struct LaunchParams {
     int32_t* error_flag;               // set nonzero on pool overflow
     uint32_t cull_cols[kCullCols];     // primary cull: slots whose rectangle misses a block column ...
     uint32_t cull_rows[kCullRows];     // ... or a block row (above); zero = none
+    // Supersampled frames (trace_direct_ss, trace_pool_ss; 0 for every other
+    // launch): n x n samples per pixel.  `cam` is then the sample camera (the
+    // output camera resized to n x width by n x height) while width, height
+    // and the tiles stay those of the output.  Last, so that no field the
+    // shipped kernels load moves.
+    uint32_t ss_grid;
 };
 
 }  // namespace rtc

@@ -314,7 +314,11 @@ std::string scene_header(const std::vector<ShapeRec<float>>& sh, const int32_t b
     return s;
 }
 
-const char* kernel_name(bool pool, bool lds) {
+const char* kernel_name(bool pool, bool lds, bool ss) {
+    if (ss) {  // the supersampled frame kernels: builds of their own, named apart (the disk cache key holds the name)
+        if (pool) return lds ? "rtc::trace_pool_ss<float, true, false>" : "rtc::trace_pool_ss<float, false, false>";
+        return lds ? "rtc::trace_direct_ss<float, true>" : "rtc::trace_direct_ss<float, false>";
+    }
     if (pool) return lds ? "rtc::trace_pool<float, true, false>" : "rtc::trace_pool<float, false, false>";
     return lds ? "rtc::trace_direct<float, true>" : "rtc::trace_direct<float, false>";
 }
@@ -577,6 +581,14 @@ const std::string& device_arch(rt_context* ctx) {
 // the 6-wave one: cover 4K (36 B/lane) 0.657 -> 0.629 ms, reflect_refract
 // and table (16) -2.4 % / -3.6 %; cylinders (44) +4 % (refused).
 constexpr int kPool7ScratchMax = 40;
+// ... and a per-scene supersampled pool build (trace_pool_ss, 6 waves/SIMD).
+// Its builds spill more than trace_pool's (32-64 B/lane on the reference
+// scenes: the sample loop around the generations) and still run about twice
+// as fast as the generic supersampled kernel, the only alternative.  Same
+// box, 1080p / 4K, n = 2, ms per frame refused (16) / taken: reflect_refract
+// (44 B/lane) 1.684 / 0.866, cover 4K (52) 7.598 / 2.575
+// (RTC_DEBUG=jit_ss_scratch=N).
+constexpr int kPoolSsScratchMax = 80;
 
 namespace {
 // One variant's build: *fn stays null while it compiles, if it failed or if
@@ -585,7 +597,8 @@ namespace {
 // RT_JIT_SYNC mode) and return without waiting for it or taking it.
 // scratch_max: the B/lane of scratch a pool build may use (direct: none).
 int jit_variant(rt_context* ctx, int variant, bool pool, bool lds, size_t dyn_lds, int static_blocks,
-                hipFunction_t* fn, bool no_skips, int pool_waves, int scratch_max, bool start_only = false) {
+                hipFunction_t* fn, bool no_skips, int pool_waves, int scratch_max, bool start_only = false,
+                bool ss = false) {
     *fn = nullptr;
     if (ctx->jit.fn[variant]) {
         *fn = ctx->jit.fn[variant];
@@ -626,7 +639,7 @@ int jit_variant(rt_context* ctx, int variant, bool pool, bool lds, size_t dyn_ld
                 make_request(scene_header(ctx->jit.shapes, ctx->jit.begin, ctx->jit.lights, ctx->jit.materials,
                                           ctx->jit.patterns,
                                           ctx->jit.pattern_kinds, ctx->jit.transparent),
-                             kernel_name(pool, lds), device_arch(ctx), &key, no_skips, pool_waves);
+                             kernel_name(pool, lds, ss), device_arch(ctx), &key, no_skips, pool_waves);
             start_build(b, rq, key, sync && !start_only);
         }
     }
@@ -642,11 +655,14 @@ int jit_variant(rt_context* ctx, int variant, bool pool, bool lds, size_t dyn_ld
         if (b->from_disk) ++ctx->jit.cache_hits;
         ctx->jit.owner[variant] = false;
     }
-    // A failed build of the optional 7-wave variant (variant >= 8) refuses
+    // A failed build of the optional 7-wave variant (bit 8 of the index) refuses
     // that variant only: jit_function falls back to the static-occupancy
     // build compiled beside it.  A failed base build keeps the generic kernel
     // for this world.
-    const bool optional = variant >= 8;
+    // So does a failed supersampled build (bit 16): its launches fall back to
+    // the generic supersampled kernel, and the world's plain frames keep
+    // their per-scene kernels.
+    const bool optional = (variant & (8 | 16)) != 0;
     if (state == 2) {
         (optional ? ctx->jit.rejected[variant] : ctx->jit.failed) = true;
         ctx->jit.log = b->log;
@@ -693,9 +709,13 @@ int jit_variant(rt_context* ctx, int variant, bool pool, bool lds, size_t dyn_ld
     int blocks = 0, scratch = 0;
     RT_HIP(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, mf.second, kBlock, dyn_lds));
     RT_HIP(hipFuncGetAttribute(&scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, mf.second));
+    // (RTC_DEBUG=jit_ss_scratch=N: the allowance of a supersampled pool
+    // build, for A/B; read here, where a build is judged, once per variant)
+    if (std::string v; ss && pool && debug_knob("jit_ss_scratch", &v)) scratch_max = std::atoi(v.c_str());
     if (blocks < static_blocks || scratch > (pool ? scratch_max : 0)) {
         ctx->jit.rejected[variant] = true;
-        ctx->jit.log = std::string("per-scene ") + (pool ? "pool" : "direct") + " kernel not used: " +
+        ctx->jit.log = std::string("per-scene ") + (ss ? "supersampled " : "") + (pool ? "pool" : "direct") +
+                       " kernel not used: " +
                        std::to_string(blocks) + " workgroups/CU (generic " + std::to_string(static_blocks) + "), " +
                        std::to_string(scratch) + " B/lane of scratch";
         return RT_OK;
@@ -707,12 +727,16 @@ int jit_variant(rt_context* ctx, int variant, bool pool, bool lds, size_t dyn_ld
 }  // namespace
 
 int jit_function(rt_context* ctx, bool pool, bool lds, size_t dyn_lds, int static_blocks, hipFunction_t* fn,
-                 bool no_skips, int* pool_waves) {
+                 bool no_skips, int* pool_waves, bool ss) {
     *fn = nullptr;
     if (pool_waves) *pool_waves = 0;
     if (ctx->jit.failed || ctx->jit.shapes.empty()) return RT_OK;
-    const int variant = (no_skips ? 4 : 0) + (pool ? 2 : 0) + (lds ? 1 : 0);
-    if (!pool) return jit_variant(ctx, variant, pool, lds, dyn_lds, static_blocks, fn, no_skips, 0, 0);
+    const int variant = (ss ? 16 : 0) + (no_skips ? 4 : 0) + (pool ? 2 : 0) + (lds ? 1 : 0);
+    if (!pool) return jit_variant(ctx, variant, pool, lds, dyn_lds, static_blocks, fn, no_skips, 0, 0, false, ss);
+    // (the supersampled pool kernel: the static occupancy's build alone)
+    if (ss)
+        return jit_variant(ctx, variant, pool, lds, dyn_lds, static_blocks, fn, no_skips, 0, kPoolSsScratchMax, false,
+                           ss);
     // The pool kernel at 7 waves/SIMD (jit_options.hpp) and, compiled beside
     // it, at the static build's occupancy: a 7-wave build that spills more
     // than kPool7ScratchMax is refused and the other is taken (also while the

@@ -35,6 +35,7 @@ RT_TILE_W = 64
 RT_TILE_H = 4
 RT_DEFAULT_MAX_DEPTH = 6  # World::MAX_REFLECTION_ITERATIONS, world.rs:15
 RT_MAX_SUPPORTED_DEPTH = 16
+RT_MAX_SAMPLE_GRID = 4  # rt_render_supersampled*: grid x grid samples per pixel
 
 RT_OK = 0
 RT_ERR_INVALID, RT_ERR_HIP, RT_ERR_NO_DEVICE, RT_ERR_NO_SCENE = -1, -2, -3, -4
@@ -182,6 +183,10 @@ def _load() -> C.CDLL:
         "rt_shard_rows": (C.c_int, [C.c_uint32, C.c_uint32, P(C.c_uint32)]),
         "rt_render": (C.c_int, [C.c_void_p, P(CameraDesc), P(RenderOptions), C.c_void_p, P(Stats)]),
         "rt_render_device": (C.c_int, [C.c_void_p, P(CameraDesc), P(RenderOptions), C.c_void_p, C.c_void_p]),
+        "rt_render_supersampled": (C.c_int, [C.c_void_p, P(CameraDesc), P(RenderOptions), C.c_uint32, C.c_void_p,
+                                             P(Stats)]),
+        "rt_render_supersampled_device": (C.c_int, [C.c_void_p, P(CameraDesc), P(RenderOptions), C.c_uint32,
+                                                    C.c_void_p, C.c_void_p]),
         "rt_color_at": (C.c_int, [C.c_void_p, P(C.c_double), C.c_uint64, C.c_uint32, C.c_uint32, P(C.c_double),
                                   P(Stats)]),
         "rt_trace_rays_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, P(RayOptions), C.c_void_p, C.c_void_p,
@@ -246,7 +251,7 @@ _lib = _load()
 EXPORTED_SYMBOLS = (
     "rt_abi_version", "rt_last_error", "rt_device_count", "rt_context_create", "rt_context_destroy",
     "rt_scene_upload", "rt_shard_rows", "rt_render", "rt_render_device", "rt_color_at", "rt_read_counters",
-    "rt_trace_rays", "rt_trace_rays_device",
+    "rt_trace_rays", "rt_trace_rays_device", "rt_render_supersampled", "rt_render_supersampled_device",
     "rt_read_generation_counts",
     "rt_debug_stamps", "rt_debug_tile_costs", "rt_debug_item_log", "rt_debug_intersect", "rt_debug_normal", "rt_camera_set_transform",
     "rt_shard_row_map", "rt_context_create_multi", "rt_comm_unique_id", "rt_context_create_rank", "rt_context_group",
@@ -565,6 +570,35 @@ class Context:
         opts = self.options(depth, precision, out_format, shard, flags)
         _check(_lib.rt_render_device(self._h, C.byref(camera), C.byref(opts), C.c_void_p(out_ptr or 0),
                                      C.c_void_p(stream_ptr or 0)))
+
+    def render_supersampled(self, camera: CameraDesc, grid: int, depth: int = RT_DEFAULT_MAX_DEPTH,
+                            precision: str = "f32", out_format: str = "real", shard=(0, 1),
+                            out: np.ndarray | None = None, flags: int = 0):
+        """render() with grid x grid samples per pixel, averaged in the frame kernel (rtc.h
+        rt_render_supersampled): `camera` is the output camera, the samples are the pixels of
+        camera_resize(camera, grid * W, grid * H), the stats count that frame's rays.  grid 1 is render()."""
+        opts = self.options(depth, precision, out_format, shard, flags)
+        rows = camera.height if shard[1] == 1 else shard_rows(camera.height, shard[1])
+        dtype = np.uint8 if out_format == "u8" else (np.float32 if precision == "f32" else np.float64)
+        if out is not None:
+            if out.shape != (rows, camera.width, 3) or out.dtype != dtype or not out.flags.c_contiguous:
+                raise ValueError(f"out must be a C-contiguous {dtype.__name__} array of shape {(rows, camera.width, 3)}")
+            img = out
+        else:
+            img = np.zeros((rows, camera.width, 3), dtype=dtype)
+        st = Stats()
+        _check(_lib.rt_render_supersampled(self._h, C.byref(camera), C.byref(opts), grid,
+                                           img.ctypes.data_as(C.c_void_p), C.byref(st)))
+        return img, st.as_dict()
+
+    def render_supersampled_device(self, camera: CameraDesc, grid: int, out_ptr: int, stream_ptr: int | None = None,
+                                   depth: int = RT_DEFAULT_MAX_DEPTH, precision: str = "f32",
+                                   out_format: str = "real", shard=(0, 1), flags: int = 0) -> None:
+        """render_device() with grid x grid samples per pixel (rtc.h rt_render_supersampled_device): the
+        W x H x 3 buffer of the output camera, asynchronous on the stream."""
+        opts = self.options(depth, precision, out_format, shard, flags)
+        _check(_lib.rt_render_supersampled_device(self._h, C.byref(camera), C.byref(opts), grid,
+                                                  C.c_void_p(out_ptr or 0), C.c_void_p(stream_ptr or 0)))
 
     def color_at(self, rays, depth: int = RT_DEFAULT_MAX_DEPTH, precision: str = "f32"):
         """Batched World::color_at: rays (n, 6) = origin, direction -> colours (n, 3) f64.  In a world with
