@@ -436,6 +436,28 @@ int rt_context_set_frames_in_flight(rt_context* ctx, uint32_t frames);
 int rt_jit_status(rt_context* ctx, int* used_last_launch, double* compile_ms, char* log, size_t log_len);
 int rt_jit_wait(rt_context* ctx, double timeout_ms, int* pending);
 
+/* The triangle hierarchy of the uploaded world.  A world
+ * of more than 255 shapes with at least 64 bounded triangles (a mesh:
+ * rtc_scene.h rt_mesh_*) gets a tree of bounding balls over its triangle
+ * records at rt_scene_upload, and the generic kernels pass by every subtree
+ * whose ball no ray of a wave can meet;
+ * pixels and rt_stats are those of the flat loop over every triangle.  Such a
+ * world runs the generic kernels only (rt_jit_status says so in its log).
+ * rt_scene_tree_info reports the tree: all zeros when the world has none (too
+ * few triangles, a world small enough for the per-scene builds' records,
+ * RTC_DEBUG=tri_tree=0 or RTC_DEBUG=cull=0 at upload).  On a
+ * group context: this process's first member, whose tables came from rank 0. */
+typedef struct rt_tree_info {
+    uint32_t nodes;            /* inner nodes and leaves */
+    uint32_t leaves;
+    uint32_t depth;            /* nodes on the longest root-to-leaf path */
+    uint32_t records_in_tree;  /* triangle records reached through the leaves */
+    uint32_t records_outside;  /* triangle records tested for every wave (unbounded ones) */
+    uint32_t reserved;
+    double build_ms;           /* host time of the tree build at upload */
+} rt_tree_info;
+int rt_scene_tree_info(rt_context* ctx, rt_tree_info* out);
+
 /* Peer canvas: a frame assembled in place instead of gathered (SURVEY.md
  * §8e; the north star's "gather of framebuffer strips over xGMI" done as the
  * shards' own stores into rank 0's image).  The owner creates a device canvas

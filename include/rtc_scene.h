@@ -50,6 +50,46 @@ int rt_scene_load_yaml_text(const char* text, rt_scene** out);
 int rt_scene_view_get(const rt_scene* scene, rt_scene_view* view);
 void rt_scene_free(rt_scene* scene);
 
+/* Triangle meshes from Wavefront OBJ text, the book's subset:
+ *   v x y z          a vertex;
+ *   f i j k ...      a face of three or more vertices, fan-triangulated as
+ *                    (1, k, k+1); indices are 1-based, negative ones count
+ *                    back from the vertices read so far, and of i/j/k, i//k
+ *                    and i/j only the vertex index i is used.
+ * Every other line (vn, vt, g, o, s, usemtl, mtllib, comments, blanks) is
+ * skipped and counted in ignored_lines.  LF or CRLF.  RT_ERR_IO, with the
+ * line number in rt_last_error(), for a number that does not parse or an
+ * index out of range on a v or f line, and for a file that cannot be read.
+ * The view's pointers live as long as the mesh. */
+typedef struct rt_mesh rt_mesh;
+
+typedef struct rt_mesh_view {
+    const double* vertices;     /* n_vertices x 3 */
+    uint32_t n_vertices;
+    const uint32_t* triangles;  /* n_triangles x 3 vertex indices, 0-based */
+    uint32_t n_triangles;
+    uint32_t ignored_lines;
+} rt_mesh_view;
+
+int rt_mesh_load_obj(const char* path, rt_mesh** out);
+int rt_mesh_load_obj_text(const char* text, rt_mesh** out);
+int rt_mesh_view_get(const rt_mesh* mesh, rt_mesh_view* view);
+void rt_mesh_free(rt_mesh* mesh);
+
+/* The mesh's faces as the reference's Triangle::new(v1, v2, v3)
+ * (triangle.rs:21-35): edge_1 = v2 - v1, edge_2 = v3 - v1, normal =
+ * normalize(edge_2 x edge_1) with Vector::cross's mul_add and
+ * Vector::normalized's plain sums, into out[0 .. n_triangles), each with
+ * `material`.  transform: a row-major forward 4x4, NULL = identity.
+ *   bake = 0  every triangle gets inverse = rt_matrix_inverse(transform)
+ *             (Shape::set_transformation);
+ *   bake = 1  the vertices are multiplied by `transform` first (Matrix<4> *
+ *             Point, matrix.rs:332-346) and the inverse stays the identity:
+ *             another, equally valid world that is cheaper per ray.
+ * A degenerate face is kept: its normal is NaN and its determinant zero, as
+ * the reference's would be.  Host only. */
+int rt_mesh_triangles(const rt_mesh* mesh, const double* transform, int bake, int32_t material, rt_shape_desc* out);
+
 /* Camera::new(width, height, fov) + set_transformation(view_transform(...)) */
 int rt_camera_make(uint32_t width, uint32_t height, double field_of_view,
                    const double from[3], const double to[3], const double up[3],

@@ -6,6 +6,8 @@
 //   direct_oversub=T              f32 direct kernel's grid: T/10 x the resident workgroups (default 25)
 //   lds_world=0                   world tables not staged in LDS
 //   cull=0                        every shape uploaded unbounded (no wave cull)
+//   tri_tree=0                    no triangle hierarchy (every triangle record visited); read at upload
+//   tri_min=N | tri_leaf=N        the sweep's values of tri_tree.hpp's kTriTreeMin and kTriLeaf
 //   kind_variants=0               no sphere/plane-only pool kernel
 //   pool_lds_rays=N               LDS-resident LIFO slots (else sized for occupancy)
 //   tile_order=0 | split=F | split_max=L | urgent=F   pool item order (rtc_host.cpp)

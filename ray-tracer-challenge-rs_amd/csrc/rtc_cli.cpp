@@ -11,8 +11,10 @@
 // f32|f64, --device N, --gpus N (split the frame across devices 0..N-1 of a
 // multi-GPU context), --samples N (N x N samples per pixel,
 // averaged on the device: rt_render_supersampled; 1, the
-// default, is the reference's one ray per pixel).  Pixels are quantized on the
-// device as canvas.rs:117-123 does.
+// default, is the reference's one ray per pixel), --obj FILE (repeatable: the
+// triangles of a Wavefront OBJ mesh, rtc_scene.h rt_mesh_*, appended after the
+// YAML world's shapes with Material::default and no transformation).  Pixels
+// are quantized on the device as canvas.rs:117-123 does.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -27,7 +29,9 @@ static int usage() {
     std::fprintf(stderr,
                  "usage: rtc <SCENE.yaml> <OUT.png|OUT.ppm> [-r serial|parallel|gpu] [-q] [--width W] [--height H]\n"
                  "           [--depth D] [--precision f32|f64] [--device N] [--gpus N] [--ppm-binary] [--timings]\n"
-                 "           [--samples N]\n"
+                 "           [--samples N] [--obj MESH.obj]...\n"
+                 "  --obj MESH.obj appends the mesh's triangles (v and f lines; faces fan-triangulated) to the\n"
+                 "  scene's shapes, with the default material and no transformation; repeatable.\n"
                  "  --samples N renders N x N samples per pixel (1..%d, default 1 = one ray per pixel centre) and\n"
                  "  averages them on the GPU.\n"
                  "  -r serial|parallel are accepted for the reference's command lines but render on the GPU like\n"
@@ -51,6 +55,7 @@ int main(int argc, char** argv) {
     uint32_t width = 0, height = 0, depth = RT_DEFAULT_MAX_DEPTH, precision = RT_PRECISION_F32;
     int device = 0, gpus = 1;
     uint32_t samples = 1;
+    std::vector<const char*> obj_paths;
     for (int i = 3; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> const char* { return i + 1 < argc ? argv[++i] : nullptr; };
@@ -75,6 +80,7 @@ int main(int argc, char** argv) {
             }
             samples = (uint32_t)n;
         }
+        else if (a == "--obj") { const char* v = next(); if (!v) return usage(); obj_paths.push_back(v); }
         else if (a == "--device") { const char* v = next(); if (!v) return usage(); device = std::atoi(v); }
         else if (a == "--precision") {
             const char* v = next();
@@ -95,6 +101,40 @@ int main(int argc, char** argv) {
     rt_scene_view_get(scene, &v);
     rt_camera_desc cam = v.camera;
     if (width || height) rt_camera_resize(&cam, width ? width : cam.width, height ? height : cam.height);
+    // --obj: the scene's tables with each mesh's triangles after its shapes, all on one Material::default
+    // (material.rs:157-161) appended to the materials
+    std::vector<rt_shape_desc> shapes(v.shapes, v.shapes + v.n_shapes);
+    std::vector<rt_material_desc> materials(v.materials, v.materials + v.n_materials);
+    if (!obj_paths.empty()) {
+        rt_material_desc m = {};
+        m.color[0] = m.color[1] = m.color[2] = 1.0;
+        m.ambient = 0.1;
+        m.diffuse = 0.9;
+        m.specular = 0.9;
+        m.shininess = 200.0;
+        m.refractive_index = 1.0;
+        m.casts_shadow = 1;
+        m.pattern = -1;
+        materials.push_back(m);
+    }
+    for (const char* path : obj_paths) {
+        rt_mesh* mesh = nullptr;
+        rt_mesh_view mv;
+        if (rt_mesh_load_obj(path, &mesh) != RT_OK || rt_mesh_view_get(mesh, &mv) != RT_OK) {
+            std::fprintf(stderr, "error: %s\n", rt_last_error());
+            return 1;
+        }
+        const size_t at = shapes.size();
+        shapes.resize(at + mv.n_triangles);
+        if (rt_mesh_triangles(mesh, nullptr, 0, (int32_t)materials.size() - 1, shapes.data() + at) != RT_OK) {
+            std::fprintf(stderr, "error: %s\n", rt_last_error());
+            return 1;
+        }
+        if (!quiet)
+            std::printf("%s: %u vertices, %u triangles, %u lines ignored\n", path, mv.n_vertices, mv.n_triangles,
+                        mv.ignored_lines);
+        rt_mesh_free(mesh);
+    }
     const double load_ms = ms_since(t_load);
     const auto t_ctx = clk::now();
     rt_context* ctx = nullptr;
@@ -104,8 +144,8 @@ int main(int argc, char** argv) {
     const double ctx_ms = ms_since(t_ctx);
     const auto t_up = clk::now();
     if (created != RT_OK ||
-        rt_scene_upload(ctx, v.shapes, v.n_shapes, v.materials, v.n_materials, v.patterns, v.n_patterns, v.lights,
-                        v.n_lights) != RT_OK) {
+        rt_scene_upload(ctx, shapes.data(), (uint32_t)shapes.size(), materials.data(), (uint32_t)materials.size(),
+                        v.patterns, v.n_patterns, v.lights, v.n_lights) != RT_OK) {
         std::fprintf(stderr, "error: %s\n", rt_last_error());
         return 1;
     }

@@ -33,6 +33,9 @@ struct DeviceWorld {
     MaterialRec<R>* materials = nullptr;
     PatternRec<R>* patterns = nullptr;
     DeviceBuffer<LightRec<R>> lights;
+    DeviceBuffer<TriNode<R>> tri_nodes;  // the triangle hierarchy (tri_tree.hpp), outside the LDS image
+    uint32_t n_tri_nodes = 0;            // 0: the world has no tree
+    uint32_t tri_flat_begin = 0;         // first triangle slot outside the tree
     int32_t* world_slot = nullptr;
     DevScene<R> scene{};
     // Point the tables into `image` for ns shapes, nm materials, np patterns.
@@ -62,6 +65,13 @@ struct DeviceWorld {
         scene.n_lights = (int32_t)nl;
         return RT_OK;
     }
+    // Room for n nodes of the triangle hierarchy, flat run from record `flat_begin`; n = 0: no tree.
+    int allocate_tree(size_t n, int32_t flat_begin) {
+        if (int rc = tri_nodes.reserve(n)) return rc;
+        n_tri_nodes = (uint32_t)n;
+        tri_flat_begin = n ? (uint32_t)flat_begin : 0u;
+        return RT_OK;
+    }
 };
 
 struct CodeBuild;  // rtc_jit.cpp: one hipRTC build of a per-scene kernel, possibly in flight
@@ -87,6 +97,9 @@ struct rt_context {
         uint32_t direct_oversub10 = 25;
         bool lds_world = true;      // RTC_DEBUG=lds_world=0 gathers shade data from global memory
         bool cull = true;  // RTC_DEBUG=cull=0 uploads every shape as unbounded (no wave cull; exactness tests)
+        bool tri_tree = true;  // RTC_DEBUG=tri_tree=0 uploads without a triangle hierarchy (flat triangle loop)
+        // RTC_DEBUG=tri_min=N,tri_leaf=N: the sweep's values of tri_tree.hpp's kTriTreeMin and kTriLeaf (0 = those)
+        uint32_t tri_min = 0, tri_leaf = 0;
         bool kind_variants = true;  // RTC_DEBUG=kind_variants=0: always the all-kinds kernels
         uint32_t pool_lds_rays = 0;  // RTC_DEBUG=pool_lds_rays=N: LDS-resident pool slots (0 = sized for occupancy)
         bool tile_order = true;      // RTC_DEBUG=tile_order=0: raster order always
@@ -224,6 +237,7 @@ struct rt_context {
     double bright_hit = 1.0, bright_w = 0.0;  // brightness bound of the world (acc_shift_f32)
     uint64_t scene_gen = 0;      // bumped by every rt_scene_upload
     uint32_t duplicate_shapes = 0;  // shapes value-equal to an earlier one (one identity class)
+    rt_tree_info tree_info{};       // the triangle hierarchy of the uploaded world (rt_scene_tree_info; zeros = none)
     std::vector<int32_t> world_slot;  // world index -> slot | kind << 24 of the uploaded table
     // ray-pool overflow regions, one per resident workgroup; a ray batch's per-lane LIFOs (launch_rays)
     rtc::DeviceBuffer<unsigned char> d_spill;

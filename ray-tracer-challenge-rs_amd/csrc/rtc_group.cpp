@@ -54,6 +54,9 @@ struct SceneHeader {
     uint32_t duplicates;
     double flops_per_ray;
     double bright_hit, bright_w;  // acc_shift_f32's bound
+    uint32_t n_tri_nodes;         // the triangle hierarchy (tri_tree.hpp): 0 = none
+    int32_t tri_flat_begin;
+    rt_tree_info tree_info;
 };
 
 // (device pointer, bytes) of every table of a member's world, in one order
@@ -62,6 +65,7 @@ template <typename R>
 void world_buffers(DeviceWorld<R>& w, const SceneHeader& h, std::vector<std::pair<void*, size_t>>& out) {
     out.push_back({w.image.get(), world_lds_bytes<R>(h.ns, h.nm, h.np)});  // shapes, materials, patterns, world_slot
     out.push_back({w.lights.get(), h.nl * sizeof(LightRec<R>)});
+    out.push_back({w.tri_nodes.get(), h.n_tri_nodes * sizeof(TriNode<R>)});
 }
 
 // Rank 0's `value` to every member of every rank, over RCCL (collective):
@@ -328,6 +332,9 @@ int group_scene_upload(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns
         root_h.flops_per_ray = ctx->flops.per_ray;
         root_h.bright_hit = ctx->bright_hit;
         root_h.bright_w = ctx->bright_w;
+        root_h.n_tri_nodes = ctx->w32.n_tri_nodes;
+        root_h.tri_flat_begin = (int32_t)ctx->w32.tri_flat_begin;
+        root_h.tree_info = ctx->tree_info;
     }
     // 1. the header
     std::vector<SceneHeader> hdr;
@@ -347,8 +354,10 @@ int group_scene_upload(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns
         if (hipSetDevice(m->device) != hipSuccess) local_rc = set_error(RT_ERR_HIP, "hipSetDevice");
         else if (m->group.rank != 0) {
             const SceneHeader& h = hdr[i];
-            if ((local_rc = m->w32.allocate(h.ns, h.nm, h.np, h.nl)) == RT_OK)
-                local_rc = m->w64.allocate(h.ns, h.nm, h.np, h.nl);
+            if ((local_rc = m->w32.allocate(h.ns, h.nm, h.np, h.nl)) == RT_OK &&
+                (local_rc = m->w64.allocate(h.ns, h.nm, h.np, h.nl)) == RT_OK &&
+                (local_rc = m->w32.allocate_tree(h.n_tri_nodes, h.tri_flat_begin)) == RT_OK)
+                local_rc = m->w64.allocate_tree(h.n_tri_nodes, h.tri_flat_begin);
         }
         if (local_rc) local_err = rt_last_error();
     }
@@ -381,6 +390,7 @@ int group_scene_upload(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns
         m->bright_hit = h.bright_hit;
         m->bright_w = h.bright_w;
         m->duplicate_shapes = h.duplicates;
+        m->tree_info = h.tree_info;
         m->have_scene = true;
         ++m->scene_gen;
     }

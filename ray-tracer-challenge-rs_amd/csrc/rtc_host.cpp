@@ -28,6 +28,7 @@
 #include "rtc_context.hpp"
 #include "rtc_internal.hpp"
 #include "shape_identity.hpp"
+#include "tri_tree.hpp"
 
 namespace rtc {
 
@@ -206,13 +207,58 @@ std::vector<uint32_t> table_order(const rt_shape_desc* shapes, uint32_t ns, cons
     return order;
 }
 
+// The triangle hierarchy of a world (tri_tree.hpp): the bounded triangles of
+// `order` (table_order's; a record is bounded when bounding_sphere gives a
+// radius and RTC_DEBUG=cull=0 is not set) are moved to the front of the
+// triangle run in the tree's leaf order, the unbounded ones follow in their
+// old order.  Classes stay adjacent (the tree never divides one, and members
+// of a class are bounded alike), so build_world's class ends still hold.
+// No tree (an empty plan, `order` untouched) below kTriTreeMin bounded
+// triangles, under RTC_DEBUG=tri_tree=0, and (build_scene) for worlds small
+// enough for the per-scene builds' records.
+struct TrianglePlan {
+    tri::Tree tree;
+    uint32_t in_tree = 0;  // records of the triangle run reached through leaves (they come first)
+    double build_ms = 0.0;
+};
+TrianglePlan plan_triangles(const rt_context::Knobs& knobs, const rt_shape_desc* shapes, std::vector<uint32_t>& order,
+                            const std::vector<uint32_t>& cls) {
+    TrianglePlan plan;
+    if (!knobs.tri_tree || !knobs.cull) return plan;
+    const auto t0 = std::chrono::steady_clock::now();
+    size_t first = 0;
+    while (first < order.size() && shapes[order[first]].kind != RT_SHAPE_TRIANGLE) ++first;
+    std::vector<uint32_t> bounded, unbounded, bcls;
+    std::vector<tri::Ball> balls;
+    for (size_t j = first; j < order.size(); ++j) {
+        double bs[4];
+        bounding_sphere(shapes[order[j]], bs);
+        if (bs[3] >= 0.0) {
+            bounded.push_back(order[j]);
+            bcls.push_back(cls[order[j]]);
+            balls.push_back({{bs[0], bs[1], bs[2]}, bs[3]});
+        } else {
+            unbounded.push_back(order[j]);
+        }
+    }
+    if (bounded.size() < (knobs.tri_min ? knobs.tri_min : tri::kTriTreeMin)) return plan;
+    plan.tree = tri::build(balls.data(), bcls.data(), (uint32_t)bounded.size(),
+                           knobs.tri_leaf ? knobs.tri_leaf : tri::kTriLeaf);
+    plan.in_tree = (uint32_t)bounded.size();
+    size_t at = first;
+    for (uint32_t from : plan.tree.order) order[at++] = bounded[from];
+    for (uint32_t i : unbounded) order[at++] = i;
+    plan.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return plan;
+}
+
 template <typename R>
 int build_world(rt_context* ctx, DeviceWorld<R>& w, const rt_shape_desc* shapes, uint32_t ns,
                 const rt_material_desc* mats, uint32_t nm, const rt_pattern_desc* pats, uint32_t np,
-                const rt_light_desc* lights, uint32_t nl, const std::vector<uint32_t>& cls) {
+                const rt_light_desc* lights, uint32_t nl, const std::vector<uint32_t>& cls,
+                const std::vector<uint32_t>& order, const TrianglePlan& plan) {
     std::vector<ShapeRec<R>> sh;
     std::vector<int32_t> begin(kNumKinds + 1, 0);
-    const std::vector<uint32_t> order = table_order(shapes, ns, cls);
     size_t next = 0;
     for (int k = 0; k < kNumKinds; ++k) {
         begin[k] = (int32_t)sh.size();
@@ -319,7 +365,26 @@ int build_world(rt_context* ctx, DeviceWorld<R>& w, const rt_shape_desc* shapes,
     // hardware queue for the null stream at its first use, ~8 ms that a one-shot
     // render would pay.
     if ((rc = w.allocate(sh.size(), nm, np, nl))) return rc;
-    if (image_bytes) RT_HIP(hipMemcpyAsync(w.image.get(), img.data(), image_bytes, hipMemcpyHostToDevice, ctx->stream));
+    // the triangle hierarchy in R, its leaves' runs as slots of the shape table
+    std::vector<TriNode<R>> nodes(plan.tree.nodes.size());
+    for (size_t i = 0; i < nodes.size(); ++i) {
+        const tri::Node& n = plan.tree.nodes[i];
+        tri::cast_ball<R>(n.ball, nodes[i].ball);
+        nodes[i].skip = n.skip;
+        nodes[i].first = n.count ? begin[RT_SHAPE_TRIANGLE] + n.first : 0;
+        nodes[i].count = n.count;
+    }
+    if ((rc = w.allocate_tree(nodes.size(), begin[RT_SHAPE_TRIANGLE] + (int32_t)plan.in_tree))) return rc;
+    if (!nodes.empty() && (rc = hip_status(hipMemcpyAsync(w.tri_nodes.get(), nodes.data(), nodes.size() * sizeof(nodes[0]),
+                                                          hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync"))) {
+        (void)hipStreamSynchronize(ctx->stream);
+        return rc;
+    }
+    if (image_bytes && (rc = hip_status(hipMemcpyAsync(w.image.get(), img.data(), image_bytes, hipMemcpyHostToDevice,
+                                                       ctx->stream), "hipMemcpyAsync"))) {
+        (void)hipStreamSynchronize(ctx->stream);  // the node copy may still read `nodes`
+        return rc;
+    }
     if (nl && (rc = hip_status(hipMemcpyAsync(w.lights.get(), lt.data(), nl * sizeof(LightRec<R>),
                                               hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync"))) {
         (void)hipStreamSynchronize(ctx->stream);  // the image copy may still read `img`
@@ -715,6 +780,9 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
     LaunchParams<R> P{};
     P.image_rows = q.image_rows ? 1u : 0u;
     P.scene = w.scene;
+    P.tri_nodes = w.n_tri_nodes ? w.tri_nodes.get() : nullptr;
+    P.n_tri_nodes = w.n_tri_nodes;
+    P.tri_flat_begin = w.tri_flat_begin;
     if (cam) {
         for (int q = 0; q < 12; ++q) P.cam.inv[q] = (R)cam->inverse[q];
         for (int q = 0; q < 3; ++q) P.cam.origin[q] = (R)cam->origin[q];
@@ -762,7 +830,11 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
         // launch times the kernel a warm renderer runs; the direct one has none)
         const uint32_t generic_only =
             RT_FLAG_NO_SHADE | RT_FLAG_NO_TRACE | RT_FLAG_GENERATIONS | (ls.pool ? 0u : RT_FLAG_STAMPS);
-        const bool want = cam && !dup && !(flags & generic_only) &&
+        // (a world with a triangle hierarchy runs the generic kernels, which walk it)
+        const bool tree = w.n_tri_nodes > 0;
+        if (tree && ctx->jit.mode != RT_JIT_OFF && ctx->jit.log.empty())
+            ctx->jit.log = "no per-scene build: the world has a triangle hierarchy, which the generic kernels walk";
+        const bool want = cam && !dup && !tree && !(flags & generic_only) &&
                           (ctx->jit.mode == RT_JIT_SYNC || (ctx->jit.mode >= RT_JIT_AUTO && P.n_tiles >= kJitMinTiles));
         if (want) {
             ++ctx->jit.frames;
@@ -925,6 +997,9 @@ int launch_rays(rt_context* ctx, DeviceWorld<R>& w, const void* d_rays, uint64_t
     int rc;
     LaunchParams<R> P{};
     P.scene = w.scene;
+    P.tri_nodes = w.n_tri_nodes ? w.tri_nodes.get() : nullptr;
+    P.n_tri_nodes = w.n_tri_nodes;
+    P.tri_flat_begin = w.tri_flat_begin;
     P.n_rays = n;
     P.n_tiles = (uint32_t)((n + kBlock - 1) / kBlock);
     P.max_depth = o->max_depth;
@@ -1098,6 +1173,9 @@ rt_context::Knobs read_knobs() {
     }
     if (debug_knob("lds_world", &v)) k.lds_world = v != "0";
     if (debug_knob("cull", &v)) k.cull = v != "0";
+    if (debug_knob("tri_tree", &v)) k.tri_tree = v != "0";
+    if (debug_knob("tri_min", &v)) k.tri_min = (uint32_t)std::max(0, std::atoi(v.c_str()));
+    if (debug_knob("tri_leaf", &v)) k.tri_leaf = (uint32_t)std::max(0, std::atoi(v.c_str()));
     if (debug_knob("kind_variants", &v)) k.kind_variants = v != "0";
     if (debug_knob("pool_lds_rays", &v)) k.pool_lds_rays = (uint32_t)std::atoi(v.c_str());
     if (debug_knob("tile_order", &v)) k.tile_order = v != "0";
@@ -1293,9 +1371,25 @@ int build_scene(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns, const
     ctx->have_scene = false;
     std::vector<uint32_t> cls;  // value-identity classes (shape_identity.hpp)
     ctx->duplicate_shapes = ident::shape_classes(shapes, ns, mats, pats, cls);
-    if ((rc = build_world<float>(ctx, ctx->w32, shapes, ns, mats, nm, pats, np, lights, nl, cls))) return rc;
+    std::vector<uint32_t> order = table_order(shapes, ns, cls);
+    // A world the per-scene builds take whole (their records: up to
+    // kJitRecordsMaxShapes shapes) keeps the flat triangle run and with it
+    // its per-scene kernels, which measured faster for f32 frames up to that
+    // size than the generic kernels with a tree (a tree inside
+    // per-scene builds is future work).  RTC_DEBUG=tri_min=N overrides.
+    const bool per_scene_world = (int64_t)ns <= (int64_t)kJitRecordsMaxShapes && !ctx->knobs.tri_min;
+    const TrianglePlan plan = per_scene_world ? TrianglePlan{} : plan_triangles(ctx->knobs, shapes, order, cls);
+    ctx->tree_info = rt_tree_info{};
+    if (!plan.tree.nodes.empty()) {
+        uint32_t triangles = 0;
+        for (uint32_t i = 0; i < ns; ++i) triangles += shapes[i].kind == RT_SHAPE_TRIANGLE;
+        ctx->tree_info = {(uint32_t)plan.tree.nodes.size(), plan.tree.leaves, plan.tree.depth, plan.in_tree,
+                          triangles - plan.in_tree, 0u, plan.build_ms};
+    }
+    if ((rc = build_world<float>(ctx, ctx->w32, shapes, ns, mats, nm, pats, np, lights, nl, cls, order, plan))) return rc;
     if ((rc = capture_jit_table(ctx))) return rc;
-    if ((rc = build_world<double>(ctx, ctx->w64, shapes, ns, mats, nm, pats, np, lights, nl, cls))) return rc;
+    if ((rc = build_world<double>(ctx, ctx->w64, shapes, ns, mats, nm, pats, np, lights, nl, cls, order, plan)))
+        return rc;
     ctx->flops = FlopScene{};
     for (uint32_t i = 0; i < ns; ++i) {
         const rt_shape_desc& d = shapes[i];
@@ -1898,6 +1992,12 @@ int rt_jit_status(rt_context* ctx, int* used_last_launch, double* compile_ms, ch
         std::strncpy(log, ctx->jit.log.c_str(), log_len - 1);
         log[log_len - 1] = '\0';
     }
+    return RT_OK;
+}
+
+int rt_scene_tree_info(rt_context* ctx, rt_tree_info* out) {
+    if (!ctx || !out) return set_error(RT_ERR_INVALID, "null argument");
+    *out = ctx->have_scene ? ctx->tree_info : rt_tree_info{};
     return RT_OK;
 }
 

@@ -355,6 +355,17 @@ struct CameraRec {
     R half_width, half_height, pixel_size;
 };
 
+// A node of the triangle hierarchy (tri_tree.hpp; rtc_kernels.hip
+// for_triangles): nodes in depth-first preorder, `skip` the first node after
+// this node's subtree, a leaf's records [first, first + count) of the shape
+// table (an inner node's count is 0).
+template <typename R>
+struct alignas(16) TriNode {
+    R ball[4];  // padded bounding ball of the subtree: centre, radius^2
+    int32_t skip, first, count, pad;
+};
+static_assert(sizeof(TriNode<float>) == 32 && sizeof(TriNode<double>) == 48);
+
 template <typename R>
 struct DevScene {
     const ShapeRec<R>* shapes;
@@ -439,6 +450,13 @@ struct LaunchParams {
     // and the tiles stay those of the output.  Last, so that no field the
     // shipped kernels load moves.
     uint32_t ss_grid;
+    // The triangle hierarchy of the world (null / 0 for a world without one;
+    // never read by per-scene builds).  The triangle step reads these from
+    // the kernel arguments where it runs (rtc_kernels.hip for_triangles), so
+    // they take no room in DevScene, which the kernels hold in registers.
+    uint32_t n_tri_nodes;
+    const TriNode<R>* tri_nodes;  // null: no tree, every triangle record is visited
+    uint32_t tri_flat_begin;      // triangle records from this slot on are outside the tree (unbounded ones)
 };
 
 }  // namespace rtc

@@ -513,16 +513,86 @@ __device__ inline void for_kind_if(const DevScene<R>& sc, F&& f) {
     if constexpr ((RTC_KINDS >> K) & 1) for_kind<R, K>(sc, f);
 }
 
-template <typename R, typename F>
-__device__ inline void for_all_kinds(const DevScene<R>& sc, F&& f) {
+template <typename R, bool kHalfLine>
+__device__ inline bool wave_ball_may_hit(R cx, R cy, R cz, R r2, V3<R> o, V3<R> d, R dd);
+template <typename R>
+__device__ inline const LaunchParams<R>& kernarg_params();
+
+// The triangle step of a wave's rays o + t d (dd = |d|^2): every record of
+// the triangle run, or, in a world with a triangle hierarchy (tri_tree.hpp,
+// generic builds only), the leaves the wave's rays may reach.  The walk is
+// wave-uniform and stackless: node, loop index and skip link live in SGPRs,
+// the node is one scalar load, and a ball no active lane's ray may meet
+// (kHalfLine: at t >= 0; else anywhere on the line, for the containers walk,
+// which counts entries at t < 0 too) sends the wave past the node's whole
+// subtree.  A hit node's records go through the caller's callback like the
+// flat loop's (an inner node has none), then the walk steps to the first
+// child.  Acceleration only: a node's ball holds the ball of every record
+// below it (tri_tree.hpp), and a record whose ball no lane's ray meets has no
+// entry for the wave, so a subtree passed by contributes what its records
+// would have: nothing.  The wave visits the union of what its lanes need.
+// Records outside the tree (unbounded ones) follow from tri_flat_begin.
+// The node table is launch-constant memory written before the launch, read
+// through the constant address space so the loads are scalar whatever the
+// compiler can prove about the kernel's stores.
+#define RTC_AS_CONST __attribute__((address_space(4)))
+template <typename R, bool kHalfLine, typename F>
+__device__ inline void for_triangles(const DevScene<R>& sc, V3<R> o, V3<R> d, R dd, F&& f) {
+#ifdef RTC_JIT
+    (void)o;
+    (void)d;
+    (void)dd;
+    for_kind<R, RT_SHAPE_TRIANGLE>(sc, f);
+#else
+    // One loop over runs of records: the hit leaves, then (i == n) the flat
+    // run, which without a tree (n = 0) is the whole triangle run; so the
+    // callback is compiled once per caller.
+    // (the five tracer kernels, the only callers, take LaunchParams first)
+    const LaunchParams<R>& P = kernarg_params<R>();
+    const TriNode<R>* const nodes = P.tri_nodes;
+    const int n = nodes ? (int)P.n_tri_nodes : 0;  // wave-uniform (launch parameters)
+    for (int i = 0; i <= n;) {
+        int first, end;
+        if (i < n) {
+            const TriNode<R>* node = &nodes[i];
+            // (whole-vector loads: the ball and the links come as two scalar loads under one wait)
+            typedef R Ball4 __attribute__((ext_vector_type(4)));
+            typedef int32_t Link4 __attribute__((ext_vector_type(4)));
+            const Ball4 ball = *(const RTC_AS_CONST Ball4*)node->ball;
+            const Link4 link = *(const RTC_AS_CONST Link4*)&node->skip;
+            const int skip = link.x;
+            first = link.y;
+            end = first + link.z;
+            if (!wave_ball_may_hit<R, kHalfLine>(ball.x, ball.y, ball.z, ball.w, o, d, dd)) {
+                i = skip;
+                continue;
+            }
+        } else {
+            first = n ? (int)kernarg_params<R>().tri_flat_begin : sc.kind_begin[RT_SHAPE_TRIANGLE];
+            end = sc.kind_begin[RT_SHAPE_TRIANGLE + 1];
+        }
+        ++i;
+        for (int j = first; j < end; ++j) {
+            const ShapeRec<R> s = ld_uniform(&sc.shapes[j]);
+            f(s, j);
+        }
+    }
+#endif
+}
+
+// Every kind in table order; the triangle step may walk the hierarchy for the
+// wave's rays.
+template <typename R, bool kHalfLine, typename F>
+__device__ inline void for_all_kinds(const DevScene<R>& sc, V3<R> o, V3<R> d, R dd, F&& f) {
     for_kind_if<R, RT_SHAPE_SPHERE>(sc, [&](const ShapeRec<R>& s, int i) { f.template operator()<RT_SHAPE_SPHERE>(s, i); });
     for_kind_if<R, RT_SHAPE_PLANE>(sc, [&](const ShapeRec<R>& s, int i) { f.template operator()<RT_SHAPE_PLANE>(s, i); });
     for_kind_if<R, RT_SHAPE_CUBE>(sc, [&](const ShapeRec<R>& s, int i) { f.template operator()<RT_SHAPE_CUBE>(s, i); });
     for_kind_if<R, RT_SHAPE_CYLINDER>(sc,
                                    [&](const ShapeRec<R>& s, int i) { f.template operator()<RT_SHAPE_CYLINDER>(s, i); });
     for_kind_if<R, RT_SHAPE_CONE>(sc, [&](const ShapeRec<R>& s, int i) { f.template operator()<RT_SHAPE_CONE>(s, i); });
-    for_kind_if<R, RT_SHAPE_TRIANGLE>(sc,
-                                   [&](const ShapeRec<R>& s, int i) { f.template operator()<RT_SHAPE_TRIANGLE>(s, i); });
+    if constexpr ((RTC_KINDS >> RT_SHAPE_TRIANGLE) & 1)
+        for_triangles<R, kHalfLine>(sc, o, d, dd,
+                                    [&](const ShapeRec<R>& s, int i) { f.template operator()<RT_SHAPE_TRIANGLE>(s, i); });
 }
 
 // The roots of a kShapeSimilar sphere (f32), in world space: with oc = c - o
@@ -798,11 +868,8 @@ __device__ inline void for_all_culled(const DevScene<R>& sc, V3<R>& o, V3<R>& d,
         return;
     }
 #endif
-    (void)o;
-    (void)d;
-    (void)dd;
     (void)skip;
-    for_all_kinds<R>(sc, f);
+    for_all_kinds<R, kHalfLine>(sc, o, d, dd, f);
 }
 
 template <typename R>
@@ -1226,7 +1293,7 @@ __device__ inline void refractive_indices(const DevScene<R>& sc, V3<R> o, V3<R> 
         const uint32_t hit_class = (uint32_t)sc.lshapes[h.slot].flags >> kShapeClassShift;
         int count = 0;  // over the current class's records
         Key last{};
-        for_all_kinds<R>(sc, [&]<int K>(const ShapeRec<R>& s, int slot) {
+        for_all_kinds<R, false>(sc, o, d, dd, [&]<int K>(const ShapeRec<R>& s, int slot) {
             if (!kWalkCull || wave_line_may_hit<R, K>(s, o, d, dd)) scan.template operator()<K>(s, count, last);
             if (!(s.flags & kShapeClassEnd)) return;  // wave-uniform: more members follow
             settle(count, last, s, (uint32_t)s.flags >> kShapeClassShift == hit_class);
@@ -1274,7 +1341,7 @@ __device__ inline void refractive_indices(const DevScene<R>& sc, V3<R> o, V3<R> 
             return points && convex && !holds(cx, cy, cz, r2);
         });
     } else {
-        for_all_kinds<R>(sc, [&]<int K>(const ShapeRec<R>& s, int slot) {
+        for_all_kinds<R, false>(sc, o, d, dd, [&]<int K>(const ShapeRec<R>& s, int slot) {
             int count = 0;
             Key last{};
             scan.template operator()<K>(s, count, last);

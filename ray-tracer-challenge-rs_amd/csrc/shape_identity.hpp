@@ -89,6 +89,13 @@ inline uint64_t geometry_hash(const rt_shape_desc& s) {
         mix(s.minimum);
         mix(s.maximum);
     }
+    // (the triangles of a mesh share one inverse: without their vertices they
+    // would share one bucket and the class search would be quadratic)
+    if (s.kind == RT_SHAPE_TRIANGLE) {
+        for (double v : s.vertex_1) mix(v);
+        for (double v : s.edge_1) mix(v);
+        for (double v : s.edge_2) mix(v);
+    }
     return h;
 }
 

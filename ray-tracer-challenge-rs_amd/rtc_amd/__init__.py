@@ -27,6 +27,7 @@ import numpy as np
 __all__ = [
     "RenderError", "lib_path", "abi_version", "device_count", "matrix_inverse", "camera_make",
     "camera_resize", "camera_set_transform", "camera_bound_rect", "load_scene", "load_scene_text", "SceneTables", "Context", "shard_rows",
+    "load_obj", "Mesh",
     "RT_DEFAULT_MAX_DEPTH", "RT_TILE_H", "RT_TILE_W",
 ]
 
@@ -139,6 +140,17 @@ class SceneView(C.Structure):
                 ("camera", CameraDesc), ("duplicate_shapes", C.c_uint32)]
 
 
+class MeshView(C.Structure):
+    _fields_ = [("vertices", C.POINTER(C.c_double)), ("n_vertices", C.c_uint32),
+                ("triangles", C.POINTER(C.c_uint32)), ("n_triangles", C.c_uint32), ("ignored_lines", C.c_uint32)]
+
+
+class TreeInfo(C.Structure):
+    _fields_ = [("nodes", C.c_uint32), ("leaves", C.c_uint32), ("depth", C.c_uint32),
+                ("records_in_tree", C.c_uint32), ("records_outside", C.c_uint32), ("reserved", C.c_uint32),
+                ("build_ms", C.c_double)]
+
+
 # --------------------------------------------------------------- library
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -204,6 +216,12 @@ def _load() -> C.CDLL:
         "rt_scene_load_yaml_text": (C.c_int, [C.c_char_p, P(C.c_void_p)]),
         "rt_scene_view_get": (C.c_int, [C.c_void_p, P(SceneView)]),
         "rt_scene_free": (None, [C.c_void_p]),
+        "rt_mesh_load_obj": (C.c_int, [C.c_char_p, P(C.c_void_p)]),
+        "rt_mesh_load_obj_text": (C.c_int, [C.c_char_p, P(C.c_void_p)]),
+        "rt_mesh_view_get": (C.c_int, [C.c_void_p, P(MeshView)]),
+        "rt_mesh_free": (None, [C.c_void_p]),
+        "rt_mesh_triangles": (C.c_int, [C.c_void_p, P(C.c_double), C.c_int, C.c_int32, P(ShapeDesc)]),
+        "rt_scene_tree_info": (C.c_int, [C.c_void_p, P(TreeInfo)]),
         "rt_image_write": (C.c_int, [C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint32]),
         "rt_image_write_format": (C.c_int, [C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int]),
         "rt_canvas_quantize": (C.c_int, [P(C.c_double), C.c_uint64, P(C.c_uint8)]),
@@ -260,6 +278,8 @@ EXPORTED_SYMBOLS = (
     "rt_assemble_shards", "rt_scene_load_yaml", "rt_scene_load_yaml_text", "rt_scene_view_get", "rt_scene_free",
     "rt_camera_make", "rt_camera_resize", "rt_camera_bound_rect", "rt_matrix_inverse", "rt_image_write", "rt_image_write_format",
     "rt_canvas_quantize",
+    "rt_mesh_load_obj", "rt_mesh_load_obj_text", "rt_mesh_view_get", "rt_mesh_free", "rt_mesh_triangles",
+    "rt_scene_tree_info",
 )
 
 
@@ -417,6 +437,47 @@ def load_scene_text(text: str) -> SceneTables:
     return _load_with(_lib.rt_scene_load_yaml_text, text.encode())
 
 
+class Mesh:
+    """A triangle mesh read from OBJ text (rtc_scene.h rt_mesh_*): vertices (n, 3) f64, triangles (m, 3)
+    uint32 (0-based) and the number of lines the loader skipped.  world.mesh() makes Shapes of it."""
+
+    def __init__(self, handle: C.c_void_p):
+        self._h = handle
+        v = MeshView()
+        _check(_lib.rt_mesh_view_get(self._h, C.byref(v)))
+        self.vertices = np.ctypeslib.as_array(v.vertices, (v.n_vertices, 3)).copy() if v.n_vertices else \
+            np.zeros((0, 3), dtype=np.float64)
+        self.triangles = np.ctypeslib.as_array(v.triangles, (v.n_triangles, 3)).copy() if v.n_triangles else \
+            np.zeros((0, 3), dtype=np.uint32)
+        self.ignored_lines = int(v.ignored_lines)
+
+    def shape_descs(self, transform=None, bake: bool = False, material: int = 0):
+        """rt_mesh_triangles: the faces as an array of ShapeDesc (Triangle::new per face)."""
+        out = (ShapeDesc * len(self.triangles))()
+        t = None if transform is None else (C.c_double * 16)(*np.asarray(transform, dtype=np.float64).reshape(16))
+        _check(_lib.rt_mesh_triangles(self._h, t, int(bool(bake)), int(material), out))
+        return out
+
+    def __del__(self):
+        try:
+            if self._h:
+                _lib.rt_mesh_free(self._h)
+                self._h = C.c_void_p()
+        except Exception:
+            pass
+
+
+def load_obj(path_or_text) -> Mesh:
+    """An OBJ file (a path: str without a newline, bytes or os.PathLike) or OBJ text (a str holding a
+    newline) -> Mesh.  Raises RenderError(RT_ERR_IO) with the line number for a bad v or f line."""
+    h = C.c_void_p()
+    if isinstance(path_or_text, str) and "\n" in path_or_text:
+        _check(_lib.rt_mesh_load_obj_text(path_or_text.encode(), C.byref(h)))
+    else:
+        _check(_lib.rt_mesh_load_obj(os.fsencode(path_or_text), C.byref(h)))
+    return Mesh(h)
+
+
 def _ray_batch_kind(rays, precision, device):
     """("torch" | "numpy", "f32" | "f64") of a ray batch for Context.trace_rays, or ValueError."""
     if precision is not None and precision not in PRECISIONS:
@@ -521,6 +582,13 @@ class Context:
         used, ms, log = C.c_int(), C.c_double(), C.create_string_buffer(4096)
         _check(_lib.rt_jit_status(self._h, C.byref(used), C.byref(ms), log, len(log)))
         return {"used": bool(used.value), "compile_ms": ms.value, "log": log.value.decode(errors="replace")}
+
+    def tree_info(self) -> dict:
+        """The uploaded world's triangle hierarchy (rtc.h rt_scene_tree_info): nodes, leaves, depth, records in
+        and outside the tree and the host build's ms; all zero when the world has none."""
+        t = TreeInfo()
+        _check(_lib.rt_scene_tree_info(self._h, C.byref(t)))
+        return {name: getattr(t, name) for name, _ in t._fields_ if name != "reserved"}
 
     def upload(self, scene: SceneTables | None) -> None:
         """rt_scene_upload; on a non-zero rank of a group, None (the scene comes from rank 0)."""

@@ -192,7 +192,10 @@ def _cross(a, b):  # vector.rs:97-103 (mul_add: exact via math.fma when availabl
         from fractions import Fraction
 
         def fma(x, y, z):
-            return float(Fraction(x) * Fraction(y) + Fraction(z))
+            r = Fraction(x) * Fraction(y) + Fraction(z)
+            # an exact zero keeps IEEE's sign (-0 + -0 = -0, as mul_add gives): the product is then
+            # exactly -z, so the plain float expression has no rounding and the right zero
+            return float(r) if r != 0 else x * y + z
     return (fma(a[1], b[2], -a[2] * b[1]), fma(a[2], b[0], -a[0] * b[2]), fma(a[0], b[1], -a[1] * b[0]))
 
 
@@ -203,6 +206,20 @@ def triangle(p1, p2, p3, material=None):
     mag = math.sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2])
     n = (n[0] / mag, n[1] / mag, n[2] / mag)
     return Shape("triangle", material or Material(), triangle=(tuple(map(float, p1)), e1, e2, n))
+
+
+def mesh(m, material=None, transform=None, bake=False):
+    """The faces of a Mesh (rtc_amd.load_obj) as Triangle shapes sharing `material`, through the host's
+    rt_mesh_triangles: Triangle::new per face; with `transform` either set_transformation on every triangle
+    (bake=False) or the vertices multiplied by it first (bake=True, identity inverse)."""
+    mat = material or Material()
+    t = None if transform is None else [v for row in transform for v in row]
+    out = []
+    for d in m.shape_descs(t, bake):
+        inv = [list(d.inverse[4 * i:4 * i + 4]) for i in range(4)]
+        out.append(Shape("triangle", mat, transformation_inverse=inv,
+                         triangle=(tuple(d.vertex_1), tuple(d.edge_1), tuple(d.edge_2), tuple(d.normal))))
+    return out
 
 
 @dataclass
