@@ -1464,6 +1464,57 @@ __device__ inline void jit_object_each(int slot, V3<float> p, V3<float>& obj) {
         jit_object_each<I + 1, E>(slot, p, obj);
     }
 }
+
+// Wave-uniform hit (per-scene f32 direct kernel, camera frames): most waves'
+// 64 hits lie on one shape (three_sphere 1080p: 97.7 % of the 16x4 blocks),
+// and the per-lane trees above then run one case under exec bookkeeping and
+// leave the record in VGPRs, so everything after them is general code.  A
+// wave whose active lanes (valid pixels that hit) all hold the slot of the
+// first one shades with that slot as a compile-time constant instead, chosen
+// by a scalar ladder (s_cmp / s_cbranch): the material's terms fold into
+// immediates, a matte surface loses its specular code, the offset class is a
+// constant.  The same source runs in both forms (shade_hit_const; only
+// constants fold, and the normal still passes its asm so the hardware rsq
+// runs): bit-identical.  Mixed waves keep the per-lane trees.  Each slot's
+// case holds a copy of everything after the hit, the shadow test included
+// (three_sphere: 1041 -> 3106 instructions), so the cap is a code-size cap;
+// with one copy of the shadow test and a ladder on either side of it the
+// scalar side did not shrink and half the gain was lost.
+#ifndef RTC_UNIFORM_HIT
+#define RTC_UNIFORM_HIT 1  // (A/B builds: 0 keeps the per-lane trees alone)
+#endif
+constexpr int kUniformHitSlots = 6;  // worlds up to this many slots
+struct LaneSlot {  // the hit's slot, per lane
+    static constexpr bool kConst = false;
+    int v;
+};
+template <int I>
+struct ConstSlot {  // the one slot of all the wave's hits
+    static constexpr bool kConst = true;
+    static constexpr int v = I;
+};
+template <int I, int E, typename F>
+__device__ inline void jit_slot_ladder(int slot, F&& f) {  // slot: wave-uniform (an SGPR)
+    if constexpr (I < E) {
+        if (slot == I) f(ConstSlot<I>{});
+        else jit_slot_ladder<I + 1, E>(slot, f);
+    }
+}
+template <typename S>
+__device__ inline void jit_record_material(S slot, V3<float> p, V3<float>& w, MaterialRec<float>& mat) {
+    if constexpr (S::kConst) {
+        const ShapeRec<float>& s = jit::kShapes[S::v];
+        w = xform_normal(s.inv, local_normal(s, jit_kind_of<S::v>(), xform_point(s.inv, p)));
+        mat = jit::kMaterials[s.material];
+    } else {
+        jit_record_material_each<0, jit::kBegin[kNumKinds]>(slot.v, p, w, mat);
+    }
+}
+template <typename S>
+__device__ inline void jit_object(S slot, V3<float> p, V3<float>& obj) {
+    if constexpr (S::kConst) obj = xform_point(jit::kShapes[S::v].inv, p);
+    else jit_object_each<0, jit::kBegin[kNumKinds]>(slot.v, p, obj);
+}
 #endif
 
 template <typename R>
@@ -1642,23 +1693,29 @@ __device__ inline R hit_offset(const Hit<R>& h, V3<R> p, V3<R> o) {
 #ifdef RTC_JIT
 // The per-scene direct kernel (no pool, few live values): prepare_hit with
 // the material as constants of the slot's branch (kJitConstMaterials).
+// slot: h.slot per lane (LaneSlot), or the one slot of a wave-uniform hit as
+// a constant (ConstSlot: the record, its kind and the material fold).
+template <typename S>
 __device__ inline void prepare_hit_const(const DevScene<float>& sc, V3<float> o, V3<float> d, const Hit<float>& h,
-                                         Prepared<float>& q, bool& patterned, MaterialRec<float>& m) {
+                                         S slot, Prepared<float>& q, bool& patterned, MaterialRec<float>& m) {
     q.p = along(o, d, h.t);
     V3<float> w = {0.0f, 0.0f, 0.0f};
-    jit_record_material_each<0, jit::kBegin[kNumKinds]>(h.slot, q.p, w, m);
+    jit_record_material(slot, q.p, w, m);
     asm volatile("" : "+v"(w.x), "+v"(w.y), "+v"(w.z));  // the hardware rsq, as hit_normal (bit for bit)
     q.n = normalized(w);
     q.eye = vneg(d);
     if (dot(q.n, q.eye) < 0.0f) q.n = vneg(q.n);
     q.mat = -1;  // (the direct kernel walks no refractive indices)
-    q.off = hit_offset(h, q.p, o);
+    int cls;
+    if constexpr (S::kConst) cls = offset_class_of_kind(jit_kind_of<S::v>());
+    else cls = offset_class(h);
+    q.off = Real<float>::surface_offset(q.p.x, q.p.y, q.p.z, o.x, o.y, o.z, cls);  // (hit_offset)
     q.over = along(q.p, q.n, q.off);
     q.base = {m.color[0], m.color[1], m.color[2]};
     patterned = m.pattern >= 0;
     if (jit::kPatterns && patterned) {
         V3<float> obj = {0.0f, 0.0f, 0.0f};
-        jit_object_each<0, jit::kBegin[kNumKinds]>(h.slot, q.over, obj);
+        jit_object(slot, q.over, obj);
         q.base = pattern_color_obj(sc, m.pattern, obj);
     }
 }
@@ -1745,18 +1802,69 @@ __device__ inline V3<R> lighting_term(const LightRec<R>& L, const MaterialRec<R>
     if (!shadowed) {
         if (!(ldn < (R)0)) {
             c = {c.x + (eff.x * m.diffuse) * ldn, c.y + (eff.y * m.diffuse) * ldn, c.z + (eff.z * m.diffuse) * ldn};
-            const R rde = dot(reflect(vneg(ld), n), eye);
             // specular 0 (every wall of three_sphere) adds exactly +0: skip the
-            // pow (two transcendentals) for those lanes
-            if (!(rde <= (R)0) && m.specular != (R)0) {
-                const R f = Real<R>::pow(rde, m.shininess);
-                c = {c.x + (L.intensity[0] * m.specular) * f, c.y + (L.intensity[1] * m.specular) * f,
-                     c.z + (L.intensity[2] * m.specular) * f};
+            // reflection and the pow (two transcendentals) for those lanes
+            if (m.specular != (R)0) {
+                const R rde = dot(reflect(vneg(ld), n), eye);
+                if (!(rde <= (R)0)) {
+                    const R f = Real<R>::pow(rde, m.shininess);
+                    c = {c.x + (L.intensity[0] * m.specular) * f, c.y + (L.intensity[1] * m.specular) * f,
+                         c.z + (L.intensity[2] * m.specular) * f};
+                }
             }
         }
     }
     return c;
 }
+
+// One light at a hit: the unit vector to it, its cosine with the normal, and
+// the shadow test (world.rs:98-112).  kDirect: any_hit's.
+template <typename R>
+struct LightSide {
+    V3<R> ld;
+    R ldn;
+    bool shadowed;
+};
+template <typename R, bool kDirect>
+__device__ __attribute__((always_inline)) inline LightSide<R> light_side(const DevScene<R>& sc, const LightRec<R>& L,
+                                                                         V3<R> over, V3<R> n) {
+    const V3<R> lpos = {L.position[0], L.position[1], L.position[2]};
+    const V3<R> to_light = vsub(lpos, over);
+    const R dist = magnitude(to_light);
+    const V3<R> ld = normalized(to_light);  // == to_light / dist (world.rs:104-106)
+    // calculate_lighting, material.rs:83-114.  The shadow test only
+    // matters where the light is in front of the surface (ldn < 0 gives
+    // ambient only, shadowed or not), so only those lanes trace it; the
+    // reference traces it for every light (world.rs:46-52) and the event
+    // counters still count one shadow ray per light.
+    const R ldn = dot(ld, n);
+    bool shadowed = false;
+    if (!(ldn < (R)0) || !skips_on(sc)) shadowed = any_hit<R, kDirect>(sc, over, ld, dist, lpos);
+    return {ld, ldn, shadowed};
+}
+
+#ifdef RTC_JIT
+// shade_ray after the hit, for the per-scene direct kernel; slot as
+// prepare_hit_const's.  Inlined where it is called: a wave-uniform hit's
+// ladder holds one copy per slot.
+template <bool kDirect, typename S>
+__device__ __attribute__((always_inline)) inline void shade_hit_const(const DevScene<float>& sc, V3<float> o, V3<float> d,
+                                                                      const Hit<float>& h, S slot, Shaded<float>& out) {
+    Prepared<float> q;
+    MaterialRec<float> m;
+    prepare_hit_const(sc, o, d, h, slot, q, out.patterned, m);
+    V3<float> surface = {0.0f, 0.0f, 0.0f};
+    for_lights(sc, [&](const LightRec<float>& L) {
+        const LightSide<float> s = light_side<float, kDirect>(sc, L, q.over, q.n);
+        const V3<float> c = lighting_term(L, m, q.base, q.n, q.eye, s.ld, s.ldn, s.shadowed);
+        surface = {surface.x + c.x, surface.y + c.y, surface.z + c.z};
+    });
+    out.surface = surface;
+    out.refl_child = out.refr_child = false;
+    // shade_hit evaluates Schlick whenever the material is both (world.rs:59-60)
+    out.schlick = (m.reflectiveness > 0.0f) & (m.transparency > 0.0f);
+}
+#endif
 
 // blk: the wave's pixel block when (o, d) are a frame's primary rays (closest_hit's primary cull)
 template <typename R, bool kChildren, bool kDup = false, typename Push = NoPush, typename B = NoBlock>
@@ -1765,37 +1873,32 @@ __device__ inline bool shade_ray(const DevScene<R>& sc, V3<R> o, V3<R> d, uint32
     using T = Real<R>;
     const Hit<R> h = closest_hit(sc, o, d, blk);
     if (h.slot < 0) return false;  // world.rs:85: miss -> BLACK
-    Prepared<R> q;
 #ifdef RTC_JIT
-    MaterialRec<R> m_const;
-    const MaterialRec<R>* mp;
     if constexpr (kJitConstMaterials && !kChildren && sizeof(R) == 4) {
-        prepare_hit_const(sc, o, d, h, q, out.patterned, m_const);
-        mp = &m_const;
-    } else {
-        mp = &prepare_hit(sc, o, d, h, q, out.patterned);
-    }
-    const MaterialRec<R>& m = *mp;
-#else
-    const MaterialRec<R>& m = prepare_hit(sc, o, d, h, q, out.patterned);
+#if !defined(RTC_NO_SKIPS) && RTC_UNIFORM_HIT
+        // (B::kOn: the frame kernel; the supersampled one stays per lane)
+        if constexpr (B::kOn && jit::kBegin[kNumKinds] <= kUniformHitSlots) {
+            // the first active lane's slot (lanes that missed have left)
+            const int first = __builtin_amdgcn_readfirstlane(h.slot);
+            if (!wave_any(h.slot != first)) {
+                jit_slot_ladder<0, jit::kBegin[kNumKinds]>(
+                    first, [&](auto slot) { shade_hit_const<B::kOn>(sc, o, d, h, slot, out); });
+                return true;
+            }
+        }
 #endif
+        shade_hit_const<B::kOn>(sc, o, d, h, LaneSlot{h.slot}, out);
+        return true;
+    }
+#endif
+    Prepared<R> q;
+    const MaterialRec<R>& m = prepare_hit(sc, o, d, h, q, out.patterned);
     const V3<R> p = q.p, n = q.n, eye = q.eye, over = q.over, base = q.base;
     const R off = q.off;
     V3<R> surface = {(R)0, (R)0, (R)0};
     for_lights(sc, [&](const LightRec<R>& L) {
-        const V3<R> lpos = {L.position[0], L.position[1], L.position[2]};
-        const V3<R> to_light = vsub(lpos, over);
-        const R dist = magnitude(to_light);
-        const V3<R> ld = normalized(to_light);  // == to_light / dist (world.rs:104-106)
-        // calculate_lighting, material.rs:83-114.  The shadow test only
-        // matters where the light is in front of the surface (ldn < 0 gives
-        // ambient only, shadowed or not), so only those lanes trace it; the
-        // reference traces it for every light (world.rs:46-52) and the event
-        // counters still count one shadow ray per light.
-        const R ldn = dot(ld, n);
-        bool shadowed = false;
-        if (!(ldn < (R)0) || !skips_on(sc)) shadowed = any_hit<R, B::kOn>(sc, over, ld, dist, lpos);
-        const V3<R> c = lighting_term(L, m, base, n, eye, ld, ldn, shadowed);
+        const LightSide<R> s = light_side<R, B::kOn>(sc, L, over, n);
+        const V3<R> c = lighting_term(L, m, base, n, eye, s.ld, s.ldn, s.shadowed);
         surface = {surface.x + c.x, surface.y + c.y, surface.z + c.z};
     });
     out.surface = surface;
