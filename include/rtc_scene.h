@@ -112,6 +112,25 @@ int rt_camera_set_transform(rt_camera_desc* camera, const double transform[16]);
  * that is no similarity); x0 > x1 for a ball behind the camera.  Host only. */
 int rt_camera_bound_rect(const rt_camera_desc* camera, const float bound[4], uint32_t rect[4]);
 
+/* The shadow cull of the same kernel, for a wave whose hits all lie on the
+ * plane n . x = h (`plane` = {n, h} in f32: row 1 of the plane record's
+ * inverse, h negated), a light at `light` and a caster's bounding ball
+ * `bound`: the inclusive rectangle {x0, y0, x1, y1} that holds every pixel
+ * whose f32 primary ray meets the plane at t > 0, within reach of the light
+ * (99, below the distance at which the kernels' shadow cull changes form),
+ * and whose shadow ray from the f32 over-point passes the kernels' ball cull
+ * of the caster.  The whole canvas where no cull applies; x0 > x1 when
+ * the shadow falls off the canvas.  Host only. */
+int rt_camera_shadow_rect(const rt_camera_desc* camera, const float plane[4], const float light[3],
+                          const float bound[4], uint32_t rect[4]);
+
+/* The pixel columns [span[0], span[2]] and rows [span[1], span[3]] of the
+ * canvas in which every primary ray that meets the plane at all meets it
+ * within that reach of the light; lo > hi = none.  A frame's launch lets a
+ * 16 x 4 pixel block take rt_camera_shadow_rect's answer only when the block
+ * lies in those columns or in those rows.  Host only. */
+int rt_camera_shadow_near(const rt_camera_desc* camera, const float plane[4], const float light[3], uint32_t span[4]);
+
 /* Matrix<4>::inverse, row-major 16 doubles. */
 int rt_matrix_inverse(const double m[16], double out[16]);
 

@@ -909,24 +909,80 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
         // The per-scene direct kernel's primary cull: each slot's screen
         // rectangle for this camera (primary_rect.hpp), from the f32 bounds
         // the kernel's own ball test reads, as miss bits per block column and
-        // block row (rtc_internal.hpp).  Recomputed every launch (the camera
-        // is the call's argument); a few hundred ns for a small world.
+        // block row (rtc_internal.hpp), and above them the shadow cull's bits
+        // for waves that hit one plane (shadow_rect).  Recomputed every launch
+        // (the camera is the call's argument): a conic per slot and per
+        // (light, plane, caster), well under a microsecond for a small world.
         const size_t ns = ctx->jit.shapes.size();
         // (a supersampled launch takes no primary cull: the tables stay zero)
         if (jf && !ls.pool && cam && !ss && ns <= (size_t)kPrimaryRectSlots && (int)ns == w.scene.kind_begin[kNumKinds] &&
             P.width <= kCullCols * kCullCellW && P.height <= kCullRows * kCullCellH) {
             const uint32_t nc = (P.width + kCullCellW - 1) / kCullCellW, nr = (P.height + kCullCellH - 1) / kCullCellH;
+            // Each bit changes at a few edges only, so the tables are built
+            // from toggles: flip_*[i] holds the bits that change value between
+            // entry i - 1 and entry i, and one running XOR fills the entries.
+            uint32_t flip_cols[kCullCols + 1] = {}, flip_rows[kCullRows + 1] = {};
+            // bit `b` set outside the rectangle's block columns and block rows
+            auto outside = [&](const uint32_t r[4], uint32_t b) {
+                const bool none = r[0] > r[2] || r[1] > r[3];  // empty: every block misses
+                const uint32_t c0 = none ? nc : r[0] / kCullCellW, c1 = none ? nc : r[2] / kCullCellW + 1;
+                const uint32_t r0 = none ? nr : r[1] / kCullCellH, r1 = none ? nr : r[3] / kCullCellH + 1;
+                flip_cols[0] ^= b, flip_cols[c0] ^= b, flip_cols[c1] ^= b;
+                flip_rows[0] ^= b, flip_rows[r0] ^= b, flip_rows[r1] ^= b;
+            };
             for (size_t s = 0; s < ns; ++s) {
                 uint32_t r[4];
                 primary_rect(P.cam, P.width, P.height, ctx->jit.shapes[s].bound, r);
-                const bool none = r[0] > r[2] || r[1] > r[3];  // empty: every block misses
-                const uint32_t c0 = none ? nc : r[0] / kCullCellW, c1 = none ? 0 : r[2] / kCullCellW + 1;
-                const uint32_t r0 = none ? nr : r[1] / kCullCellH, r1 = none ? 0 : r[3] / kCullCellH + 1;
-                for (uint32_t i = 0; i < nc; ++i)
-                    if (i < c0 || i >= c1) P.cull_cols[i] |= 1u << s;
-                for (uint32_t j = 0; j < nr; ++j)
-                    if (j < r0 || j >= r1) P.cull_rows[j] |= 1u << s;
+                outside(r, 1u << s);
             }
+            // The shadow cull's bits (rtc_internal.hpp ShadowLayout), from the
+            // f32 records and lights the per-scene kernel holds as constants.
+            const ShadowLayout lay(w.scene.kind_begin, (int)ctx->jit.lights.size());
+            if (lay.fits() &&(int)ctx->jit.lights.size() == w.scene.n_lights) {
+                for (int p = lay.plane0; p < lay.plane0 + lay.planes; ++p) {
+                    const ShapeRec<float>& pl = ctx->jit.shapes[p];
+                    const float n[3] = {pl.inv[4], pl.inv[5], pl.inv[6]}, h = -pl.inv[7];  // object y = n . x - h
+                    uint32_t near[4] = {0, 0, P.width - 1, P.height - 1};  // the columns and rows within every light's reach
+                    for (int l = 0; l < lay.lights; ++l) {
+                        const float* lp = ctx->jit.lights[l].position;
+                        uint32_t sp[4];
+                        shadow_near(P.cam, P.width, P.height, n, h, lp, sp);
+                        for (int a = 0; a < 2; ++a) {
+                            near[a] = sp[a] > near[a] ? sp[a] : near[a];
+                            near[a + 2] = sp[a + 2] < near[a + 2] ? sp[a + 2] : near[a + 2];
+                        }
+                        for (size_t c = 0; c < ns; ++c) {
+                            const int bit = lay.pair_bit(l, p, (int)c);
+                            if (bit < 0) continue;
+                            if ((int)c == p) {  // the plane itself: every block or none
+                                if (shadow_self_clear(P.cam, n, h, lp)) flip_cols[0] ^= 1u << bit;
+                                continue;
+                            }
+                            uint32_t r[4];
+                            shadow_rect(P.cam, P.width, P.height, n, h, lp, ctx->jit.shapes[c].bound, r);
+                            outside(r, 1u << bit);
+                        }
+                    }
+                    // whole blocks inside the span (the canvas's last, ragged block ends with the canvas)
+                    auto blocks = [](uint32_t lo, uint32_t hi, uint32_t cell, uint32_t pixels, uint32_t& b0, uint32_t& b1) {
+                        b0 = b1 = 0;
+                        if (lo > hi) return;
+                        b0 = (lo + cell - 1) / cell;
+                        b1 = hi + 1 >= pixels ? (pixels + cell - 1) / cell : (hi + 1) / cell;
+                        if (b1 < b0) b1 = b0;
+                    };
+                    const uint32_t nb = 1u << lay.near_bit(p);
+                    uint32_t b0, b1;
+                    blocks(near[0], near[2], kCullCellW, P.width, b0, b1);
+                    flip_cols[b0] ^= nb, flip_cols[b1] ^= nb;
+                    blocks(near[1], near[3], kCullCellH, P.height, b0, b1);
+                    flip_rows[b0] ^= nb, flip_rows[b1] ^= nb;
+                }
+            }
+            uint32_t acc = 0;
+            for (uint32_t i = 0; i < nc; ++i) P.cull_cols[i] = acc ^= flip_cols[i];
+            acc = 0;
+            for (uint32_t j = 0; j < nr; ++j) P.cull_rows[j] = acc ^= flip_rows[j];
         }
     }
     if (jf) {

@@ -405,6 +405,39 @@ constexpr int kPrimaryRectSlots = 8;
 constexpr uint32_t kCullCellW = 16, kCullCellH = 4;
 constexpr uint32_t kCullCols = 128, kCullRows = 512;  // canvases up to 2048 x 2048
 
+// Shadow cull of the same kernel (rtc_kernels.hip any_hit under
+// shade_hit_const, primary_rect.hpp shadow_rect): bits 8..31 of the same
+// words.  A wave whose hits all lie on plane p asks, per light l and caster c,
+// whether its block lies outside the screen rectangle in which c's ball can
+// shadow p from l; the plane as its own caster has a bit too (set in every
+// column when the eye and the light share a side of it).  The rectangles speak
+// only for hits within reach of the light (shadow_near), so each plane has one
+// more bit, set where a block column or row holds no hit beyond it; the pair
+// bits count only under it.  One mapping for the host (scene.kind_begin) and
+// the kernel (jit::kBegin); a world whose bits do not fit takes none, and
+// every launch the primary cull leaves at zero leaves these at zero too.
+constexpr int kShadowRectSlots = 6;  // the wave-uniform hit's cap (rtc_kernels.hip kUniformHitSlots)
+constexpr int kShadowBit0 = kPrimaryRectSlots, kShadowBits = 32 - kPrimaryRectSlots;
+struct ShadowLayout {
+    int planes, casters, lights, plane0;  // casters: the slots that are no planes
+    constexpr ShadowLayout(const int32_t* kb, int n_lights)
+        : planes(kb[RT_SHAPE_PLANE + 1] - kb[RT_SHAPE_PLANE]), casters(kb[kNumKinds] - planes), lights(n_lights),
+          plane0(kb[RT_SHAPE_PLANE]) {}
+    constexpr bool fits() const {
+        return planes > 0 && lights > 0 && planes + casters <= kShadowRectSlots &&
+               planes + lights * planes * (casters + 1) <= kShadowBits;
+    }
+    constexpr bool is_plane(int slot) const { return slot >= plane0 && slot < plane0 + planes; }
+    // the bit under which plane `slot`'s pair bits count
+    constexpr int near_bit(int slot) const { return kShadowBit0 + (slot - plane0); }
+    // caster `c` on plane `slot` from `light`; -1: no bit (another plane)
+    constexpr int pair_bit(int light, int slot, int c) const {
+        if (is_plane(c) && c != slot) return -1;
+        const int rank = c == slot ? casters : (c < plane0 ? c : c - planes);
+        return kShadowBit0 + planes + (light * planes + (slot - plane0)) * (casters + 1) + rank;
+    }
+};
+
 // One launch of the tracer.
 template <typename R>
 struct LaunchParams {
@@ -443,7 +476,7 @@ struct LaunchParams {
     unsigned long long* gen_counts;    // RT_FLAG_GENERATIONS: traced[kGenSlots], shaded[kGenSlots]; else null
     int32_t* error_flag;               // set nonzero on pool overflow
     uint32_t cull_cols[kCullCols];     // primary cull: slots whose rectangle misses a block column ...
-    uint32_t cull_rows[kCullRows];     // ... or a block row (above); zero = none
+    uint32_t cull_rows[kCullRows];     // ... or a block row (above); zero = none.  Bits 8..31: ShadowLayout's
     // Supersampled frames (trace_direct_ss, trace_pool_ss; 0 for every other
     // launch): n x n samples per pixel.  `cam` is then the sample camera (the
     // output camera resized to n x width by n x height) while width, height

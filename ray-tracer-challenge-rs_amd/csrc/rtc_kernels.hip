@@ -1099,11 +1099,56 @@ struct Blocker {
     }
 };
 
+// Shadow cull by screen rectangles (per-scene f32 direct kernel, camera
+// frames, waves whose hits all lie on one plane: shade_hit_const): whether a
+// caster's ball can shadow that plane from a light, anywhere in the wave's
+// pixel block, is a question about pixel rectangles too, and the launch
+// answers it in bits 8..31 of the words the primary cull loads
+// (rtc_internal.hpp ShadowLayout, primary_rect.hpp shadow_rect).  any_hit
+// passes a caster by on one scalar bit test, ahead of its ball test (for the
+// plane itself, ahead of its side test).  NoShadowBits: every other caller.
+#ifndef RTC_SHADOW_RECTS
+#define RTC_SHADOW_RECTS 1  // (A/B builds: 0 keeps the per-lane tests alone)
+#endif
+struct NoShadowBits {
+    static constexpr bool kOn = false;
+    __device__ bool skips(int) const { return false; }
+    __device__ bool skips_every_ball() const { return false; }
+};
+#ifdef RTC_JIT
+template <int kPlane, int kLightIndex>
+struct ShadowBits {
+    static constexpr bool kOn = true;
+    uint32_t w;  // the block's word; zero unless the plane's near bit is set
+    // (the layout as a local constant everywhere: a static member is read from memory)
+    __device__ inline bool skips(int caster) const {  // caster: a constant once the shape's step is inlined
+        constexpr ShadowLayout lay{jit::kBegin, jit::kNumLights};
+        const int bit = lay.pair_bit(kLightIndex, kPlane, caster);
+        return bit >= 0 && ((w >> (bit & 31)) & 1u);
+    }
+    // the casters whose cull reads the light's distance (any_hit's `near`)
+    static constexpr uint32_t ball_mask() {
+        constexpr ShadowLayout lay{jit::kBegin, jit::kNumLights};
+        uint32_t m = 0;
+        for (int c = 0; c < jit::kBegin[kNumKinds]; ++c)
+            if (!lay.is_plane(c) && jit::kShapes[c].casts_shadow && jit::kShapes[c].bound[3] >= 0.0f &&
+                jit::kShapes[c].bound[3] < __builtin_huge_valf())
+                m |= 1u << lay.pair_bit(kLightIndex, kPlane, c);
+        return m;
+    }
+    __device__ inline bool skips_every_ball() const {
+        constexpr uint32_t kBalls = ball_mask();
+        return (w & kBalls) == kBalls;
+    }
+};
+#endif
+
 // is_in_shadow (world.rs:98-112): any casting shape with 0 <= t < distance.
 // lpos: the light the ray runs to (o + dist d).  kDirect: called by the
-// direct kernel (its per-scene build culls from the light's side).
-template <typename R, bool kDirect = false>
-__device__ inline bool any_hit(const DevScene<R>& sc, V3<R> o, V3<R> d, R dist, V3<R> lpos) {
+// direct kernel (its per-scene build culls from the light's side).  sb: the
+// wave's shadow-rectangle bits for this light and the plane it hit.
+template <typename R, bool kDirect = false, typename SB = NoShadowBits>
+__device__ inline bool any_hit(const DevScene<R>& sc, V3<R> o, V3<R> d, R dist, V3<R> lpos, SB sb = SB{}) {
     Blocker<R> b;
 #if defined(RTC_JIT) && !defined(RTC_NO_SKIPS) && RTC_SHADOW_LIGHT_CULL
     // the per-scene f32 direct build culls from the light's side (wave_ball_may_hit_from)
@@ -1126,7 +1171,8 @@ __device__ inline bool any_hit(const DevScene<R>& sc, V3<R> o, V3<R> d, R dist, 
     constexpr R kLightCullFar = (R)100;
     const V3<R> tl = vsub(lpos, o);
     const R tt = Real<R>::madd(tl.z, tl.z, Real<R>::madd(tl.y, tl.y, tl.x * tl.x));
-    const bool near = kLight && !wave_any(!(tt <= kLightCullFar * kLightCullFar));
+    // (a wave whose bits pass every ball by asks nobody: its block holds near hits only)
+    const bool near = kLight && (sb.skips_every_ball() || !wave_any(!(tt <= kLightCullFar * kLightCullFar)));
     auto ball_may_hit = [&](R cx, R cy, R cz, R r2) {
         if (kLight && near) return wave_ball_may_hit_from<R>(cx, cy, cz, r2, lpos, tl, tt);
         return wave_ball_may_hit<R, true>(cx, cy, cz, r2, o, d, kLight ? dot(d, d) : dd0);
@@ -1142,6 +1188,8 @@ __device__ inline bool any_hit(const DevScene<R>& sc, V3<R> o, V3<R> d, R dist, 
     };
     for_all_culled<R, true, !kLight>(sc, o, d, dd0, [&]<int K>(const ShapeRec<R>& s, int slot) {
         if (!s.casts_shadow) return;  // wave-uniform
+        if constexpr (SB::kOn)
+            if (sb.skips(slot)) return;  // wave-uniform, SALU
         jit_fence(o, d, slot);
         if (K == RT_SHAPE_CUBE && skips) {
             // A cube blocks the segment from o to the light only if no face
@@ -1484,6 +1532,7 @@ __device__ inline void jit_object_each(int slot, V3<float> p, V3<float>& obj) {
 #define RTC_UNIFORM_HIT 1  // (A/B builds: 0 keeps the per-lane trees alone)
 #endif
 constexpr int kUniformHitSlots = 6;  // worlds up to this many slots
+static_assert(kUniformHitSlots == kShadowRectSlots, "the shadow bits are cut for the wave-uniform hit's worlds");
 struct LaneSlot {  // the hit's slot, per lane
     static constexpr bool kConst = false;
     int v;
@@ -1825,9 +1874,9 @@ struct LightSide {
     R ldn;
     bool shadowed;
 };
-template <typename R, bool kDirect>
+template <typename R, bool kDirect, typename SB = NoShadowBits>
 __device__ __attribute__((always_inline)) inline LightSide<R> light_side(const DevScene<R>& sc, const LightRec<R>& L,
-                                                                         V3<R> over, V3<R> n) {
+                                                                         V3<R> over, V3<R> n, SB sb = SB{}) {
     const V3<R> lpos = {L.position[0], L.position[1], L.position[2]};
     const V3<R> to_light = vsub(lpos, over);
     const R dist = magnitude(to_light);
@@ -1839,26 +1888,52 @@ __device__ __attribute__((always_inline)) inline LightSide<R> light_side(const D
     // counters still count one shadow ray per light.
     const R ldn = dot(ld, n);
     bool shadowed = false;
-    if (!(ldn < (R)0) || !skips_on(sc)) shadowed = any_hit<R, kDirect>(sc, over, ld, dist, lpos);
+    if (!(ldn < (R)0) || !skips_on(sc)) shadowed = any_hit<R, kDirect, SB>(sc, over, ld, dist, lpos, sb);
     return {ld, ldn, shadowed};
 }
 
 #ifdef RTC_JIT
+// the lights again, each with the shadow bits of (light, plane kPlane) in the block's word w
+template <int I, int E, int kPlane, typename F>
+__device__ inline void jit_light_each_bits(uint32_t w, F&& f) {
+    if constexpr (I < E) {
+        f(jit::kLights[I], ShadowBits<kPlane, I>{w});
+        jit_light_each_bits<I + 1, E, kPlane>(w, f);
+    }
+}
 // shade_ray after the hit, for the per-scene direct kernel; slot as
 // prepare_hit_const's.  Inlined where it is called: a wave-uniform hit's
-// ladder holds one copy per slot.
+// ladder holds one copy per slot.  miss: the wave's pixel-block word
+// (wave_pixel_block) where the slot is the one slot of the wave's hits.
 template <bool kDirect, typename S>
 __device__ __attribute__((always_inline)) inline void shade_hit_const(const DevScene<float>& sc, V3<float> o, V3<float> d,
-                                                                      const Hit<float>& h, S slot, Shaded<float>& out) {
+                                                                      const Hit<float>& h, S slot, Shaded<float>& out,
+                                                                      uint32_t miss = 0u) {
     Prepared<float> q;
     MaterialRec<float> m;
     prepare_hit_const(sc, o, d, h, slot, q, out.patterned, m);
     V3<float> surface = {0.0f, 0.0f, 0.0f};
-    for_lights(sc, [&](const LightRec<float>& L) {
-        const LightSide<float> s = light_side<float, kDirect>(sc, L, q.over, q.n);
+    auto light = [&](const LightRec<float>& L, auto sb) {
+        const LightSide<float> s = light_side<float, kDirect>(sc, L, q.over, q.n, sb);
         const V3<float> c = lighting_term(L, m, q.base, q.n, q.eye, s.ld, s.ldn, s.shadowed);
         surface = {surface.x + c.x, surface.y + c.y, surface.z + c.z};
-    });
+    };
+    constexpr ShadowLayout kLay{jit::kBegin, jit::kNumLights};
+    constexpr int kSlot = [] { if constexpr (S::kConst) return S::v; else return -1; }();
+#if !defined(RTC_NO_SKIPS) && RTC_SHADOW_RECTS
+    constexpr bool kBits = kDirect && kSlot >= 0 && kLay.fits() && kLay.is_plane(kSlot);
+#else
+    constexpr bool kBits = false;
+#endif
+    if constexpr (kBits) {
+        // the rectangles speak for blocks whose hits lie within reach of the lights only
+        constexpr uint32_t kNear = 1u << kLay.near_bit(kSlot);
+        const uint32_t w = miss & kNear ? miss : 0u;
+        jit_light_each_bits<0, jit::kNumLights, kSlot>(w, light);
+    } else {
+        (void)miss;
+        for_lights(sc, [&](const LightRec<float>& L) { light(L, NoShadowBits{}); });
+    }
     out.surface = surface;
     out.refl_child = out.refr_child = false;
     // shade_hit evaluates Schlick whenever the material is both (world.rs:59-60)
@@ -1882,7 +1957,7 @@ __device__ inline bool shade_ray(const DevScene<R>& sc, V3<R> o, V3<R> d, uint32
             const int first = __builtin_amdgcn_readfirstlane(h.slot);
             if (!wave_any(h.slot != first)) {
                 jit_slot_ladder<0, jit::kBegin[kNumKinds]>(
-                    first, [&](auto slot) { shade_hit_const<B::kOn>(sc, o, d, h, slot, out); });
+                    first, [&](auto slot) { shade_hit_const<B::kOn>(sc, o, d, h, slot, out, blk.miss); });
                 return true;
             }
         }

@@ -830,6 +830,31 @@ int rt_camera_bound_rect(const rt_camera_desc* cam, const float bound[4], uint32
     return RT_OK;
 }
 
+static rtc::CameraRec<float> launch_camera(const rt_camera_desc* cam) {  // as a launch casts it (rtc_host.cpp launch)
+    rtc::CameraRec<float> c;
+    for (int q = 0; q < 12; ++q) c.inv[q] = (float)cam->inverse[q];
+    for (int q = 0; q < 3; ++q) c.origin[q] = (float)cam->origin[q];
+    c.half_width = (float)cam->half_width;
+    c.half_height = (float)cam->half_height;
+    c.pixel_size = (float)cam->pixel_size;
+    return c;
+}
+
+int rt_camera_shadow_rect(const rt_camera_desc* cam, const float plane[4], const float light[3], const float bound[4],
+                          uint32_t rect[4]) {
+    if (!cam || !plane || !light || !bound || !rect) return rtc::set_error(RT_ERR_INVALID, "rt_camera_shadow_rect: null argument");
+    if (cam->width == 0 || cam->height == 0) return rtc::set_error(RT_ERR_INVALID, "rt_camera_shadow_rect: empty canvas");
+    rtc::shadow_rect(launch_camera(cam), cam->width, cam->height, plane, plane[3], light, bound, rect);
+    return RT_OK;
+}
+
+int rt_camera_shadow_near(const rt_camera_desc* cam, const float plane[4], const float light[3], uint32_t span[4]) {
+    if (!cam || !plane || !light || !span) return rtc::set_error(RT_ERR_INVALID, "rt_camera_shadow_near: null argument");
+    if (cam->width == 0 || cam->height == 0) return rtc::set_error(RT_ERR_INVALID, "rt_camera_shadow_near: empty canvas");
+    rtc::shadow_near(launch_camera(cam), cam->width, cam->height, plane, plane[3], light, span);
+    return RT_OK;
+}
+
 int rt_matrix_inverse(const double m[16], double out[16]) {
     if (!m || !out) return rtc::set_error(RT_ERR_INVALID, "rt_matrix_inverse: null argument");
     rtc::hm::M4 a;

@@ -229,6 +229,8 @@ def _load() -> C.CDLL:
                                      P(C.c_double), P(CameraDesc)]),
         "rt_camera_resize": (C.c_int, [P(CameraDesc), C.c_uint32, C.c_uint32]),
         "rt_camera_bound_rect": (C.c_int, [P(CameraDesc), P(C.c_float), P(C.c_uint32)]),
+        "rt_camera_shadow_rect": (C.c_int, [P(CameraDesc), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_uint32)]),
+        "rt_camera_shadow_near": (C.c_int, [P(CameraDesc), P(C.c_float), P(C.c_float), P(C.c_uint32)]),
         "rt_matrix_inverse": (C.c_int, [P(C.c_double), P(C.c_double)]),
         "rt_camera_set_transform": (C.c_int, [P(CameraDesc), P(C.c_double)]),
         "rt_shard_row_map": (C.c_int, [C.c_uint32, C.c_uint32, P(C.c_uint32), P(C.c_uint32)]),
@@ -276,7 +278,8 @@ EXPORTED_SYMBOLS = (
     "rt_context_set_jit", "rt_context_set_frames_in_flight", "rt_jit_status", "rt_jit_wait", "rt_canvas_create", "rt_canvas_open", "rt_canvas_close",
     "rt_render_to_canvas", "rt_canvas_wait", "rt_canvas_release", "rt_canvas_read", "rt_context_set_gather",
     "rt_assemble_shards", "rt_scene_load_yaml", "rt_scene_load_yaml_text", "rt_scene_view_get", "rt_scene_free",
-    "rt_camera_make", "rt_camera_resize", "rt_camera_bound_rect", "rt_matrix_inverse", "rt_image_write", "rt_image_write_format",
+    "rt_camera_make", "rt_camera_resize", "rt_camera_bound_rect", "rt_camera_shadow_rect", "rt_camera_shadow_near",
+    "rt_matrix_inverse", "rt_image_write", "rt_image_write_format",
     "rt_canvas_quantize",
     "rt_mesh_load_obj", "rt_mesh_load_obj_text", "rt_mesh_view_get", "rt_mesh_free", "rt_mesh_triangles",
     "rt_scene_tree_info",
@@ -335,6 +338,27 @@ def camera_bound_rect(cam: CameraDesc, bound) -> tuple:
     b = (C.c_float * 4)(*np.asarray(bound, dtype=np.float32).reshape(4))
     r = (C.c_uint32 * 4)()
     _check(_lib.rt_camera_bound_rect(C.byref(cam), b, r))
+    return tuple(r[:])
+
+
+def _f32s(values, n):
+    return (C.c_float * n)(*np.asarray(values, dtype=np.float32).reshape(n))
+
+
+def camera_shadow_rect(cam: CameraDesc, plane, light, bound) -> tuple:
+    """(x0, y0, x1, y1), inclusive: the pixels of `cam` that meet the plane `plane` = (n, h), n . x = h, within
+    reach of `light` and whose shadow rays can pass the wave cull of the caster's ball `bound` = (centre,
+    radius^2), all in f32; x0 > x1 = none (rt_camera_shadow_rect)."""
+    r = (C.c_uint32 * 4)()
+    _check(_lib.rt_camera_shadow_rect(C.byref(cam), _f32s(plane, 4), _f32s(light, 3), _f32s(bound, 4), r))
+    return tuple(r[:])
+
+
+def camera_shadow_near(cam: CameraDesc, plane, light) -> tuple:
+    """(x0, y0, x1, y1): the columns x0..x1 and the rows y0..y1 of `cam` whose every hit on `plane` lies within
+    reach of `light`; lo > hi = none (rt_camera_shadow_near)."""
+    r = (C.c_uint32 * 4)()
+    _check(_lib.rt_camera_shadow_near(C.byref(cam), _f32s(plane, 4), _f32s(light, 3), r))
     return tuple(r[:])
 
 
