@@ -458,6 +458,67 @@ typedef struct rt_tree_info {
 } rt_tree_info;
 int rt_scene_tree_info(rt_context* ctx, rt_tree_info* out);
 
+/* Mesh instances: one mesh, many placements.  An instanced
+ * world is three lists: the plain shapes, meshes (local-space triangles with
+ * the identity inverse, as rt_mesh_triangles(mesh, NULL, 0, any) writes them;
+ * their `material` is ignored) and instances (mesh, inverse, material).  It
+ * MEANS the flat world
+ *     shapes ++ E(0) ++ E(1) ++ ...
+ * where E(k) is mesh instances[k].mesh's triangles in mesh order, each with
+ * inverse = instances[k].inverse and material = instances[k].material: what
+ * rt_mesh_triangles(mesh, transform, 0, material) writes when inverse =
+ * rt_matrix_inverse(transform).  rt_instances_expand writes that list (host
+ * only; `out` holds n_shapes + the sum of the instances' triangle counts).
+ * World indices are the expansion's (triangle j of instance k: n_shapes +
+ * the triangle counts of instances 0..k-1 + j): tie rule, rt_ray_hit_*::shape.
+ * Every entry point returns for an instanced upload what it returns for the
+ * expansion uploaded with rt_scene_upload, bytes and rt_stats, while the
+ * device holds each mesh's records and bounding-ball hierarchy once and one
+ * small record per instance.  An instance with a triangle value-equal to
+ * another of the world (shape_identity: equal inverse, material and geometry;
+ * in itself, in another instance or among the plain shapes) is uploaded as
+ * plain records, and rt_instance_info counts it in `expanded`.  A world with
+ * an instance not expanded runs the generic kernels only (rt_jit_status says
+ * so); n_instances = 0 is rt_scene_upload itself.
+ * RT_ERR_INVALID, each with its own rt_last_error text: a mesh record that is
+ * no triangle or whose inverse is not the identity, an empty mesh, a mesh or
+ * material index out of range, an expansion of 2^24 shapes or more. */
+typedef struct rt_mesh_desc {
+    const rt_shape_desc* triangles;
+    uint32_t n_triangles;
+    uint32_t reserved;
+} rt_mesh_desc;
+typedef struct rt_instance_desc {
+    uint32_t mesh;       /* index into the mesh list     */
+    int32_t material;    /* index into the material table */
+    double inverse[16];  /* row-major Matrix<4>: the inverse of the placement */
+} rt_instance_desc;
+int rt_scene_upload_instanced(rt_context* ctx,
+                              const rt_shape_desc* shapes, uint32_t n_shapes,
+                              const rt_mesh_desc* meshes, uint32_t n_meshes,
+                              const rt_instance_desc* instances, uint32_t n_instances,
+                              const rt_material_desc* materials, uint32_t n_materials,
+                              const rt_pattern_desc* patterns, uint32_t n_patterns,
+                              const rt_light_desc* lights, uint32_t n_lights);
+int rt_instances_expand(const rt_shape_desc* shapes, uint32_t n_shapes,
+                        const rt_mesh_desc* meshes, uint32_t n_meshes,
+                        const rt_instance_desc* instances, uint32_t n_instances,
+                        rt_shape_desc* out);
+/* What the last upload holds of meshes and instances (zeros after
+ * rt_scene_upload).  Bytes are device bytes of both precisions' tables. */
+typedef struct rt_instance_info {
+    uint32_t meshes;
+    uint32_t instances;
+    uint32_t expanded;          /* instances uploaded as plain records (value-equal partners) */
+    uint32_t top_depth;         /* depth of the hierarchy over the instances; 0: a flat loop */
+    uint32_t local_records;     /* local triangle records per precision (not expanded meshes') */
+    uint32_t local_nodes;       /* nodes of the meshes' hierarchies per precision */
+    uint64_t instanced_bytes;   /* local records, nodes, instance records and index tables */
+    uint64_t expansion_bytes;   /* records and nodes the not expanded instances' triangles would take as plain shapes */
+    double build_ms;            /* host time of the mesh builds and the identity decisions */
+} rt_instance_info;
+int rt_scene_instance_info(rt_context* ctx, rt_instance_info* out);
+
 /* Peer canvas: a frame assembled in place instead of gathered (SURVEY.md
  * §8e; the north star's "gather of framebuffer strips over xGMI" done as the
  * shards' own stores into rank 0's image).  The owner creates a device canvas

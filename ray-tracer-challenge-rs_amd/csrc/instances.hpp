@@ -1,0 +1,325 @@
+// instances.hpp — the host side of mesh instances (rtc.h
+// rt_scene_upload_instanced; header only: rtc_host.cpp, tests/instances.cpp).
+//
+// An instanced world MEANS its expansion, shapes ++ E(0) ++ E(1) ++ ... with
+// E(k) the triangles of mesh instances[k].mesh under instances[k]'s inverse
+// and material (expand() is that definition in code).  What is here:
+//   validate()      the refusals of rtc.h, each with its own text;
+//   plan_mesh()     a mesh's local balls, its hierarchy (tri_tree.hpp), the
+//                   record order the tree leaves it in and the table from
+//                   local index to record position;
+//   instance_ball() the world ball of a placed mesh;
+//   decide_expanded() which instances have a value-equal partner and are
+//                   uploaded as plain records (the containers walk identifies
+//                   shapes by value: shape_identity.hpp);
+//   world_bases()   the world index of each instance's first triangle.
+#pragma once
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <string>
+#include <unordered_map>
+#include <utility>
+#include <vector>
+
+#include "../../include/rtc.h"
+#include "host_math.hpp"
+#include "shape_identity.hpp"
+#include "tri_tree.hpp"
+
+namespace rtc {
+namespace inst {
+
+// world_slot keeps 24 bits of slot (rtc_internal.hpp DevScene::world_slot)
+constexpr uint64_t kMaxWorldShapes = 1ull << 24;
+
+inline bool identity_inverse(const double m[16]) {
+    for (int i = 0; i < 16; ++i)
+        if (!(m[i] == (i % 5 == 0 ? 1.0 : 0.0))) return false;
+    return true;
+}
+
+// Empty when the lists are well formed, else the reason (RT_ERR_INVALID).
+inline std::string validate(const rt_shape_desc* shapes, uint32_t ns, const rt_mesh_desc* meshes, uint32_t n_meshes,
+                            const rt_instance_desc* instances, uint32_t n_inst, uint32_t n_materials) {
+    if ((ns && !shapes) || (n_meshes && !meshes) || (n_inst && !instances))
+        return "rt_scene_upload_instanced: null table with nonzero count";
+    for (uint32_t m = 0; m < n_meshes; ++m) {
+        if (meshes[m].n_triangles == 0 || !meshes[m].triangles) return "mesh " + std::to_string(m) + ": empty mesh";
+        for (uint32_t j = 0; j < meshes[m].n_triangles; ++j) {
+            const rt_shape_desc& d = meshes[m].triangles[j];
+            if (d.kind != RT_SHAPE_TRIANGLE)
+                return "mesh " + std::to_string(m) + " record " + std::to_string(j) + ": not a triangle";
+            if (!identity_inverse(d.inverse))
+                return "mesh " + std::to_string(m) + " record " + std::to_string(j) + ": inverse is not the identity";
+        }
+    }
+    uint64_t total = ns;
+    for (uint32_t k = 0; k < n_inst; ++k) {
+        if (instances[k].mesh >= n_meshes) return "instance " + std::to_string(k) + ": mesh index out of range";
+        if (instances[k].material < 0 || (uint32_t)instances[k].material >= n_materials)
+            return "instance " + std::to_string(k) + ": material index out of range";
+        total += meshes[instances[k].mesh].n_triangles;
+        if (total >= kMaxWorldShapes) return "instanced world: the expansion has 2^24 shapes or more";
+    }
+    return "";
+}
+
+// World index of each instance's triangle 0; bases[n_inst] = the world's size.
+inline std::vector<uint32_t> world_bases(uint32_t ns, const rt_mesh_desc* meshes, const rt_instance_desc* instances,
+                                         uint32_t n_inst) {
+    std::vector<uint32_t> b(n_inst + 1);
+    uint32_t at = ns;
+    for (uint32_t k = 0; k < n_inst; ++k) {
+        b[k] = at;
+        at += meshes[instances[k].mesh].n_triangles;
+    }
+    b[n_inst] = at;
+    return b;
+}
+
+// E(k) into out[0 .. n_triangles): the mesh's records with the instance's inverse and material.
+inline void expand_instance(const rt_mesh_desc& mesh, const rt_instance_desc& in, rt_shape_desc* out) {
+    for (uint32_t j = 0; j < mesh.n_triangles; ++j) {
+        out[j] = mesh.triangles[j];
+        std::memcpy(out[j].inverse, in.inverse, sizeof in.inverse);
+        out[j].material = in.material;
+    }
+}
+inline void expand(const rt_shape_desc* shapes, uint32_t ns, const rt_mesh_desc* meshes, const rt_instance_desc* instances,
+                   uint32_t n_inst, rt_shape_desc* out) {
+    for (uint32_t i = 0; i < ns; ++i) out[i] = shapes[i];
+    rt_shape_desc* at = out + ns;
+    for (uint32_t k = 0; k < n_inst; ++k) {
+        expand_instance(meshes[instances[k].mesh], instances[k], at);
+        at += meshes[instances[k].mesh].n_triangles;
+    }
+}
+
+// The ball rtc_host.cpp bounding_sphere gives a triangle record whose inverse
+// is the identity (the forward matrix is the identity too: stretch 1, the
+// centre unmoved); false for one without a finite ball.
+inline bool local_ball(const rt_shape_desc& d, tri::Ball* out) {
+    double p[3][3], c[3], r = 0.0;
+    for (int q = 0; q < 3; ++q) {
+        p[0][q] = d.vertex_1[q];
+        p[1][q] = d.vertex_1[q] + d.edge_1[q];
+        p[2][q] = d.vertex_1[q] + d.edge_2[q];
+    }
+    for (int q = 0; q < 3; ++q) c[q] = (p[0][q] + p[1][q] + p[2][q]) / 3.0;
+    for (auto& v : p)
+        r = std::max(r, std::sqrt((v[0] - c[0]) * (v[0] - c[0]) + (v[1] - c[1]) * (v[1] - c[1]) +
+                                  (v[2] - c[2]) * (v[2] - c[2])));
+    const double pr = tri::padded_radius(c, r);
+    if (!std::isfinite(c[0]) || !std::isfinite(c[1]) || !std::isfinite(c[2]) || !std::isfinite(pr) || pr > 1e18)
+        return false;
+    *out = {{c[0], c[1], c[2]}, pr};
+    return true;
+}
+
+// One mesh as the device holds it: the records with a ball first, in the
+// leaf order of the tree over them, the others after them in mesh order (a
+// flat run every wave that reaches an instance tests).
+struct MeshPlan {
+    tri::Tree tree;                // leaves' runs are positions
+    std::vector<uint32_t> order;   // position -> local index
+    std::vector<uint32_t> pos;     // local index -> position
+    std::vector<tri::Ball> balls;  // by local index; r < 0: none
+    uint32_t in_tree = 0;          // positions [0, in_tree) are reached through leaves
+};
+// cull = false (RTC_DEBUG=cull=0): no balls, no tree, every record in the flat run.
+// tree = false (RTC_DEBUG=tri_tree=0): the balls, and every record in the flat run.
+inline MeshPlan plan_mesh(const rt_mesh_desc& mesh, bool cull, bool tree = true, uint32_t leaf_max = tri::kTriLeaf) {
+    MeshPlan p;
+    const uint32_t n = mesh.n_triangles;
+    p.balls.assign(n, tri::Ball{{0.0, 0.0, 0.0}, -1.0});
+    std::vector<uint32_t> bounded, unbounded;
+    std::vector<tri::Ball> bb;
+    for (uint32_t j = 0; j < n; ++j) {
+        tri::Ball b;
+        const bool have = cull && local_ball(mesh.triangles[j], &b);
+        if (have) p.balls[j] = b;
+        if (have && tree) {
+            bounded.push_back(j);
+            bb.push_back(b);
+        } else {
+            unbounded.push_back(j);
+        }
+    }
+    // (every record a class of its own: an instanced mesh has no repeated face, decide_expanded)
+    p.tree = tri::build(bb.data(), bounded.data(), (uint32_t)bounded.size(), leaf_max);
+    p.in_tree = (uint32_t)bounded.size();
+    p.order.reserve(n);
+    for (uint32_t from : p.tree.order) p.order.push_back(bounded[from]);
+    for (uint32_t j : unbounded) p.order.push_back(j);
+    p.pos.assign(n, 0);
+    for (uint32_t at = 0; at < n; ++at) p.pos[p.order[at]] = at;
+    return p;
+}
+
+// The world ball of a mesh (its root ball, local space) under an instance:
+// the centre's image, the radius times an upper bound of the linear part's
+// largest stretch (sqrt of the largest absolute row sum of F^T F, as
+// bounding_sphere), padded by bounding_sphere's rule.  false: no ball (a
+// singular or non-finite forward matrix).
+inline bool instance_ball(const tri::Ball& root, const double inverse[16], tri::Ball* out) {
+    hm::M4 inv;
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) inv.m[i][j] = inverse[4 * i + j];
+    const hm::M4 f = hm::inverse(inv);
+    double ftf[3][3] = {}, sigma2 = 0.0;
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j)
+            for (int k = 0; k < 3; ++k) ftf[i][j] += f.m[k][i] * f.m[k][j];
+    for (auto& row : ftf) sigma2 = std::max(sigma2, std::fabs(row[0]) + std::fabs(row[1]) + std::fabs(row[2]));
+    double wc[3];
+    for (int i = 0; i < 3; ++i)
+        wc[i] = f.m[i][0] * root.c[0] + f.m[i][1] * root.c[1] + f.m[i][2] * root.c[2] + f.m[i][3];
+    const double wr = root.r * std::sqrt(sigma2);
+    const double pr = tri::padded_radius(wc, wr);
+    if (!std::isfinite(wc[0]) || !std::isfinite(wc[1]) || !std::isfinite(wc[2]) || !std::isfinite(wr) ||
+        !std::isfinite(sigma2) || !(pr <= 1e18))
+        return false;
+    *out = {{wc[0], wc[1], wc[2]}, pr};
+    return true;
+}
+
+// ---- identity ---------------------------------------------------------------
+// Two triangles of the expansion are value-equal (shape_identity.hpp shape_eq)
+// only when their inverses are equal, their materials value-equal and their
+// local geometry equal.  So: holders of an (inverse, material), the instances
+// and the plain triangles, are bucketed by the inverse's hash; two holders of
+// one bucket with equal inverse and material are partners when their geometry
+// meets: two instances of one mesh always, of two meshes when the meshes share
+// a face, an instance and a plain triangle when the mesh has that face.  A
+// mesh with a repeated face makes every instance of it its own partner.  (An
+// inverse that holds a NaN equals nothing, itself included.)
+inline bool geometry_eq(const rt_shape_desc& x, const rt_shape_desc& y) {
+    return ident::reals_eq(x.vertex_1, y.vertex_1, 3) && ident::reals_eq(x.edge_1, y.edge_1, 3) &&
+           ident::reals_eq(x.edge_2, y.edge_2, 3) && ident::reals_eq(x.normal, y.normal, 3);
+}
+inline uint64_t local_hash(const rt_shape_desc& s) {  // consistent with geometry_eq (-0 and +0 alike)
+    uint64_t h = 1469598103934665603ull;
+    auto mix = [&h](double v) {
+        if (v == 0.0) v = 0.0;
+        uint64_t b;
+        std::memcpy(&b, &v, sizeof b);
+        h = (h ^ b) * 1099511628211ull;
+        h ^= h >> 29;
+    };
+    for (double v : s.vertex_1) mix(v);
+    for (double v : s.edge_1) mix(v);
+    for (double v : s.edge_2) mix(v);
+    return h;
+}
+inline uint64_t inverse_hash(const double m[16]) {
+    uint64_t h = 1469598103934665603ull;
+    for (int i = 0; i < 16; ++i) {
+        double v = m[i];
+        if (v == 0.0) v = 0.0;
+        uint64_t b;
+        std::memcpy(&b, &v, sizeof b);
+        h = (h ^ b) * 1099511628211ull;
+        h ^= h >> 29;
+    }
+    return h;
+}
+// A mesh's faces by hash, sorted: (hash, local index)
+using FaceIndex = std::vector<std::pair<uint64_t, uint32_t>>;
+inline FaceIndex face_index(const rt_mesh_desc& mesh) {
+    FaceIndex f(mesh.n_triangles);
+    for (uint32_t j = 0; j < mesh.n_triangles; ++j) f[j] = {local_hash(mesh.triangles[j]), j};
+    std::sort(f.begin(), f.end());
+    return f;
+}
+inline bool repeated_face(const rt_mesh_desc& mesh, const FaceIndex& f) {
+    for (size_t a = 0; a < f.size(); ++a)
+        for (size_t b = a + 1; b < f.size() && f[b].first == f[a].first; ++b)
+            if (geometry_eq(mesh.triangles[f[a].second], mesh.triangles[f[b].second])) return true;
+    return false;
+}
+inline bool has_face(const rt_mesh_desc& mesh, const FaceIndex& f, const rt_shape_desc& t) {
+    const uint64_t h = local_hash(t);
+    for (auto it = std::lower_bound(f.begin(), f.end(), std::make_pair(h, 0u)); it != f.end() && it->first == h; ++it)
+        if (geometry_eq(mesh.triangles[it->second], t)) return true;
+    return false;
+}
+inline bool share_face(const rt_mesh_desc& a, const FaceIndex& fa, const rt_mesh_desc& b, const FaceIndex& fb) {
+    size_t i = 0, j = 0;
+    while (i < fa.size() && j < fb.size()) {
+        if (fa[i].first < fb[j].first) ++i;
+        else if (fb[j].first < fa[i].first) ++j;
+        else {
+            const uint64_t h = fa[i].first;
+            size_t ie = i, je = j;
+            while (ie < fa.size() && fa[ie].first == h) ++ie;
+            while (je < fb.size() && fb[je].first == h) ++je;
+            for (size_t x = i; x < ie; ++x)
+                for (size_t y = j; y < je; ++y)
+                    if (geometry_eq(a.triangles[fa[x].second], b.triangles[fb[y].second])) return true;
+            i = ie;
+            j = je;
+        }
+    }
+    return false;
+}
+
+// expanded[k] = 1: instance k has a triangle value-equal to another triangle
+// of the expansion and is uploaded as plain records.
+inline std::vector<char> decide_expanded(const rt_shape_desc* shapes, uint32_t ns, const rt_mesh_desc* meshes,
+                                         uint32_t n_meshes, const rt_instance_desc* instances, uint32_t n_inst,
+                                         const rt_material_desc* mats, const rt_pattern_desc* pats) {
+    std::vector<char> expanded(n_inst, 0);
+    if (!n_inst) return expanded;
+    std::vector<FaceIndex> faces(n_meshes);
+    std::vector<char> used(n_meshes, 0), repeated(n_meshes, 0);
+    for (uint32_t k = 0; k < n_inst; ++k) used[instances[k].mesh] = 1;
+    for (uint32_t m = 0; m < n_meshes; ++m)
+        if (used[m]) {
+            faces[m] = face_index(meshes[m]);
+            repeated[m] = repeated_face(meshes[m], faces[m]);
+        }
+    struct Holder {
+        const double* inverse;
+        int32_t material;
+        int64_t instance;  // or -1: plain triangle `shape`
+        uint32_t shape;
+    };
+    std::unordered_map<uint64_t, std::vector<Holder>> buckets;
+    for (uint32_t k = 0; k < n_inst; ++k)
+        buckets[inverse_hash(instances[k].inverse)].push_back({instances[k].inverse, instances[k].material, k, 0u});
+    for (uint32_t i = 0; i < ns; ++i)
+        if (shapes[i].kind == RT_SHAPE_TRIANGLE) {
+            auto it = buckets.find(inverse_hash(shapes[i].inverse));
+            if (it != buckets.end()) it->second.push_back({shapes[i].inverse, shapes[i].material, -1, i});
+        }
+    for (auto& kv : buckets) {
+        const std::vector<Holder>& hs = kv.second;
+        for (size_t a = 0; a < hs.size(); ++a) {
+            if (hs[a].instance < 0) continue;  // (instances come first in a bucket)
+            const uint32_t ka = (uint32_t)hs[a].instance, ma = instances[ka].mesh;
+            if (!ident::reals_eq(hs[a].inverse, hs[a].inverse, 16)) continue;  // a NaN: equal to nothing
+            if (repeated[ma]) expanded[ka] = 1;
+            for (size_t b = a + 1; b < hs.size(); ++b) {
+                if (hs[b].instance >= 0 && expanded[ka] && expanded[(uint32_t)hs[b].instance]) continue;
+                if (hs[b].instance < 0 && expanded[ka]) continue;
+                if (!ident::reals_eq(hs[a].inverse, hs[b].inverse, 16) ||
+                    !ident::material_eq(mats, pats, hs[a].material, hs[b].material))
+                    continue;
+                if (hs[b].instance >= 0) {
+                    const uint32_t kb = (uint32_t)hs[b].instance, mb = instances[kb].mesh;
+                    if (ma == mb || share_face(meshes[ma], faces[ma], meshes[mb], faces[mb]))
+                        expanded[ka] = expanded[kb] = 1;
+                } else if (has_face(meshes[ma], faces[ma], shapes[hs[b].shape])) {
+                    expanded[ka] = 1;
+                }
+            }
+        }
+    }
+    return expanded;
+}
+
+}  // namespace inst
+}  // namespace rtc

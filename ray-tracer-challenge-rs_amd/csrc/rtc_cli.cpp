@@ -13,12 +13,17 @@
 // averaged on the device: rt_render_supersampled; 1, the
 // default, is the reference's one ray per pixel), --obj FILE (repeatable: the
 // triangles of a Wavefront OBJ mesh, rtc_scene.h rt_mesh_*, appended after the
-// YAML world's shapes with Material::default and no transformation).  Pixels
+// YAML world's shapes with Material::default and no transformation),
+// --instance FILE:tx,ty,tz[:s] (repeatable: a copy of the mesh scaled by s,
+// default 1, and moved by (tx, ty, tz), with Material::default, after every
+// shape and --obj triangle, in command-line order; each FILE is loaded once and
+// the world goes up through rt_scene_upload_instanced).  Pixels
 // are quantized on the device as canvas.rs:117-123 does.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <string>
 #include <vector>
 
@@ -29,15 +34,42 @@ static int usage() {
     std::fprintf(stderr,
                  "usage: rtc <SCENE.yaml> <OUT.png|OUT.ppm> [-r serial|parallel|gpu] [-q] [--width W] [--height H]\n"
                  "           [--depth D] [--precision f32|f64] [--device N] [--gpus N] [--ppm-binary] [--timings]\n"
-                 "           [--samples N] [--obj MESH.obj]...\n"
+                 "           [--samples N] [--obj MESH.obj]... [--instance MESH.obj:tx,ty,tz[:s]]...\n"
                  "  --obj MESH.obj appends the mesh's triangles (v and f lines; faces fan-triangulated) to the\n"
                  "  scene's shapes, with the default material and no transformation; repeatable.\n"
+                 "  --instance MESH.obj:tx,ty,tz[:s] places a copy of the mesh, scaled by s (default 1) and moved by\n"
+                 "  (tx, ty, tz), with the default material, after the shapes; repeatable, each file is read once.\n"
                  "  --samples N renders N x N samples per pixel (1..%d, default 1 = one ray per pixel centre) and\n"
                  "  averages them on the GPU.\n"
                  "  -r serial|parallel are accepted for the reference's command lines but render on the GPU like\n"
                  "  -r gpu: this build ships no CPU renderer (Camera::render / render_parallel are not in it).\n",
                  RT_MAX_SAMPLE_GRID);
     return 2;
+}
+
+// One --instance argument: FILE:tx,ty,tz[:s]
+struct Placement {
+    std::string file;
+    double t[3], s;
+};
+static bool parse_placement(const std::string& a, Placement* out) {
+    auto triple = [](const std::string& v, double t[3]) {
+        char tail = 0;
+        return std::sscanf(v.c_str(), "%lf,%lf,%lf%c", &t[0], &t[1], &t[2], &tail) == 3;
+    };
+    const size_t last = a.rfind(':');
+    if (last == std::string::npos || last == 0) return false;
+    out->s = 1.0;
+    if (triple(a.substr(last + 1), out->t)) {
+        out->file = a.substr(0, last);
+        return true;
+    }
+    char* end = nullptr;
+    out->s = std::strtod(a.c_str() + last + 1, &end);
+    const size_t mid = a.rfind(':', last - 1);
+    if (end == a.c_str() + last + 1 || *end || mid == std::string::npos || mid == 0) return false;
+    out->file = a.substr(0, mid);
+    return triple(a.substr(mid + 1, last - mid - 1), out->t);
 }
 
 int main(int argc, char** argv) {
@@ -56,6 +88,7 @@ int main(int argc, char** argv) {
     int device = 0, gpus = 1;
     uint32_t samples = 1;
     std::vector<const char*> obj_paths;
+    std::vector<Placement> placements;
     for (int i = 3; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> const char* { return i + 1 < argc ? argv[++i] : nullptr; };
@@ -81,6 +114,15 @@ int main(int argc, char** argv) {
             samples = (uint32_t)n;
         }
         else if (a == "--obj") { const char* v = next(); if (!v) return usage(); obj_paths.push_back(v); }
+        else if (a == "--instance") {
+            const char* v = next();
+            Placement p;
+            if (!v || !parse_placement(v, &p)) {
+                std::fprintf(stderr, "error: --instance takes FILE:tx,ty,tz[:s]\n");
+                return usage();
+            }
+            placements.push_back(p);
+        }
         else if (a == "--device") { const char* v = next(); if (!v) return usage(); device = std::atoi(v); }
         else if (a == "--precision") {
             const char* v = next();
@@ -105,7 +147,7 @@ int main(int argc, char** argv) {
     // (material.rs:157-161) appended to the materials
     std::vector<rt_shape_desc> shapes(v.shapes, v.shapes + v.n_shapes);
     std::vector<rt_material_desc> materials(v.materials, v.materials + v.n_materials);
-    if (!obj_paths.empty()) {
+    if (!obj_paths.empty() || !placements.empty()) {
         rt_material_desc m = {};
         m.color[0] = m.color[1] = m.color[2] = 1.0;
         m.ambient = 0.1;
@@ -135,6 +177,41 @@ int main(int argc, char** argv) {
                         mv.ignored_lines);
         rt_mesh_free(mesh);
     }
+    // --instance: each file's local triangles once, and one (mesh, inverse, material) per placement
+    std::map<std::string, uint32_t> mesh_of;
+    std::vector<std::vector<rt_shape_desc>> mesh_triangles;
+    std::vector<rt_instance_desc> instances;
+    for (const Placement& p : placements) {
+        auto found = mesh_of.find(p.file);
+        if (found == mesh_of.end()) {
+            rt_mesh* mesh = nullptr;
+            rt_mesh_view mv;
+            if (rt_mesh_load_obj(p.file.c_str(), &mesh) != RT_OK || rt_mesh_view_get(mesh, &mv) != RT_OK) {
+                std::fprintf(stderr, "error: %s\n", rt_last_error());
+                return 1;
+            }
+            std::vector<rt_shape_desc> tri(mv.n_triangles);
+            if (rt_mesh_triangles(mesh, nullptr, 0, 0, tri.data()) != RT_OK) {
+                std::fprintf(stderr, "error: %s\n", rt_last_error());
+                return 1;
+            }
+            if (!quiet)
+                std::printf("%s: %u vertices, %u triangles, %u lines ignored\n", p.file.c_str(), mv.n_vertices,
+                            mv.n_triangles, mv.ignored_lines);
+            rt_mesh_free(mesh);
+            found = mesh_of.emplace(p.file, (uint32_t)mesh_triangles.size()).first;
+            mesh_triangles.push_back(std::move(tri));
+        }
+        // translation(t) * scaling(s, s, s) (transformations.rs), inverted as Shape::set_transformation does
+        const double forward[16] = {p.s, 0, 0, p.t[0], 0, p.s, 0, p.t[1], 0, 0, p.s, p.t[2], 0, 0, 0, 1};
+        rt_instance_desc d = {};
+        d.mesh = found->second;
+        d.material = (int32_t)materials.size() - 1;
+        rt_matrix_inverse(forward, d.inverse);
+        instances.push_back(d);
+    }
+    std::vector<rt_mesh_desc> meshes;
+    for (const auto& tri : mesh_triangles) meshes.push_back({tri.data(), (uint32_t)tri.size(), 0u});
     const double load_ms = ms_since(t_load);
     const auto t_ctx = clk::now();
     rt_context* ctx = nullptr;
@@ -144,8 +221,10 @@ int main(int argc, char** argv) {
     const double ctx_ms = ms_since(t_ctx);
     const auto t_up = clk::now();
     if (created != RT_OK ||
-        rt_scene_upload(ctx, shapes.data(), (uint32_t)shapes.size(), materials.data(), (uint32_t)materials.size(),
-                        v.patterns, v.n_patterns, v.lights, v.n_lights) != RT_OK) {
+        rt_scene_upload_instanced(ctx, shapes.data(), (uint32_t)shapes.size(), meshes.data(), (uint32_t)meshes.size(),
+                                  instances.data(), (uint32_t)instances.size(), materials.data(),
+                                  (uint32_t)materials.size(), v.patterns, v.n_patterns, v.lights,
+                                  v.n_lights) != RT_OK) {  // (no instances: rt_scene_upload itself)
         std::fprintf(stderr, "error: %s\n", rt_last_error());
         return 1;
     }

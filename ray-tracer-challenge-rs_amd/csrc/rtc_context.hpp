@@ -26,6 +26,12 @@ namespace rtc {
 // allocation in the kernels' LDS layout ([shapes][materials][patterns]
 // [world_slot], world_lds_bytes), so a workgroup stages the world into LDS
 // with one contiguous copy (scene_view).
+// Sizes of a world's instance tables (the same for both precisions; a group's header carries them).
+struct InstanceCounts {
+    uint32_t instances = 0, records = 0, nodes = 0, pos = 0;
+    int32_t world_begin = 0;  // world indices from here on are instances' triangles
+};
+
 template <typename R>
 struct DeviceWorld {
     DeviceBuffer<unsigned char> image;  // the allocation holding the four tables
@@ -37,6 +43,12 @@ struct DeviceWorld {
     uint32_t n_tri_nodes = 0;            // 0: the world has no tree
     uint32_t tri_flat_begin = 0;         // first triangle slot outside the tree
     int32_t* world_slot = nullptr;
+    // Mesh instances (rt_scene_upload_instanced; rtc_internal.hpp InstRec): outside the LDS image like the tree
+    DeviceBuffer<InstRec<R>> inst;
+    DeviceBuffer<ShapeRec<R>> inst_shapes;  // every mesh's local records
+    DeviceBuffer<TriNode<R>> inst_nodes;    // every mesh's hierarchy
+    DeviceBuffer<int32_t> inst_pos;         // local index -> record (InstRec::pos_begin)
+    InstanceCounts inst_counts{};           // zeros: a world without instances
     DevScene<R> scene{};
     // Point the tables into `image` for ns shapes, nm materials, np patterns.
     void carve(size_t ns, size_t nm, size_t np) {
@@ -72,7 +84,23 @@ struct DeviceWorld {
         tri_flat_begin = n ? (uint32_t)flat_begin : 0u;
         return RT_OK;
     }
+    // Room for the instance tables of `c`; all zero: the world has no instances.
+    int allocate_instances(const InstanceCounts& c) {
+        int rc;
+        if ((rc = inst.reserve(c.instances)) || (rc = inst_shapes.reserve(c.records)) ||
+            (rc = inst_nodes.reserve(c.nodes)) || (rc = inst_pos.reserve(c.pos)))
+            return rc;
+        inst_counts = c;
+        return RT_OK;
+    }
 };
+
+// Does the world hold instances the kernels walk?  (A world whose instances
+// were all uploaded expanded is a plain world and holds none.)
+template <typename R>
+inline bool walked_instances(const DeviceWorld<R>& w) {
+    return w.inst_counts.instances > 0;
+}
 
 struct CodeBuild;  // rtc_jit.cpp: one hipRTC build of a per-scene kernel, possibly in flight
 
@@ -238,6 +266,7 @@ struct rt_context {
     uint64_t scene_gen = 0;      // bumped by every rt_scene_upload
     uint32_t duplicate_shapes = 0;  // shapes value-equal to an earlier one (one identity class)
     rt_tree_info tree_info{};       // the triangle hierarchy of the uploaded world (rt_scene_tree_info; zeros = none)
+    rt_instance_info instance_info{};  // meshes and instances of the uploaded world (rt_scene_instance_info)
     std::vector<int32_t> world_slot;  // world index -> slot | kind << 24 of the uploaded table
     // ray-pool overflow regions, one per resident workgroup; a ray batch's per-lane LIFOs (launch_rays)
     rtc::DeviceBuffer<unsigned char> d_spill;
@@ -299,9 +328,24 @@ int copy_to_host(rt_context* ctx, void* out, size_t bytes);  // d_scratch -> cal
 uint32_t tile_rows_for(uint32_t height, uint32_t shards, uint32_t shard);
 int validate_scene(const rt_shape_desc* shapes, uint32_t ns, const rt_material_desc* mats, uint32_t nm,
                    const rt_pattern_desc* pats, uint32_t np, const rt_light_desc* lights, uint32_t nl);
+// The mesh and instance lists of rt_scene_upload_instanced
+struct InstancedLists {
+    const rt_mesh_desc* meshes;
+    uint32_t n_meshes;
+    const rt_instance_desc* instances;
+    uint32_t n_instances;
+};
+int validate_scene_instanced(const rt_shape_desc* shapes, uint32_t ns, const InstancedLists& il,
+                             const rt_material_desc* mats, uint32_t nm, const rt_pattern_desc* pats, uint32_t np,
+                             const rt_light_desc* lights, uint32_t nl);
 // Flatten and upload the world tables to this device (no validation, no sync).
 int build_scene(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns, const rt_material_desc* mats, uint32_t nm,
                 const rt_pattern_desc* pats, uint32_t np, const rt_light_desc* lights, uint32_t nl);
+// ... of an instanced world (rtc.h rt_scene_upload_instanced; validated lists)
+int build_scene_instanced(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns, const rt_mesh_desc* meshes,
+                          uint32_t n_meshes, const rt_instance_desc* instances, uint32_t n_inst,
+                          const rt_material_desc* mats, uint32_t nm, const rt_pattern_desc* pats, uint32_t np,
+                          const rt_light_desc* lights, uint32_t nl);
 void scene_brightness(const rt_shape_desc* shapes, uint32_t ns, const rt_material_desc* mats, uint32_t nm,
                       const rt_pattern_desc* pats, uint32_t np,
                       const rt_light_desc* lights, uint32_t nl, double* bright_hit, double* bright_w);
@@ -334,7 +378,7 @@ const std::string& device_arch(rt_context* ctx);  // rtc_jit.cpp: the device's g
 // rtc_group.cpp: the same entry points on a multi-GPU context
 int group_scene_upload(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns, const rt_material_desc* mats,
                        uint32_t nm, const rt_pattern_desc* pats, uint32_t np, const rt_light_desc* lights,
-                       uint32_t nl);
+                       uint32_t nl, const InstancedLists* il = nullptr);  // il: rt_scene_upload_instanced's lists
 int group_render_device(rt_context* ctx, const rt_camera_desc* cam, const rt_render_options* o, void* out_device,
                         hipStream_t stream);
 int group_render(rt_context* ctx, const rt_camera_desc* cam, const rt_render_options* o, void* out_host,

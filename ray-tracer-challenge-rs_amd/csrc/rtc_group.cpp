@@ -49,6 +49,7 @@ namespace {
 struct SceneHeader {
     int32_t status;  // rank 0's validation/upload result: the others fail with it too
     uint32_t ns, nm, np, nl;
+    uint32_t n_world_slots;  // world indices world_slot answers for (ns, but for an instanced world)
     int32_t kind_begin[kNumKinds + 1];
     int32_t any_secondary;
     uint32_t duplicates;
@@ -57,6 +58,8 @@ struct SceneHeader {
     uint32_t n_tri_nodes;         // the triangle hierarchy (tri_tree.hpp): 0 = none
     int32_t tri_flat_begin;
     rt_tree_info tree_info;
+    InstanceCounts inst;  // mesh instances (rt_scene_upload_instanced): zeros = none
+    rt_instance_info instance_info;
 };
 
 // (device pointer, bytes) of every table of a member's world, in one order
@@ -66,6 +69,10 @@ void world_buffers(DeviceWorld<R>& w, const SceneHeader& h, std::vector<std::pai
     out.push_back({w.image.get(), world_lds_bytes<R>(h.ns, h.nm, h.np)});  // shapes, materials, patterns, world_slot
     out.push_back({w.lights.get(), h.nl * sizeof(LightRec<R>)});
     out.push_back({w.tri_nodes.get(), h.n_tri_nodes * sizeof(TriNode<R>)});
+    out.push_back({w.inst.get(), h.inst.instances * sizeof(InstRec<R>)});
+    out.push_back({w.inst_shapes.get(), h.inst.records * sizeof(ShapeRec<R>)});
+    out.push_back({w.inst_nodes.get(), h.inst.nodes * sizeof(TriNode<R>)});
+    out.push_back({w.inst_pos.get(), h.inst.pos * sizeof(int32_t)});
 }
 
 // Rank 0's `value` to every member of every rank, over RCCL (collective):
@@ -303,7 +310,7 @@ int agree_status(const std::vector<rt_context*>& ms, int local) {
 
 int group_scene_upload(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns, const rt_material_desc* mats,
                        uint32_t nm, const rt_pattern_desc* pats, uint32_t np, const rt_light_desc* lights,
-                       uint32_t nl) {
+                       uint32_t nl, const InstancedLists* il) {
     const std::vector<rt_context*> ms = members(ctx);
     int rc;
     SceneHeader root_h{};
@@ -317,11 +324,20 @@ int group_scene_upload(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns
     if (ctx->group.rank == 0) {  // only rank 0's tables are used (rtc.h)
         // a failure here still takes part in the header broadcast, so the
         // other ranks return it instead of waiting in the table broadcast
-        root_rc = validate_scene(shapes, ns, mats, nm, pats, np, lights, nl);
+        root_rc = il ? validate_scene_instanced(shapes, ns, *il, mats, nm, pats, np, lights, nl)
+                     : validate_scene(shapes, ns, mats, nm, pats, np, lights, nl);
         if (!root_rc && hipSetDevice(ctx->device) != hipSuccess) root_rc = set_error(RT_ERR_HIP, "hipSetDevice");
-        if (!root_rc) root_rc = build_scene(ctx, shapes, ns, mats, nm, pats, np, lights, nl);
+        if (!root_rc)
+            root_rc = il ? build_scene_instanced(ctx, shapes, ns, il->meshes, il->n_meshes, il->instances, il->n_instances,
+                                                 mats, nm, pats, np, lights, nl)
+                         : build_scene(ctx, shapes, ns, mats, nm, pats, np, lights, nl);
         if (root_rc) root_err = rt_last_error();
         root_h.status = root_rc;
+        // (the shape table's size: an instanced world's also holds the instances uploaded expanded)
+        ns = root_rc ? ns : (uint32_t)ctx->w32.scene.kind_begin[kNumKinds];
+        root_h.n_world_slots = (uint32_t)ctx->world_slot.size();
+        root_h.inst = ctx->w32.inst_counts;
+        root_h.instance_info = ctx->instance_info;
         root_h.ns = ns;
         root_h.nm = nm;
         root_h.np = np;
@@ -354,10 +370,15 @@ int group_scene_upload(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns
         if (hipSetDevice(m->device) != hipSuccess) local_rc = set_error(RT_ERR_HIP, "hipSetDevice");
         else if (m->group.rank != 0) {
             const SceneHeader& h = hdr[i];
+            // (worlds with and without instances run different kernels: the cached occupancies go)
+            if ((h.inst.instances > 0) != walked_instances(m->w32))
+                std::fill(std::begin(m->occ_blocks), std::end(m->occ_blocks), 0);
             if ((local_rc = m->w32.allocate(h.ns, h.nm, h.np, h.nl)) == RT_OK &&
                 (local_rc = m->w64.allocate(h.ns, h.nm, h.np, h.nl)) == RT_OK &&
-                (local_rc = m->w32.allocate_tree(h.n_tri_nodes, h.tri_flat_begin)) == RT_OK)
-                local_rc = m->w64.allocate_tree(h.n_tri_nodes, h.tri_flat_begin);
+                (local_rc = m->w32.allocate_tree(h.n_tri_nodes, h.tri_flat_begin)) == RT_OK &&
+                (local_rc = m->w64.allocate_tree(h.n_tri_nodes, h.tri_flat_begin)) == RT_OK &&
+                (local_rc = m->w32.allocate_instances(h.inst)) == RT_OK)
+                local_rc = m->w64.allocate_instances(h.inst);
         }
         if (local_rc) local_err = rt_last_error();
     }
@@ -380,9 +401,10 @@ int group_scene_upload(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns
         const SceneHeader& h = hdr[i];
         for (int k = 0; k <= kNumKinds; ++k) m->w32.scene.kind_begin[k] = m->w64.scene.kind_begin[k] = h.kind_begin[k];
         m->w32.scene.any_secondary = m->w64.scene.any_secondary = h.any_secondary;
-        m->world_slot.assign(h.ns, 0);
-        if (h.ns)
-            RT_HIP(hipMemcpy(m->world_slot.data(), m->w32.world_slot, h.ns * sizeof(int32_t), hipMemcpyDeviceToHost));
+        m->world_slot.assign(h.n_world_slots, 0);
+        if (h.n_world_slots)
+            RT_HIP(hipMemcpy(m->world_slot.data(), m->w32.world_slot, h.n_world_slots * sizeof(int32_t),
+                             hipMemcpyDeviceToHost));
         if ((rc = fetch_jit_tables(m)) || (rc = capture_jit_table(m))) return rc;
         m->flops = FlopScene{};
         m->flops.per_ray = h.flops_per_ray;
@@ -391,6 +413,7 @@ int group_scene_upload(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns
         m->bright_w = h.bright_w;
         m->duplicate_shapes = h.duplicates;
         m->tree_info = h.tree_info;
+        m->instance_info = h.instance_info;
         m->have_scene = true;
         ++m->scene_gen;
     }

@@ -29,6 +29,7 @@
 #include "rtc_internal.hpp"
 #include "shape_identity.hpp"
 #include "tri_tree.hpp"
+#include "instances.hpp"
 
 namespace rtc {
 
@@ -49,6 +50,23 @@ hipError_t launch_trace_ss(const LaunchParams<R>& P, bool pool, bool dup, uint32
 template <typename R>
 hipError_t occupancy_ss(bool pool, bool lds, size_t dyn_lds, int* blocks_per_cu);
 
+namespace instanced {  // rtc_kernels_inst*.o: every tracer kernel with the instance level, for worlds with mesh instances
+template <typename R>
+hipError_t launch_trace(const LaunchParams<R>& P, bool pool, bool dup, uint32_t grid, size_t dyn_lds,
+                        hipStream_t stream);
+template <typename R>
+hipError_t occupancy(bool pool, bool lds, size_t dyn_lds, int* blocks_per_cu);
+template <typename R>
+hipError_t launch_trace_rays(const LaunchParams<R>& P, bool dup, uint32_t grid, size_t dyn_lds, const void* rays,
+                             void* rgb, void* hits, hipStream_t stream);
+template <typename R>
+hipError_t occupancy_rays(bool lds, size_t dyn_lds, int* blocks_per_cu);
+template <typename R>
+hipError_t launch_trace_ss(const LaunchParams<R>& P, bool pool, bool dup, uint32_t grid, size_t dyn_lds,
+                           hipStream_t stream);
+template <typename R>
+hipError_t occupancy_ss(bool pool, bool lds, size_t dyn_lds, int* blocks_per_cu);
+}  // namespace instanced
 namespace sp {  // rtc_kernels_sp.o: the f32 pool kernel for worlds of spheres and planes only
 template <typename R>
 hipError_t launch_trace(const LaunchParams<R>& P, bool pool, bool dup, uint32_t grid, size_t dyn_lds,
@@ -252,11 +270,23 @@ TrianglePlan plan_triangles(const rt_context::Knobs& knobs, const rt_shape_desc*
     return plan;
 }
 
+// World indices of a shape list that is not the whole world (an instanced
+// world's plain records: the shapes, then the triangles of the instances
+// uploaded expanded, whose world indices are the expansion's).  Default: the
+// list is the world, shape i is world index i.
+struct WorldIndices {
+    const uint32_t* index = nullptr;  // world index of list entry i; null: i
+    uint32_t n_plain = 0;             // with `index`: entries [0, n_plain) are the world's first shapes (world_slot's reach)
+    std::vector<int32_t>* slot_of = nullptr;  // out: slot | kind << 24 of list entry i
+    uint32_t of(uint32_t i) const { return index ? index[i] : i; }
+    uint32_t plain(uint32_t ns) const { return index ? n_plain : ns; }
+};
+
 template <typename R>
 int build_world(rt_context* ctx, DeviceWorld<R>& w, const rt_shape_desc* shapes, uint32_t ns,
                 const rt_material_desc* mats, uint32_t nm, const rt_pattern_desc* pats, uint32_t np,
                 const rt_light_desc* lights, uint32_t nl, const std::vector<uint32_t>& cls,
-                const std::vector<uint32_t>& order, const TrianglePlan& plan) {
+                const std::vector<uint32_t>& order, const TrianglePlan& plan, const WorldIndices& wi = WorldIndices{}) {
     std::vector<ShapeRec<R>> sh;
     std::vector<int32_t> begin(kNumKinds + 1, 0);
     size_t next = 0;
@@ -298,11 +328,11 @@ int build_world(rt_context* ctx, DeviceWorld<R>& w, const rt_shape_desc* shapes,
                     r.tri[6 + q] = (R)feps[q];
                     r.tri[9 + q] = (R)fsgn[q];
                 }
-            r.world_index = (int32_t)i;
+            r.world_index = (int32_t)wi.of(i);
             r.material = d.material;
             const bool class_end = next + 1 >= order.size() || cls[order[next + 1]] != cls[i];
             r.flags = (d.closed ? kShapeClosed : 0) | (class_end ? kShapeClassEnd : 0) | (similar ? kShapeSimilar : 0) | (aligned ? kShapeAxisAligned : 0) |
-                      (int32_t)(cls[i] << kShapeClassShift);
+                      (int32_t)(wi.of(cls[i]) << kShapeClassShift);
             r.casts_shadow = mats[d.material].casts_shadow ? 1 : 0;
             sh.push_back(r);
         }
@@ -311,7 +341,12 @@ int build_world(rt_context* ctx, DeviceWorld<R>& w, const rt_shape_desc* shapes,
     // world order -> (slot | kind << 24), padded to whole 16-byte words
     std::vector<int32_t> ws((sh.size() + 3) / 4 * 4, -1);
     for (int k = 0; k < kNumKinds; ++k)
-        for (int32_t j = begin[k]; j < begin[k + 1]; ++j) ws[sh[j].world_index] = j | (k << 24);
+        for (int32_t j = begin[k]; j < begin[k + 1]; ++j)
+            if ((uint32_t)sh[j].world_index < wi.plain(ns)) ws[sh[j].world_index] = j | (k << 24);
+    if (wi.slot_of) {  // the records of instances uploaded expanded: table positions by input index
+        wi.slot_of->assign(ns, -1);
+        for (size_t at = 0, j = 0; at < order.size(); ++at, ++j) (*wi.slot_of)[order[at]] = (int32_t)j | (shapes[order[at]].kind << 24);
+    }
     std::vector<MaterialRec<R>> mt(nm);
     bool any_secondary = false;
     for (uint32_t i = 0; i < nm; ++i) {
@@ -397,10 +432,18 @@ int build_world(rt_context* ctx, DeviceWorld<R>& w, const rt_shape_desc* shapes,
         ctx->jit.materials = mt;
         ctx->jit.pattern_recs = pt;
     }
-    ctx->world_slot.assign(ws.begin(), ws.begin() + ns);
+    ctx->world_slot.assign(ws.begin(), ws.begin() + wi.plain(ns));
     for (int k = 0; k <= kNumKinds; ++k) w.scene.kind_begin[k] = begin[k];
     w.scene.any_secondary = any_secondary ? 1 : 0;
     return RT_OK;
+}
+
+int validate_scene_instanced(const rt_shape_desc* shapes, uint32_t ns, const InstancedLists& il,
+                             const rt_material_desc* mats, uint32_t nm, const rt_pattern_desc* pats, uint32_t np,
+                             const rt_light_desc* lights, uint32_t nl) {
+    if (int rc = validate_scene(shapes, ns, mats, nm, pats, np, lights, nl)) return rc;
+    const std::string why = inst::validate(shapes, ns, il.meshes, il.n_meshes, il.instances, il.n_instances, nm);
+    return why.empty() ? RT_OK : set_error(RT_ERR_INVALID, why);
 }
 
 int validate_scene(const rt_shape_desc* shapes, uint32_t ns, const rt_material_desc* mats, uint32_t nm,
@@ -524,7 +567,12 @@ int blocks_per_cu(rt_context* ctx, bool pool, bool lds_world, size_t lds, int* p
         return RT_OK;
     }
     int api = 0;
-    RT_HIP(ss ? occupancy_ss<R>(pool, lds_world, lds, &api) : occupancy<R>(pool, lds_world, lds, &api));
+    // (a world with mesh instances runs the instance variant of every kernel; an upload that changes that clears the cache)
+    if (walked_instances(ctx->w32))
+        RT_HIP(ss ? instanced::occupancy_ss<R>(pool, lds_world, lds, &api)
+                  : instanced::occupancy<R>(pool, lds_world, lds, &api));
+    else
+        RT_HIP(ss ? occupancy_ss<R>(pool, lds_world, lds, &api) : occupancy<R>(pool, lds_world, lds, &api));
     *per_cu = cap_by_lds(api, lds);
     ctx->occ_lds[key] = lds;
     ctx->occ_blocks[key] = *per_cu;
@@ -771,6 +819,18 @@ struct LaunchRequest {
     uint32_t out_w = 0, out_h = 0;
 };
 
+// The launch's view of the world's mesh instances (none: no world index reaches inst_world_begin).
+template <typename R>
+void set_instance_params(LaunchParams<R>& P, const DeviceWorld<R>& w) {
+    const InstanceCounts& c = w.inst_counts;
+    P.n_instances = c.instances;
+    P.inst_world_begin = c.instances ? c.world_begin : std::numeric_limits<int32_t>::max();
+    P.inst = c.instances ? w.inst.get() : nullptr;
+    P.inst_shapes = w.inst_shapes.get();
+    P.inst_nodes = w.inst_nodes.get();
+    P.inst_pos = w.inst_pos.get();
+}
+
 template <typename R>
 int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
     const rt_camera_desc* cam = q.cam;
@@ -783,6 +843,7 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
     P.tri_nodes = w.n_tri_nodes ? w.tri_nodes.get() : nullptr;
     P.n_tri_nodes = w.n_tri_nodes;
     P.tri_flat_begin = w.tri_flat_begin;
+    set_instance_params(P, w);
     if (cam) {
         for (int q = 0; q < 12; ++q) P.cam.inv[q] = (R)cam->inverse[q];
         for (int q = 0; q < 3; ++q) P.cam.origin[q] = (R)cam->origin[q];
@@ -831,9 +892,12 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
         const uint32_t generic_only =
             RT_FLAG_NO_SHADE | RT_FLAG_NO_TRACE | RT_FLAG_GENERATIONS | (ls.pool ? 0u : RT_FLAG_STAMPS);
         // (a world with a triangle hierarchy runs the generic kernels, which walk it)
-        const bool tree = w.n_tri_nodes > 0;
+        const bool instanced = walked_instances(w);
+        const bool tree = w.n_tri_nodes > 0 || instanced;
         if (tree && ctx->jit.mode != RT_JIT_OFF && ctx->jit.log.empty())
-            ctx->jit.log = "no per-scene build: the world has a triangle hierarchy, which the generic kernels walk";
+            ctx->jit.log = instanced
+                               ? "no per-scene build: the world has mesh instances, which the generic kernels walk"
+                               : "no per-scene build: the world has a triangle hierarchy, which the generic kernels walk";
         const bool want = cam && !dup && !tree && !(flags & generic_only) &&
                           (ctx->jit.mode == RT_JIT_SYNC || (ctx->jit.mode >= RT_JIT_AUTO && P.n_tiles >= kJitMinTiles));
         if (want) {
@@ -903,7 +967,8 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
     for (int k = 0; k < kNumKinds; ++k)
         if (w.scene.kind_begin[k + 1] > w.scene.kind_begin[k]) kinds |= 1u << k;
     // (supersampled launches: the all-kinds build only)
-    const bool sp = sizeof(R) == 4 && ls.pool && ctx->knobs.kind_variants && (kinds & ~kKindsSp) == 0 && !dup && !ss;
+    const bool sp = sizeof(R) == 4 && ls.pool && ctx->knobs.kind_variants && (kinds & ~kKindsSp) == 0 && !dup && !ss &&
+                    !walked_instances(w);  // (instances are triangles)
     if (flags & RT_FLAG_FAIL_LAUNCH) return set_error(RT_ERR_HIP, "launch refused (RT_FLAG_FAIL_LAUNCH)");
     if constexpr (sizeof(R) == 4) {
         // The per-scene direct kernel's primary cull: each slot's screen
@@ -993,7 +1058,10 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
         void* args[] = {&P, &sh, &mt, &pt, &lt};
         (void)hipGetLastError();
         RT_HIP(hipModuleLaunchKernel(jf, ls.grid, 1, 1, kBlock, 1, 1, (unsigned)ls.lds, stream, args, nullptr));
-    } else if (hipError_t e = ss   ? launch_trace_ss<R>(P, ls.pool, dup, ls.grid, ls.lds, stream)
+    } else if (hipError_t e = walked_instances(w)
+                                  ? (ss ? instanced::launch_trace_ss<R>(P, ls.pool, dup, ls.grid, ls.lds, stream)
+                                        : instanced::launch_trace<R>(P, ls.pool, dup, ls.grid, ls.lds, stream))
+                              : ss ? launch_trace_ss<R>(P, ls.pool, dup, ls.grid, ls.lds, stream)
                               : sp ? sp::launch_trace<R>(P, ls.pool, dup, ls.grid, ls.lds, stream)
                                    : launch_trace<R>(P, ls.pool, dup, ls.grid, ls.lds, stream);
                e != hipSuccess)
@@ -1016,7 +1084,8 @@ int ray_blocks_per_cu(rt_context* ctx, bool lds_world, size_t lds, int* per_cu) 
         return RT_OK;
     }
     int api = 0;
-    RT_HIP(occupancy_rays<R>(lds_world, lds, &api));
+    if (walked_instances(ctx->w32)) RT_HIP(instanced::occupancy_rays<R>(lds_world, lds, &api));
+    else RT_HIP(occupancy_rays<R>(lds_world, lds, &api));
     *per_cu = cap_by_lds(api, lds);
     ctx->occ_lds[key] = lds;
     ctx->occ_blocks[key] = *per_cu;
@@ -1056,6 +1125,7 @@ int launch_rays(rt_context* ctx, DeviceWorld<R>& w, const void* d_rays, uint64_t
     P.tri_nodes = w.n_tri_nodes ? w.tri_nodes.get() : nullptr;
     P.n_tri_nodes = w.n_tri_nodes;
     P.tri_flat_begin = w.tri_flat_begin;
+    set_instance_params(P, w);
     P.n_rays = n;
     P.n_tiles = (uint32_t)((n + kBlock - 1) / kBlock);
     P.max_depth = o->max_depth;
@@ -1079,7 +1149,10 @@ int launch_rays(rt_context* ctx, DeviceWorld<R>& w, const void* d_rays, uint64_t
     }
     ctx->jit.used = false;
     if (o->flags & RT_FLAG_FAIL_LAUNCH) return set_error(RT_ERR_HIP, "launch refused (RT_FLAG_FAIL_LAUNCH)");
-    if (hipError_t e = launch_trace_rays<R>(P, ctx->duplicate_shapes > 0, ls.grid, ls.lds, d_rays, d_rgb, d_hits, stream);
+    if (hipError_t e = walked_instances(w) ? instanced::launch_trace_rays<R>(P, ctx->duplicate_shapes > 0, ls.grid, ls.lds,
+                                                                             d_rays, d_rgb, d_hits, stream)
+                                           : launch_trace_rays<R>(P, ctx->duplicate_shapes > 0, ls.grid, ls.lds, d_rays,
+                                                                  d_rgb, d_hits, stream);
         e != hipSuccess)
         return set_error(RT_ERR_HIP, "launch of the ray-batch kernel (grid " + std::to_string(ls.grid) +
                                          ", dynamic LDS " + std::to_string(ls.lds) + " B, " + std::to_string(ls.cap) +
@@ -1324,6 +1397,37 @@ int rt_scene_upload(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns, c
     return build_scene(ctx, shapes, ns, mats, nm, pats, np, lights, nl);
 }
 
+int rt_scene_upload_instanced(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns, const rt_mesh_desc* meshes,
+                              uint32_t n_meshes, const rt_instance_desc* instances, uint32_t n_inst,
+                              const rt_material_desc* mats, uint32_t nm, const rt_pattern_desc* pats, uint32_t np,
+                              const rt_light_desc* lights, uint32_t nl) {
+    const InstancedLists il{meshes, n_meshes, instances, n_inst};
+    // (the lists are checked before the context is looked at; a group's rank 0 checks its own)
+    if (!ctx || !ctx->group.comm)
+        if (int rc = validate_scene_instanced(shapes, ns, il, mats, nm, pats, np, lights, nl)) return rc;
+    if (!ctx) return set_error(RT_ERR_INVALID, "null context");
+    if (ctx->group.comm) return group_scene_upload(ctx, shapes, ns, mats, nm, pats, np, lights, nl, &il);
+    RT_HIP(hipSetDevice(ctx->device));
+    RT_HIP(hipDeviceSynchronize());  // launches on caller streams may still read the old tables
+    return build_scene_instanced(ctx, shapes, ns, meshes, n_meshes, instances, n_inst, mats, nm, pats, np, lights, nl);
+}
+
+int rt_instances_expand(const rt_shape_desc* shapes, uint32_t ns, const rt_mesh_desc* meshes, uint32_t n_meshes,
+                        const rt_instance_desc* instances, uint32_t n_inst, rt_shape_desc* out) {
+    // (materials are the upload's to check: any index passes here)
+    const std::string why = inst::validate(shapes, ns, meshes, n_meshes, instances, n_inst, 0x7FFFFFFFu);
+    if (!why.empty()) return set_error(RT_ERR_INVALID, why);
+    if (!out && (ns || n_inst)) return set_error(RT_ERR_INVALID, "rt_instances_expand: null output");
+    inst::expand(shapes, ns, meshes, instances, n_inst, out);
+    return RT_OK;
+}
+
+int rt_scene_instance_info(rt_context* ctx, rt_instance_info* out) {
+    if (!ctx || !out) return set_error(RT_ERR_INVALID, "null argument");
+    *out = ctx->have_scene ? ctx->instance_info : rt_instance_info{};
+    return RT_OK;
+}
+
 }  // extern "C"
 
 namespace rtc {
@@ -1421,8 +1525,13 @@ void scene_brightness(const rt_shape_desc* shapes, uint32_t ns, const rt_materia
     *bright_w = std::isfinite(w) ? w : std::numeric_limits<double>::infinity();
 }
 
-int build_scene(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns, const rt_material_desc* mats, uint32_t nm,
-                const rt_pattern_desc* pats, uint32_t np, const rt_light_desc* lights, uint32_t nl) {
+namespace {
+// build_scene for a shape list with the world indices `wi`; generic_only: the
+// world also has instances the generic kernels walk, so no per-scene build
+// will run and the plain triangle run gets its tree at any world size.
+int build_plain_tables(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns, const rt_material_desc* mats,
+                       uint32_t nm, const rt_pattern_desc* pats, uint32_t np, const rt_light_desc* lights, uint32_t nl,
+                       const WorldIndices& wi, bool generic_only) {
     int rc;
     ctx->have_scene = false;
     std::vector<uint32_t> cls;  // value-identity classes (shape_identity.hpp)
@@ -1433,7 +1542,7 @@ int build_scene(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns, const
     // its per-scene kernels, which measured faster for f32 frames up to that
     // size than the generic kernels with a tree (a tree inside
     // per-scene builds is future work).  RTC_DEBUG=tri_min=N overrides.
-    const bool per_scene_world = (int64_t)ns <= (int64_t)kJitRecordsMaxShapes && !ctx->knobs.tri_min;
+    const bool per_scene_world = (int64_t)ns <= (int64_t)kJitRecordsMaxShapes && !ctx->knobs.tri_min && !generic_only;
     const TrianglePlan plan = per_scene_world ? TrianglePlan{} : plan_triangles(ctx->knobs, shapes, order, cls);
     ctx->tree_info = rt_tree_info{};
     if (!plan.tree.nodes.empty()) {
@@ -1442,9 +1551,10 @@ int build_scene(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns, const
         ctx->tree_info = {(uint32_t)plan.tree.nodes.size(), plan.tree.leaves, plan.tree.depth, plan.in_tree,
                           triangles - plan.in_tree, 0u, plan.build_ms};
     }
-    if ((rc = build_world<float>(ctx, ctx->w32, shapes, ns, mats, nm, pats, np, lights, nl, cls, order, plan))) return rc;
+    if ((rc = build_world<float>(ctx, ctx->w32, shapes, ns, mats, nm, pats, np, lights, nl, cls, order, plan, wi)))
+        return rc;
     if ((rc = capture_jit_table(ctx))) return rc;
-    if ((rc = build_world<double>(ctx, ctx->w64, shapes, ns, mats, nm, pats, np, lights, nl, cls, order, plan)))
+    if ((rc = build_world<double>(ctx, ctx->w64, shapes, ns, mats, nm, pats, np, lights, nl, cls, order, plan, wi)))
         return rc;
     ctx->flops = FlopScene{};
     for (uint32_t i = 0; i < ns; ++i) {
@@ -1455,6 +1565,229 @@ int build_scene(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns, const
     scene_brightness(shapes, ns, mats, nm, pats, np, lights, nl, &ctx->bright_hit, &ctx->bright_w);
     ctx->have_scene = true;
     ++ctx->scene_gen;  // invalidates the recorded tile costs
+    return RT_OK;
+}
+
+// The instance tables of one precision (rtc_internal.hpp InstRec), from the
+// plans of the meshes in use and the per-instance decisions.
+struct InstancePlan {
+    std::vector<inst::MeshPlan> meshes;             // by mesh; empty for a mesh no walked instance uses
+    std::vector<uint32_t> rec_begin, node_begin, pos_begin;  // by mesh
+    std::vector<uint32_t> bases;                    // inst::world_bases
+    std::vector<char> expanded;                     // by instance
+    std::vector<uint32_t> expanded_pos;             // by instance: its run of the position table (expanded ones)
+    std::vector<int32_t> slot_of;                   // build_world's, by entry of the plain list
+    std::vector<uint32_t> list_begin;               // by instance: its first entry of the plain list (expanded ones)
+    InstanceCounts counts;
+};
+
+template <typename R>
+int upload_instances(rt_context* ctx, DeviceWorld<R>& w, const InstancePlan& ip, const rt_mesh_desc* meshes,
+                     const rt_instance_desc* instances, uint32_t n_inst, const rt_material_desc* mats) {
+    int rc;
+    if ((rc = w.allocate_instances(ip.counts))) return rc;
+    std::vector<ShapeRec<R>> recs(ip.counts.records);
+    std::vector<TriNode<R>> nodes(ip.counts.nodes);
+    std::vector<int32_t> pos(ip.counts.pos, 0);
+    for (size_t m = 0; m < ip.meshes.size(); ++m) {
+        const inst::MeshPlan& mp = ip.meshes[m];
+        if (mp.order.empty()) continue;
+        for (uint32_t at = 0; at < mp.order.size(); ++at) {
+            const uint32_t j = mp.order[at];
+            const rt_shape_desc& d = meshes[m].triangles[j];
+            ShapeRec<R> r{};
+            for (int q = 0; q < 12; ++q) r.inv[q] = (R)d.inverse[q];
+            const tri::Ball& b = mp.balls[j];
+            for (int q = 0; q < 3; ++q) r.bound[q] = (R)b.c[q];
+            r.bound[3] = b.r >= 0.0 ? (R)(b.r * b.r) : (R)-1;
+            r.ymin = (R)d.minimum;
+            r.ymax = (R)d.maximum;
+            for (int q = 0; q < 3; ++q) {
+                r.tri[q] = (R)d.vertex_1[q];
+                r.tri[3 + q] = (R)d.edge_1[q];
+                r.tri[6 + q] = (R)d.edge_2[q];
+                r.tri[9 + q] = (R)d.normal[q];
+            }
+            r.world_index = (int32_t)j;  // the local index: for_instances adds the instance's base
+            r.flags = kShapeClassEnd;
+            recs[ip.rec_begin[m] + at] = r;
+            pos[ip.pos_begin[m] + j] = (int32_t)(ip.rec_begin[m] + at);
+        }
+        for (size_t i = 0; i < mp.tree.nodes.size(); ++i) {
+            const tri::Node& n = mp.tree.nodes[i];
+            TriNode<R>& out = nodes[ip.node_begin[m] + i];
+            tri::cast_ball<R>(n.ball, out.ball);
+            out.skip = n.skip;
+            out.first = n.count ? n.first : 0;  // from the mesh's first record (InstRec::rec_begin)
+            out.count = n.count;
+        }
+    }
+    std::vector<InstRec<R>> ir(n_inst);
+    for (uint32_t k = 0; k < n_inst; ++k) {
+        const rt_instance_desc& d = instances[k];
+        const uint32_t m = d.mesh;
+        InstRec<R>& r = ir[k];
+        r = InstRec<R>{};
+        for (int q = 0; q < 12; ++q) r.inv[q] = (R)d.inverse[q];
+        r.ball[3] = (R)-1;
+        r.world_base = (int32_t)ip.bases[k];
+        r.casts_shadow = mats[d.material].casts_shadow ? 1 : 0;
+        r.material = d.material;
+        r.n_triangles = (int32_t)meshes[m].n_triangles;
+        if (ip.expanded[k]) {
+            r.expanded = 1;
+            r.pos_begin = (int32_t)ip.expanded_pos[k];
+            for (uint32_t j = 0; j < meshes[m].n_triangles; ++j) pos[r.pos_begin + j] = ip.slot_of[ip.list_begin[k] + j];
+            continue;
+        }
+        const inst::MeshPlan& mp = ip.meshes[m];
+        r.node_begin = (int32_t)ip.node_begin[m];
+        r.n_nodes = (int32_t)mp.tree.nodes.size();
+        r.rec_begin = (int32_t)ip.rec_begin[m];
+        r.rec_flat = r.rec_begin + (int32_t)mp.in_tree;
+        r.rec_end = r.rec_begin + (int32_t)mp.order.size();
+        r.pos_begin = (int32_t)ip.pos_begin[m];
+        tri::Ball wb;
+        // (a mesh with records outside its tree has no ball: every wave tests those)
+        if (!mp.tree.nodes.empty() && mp.in_tree == mp.order.size() &&
+            inst::instance_ball(mp.tree.nodes[0].ball, d.inverse, &wb))
+            tri::cast_ball<R>(wb, r.ball);
+    }
+    auto put = [&](void* dst, const void* src, size_t bytes) -> int {
+        return bytes ? hip_status(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync")
+                     : RT_OK;
+    };
+    rc = put(w.inst.get(), ir.data(), ir.size() * sizeof(ir[0]));
+    if (!rc) rc = put(w.inst_shapes.get(), recs.data(), recs.size() * sizeof(recs[0]));
+    if (!rc) rc = put(w.inst_nodes.get(), nodes.data(), nodes.size() * sizeof(nodes[0]));
+    if (!rc) rc = put(w.inst_pos.get(), pos.data(), pos.size() * sizeof(pos[0]));
+    const int rs = hip_status(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");  // (host temporaries)
+    return rc ? rc : rs;
+}
+}  // namespace
+
+int build_scene(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns, const rt_material_desc* mats, uint32_t nm,
+                const rt_pattern_desc* pats, uint32_t np, const rt_light_desc* lights, uint32_t nl) {
+    ctx->instance_info = rt_instance_info{};
+    if (walked_instances(ctx->w32)) std::fill(std::begin(ctx->occ_blocks), std::end(ctx->occ_blocks), 0);  // other kernels now
+    ctx->w32.inst_counts = ctx->w64.inst_counts = InstanceCounts{};
+    return build_plain_tables(ctx, shapes, ns, mats, nm, pats, np, lights, nl, WorldIndices{}, false);
+}
+
+int build_scene_instanced(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns, const rt_mesh_desc* meshes,
+                          uint32_t n_meshes, const rt_instance_desc* instances, uint32_t n_inst,
+                          const rt_material_desc* mats, uint32_t nm, const rt_pattern_desc* pats, uint32_t np,
+                          const rt_light_desc* lights, uint32_t nl) {
+    if (!n_inst) return build_scene(ctx, shapes, ns, mats, nm, pats, np, lights, nl);  // rt_scene_upload itself
+    int rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    InstancePlan ip;
+    ip.expanded = inst::decide_expanded(shapes, ns, meshes, n_meshes, instances, n_inst, mats, pats);
+    ip.bases = inst::world_bases(ns, meshes, instances, n_inst);
+    // the plain list: the shapes, then the triangles of the instances uploaded expanded
+    std::vector<rt_shape_desc> list(shapes, shapes + ns);
+    std::vector<uint32_t> index(ns);
+    for (uint32_t i = 0; i < ns; ++i) index[i] = i;
+    ip.list_begin.assign(n_inst, 0);
+    ip.expanded_pos.assign(n_inst, 0);
+    uint32_t n_expanded = 0, walked_triangles = 0;
+    std::vector<char> walked(n_meshes, 0);
+    for (uint32_t k = 0; k < n_inst; ++k) {
+        const rt_mesh_desc& mesh = meshes[instances[k].mesh];
+        if (!ip.expanded[k]) {
+            walked[instances[k].mesh] = 1;
+            walked_triangles += mesh.n_triangles;
+            continue;
+        }
+        ++n_expanded;
+        ip.list_begin[k] = (uint32_t)list.size();
+        list.resize(list.size() + mesh.n_triangles);
+        inst::expand_instance(mesh, instances[k], list.data() + ip.list_begin[k]);
+        for (uint32_t j = 0; j < mesh.n_triangles; ++j) index.push_back(ip.bases[k] + j);
+    }
+    if (n_expanded == n_inst) {
+        // every instance has a value-equal partner: the plain list is the
+        // expansion, uploaded as rt_scene_upload would (per-scene builds included)
+        if ((rc = build_scene(ctx, list.data(), (uint32_t)list.size(), mats, nm, pats, np, lights, nl))) return rc;
+        ctx->instance_info.meshes = n_meshes;
+        ctx->instance_info.instances = ctx->instance_info.expanded = n_inst;
+        ctx->instance_info.build_ms =
+            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        return RT_OK;
+    }
+    // the meshes the kernels walk: records, nodes and local-to-position tables, once each
+    ip.meshes.resize(n_meshes);
+    ip.rec_begin.assign(n_meshes, 0);
+    ip.node_begin.assign(n_meshes, 0);
+    ip.pos_begin.assign(n_meshes, 0);
+    for (uint32_t m = 0; m < n_meshes; ++m) {
+        if (!walked[m]) continue;
+        ip.meshes[m] = inst::plan_mesh(meshes[m], ctx->knobs.cull, ctx->knobs.tri_tree, ctx->knobs.tri_leaf ? ctx->knobs.tri_leaf : tri::kTriLeaf);
+        ip.rec_begin[m] = ip.counts.records;
+        ip.node_begin[m] = ip.counts.nodes;
+        ip.pos_begin[m] = ip.counts.pos;
+        ip.counts.records += meshes[m].n_triangles;
+        ip.counts.nodes += (uint32_t)ip.meshes[m].tree.nodes.size();
+        ip.counts.pos += meshes[m].n_triangles;
+    }
+    for (uint32_t k = 0; k < n_inst; ++k)
+        if (ip.expanded[k]) {
+            ip.expanded_pos[k] = ip.counts.pos;
+            ip.counts.pos += meshes[instances[k].mesh].n_triangles;
+        }
+    ip.counts.instances = n_inst;
+    ip.counts.world_begin = (int32_t)ns;
+    const double plan_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    WorldIndices wi;
+    wi.index = index.data();
+    wi.n_plain = ns;
+    wi.slot_of = &ip.slot_of;
+    if ((rc = build_plain_tables(ctx, list.data(), (uint32_t)list.size(), mats, nm, pats, np, lights, nl, wi, true)))
+        return rc;
+    ctx->have_scene = false;
+    if (!walked_instances(ctx->w32)) std::fill(std::begin(ctx->occ_blocks), std::end(ctx->occ_blocks), 0);  // other kernels now
+    if ((rc = upload_instances<float>(ctx, ctx->w32, ip, meshes, instances, n_inst, mats)) ||
+        (rc = upload_instances<double>(ctx, ctx->w64, ip, meshes, instances, n_inst, mats)))
+        return rc;
+    // what the expansion's other tables would have come to: the triangle tests
+    // of the flop model, and the brightness bound (a TestPattern's reach is
+    // the object-space extent of the mesh, whatever the placement)
+    ctx->flops.per_ray += (double)walked_triangles * shape_test_flops(RT_SHAPE_TRIANGLE, false);
+    {
+        std::vector<double> extent(n_meshes, 0.0);
+        for (uint32_t m = 0; m < n_meshes; ++m)
+            if (walked[m])
+                for (uint32_t j = 0; j < meshes[m].n_triangles; ++j)
+                    extent[m] = std::max(extent[m], object_extent(meshes[m].triangles[j]));
+        std::vector<rt_shape_desc> reach = list;
+        for (uint32_t k = 0; k < n_inst; ++k)
+            if (!ip.expanded[k]) {
+                rt_shape_desc d{};
+                d.kind = RT_SHAPE_TRIANGLE;
+                d.material = instances[k].material;
+                for (int q = 0; q < 3; ++q) d.vertex_1[q] = extent[instances[k].mesh];
+                reach.push_back(d);
+            }
+        scene_brightness(reach.data(), (uint32_t)reach.size(), mats, nm, pats, np, lights, nl, &ctx->bright_hit,
+                         &ctx->bright_w);
+    }
+    rt_instance_info& info = ctx->instance_info;
+    info = rt_instance_info{};
+    info.meshes = n_meshes;
+    info.instances = n_inst;
+    info.expanded = n_expanded;
+    info.top_depth = 0;
+    info.local_records = ip.counts.records;
+    info.local_nodes = ip.counts.nodes;
+    info.instanced_bytes =
+        (uint64_t)ip.counts.records * (sizeof(ShapeRec<float>) + sizeof(ShapeRec<double>)) +
+        (uint64_t)ip.counts.nodes * (sizeof(TriNode<float>) + sizeof(TriNode<double>)) +
+        (uint64_t)n_inst * (sizeof(InstRec<float>) + sizeof(InstRec<double>)) + (uint64_t)ip.counts.pos * 2 * sizeof(int32_t);
+    // (a tree over n records of leaves of kTriLeaf has about n / 4 nodes; the expansion also takes a world_slot word per shape)
+    info.expansion_bytes = (uint64_t)walked_triangles * (sizeof(ShapeRec<float>) + sizeof(ShapeRec<double>) + 2 * sizeof(int32_t)) +
+                           (uint64_t)(walked_triangles / 4) * (sizeof(TriNode<float>) + sizeof(TriNode<double>));
+    info.build_ms = plan_ms;
+    ctx->have_scene = true;
     return RT_OK;
 }
 

@@ -366,6 +366,47 @@ struct alignas(16) TriNode {
 };
 static_assert(sizeof(TriNode<float>) == 32 && sizeof(TriNode<double>) == 48);
 
+// A placed copy of a mesh (rt_scene_upload_instanced): the world is the flat
+// list `shapes ++ E(0) ++ E(1) ...`, E(k) the mesh's triangles under instance
+// k's inverse and material, and the kernels walk it without writing it out.
+// The mesh's triangles sit once in a table of local records (identity
+// inverse; ShapeRec::world_index holds the triangle's index in the mesh,
+// ShapeRec::bound its padded local ball) under a local hierarchy of TriNode
+// whose leaf runs count from the mesh's first record.  An instance uploaded
+// expanded (it has a value-equal partner: rtc_host.cpp) keeps its record for
+// the hit's lookup only: its triangles are plain records of the shape table.
+template <typename R>
+struct alignas(16) InstRec {
+    R inv[12];   // rows 0..2 of the instance's inverse
+    R ball[4];   // world ball of the whole mesh under this instance (centre, r^2); r^2 < 0: none
+    int32_t world_base;    // world index of the mesh's triangle 0 under this instance
+    int32_t casts_shadow;  // of `material`
+    int32_t material;
+    int32_t n_triangles;
+    int32_t node_begin, n_nodes;  // the mesh's nodes in the instance node table
+    int32_t rec_begin;            // the mesh's first local record; leaves' runs count from here
+    int32_t rec_flat;             // the mesh's records outside its tree: [rec_flat, rec_end)
+    int32_t rec_end;
+    int32_t pos_begin;  // local index j -> inst_pos[pos_begin + j]: the local record (or, expanded: slot | kind << 24)
+    int32_t expanded;   // 1: uploaded as plain records, the walk passes it by
+    int32_t pad;
+};
+static_assert(sizeof(InstRec<float>) % 16 == 0 && sizeof(InstRec<double>) % 16 == 0);
+
+// The instance a world index belongs to: the last one whose base is <= w
+// (bases ascend).  One definition for the kernels' per-hit lookup and the
+// host (tests/instances.cpp).  n >= 1 and w >= base(0).
+template <typename Base>
+RTC_HD inline int instance_of_world(Base&& base, int n, int w) {
+    int lo = 0, hi = n;  // base(lo) <= w < base(hi) (base(n) = +inf)
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (base(mid) <= w) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
 template <typename R>
 struct DevScene {
     const ShapeRec<R>* shapes;
@@ -490,6 +531,14 @@ struct LaunchParams {
     uint32_t n_tri_nodes;
     const TriNode<R>* tri_nodes;  // null: no tree, every triangle record is visited
     uint32_t tri_flat_begin;      // triangle records from this slot on are outside the tree (unbounded ones)
+    // Mesh instances (null / 0 for a world without them; read where the
+    // triangle step and the hit's lookup run, like the tree's fields above).
+    uint32_t n_instances;
+    int32_t inst_world_begin;          // world indices from here on are instances' triangles (n_shapes)
+    const InstRec<R>* inst;            // by ascending world_base
+    const ShapeRec<R>* inst_shapes;    // every mesh's local records
+    const TriNode<R>* inst_nodes;      // every mesh's hierarchy
+    const int32_t* inst_pos;           // InstRec::pos_begin
 };
 
 }  // namespace rtc

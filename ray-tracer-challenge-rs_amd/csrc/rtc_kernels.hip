@@ -41,6 +41,21 @@
 // shape loops of those kinds only (rtc::<namespace>::launch_trace).  Same
 // code for the kinds it keeps, so the same pixels; the host uses it for
 // worlds whose kinds it covers (rtc_host.cpp, pool_variant).
+//
+// Instance variant: built with -DRTC_INSTANCES=1 -DRTC_VARIANT=instanced (one TU
+// per precision), the TU compiles every tracer kernel with the instance level
+// of the triangle step and the hit's instance lookup (for_instances,
+// Nearest::hit, prepare_hit) as rtc::instanced::launch_trace*, for worlds uploaded
+// with rt_scene_upload_instanced.  Every other build compiles none of it, so
+// worlds without instances run the kernels they ran before: as a runtime
+// branch the instance level cost the f32 pool kernel 72 B/lane of scratch
+// against the 64 of tests/test_isa_budget.py.
+#ifndef RTC_INSTANCES
+#define RTC_INSTANCES 0
+#endif
+#if defined(RTC_VARIANT) && !RTC_INSTANCES
+#define RTC_POOL_ONLY 1  // a kind variant: the f32 pool kernel alone
+#endif
 #ifndef __HIPCC_RTC__  // hipRTC (per-scene build, rtc_jit.cpp) pre-includes the HIP runtime
 #include <hip/hip_runtime.h>
 
@@ -536,6 +551,90 @@ __device__ inline const LaunchParams<R>& kernarg_params();
 // through the constant address space so the loads are scalar whatever the
 // compiler can prove about the kernel's stores.
 #define RTC_AS_CONST __attribute__((address_space(4)))
+#if !defined(RTC_JIT) && RTC_INSTANCES
+// A wave-uniform record through the constant address space (scalar loads whatever the compiler can prove), 16 bytes at a time.
+template <typename T>
+__device__ inline T ld_const(const T* p) {
+    typedef uint32_t Word4 __attribute__((ext_vector_type(4)));
+    static_assert(sizeof(T) % 16 == 0 && alignof(T) >= 16);
+    T out;
+    const RTC_AS_CONST Word4* src = (const RTC_AS_CONST Word4*)p;
+#pragma unroll
+    for (unsigned i = 0; i < sizeof(T) / 16; ++i) {
+        const Word4 v = src[i];
+        __builtin_memcpy((char*)&out + 16 * i, &v, 16);
+    }
+    return out;
+}
+// The instance level of the triangle step (rt_scene_upload_instanced; generic
+// builds only): the world's virtual triangles, instance by instance in world
+// order.  Wave-uniform like for_triangles: the instance index, its record
+// (rtc_internal.hpp InstRec) and the mesh's nodes and local records are scalar
+// loads through the constant address space.  An instance whose world ball no
+// lane's ray may meet is passed by.  Otherwise each lane forms its local ray
+// once, lo = inv o, ld = inv d, and the wave walks the mesh's hierarchy with
+// it against the local balls (nodes, then each record's own): the ball tests
+// and the triangle test see the same local ray, so what a passed ball holds
+// has no entry for the wave whatever the transformation.  A record that
+// survives goes to the caller's callback as the record of the expansion:
+// the instance's inverse, material and casts_shadow, world index base + local
+// index, a class of its own (virtual triangles have no value-equal partner:
+// rtc_host.cpp uploads those instances expanded) and no ball, its cull being
+// done.  The callback's own inv o and inv d of the same scalar matrix are the
+// values formed here.
+template <typename R, bool kHalfLine, typename F>
+__device__ inline void for_instances(V3<R> o, V3<R> d, R dd, F&& f) {
+    typedef R Ball4 __attribute__((ext_vector_type(4)));
+    typedef int32_t Link4 __attribute__((ext_vector_type(4)));
+    const LaunchParams<R>& P = kernarg_params<R>();
+    const int n_inst = (int)P.n_instances;
+    const InstRec<R>* const inst = P.inst;
+    const ShapeRec<R>* const recs = P.inst_shapes;
+    const TriNode<R>* const all_nodes = P.inst_nodes;
+    for (int k = 0; k < n_inst; ++k) {
+        const InstRec<R> I = ld_const(&inst[k]);
+        if (I.expanded) continue;
+        if (I.ball[3] >= (R)0 && !wave_ball_may_hit<R, kHalfLine>(I.ball[0], I.ball[1], I.ball[2], I.ball[3], o, d, dd))
+            continue;
+        const V3<R> lo = xform_point(I.inv, o);
+        const V3<R> ld = xform_vector(I.inv, d);
+        const R ldd = dot(ld, ld);
+        const TriNode<R>* const nodes = all_nodes + I.node_begin;
+        const int n = I.n_nodes;
+        for (int i = 0; i <= n;) {
+            int first, end;
+            if (i < n) {
+                const TriNode<R>* node = &nodes[i];
+                const Ball4 ball = *(const RTC_AS_CONST Ball4*)node->ball;
+                const Link4 link = *(const RTC_AS_CONST Link4*)&node->skip;
+                first = I.rec_begin + link.y;
+                end = first + link.z;
+                if (!wave_ball_may_hit<R, kHalfLine>(ball.x, ball.y, ball.z, ball.w, lo, ld, ldd)) {
+                    i = link.x;
+                    continue;
+                }
+            } else {
+                first = I.rec_flat;
+                end = I.rec_end;
+            }
+            ++i;
+            for (int j = first; j < end; ++j) {
+                ShapeRec<R> s = ld_const(&recs[j]);
+                if (s.bound[3] >= (R)0 &&
+                    !wave_ball_may_hit<R, kHalfLine>(s.bound[0], s.bound[1], s.bound[2], s.bound[3], lo, ld, ldd))
+                    continue;
+                for (int q = 0; q < 12; ++q) s.inv[q] = I.inv[q];
+                s.bound[3] = (R)-1;
+                s.world_index = I.world_base + s.world_index;
+                s.material = I.material;
+                s.casts_shadow = I.casts_shadow;
+                s.flags = kShapeClassEnd | (int32_t)((uint32_t)s.world_index << kShapeClassShift);
+                f(s, -1);
+            }
+        }
+    }
+}
+#endif
 template <typename R, bool kHalfLine, typename F>
 __device__ inline void for_triangles(const DevScene<R>& sc, V3<R> o, V3<R> d, R dd, F&& f) {
 #ifdef RTC_JIT
@@ -577,6 +676,9 @@ __device__ inline void for_triangles(const DevScene<R>& sc, V3<R> o, V3<R> d, R 
             f(s, j);
         }
     }
+#if RTC_INSTANCES
+    if (P.n_instances) for_instances<R, kHalfLine>(o, d, dd, f);  // wave-uniform (launch parameters)
+#endif
 #endif
 }
 
@@ -924,6 +1026,24 @@ struct Nearest {
             }
             return h;
         }
+#if !defined(RTC_JIT) && RTC_INSTANCES
+        // A triangle of a mesh instance (world indices from inst_world_begin
+        // on; INT_MAX in a world without instances): once per hit, the
+        // instance by a search over the ascending bases, then the mesh's
+        // local-to-position table.  slot = the local record and kind =
+        // triangle | (instance + 1) << 8; an instance uploaded expanded has
+        // plain records, and its table holds their slots.
+        if (hw != __INT_MAX__ && hw >= kernarg_params<R>().inst_world_begin) {
+            const LaunchParams<R>& P = kernarg_params<R>();
+            const InstRec<R>* const inst = P.inst;
+            const int k = instance_of_world([&](int i) { return inst[i].world_base; }, (int)P.n_instances, hw);
+            const int32_t e = P.inst_pos[inst[k].pos_begin + (hw - inst[k].world_base)];
+            const bool plain = inst[k].expanded != 0;
+            h.slot = plain ? (int)((uint32_t)e & 0xFFFFFFu) : e;
+            h.kind = plain ? (int)((uint32_t)e >> 24) : (RT_SHAPE_TRIANGLE | ((k + 1) << 8));
+            return h;
+        }
+#endif
         if (hw != __INT_MAX__) {
             const uint32_t ws = (uint32_t)sc.lworld_slot[hw];
             h.slot = (int)(ws & 0xFFFFFFu);
@@ -1338,7 +1458,9 @@ __device__ inline void refractive_indices(const DevScene<R>& sc, V3<R> o, V3<R> 
 #endif
     const R dd = dot(d, d);
     if constexpr (kDup) {
-        const uint32_t hit_class = (uint32_t)sc.lshapes[h.slot].flags >> kShapeClassShift;
+        // (a virtual triangle of a mesh instance is a class of its own, named by its world index: for_instances)
+        const uint32_t hit_class =
+            (RTC_INSTANCES && (h.kind >> 8)) ? (uint32_t)h.world : (uint32_t)sc.lshapes[h.slot].flags >> kShapeClassShift;
         int count = 0;  // over the current class's records
         Key last{};
         for_all_kinds<R, false>(sc, o, d, dd, [&]<int K>(const ShapeRec<R>& s, int slot) {
@@ -1389,11 +1511,12 @@ __device__ inline void refractive_indices(const DevScene<R>& sc, V3<R> o, V3<R> 
             return points && convex && !holds(cx, cy, cz, r2);
         });
     } else {
-        for_all_kinds<R, false>(sc, o, d, dd, [&]<int K>(const ShapeRec<R>& s, int slot) {
+        // ("is the hit's shape" by world index: a virtual triangle of a mesh instance has no slot)
+        for_all_kinds<R, false>(sc, o, d, dd, [&]<int K>(const ShapeRec<R>& s, int) {
             int count = 0;
             Key last{};
             scan.template operator()<K>(s, count, last);
-            settle(count, last, s, slot == h.slot);
+            settle(count, last, s, s.world_index == h.world);
         });
     }
     n1 = (flags & kHaveAll) ? sc.lmats[mat_all].refractive_index : (R)1;
@@ -1794,6 +1917,33 @@ __device__ inline const MaterialRec<R>& prepare_hit(const DevScene<R>& sc, V3<R>
             jit_object_each<0, jit::kBegin[kNumKinds]>(h.slot, q.over, obj);
             q.base = pattern_color_obj(sc, m.pattern, obj);
         }
+        return m;
+    }
+#endif
+#if !defined(RTC_JIT) && RTC_INSTANCES
+    if (kernarg_params<R>().n_instances) {  // wave-uniform (launch parameters)
+        // A world with mesh instances: a virtual triangle's record is put
+        // together from its instance (inverse, material) and the mesh's local
+        // record (the normal), the expansion's record field by field, so the
+        // normal, the pattern-space point and the offset are the expansion's.
+        const LaunchParams<R>& P = kernarg_params<R>();
+        const bool virt = (h.kind >> 8) != 0;
+        const InstRec<R>* const I = &P.inst[virt ? (h.kind >> 8) - 1 : 0];
+        const ShapeRec<R>* const g = virt ? &P.inst_shapes[h.slot] : &sc.lshapes[h.slot];
+        const R* const inv = virt ? I->inv : g->inv;
+        const int material = *(virt ? &I->material : &g->material);
+        const int kind = h.kind & 0xFF;
+        q.p = along(o, d, h.t);
+        q.n = normalized(xform_normal(inv, local_normal(*g, kind, xform_point(inv, q.p))));  // normal_at
+        q.eye = vneg(d);
+        if (dot(q.n, q.eye) < (R)0) q.n = vneg(q.n);
+        q.mat = material;
+        const MaterialRec<R>& m = sc.lmats[material];
+        q.off = hit_offset(h, q.p, o);
+        q.over = along(q.p, q.n, q.off);
+        q.base = {m.color[0], m.color[1], m.color[2]};
+        patterned = m.pattern >= 0;
+        if (patterned) q.base = pattern_color_obj(sc, m.pattern, xform_point(inv, q.over));  // pattern_color
         return m;
     }
 #endif
@@ -3024,7 +3174,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(sizeof(R
 #ifndef RTC_PRECISION
 #define RTC_PRECISION 0
 #endif
-#if !defined(RTC_JIT) && RTC_PRECISION != 2  // the per-scene build holds the tracer kernels only; helpers in the f32 TU
+#if !defined(RTC_JIT) && RTC_PRECISION != 2 && !RTC_INSTANCES  // the per-scene build holds the tracer kernels only; helpers in the f32 TU
 // Heaviest-first work order from the previous launch's per-tile costs: a
 // one-workgroup bucket sort (8 buckets per octave of cost, descending).  The
 // pool kernel's time is set by its last, heaviest tiles (a glass-sphere tile
@@ -3267,7 +3417,7 @@ hipError_t launch_trace(const LaunchParams<R>& P, bool pool, bool dup, uint32_t 
     hipLaunchKernelGGL((K<R, __VA_ARGS__>), dim3(grid), dim3(kBlock), dyn_lds, stream, P, P.scene.shapes,         \
                        P.scene.materials, P.scene.patterns, P.scene.lights)
     if (pool) {
-#ifdef RTC_VARIANT
+#ifdef RTC_POOL_ONLY
         if (dup) return hipErrorInvalidValue;  // worlds with value-equal shapes use the all-kinds build
         if (lds) RTC_LAUNCH(trace_pool, true, false);
         else RTC_LAUNCH(trace_pool, false, false);
@@ -3281,7 +3431,7 @@ hipError_t launch_trace(const LaunchParams<R>& P, bool pool, bool dup, uint32_t 
         }
 #endif
     } else {
-#ifdef RTC_VARIANT
+#ifdef RTC_POOL_ONLY
         return hipErrorInvalidValue;  // kind variants hold the pool kernel only
 #else
         if (lds) RTC_LAUNCH(trace_direct, true);
@@ -3299,7 +3449,7 @@ hipError_t occupancy(bool pool, bool lds, size_t dyn_lds, int* blocks_per_cu) {
                                                                   dyn_lds)
                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, trace_pool<R, false, false>, kBlock,
                                                                   dyn_lds);
-#ifdef RTC_VARIANT
+#ifdef RTC_POOL_ONLY
     return hipErrorInvalidValue;
 #endif
     return lds ? hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, trace_direct<R, true>, kBlock, dyn_lds)
@@ -3310,7 +3460,7 @@ hipError_t occupancy(bool pool, bool lds, size_t dyn_lds, int* blocks_per_cu) {
 template hipError_t launch_trace<float>(const LaunchParams<float>&, bool, bool, uint32_t, size_t, hipStream_t);
 template hipError_t occupancy<float>(bool, bool, size_t, int*);
 #endif
-#ifndef RTC_VARIANT
+#ifndef RTC_POOL_ONLY
 #if RTC_PRECISION != 1
 template hipError_t launch_trace<double>(const LaunchParams<double>&, bool, bool, uint32_t, size_t, hipStream_t);
 template hipError_t occupancy<double>(bool, bool, size_t, int*);
@@ -3399,7 +3549,7 @@ template hipError_t launch_trace_ss<double>(const LaunchParams<double>&, bool, b
 template hipError_t occupancy_ss<double>(bool, bool, size_t, int*);
 #endif
 
-#if RTC_PRECISION != 2
+#if RTC_PRECISION != 2 && !RTC_INSTANCES
 hipError_t launch_order_tiles(uint32_t* cost, uint32_t* order, uint32_t n, uint32_t* n_items, float split_per_cost,
                               uint32_t max_split_log2, float urgent_per_cost, uint32_t graded, uint32_t min_split_log2,
                               hipStream_t stream) {
@@ -3410,6 +3560,7 @@ hipError_t launch_order_tiles(uint32_t* cost, uint32_t* order, uint32_t n, uint3
 }
 #endif
 
+#if !RTC_INSTANCES
 template <typename R>
 hipError_t launch_debug_shape(const ShapeRec<R>* shapes, int slot, int kind, uint32_t mode, uint32_t world_space,
                               const double* in, uint32_t n, double* out, hipStream_t stream) {
@@ -3427,7 +3578,9 @@ template hipError_t launch_debug_shape<double>(const ShapeRec<double>*, int, int
                                                uint32_t, double*, hipStream_t);
 #endif
 
-#if RTC_PRECISION != 2
+#endif  // !RTC_INSTANCES
+
+#if RTC_PRECISION != 2 && !RTC_INSTANCES
 hipError_t launch_canvas_signal(unsigned long long* flag, unsigned long long seq, hipStream_t stream) {
     (void)hipGetLastError();  // see launch_trace
     hipLaunchKernelGGL(canvas_signal, dim3(1), dim3(64), 0, stream, flag, seq);
@@ -3441,7 +3594,7 @@ hipError_t launch_canvas_wait(const unsigned long long* flags, uint32_t n, unsig
 }
 #endif
 
-#if RTC_PRECISION != 2
+#if RTC_PRECISION != 2 && !RTC_INSTANCES
 hipError_t launch_assemble(const void* gathered, void* image, uint32_t width, uint32_t height, uint32_t shards,
                            uint32_t strip_rows, uint32_t bpp, hipStream_t stream) {
     (void)hipGetLastError();  // see launch_trace
@@ -3455,7 +3608,7 @@ hipError_t launch_assemble(const void* gathered, void* image, uint32_t width, ui
 }
 #endif
 
-#endif  // !RTC_VARIANT
+#endif  // !RTC_POOL_ONLY
 #endif  // !RTC_JIT
 #ifdef RTC_VARIANT
 }  // namespace RTC_VARIANT

@@ -151,6 +151,20 @@ class TreeInfo(C.Structure):
                 ("build_ms", C.c_double)]
 
 
+class MeshDesc(C.Structure):
+    _fields_ = [("triangles", C.POINTER(ShapeDesc)), ("n_triangles", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class InstanceDesc(C.Structure):
+    _fields_ = [("mesh", C.c_uint32), ("material", C.c_int32), ("inverse", C.c_double * 16)]
+
+
+class InstanceInfo(C.Structure):
+    _fields_ = [("meshes", C.c_uint32), ("instances", C.c_uint32), ("expanded", C.c_uint32),
+                ("top_depth", C.c_uint32), ("local_records", C.c_uint32), ("local_nodes", C.c_uint32),
+                ("instanced_bytes", C.c_uint64), ("expansion_bytes", C.c_uint64), ("build_ms", C.c_double)]
+
+
 # --------------------------------------------------------------- library
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -222,6 +236,12 @@ def _load() -> C.CDLL:
         "rt_mesh_free": (None, [C.c_void_p]),
         "rt_mesh_triangles": (C.c_int, [C.c_void_p, P(C.c_double), C.c_int, C.c_int32, P(ShapeDesc)]),
         "rt_scene_tree_info": (C.c_int, [C.c_void_p, P(TreeInfo)]),
+        "rt_scene_upload_instanced": (C.c_int, [C.c_void_p, P(ShapeDesc), C.c_uint32, P(MeshDesc), C.c_uint32,
+                                                P(InstanceDesc), C.c_uint32, P(MaterialDesc), C.c_uint32,
+                                                P(PatternDesc), C.c_uint32, P(LightDesc), C.c_uint32]),
+        "rt_instances_expand": (C.c_int, [P(ShapeDesc), C.c_uint32, P(MeshDesc), C.c_uint32, P(InstanceDesc),
+                                          C.c_uint32, P(ShapeDesc)]),
+        "rt_scene_instance_info": (C.c_int, [C.c_void_p, P(InstanceInfo)]),
         "rt_image_write": (C.c_int, [C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint32]),
         "rt_image_write_format": (C.c_int, [C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int]),
         "rt_canvas_quantize": (C.c_int, [P(C.c_double), C.c_uint64, P(C.c_uint8)]),
@@ -283,6 +303,7 @@ EXPORTED_SYMBOLS = (
     "rt_canvas_quantize",
     "rt_mesh_load_obj", "rt_mesh_load_obj_text", "rt_mesh_view_get", "rt_mesh_free", "rt_mesh_triangles",
     "rt_scene_tree_info",
+    "rt_scene_upload_instanced", "rt_instances_expand", "rt_scene_instance_info",
 )
 
 
@@ -416,6 +437,41 @@ class SceneTables:
     lights: C.Array
     camera: CameraDesc
     duplicate_shapes: int = 0
+    # Mesh instances (rtc.h rt_scene_upload_instanced): each mesh an array of ShapeDesc (local triangles,
+    # identity inverse) and an array of InstanceDesc; None / empty = a plain world.
+    meshes: list | None = None
+    instances: C.Array | None = None
+
+    @property
+    def instanced(self) -> bool:
+        return self.instances is not None and len(self.instances) > 0
+
+    def mesh_descs(self):
+        """The MeshDesc array over `meshes` (it borrows their memory: keep the tables alive)."""
+        meshes = self.meshes or []
+        arr = (MeshDesc * len(meshes))()
+        for i, m in enumerate(meshes):
+            arr[i].triangles = C.cast(m, C.POINTER(ShapeDesc))
+            arr[i].n_triangles = len(m)
+        return arr
+
+    def instanced_args(self):
+        """(shapes, n, meshes, n, instances, n, materials, n, patterns, n, lights, n) for C calls."""
+        inst = self.instances if self.instances is not None else (InstanceDesc * 0)()
+        md = self.mesh_descs()
+        return (self.shapes, len(self.shapes), md, len(md), inst, len(inst), self.materials, len(self.materials),
+                self.patterns, len(self.patterns), self.lights, len(self.lights))
+
+    def expanded(self) -> "SceneTables":
+        """The flat world an instanced one means (rt_instances_expand): the shapes, then every instance's
+        triangles with its inverse and material; the other tables are shared.  A plain world: itself."""
+        if not self.instanced:
+            return self
+        md, inst = self.mesh_descs(), self.instances
+        total = len(self.shapes) + sum(len(self.meshes[i.mesh]) for i in inst if i.mesh < len(self.meshes))
+        out = (ShapeDesc * total)()
+        _check(_lib.rt_instances_expand(self.shapes, len(self.shapes), md, len(md), inst, len(inst), out))
+        return SceneTables(out, self.materials, self.patterns, self.lights, self.camera)
 
     @property
     def counts(self):
@@ -614,10 +670,20 @@ class Context:
         _check(_lib.rt_scene_tree_info(self._h, C.byref(t)))
         return {name: getattr(t, name) for name, _ in t._fields_ if name != "reserved"}
 
+    def instance_info(self) -> dict:
+        """The uploaded world's meshes and instances (rtc.h rt_scene_instance_info): counts, the instances
+        uploaded expanded, local records and nodes, device bytes against the expansion's, build ms."""
+        t = InstanceInfo()
+        _check(_lib.rt_scene_instance_info(self._h, C.byref(t)))
+        return {name: getattr(t, name) for name, _ in t._fields_}
+
     def upload(self, scene: SceneTables | None) -> None:
-        """rt_scene_upload; on a non-zero rank of a group, None (the scene comes from rank 0)."""
+        """rt_scene_upload, or rt_scene_upload_instanced for tables with instances; on a non-zero rank of a
+        group, None (the scene comes from rank 0)."""
         if scene is None:
             _check(_lib.rt_scene_upload(self._h, None, 0, None, 0, None, 0, None, 0))
+        elif scene.instanced:
+            _check(_lib.rt_scene_upload_instanced(self._h, *scene.instanced_args()))
         else:
             _check(_lib.rt_scene_upload(self._h, *scene.args()))
         self.scene = scene

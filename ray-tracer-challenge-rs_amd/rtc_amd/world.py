@@ -20,7 +20,7 @@ import ctypes as C
 import math
 from dataclasses import dataclass, field
 
-from . import (CameraDesc, LightDesc, MaterialDesc, PatternDesc, PATTERN_KINDS, SceneTables, ShapeDesc,
+from . import (CameraDesc, InstanceDesc, LightDesc, MaterialDesc, PatternDesc, PATTERN_KINDS, SceneTables, ShapeDesc,
                SHAPE_KINDS, camera_make, matrix_inverse)
 
 F64_MAX = 1.7976931348623157e308
@@ -223,6 +223,24 @@ def mesh(m, material=None, transform=None, bake=False):
 
 
 @dataclass
+class Instance:
+    """One placement of a Mesh (rtc.h rt_instance_desc): in World.instances it stands for what
+    mesh(m, material, transform) appends to World.shapes, triangle for triangle, after every shape."""
+    mesh: object
+    material: Material = field(default_factory=Material)
+    transformation_inverse: list = field(default_factory=lambda: [row[:] for row in IDENTITY])
+
+
+def instance(m, material=None, transform=None):
+    """A Mesh (rtc_amd.load_obj) placed by `transform` with `material`: an Instance for World.instances.
+    The device keeps the mesh's triangles once however many instances place it."""
+    i = Instance(m, material or Material())
+    if transform is not None:
+        i.transformation_inverse = inverse(transform)
+    return i
+
+
+@dataclass
 class Light:
     position: tuple
     intensity: tuple = (1.0, 1.0, 1.0)
@@ -232,6 +250,7 @@ class Light:
 class World:
     lights: list = field(default_factory=list)
     shapes: list = field(default_factory=list)
+    instances: list = field(default_factory=list)  # of Instance: their triangles follow the shapes in world order
 
     @staticmethod
     def default() -> "World":
@@ -257,8 +276,30 @@ class World:
                 pat_index(p.sub_b)
             return idx
 
+        def put_material(md, m):
+            md.color[:] = list(map(float, m.color))
+            md.ambient, md.diffuse, md.specular, md.shininess = m.ambient, m.diffuse, m.specular, m.shininess
+            md.reflectiveness, md.transparency, md.refractive_index = (m.reflectiveness, m.transparency,
+                                                                       m.refractive_index)
+            md.casts_shadow = int(m.casts_shadow)
+            md.pattern = pat_index(m.pattern)
+
         shapes = (ShapeDesc * len(self.shapes))()
-        mats = (MaterialDesc * len(self.shapes))()
+        # one material entry per shape, then one per instance
+        mats = (MaterialDesc * (len(self.shapes) + len(self.instances)))()
+        meshes, mesh_of, inst = [], [], (InstanceDesc * len(self.instances))()
+        for k, it in enumerate(self.instances):
+            for j, seen in enumerate(mesh_of):
+                if seen is it.mesh:
+                    inst[k].mesh = j
+                    break
+            else:
+                inst[k].mesh = len(meshes)
+                mesh_of.append(it.mesh)
+                meshes.append(it.mesh.shape_descs())  # local triangles: identity inverse
+            inst[k].material = len(self.shapes) + k
+            inst[k].inverse[:] = [float(v) for row in it.transformation_inverse for v in row]
+            put_material(mats[len(self.shapes) + k], it.material)
         for i, s in enumerate(self.shapes):
             d = shapes[i]
             d.kind = SHAPE_KINDS[s.kind]
@@ -267,13 +308,7 @@ class World:
             d.minimum, d.maximum, d.closed = s.minimum, s.maximum, int(s.closed)
             if s.triangle:
                 d.vertex_1[:], d.edge_1[:], d.edge_2[:], d.normal[:] = [list(map(float, v)) for v in s.triangle]
-            m, md = s.material, mats[i]
-            md.color[:] = list(map(float, m.color))
-            md.ambient, md.diffuse, md.specular, md.shininess = m.ambient, m.diffuse, m.specular, m.shininess
-            md.reflectiveness, md.transparency, md.refractive_index = (m.reflectiveness, m.transparency,
-                                                                       m.refractive_index)
-            md.casts_shadow = int(m.casts_shadow)
-            md.pattern = pat_index(m.pattern)
+            put_material(mats[i], s.material)
         ptab = (PatternDesc * len(pats))()
         for i, p in enumerate(pats):
             d = ptab[i]
@@ -287,7 +322,8 @@ class World:
         for i, lt in enumerate(self.lights):
             lts[i].position[:] = list(map(float, lt.position))
             lts[i].intensity[:] = list(map(float, lt.intensity))
-        return SceneTables(shapes, mats, ptab, lts, camera if camera is not None else CameraDesc())
+        return SceneTables(shapes, mats, ptab, lts, camera if camera is not None else CameraDesc(),
+                           meshes=meshes or None, instances=inst if len(inst) else None)
 
 
 def camera(width, height, fov, frm=(0, 0, 0), to=(0, 0, -1), up=(0, 1, 0)) -> CameraDesc:
