@@ -519,6 +519,67 @@ typedef struct rt_instance_info {
 } rt_instance_info;
 int rt_scene_instance_info(rt_context* ctx, rt_instance_info* out);
 
+/* Smooth triangles (the book's chapter 15): a Triangle plus
+ * three vertex normals n1, n2, n3 that belong to p1, p2, p3 in the face's own
+ * vertex order, used as given (never normalized on upload).  Intersection is
+ * Triangle::local_intersect (triangle.rs:39-56) itself, same t and same
+ * decisions; the local normal at a hit is
+ *     n2 * u + n3 * v + n1 * (1 - u - v)
+ * per component, left to right with plain multiplies and adds, u and v the two
+ * barycentric values that test computed; it goes through Shape::normal_at's
+ * tail (shape.rs:22-27, normalize(inverse^T * ln)) and everything downstream
+ * (the flip by n . eye < 0, reflectv, over_point / under_point, Schlick,
+ * refraction) uses that normal.  The pattern-space point, casts_shadow, the
+ * bounding ball, the hierarchy and every geometric cull are the flat
+ * triangle's.  Value identity (the containers walk): two smooth triangles are
+ * equal iff their flat parts and all nine normal components are (== on
+ * doubles); a smooth and a flat triangle never are.
+ * The normals travel in a sparse side list next to rt_scene_upload_instanced's
+ * lists: entry {list, index} names triangle `index` of the plain shapes
+ * (list = RT_SMOOTH_SHAPES) or of mesh `list`.  An instanced mesh's smooth
+ * triangles keep their local normals under every placement: the expansion of
+ * instance k gives triangle j the same three normals with the instance's
+ * inverse.  rt_smooth_expand writes the expansion's list (host only): every
+ * entry with RT_SMOOTH_SHAPES and the world index of rt_instances_expand's
+ * shape, ascending; `out` holds the plain entries plus, per instance, its
+ * mesh's entries; *n_out the number written (out may be NULL to count).
+ * n_smooth = 0 is rt_scene_upload_instanced itself.  A world with a smooth
+ * triangle runs the generic kernels only (rt_jit_status says so in its log),
+ * those of the instance build, whatever n_instances is.
+ * RT_ERR_INVALID, each with its own rt_last_error text and checked before the
+ * context is looked at: a null list with n_smooth > 0, a list index out of
+ * range, a triangle index out of range, a named record that is no triangle,
+ * the same triangle named twice, a normal component that is not finite. */
+#define RT_SMOOTH_SHAPES 0xFFFFFFFFu
+typedef struct rt_smooth_desc {   /* 80 bytes */
+    uint32_t list;    /* RT_SMOOTH_SHAPES: `index` counts the plain shapes; else an index into the mesh list */
+    uint32_t index;   /* the triangle in that list */
+    double normal_1[3], normal_2[3], normal_3[3];
+} rt_smooth_desc;
+int rt_scene_upload_smooth(rt_context* ctx,
+                           const rt_shape_desc* shapes, uint32_t n_shapes,
+                           const rt_mesh_desc* meshes, uint32_t n_meshes,
+                           const rt_instance_desc* instances, uint32_t n_instances,
+                           const rt_smooth_desc* smooth, uint32_t n_smooth,
+                           const rt_material_desc* materials, uint32_t n_materials,
+                           const rt_pattern_desc* patterns, uint32_t n_patterns,
+                           const rt_light_desc* lights, uint32_t n_lights);
+int rt_smooth_expand(const rt_shape_desc* shapes, uint32_t n_shapes,
+                     const rt_mesh_desc* meshes, uint32_t n_meshes,
+                     const rt_instance_desc* instances, uint32_t n_instances,
+                     const rt_smooth_desc* smooth, uint32_t n_smooth,
+                     rt_smooth_desc* out, uint32_t* n_out);
+/* The smooth triangles of the last upload (zeros after any other upload):
+ * how many the world means (an instance counts its mesh's once per
+ * placement), the device bytes of both precisions' normal tables, and whether
+ * the last launch ran kernels that hold the smooth code. */
+typedef struct rt_smooth_info {
+    uint32_t smooth_triangles;
+    uint32_t ran_smooth;
+    uint64_t normal_bytes;
+} rt_smooth_info;
+int rt_scene_smooth_info(rt_context* ctx, rt_smooth_info* out);
+
 /* Peer canvas: a frame assembled in place instead of gathered (SURVEY.md
  * §8e; the north star's "gather of framebuffer strips over xGMI" done as the
  * shards' own stores into rank 0's image).  The owner creates a device canvas

@@ -90,6 +90,46 @@ void rt_mesh_free(rt_mesh* mesh);
  * the reference's would be.  Host only. */
 int rt_mesh_triangles(const rt_mesh* mesh, const double* transform, int bake, int32_t material, rt_shape_desc* out);
 
+/* OBJ vertex normals (smooth triangles: rtc.h rt_scene_upload_smooth).
+ * rt_mesh_load_obj_ex reads a file (`path`) or a text (`text`); exactly one of
+ * the two is given.  flags = 0 is rt_mesh_load_obj / rt_mesh_load_obj_text.
+ * Under RT_OBJ_NORMALS:
+ *   vn x y z         a normal, kept as written (not normalized) and not
+ *                    counted in ignored_lines;
+ *   f i/j/k, i//k    the third index names the vertex's normal: 1-based,
+ *                    negative ones count back from the normals read so far.
+ * A face is smooth iff every one of its vertices names a normal, otherwise the
+ * whole face is flat; the fan (1, k, k+1) carries each vertex's normal with
+ * it.  RT_ERR_IO with the line number, each with its own text: a vn with fewer
+ * than three numbers, a vn with something that is not a number, a normal
+ * index that is no integer, a normal index out of range (or naming a normal
+ * not yet read). */
+#define RT_OBJ_NORMALS 1u
+#define RT_NO_NORMAL 0xFFFFFFFFu
+int rt_mesh_load_obj_ex(const char* path, const char* text, uint32_t flags, rt_mesh** out);
+
+typedef struct rt_mesh_normals_view {
+    const double* normals;            /* n_normals x 3 */
+    uint32_t n_normals;
+    uint32_t n_smooth;                /* triangles with three normals */
+    const uint32_t* triangle_normals; /* n_triangles x 3, 0-based; RT_NO_NORMAL (0xFFFFFFFF) x 3 for a flat face */
+} rt_mesh_normals_view;
+/* all zero for a mesh loaded without RT_OBJ_NORMALS */
+int rt_mesh_normals_get(const rt_mesh* mesh, rt_mesh_normals_view* view);
+
+/* One rt_smooth_desc per smooth triangle of the mesh, in triangle order, with
+ * `list` as given (RT_SMOOTH_SHAPES or a mesh index) and index = the
+ * triangle's index in the mesh: the list that pairs with
+ * rt_mesh_triangles(mesh, transform, bake, ...) written at the head of that
+ * list (a caller that appends the triangles after other shapes adds their
+ * count to every index).  bake = 0 writes the file's normals (the triangles' inverse
+ * carries the transformation); bake = 1 writes (T^-1)^T n, not normalized:
+ * normals map linearly, so the baked world is the same picture up to rounding,
+ * as rt_mesh_triangles says of its vertices.  out may be NULL to count;
+ * *n_out = the mesh's n_smooth.  Host only. */
+int rt_mesh_smooth_normals(const rt_mesh* mesh, const double* transform, int bake, rt_smooth_desc* out,
+                           uint32_t list, uint32_t* n_out);
+
 /* Camera::new(width, height, fov) + set_transformation(view_transform(...)) */
 int rt_camera_make(uint32_t width, uint32_t height, double field_of_view,
                    const double from[3], const double to[3], const double up[3],

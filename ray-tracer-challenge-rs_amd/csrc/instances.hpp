@@ -17,6 +17,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
 #include <cstring>
 #include <string>
@@ -196,11 +197,15 @@ inline bool instance_ball(const tri::Ball& root, const double inverse[16], tri::
 // a face, an instance and a plain triangle when the mesh has that face.  A
 // mesh with a repeated face makes every instance of it its own partner.  (An
 // inverse that holds a NaN equals nothing, itself included.)
-inline bool geometry_eq(const rt_shape_desc& x, const rt_shape_desc& y) {
+// (nx, ny: the triangles' nine vertex normals, null for a flat one: smooth
+// triangles are equal when those are too, a smooth and a flat one never)
+inline bool geometry_eq(const rt_shape_desc& x, const rt_shape_desc& y, const double* nx = nullptr,
+                        const double* ny = nullptr) {
     return ident::reals_eq(x.vertex_1, y.vertex_1, 3) && ident::reals_eq(x.edge_1, y.edge_1, 3) &&
-           ident::reals_eq(x.edge_2, y.edge_2, 3) && ident::reals_eq(x.normal, y.normal, 3);
+           ident::reals_eq(x.edge_2, y.edge_2, 3) && ident::reals_eq(x.normal, y.normal, 3) &&
+           ident::normals_eq(nx, ny);
 }
-inline uint64_t local_hash(const rt_shape_desc& s) {  // consistent with geometry_eq (-0 and +0 alike)
+inline uint64_t local_hash(const rt_shape_desc& s) {  // consistent with geometry_eq (-0 and +0 alike; normals not hashed)
     uint64_t h = 1469598103934665603ull;
     auto mix = [&h](double v) {
         if (v == 0.0) v = 0.0;
@@ -234,19 +239,24 @@ inline FaceIndex face_index(const rt_mesh_desc& mesh) {
     std::sort(f.begin(), f.end());
     return f;
 }
-inline bool repeated_face(const rt_mesh_desc& mesh, const FaceIndex& f) {
+// (na, nb, tn: the vertex normals of the meshes' triangles by local index and of `t`: ident::Normals)
+inline bool repeated_face(const rt_mesh_desc& mesh, const FaceIndex& f, ident::Normals na = nullptr) {
     for (size_t a = 0; a < f.size(); ++a)
         for (size_t b = a + 1; b < f.size() && f[b].first == f[a].first; ++b)
-            if (geometry_eq(mesh.triangles[f[a].second], mesh.triangles[f[b].second])) return true;
+            if (geometry_eq(mesh.triangles[f[a].second], mesh.triangles[f[b].second], ident::normals_of(na, f[a].second),
+                            ident::normals_of(na, f[b].second)))
+                return true;
     return false;
 }
-inline bool has_face(const rt_mesh_desc& mesh, const FaceIndex& f, const rt_shape_desc& t) {
+inline bool has_face(const rt_mesh_desc& mesh, const FaceIndex& f, const rt_shape_desc& t, ident::Normals na = nullptr,
+                     const double* tn = nullptr) {
     const uint64_t h = local_hash(t);
     for (auto it = std::lower_bound(f.begin(), f.end(), std::make_pair(h, 0u)); it != f.end() && it->first == h; ++it)
-        if (geometry_eq(mesh.triangles[it->second], t)) return true;
+        if (geometry_eq(mesh.triangles[it->second], t, ident::normals_of(na, it->second), tn)) return true;
     return false;
 }
-inline bool share_face(const rt_mesh_desc& a, const FaceIndex& fa, const rt_mesh_desc& b, const FaceIndex& fb) {
+inline bool share_face(const rt_mesh_desc& a, const FaceIndex& fa, const rt_mesh_desc& b, const FaceIndex& fb,
+                       ident::Normals na = nullptr, ident::Normals nb = nullptr) {
     size_t i = 0, j = 0;
     while (i < fa.size() && j < fb.size()) {
         if (fa[i].first < fb[j].first) ++i;
@@ -258,7 +268,9 @@ inline bool share_face(const rt_mesh_desc& a, const FaceIndex& fa, const rt_mesh
             while (je < fb.size() && fb[je].first == h) ++je;
             for (size_t x = i; x < ie; ++x)
                 for (size_t y = j; y < je; ++y)
-                    if (geometry_eq(a.triangles[fa[x].second], b.triangles[fb[y].second])) return true;
+                    if (geometry_eq(a.triangles[fa[x].second], b.triangles[fb[y].second],
+                                    ident::normals_of(na, fa[x].second), ident::normals_of(nb, fb[y].second)))
+                        return true;
             i = ie;
             j = je;
         }
@@ -266,11 +278,96 @@ inline bool share_face(const rt_mesh_desc& a, const FaceIndex& fa, const rt_mesh
     return false;
 }
 
+// ---- smooth triangles (rtc.h rt_scene_upload_smooth) -------------------------
+// Empty when the list is well formed against validated instanced lists, else
+// the reason (RT_ERR_INVALID), each with its own text.
+inline std::string validate_smooth(const rt_shape_desc* shapes, uint32_t ns, const rt_mesh_desc* meshes,
+                                   uint32_t n_meshes, const rt_smooth_desc* smooth, uint32_t n_smooth) {
+    if (n_smooth && !smooth) return "rt_scene_upload_smooth: null smooth list with nonzero count";
+    std::vector<std::vector<char>> seen(n_meshes + 1);  // [n_meshes]: the plain shapes
+    for (uint32_t k = 0; k < n_smooth; ++k) {
+        const rt_smooth_desc& d = smooth[k];
+        const std::string who = "smooth entry " + std::to_string(k);
+        if (d.list != RT_SMOOTH_SHAPES && d.list >= n_meshes) return who + ": list index out of range";
+        const bool plain = d.list == RT_SMOOTH_SHAPES;
+        const uint32_t n = plain ? ns : meshes[d.list].n_triangles;
+        if (d.index >= n) return who + ": triangle index out of range";
+        const rt_shape_desc& t = plain ? shapes[d.index] : meshes[d.list].triangles[d.index];
+        if (t.kind != RT_SHAPE_TRIANGLE) return who + ": the named record is not a triangle";
+        std::vector<char>& s = seen[plain ? n_meshes : d.list];
+        if (s.empty()) s.assign(n, 0);
+        if (s[d.index]) return who + ": the same triangle is named twice";
+        s[d.index] = 1;
+        for (const double* n : {d.normal_1, d.normal_2, d.normal_3})
+            for (int q = 0; q < 3; ++q)
+                if (!std::isfinite(n[q])) return who + ": a normal component is not finite";
+    }
+    return "";
+}
+static_assert(sizeof(rt_smooth_desc) == 80 && offsetof(rt_smooth_desc, normal_1) == 8 &&
+                  offsetof(rt_smooth_desc, normal_3) == 8 + 6 * sizeof(double),
+              "the nine normal components are contiguous");
+
+// The normals of a validated smooth list by triangle: per plain shape and per
+// mesh triangle the entry's nine doubles, or null for a flat one.
+struct SmoothIndex {
+    std::vector<const double*> plain;              // by shape; empty: none is smooth
+    std::vector<std::vector<const double*>> mesh;  // by mesh, by local index; empty: none of the mesh's is
+    ident::Normals of_plain() const { return plain.empty() ? nullptr : plain.data(); }
+    ident::Normals of_mesh(uint32_t m) const { return mesh[m].empty() ? nullptr : mesh[m].data(); }
+    uint32_t smooth_in_mesh(uint32_t m) const {
+        return (uint32_t)std::count_if(mesh[m].begin(), mesh[m].end(), [](const double* p) { return p != nullptr; });
+    }
+};
+inline SmoothIndex smooth_index(uint32_t ns, const rt_mesh_desc* meshes, uint32_t n_meshes, const rt_smooth_desc* smooth,
+                                uint32_t n_smooth) {
+    SmoothIndex si;
+    si.mesh.resize(n_meshes);
+    for (uint32_t k = 0; k < n_smooth; ++k) {
+        const rt_smooth_desc& d = smooth[k];
+        std::vector<const double*>& v = d.list == RT_SMOOTH_SHAPES ? si.plain : si.mesh[d.list];
+        if (v.empty()) v.assign(d.list == RT_SMOOTH_SHAPES ? ns : meshes[d.list].n_triangles, nullptr);
+        v[d.index] = d.normal_1;
+    }
+    return si;
+}
+// The smooth list of the expansion (expand()): the plain entries, then per
+// instance its mesh's entries at the instance's world indices, every entry with
+// RT_SMOOTH_SHAPES, in ascending world index.  Returns the count; out may be null.
+inline uint32_t expand_smooth(uint32_t ns, const rt_mesh_desc* meshes, uint32_t n_meshes,
+                              const rt_instance_desc* instances, uint32_t n_inst, const rt_smooth_desc* smooth,
+                              uint32_t n_smooth, rt_smooth_desc* out) {
+    const SmoothIndex si = smooth_index(ns, meshes, n_meshes, smooth, n_smooth);
+    uint32_t at = 0;
+    auto put = [&](uint32_t world, const double* n) {
+        if (out) {
+            out[at].list = RT_SMOOTH_SHAPES;
+            out[at].index = world;
+            std::memcpy(out[at].normal_1, n, 9 * sizeof(double));
+        }
+        ++at;
+    };
+    for (uint32_t i = 0; i < (uint32_t)si.plain.size(); ++i)
+        if (si.plain[i]) put(i, si.plain[i]);
+    uint32_t base = ns;
+    for (uint32_t k = 0; k < n_inst; ++k) {
+        const uint32_t m = instances[k].mesh;
+        for (uint32_t j = 0; j < (uint32_t)si.mesh[m].size(); ++j)
+            if (si.mesh[m][j]) put(base + j, si.mesh[m][j]);
+        base += meshes[m].n_triangles;
+    }
+    return at;
+}
+
 // expanded[k] = 1: instance k has a triangle value-equal to another triangle
-// of the expansion and is uploaded as plain records.
+// of the expansion and is uploaded as plain records.  si: the world's smooth
+// triangles (null: none), whose normals are part of a triangle's value.
 inline std::vector<char> decide_expanded(const rt_shape_desc* shapes, uint32_t ns, const rt_mesh_desc* meshes,
                                          uint32_t n_meshes, const rt_instance_desc* instances, uint32_t n_inst,
-                                         const rt_material_desc* mats, const rt_pattern_desc* pats) {
+                                         const rt_material_desc* mats, const rt_pattern_desc* pats,
+                                         const SmoothIndex* si = nullptr) {
+    auto mesh_normals = [&](uint32_t m) { return si ? si->of_mesh(m) : nullptr; };
+    const ident::Normals plain_normals = si ? si->of_plain() : nullptr;
     std::vector<char> expanded(n_inst, 0);
     if (!n_inst) return expanded;
     std::vector<FaceIndex> faces(n_meshes);
@@ -279,7 +376,7 @@ inline std::vector<char> decide_expanded(const rt_shape_desc* shapes, uint32_t n
     for (uint32_t m = 0; m < n_meshes; ++m)
         if (used[m]) {
             faces[m] = face_index(meshes[m]);
-            repeated[m] = repeated_face(meshes[m], faces[m]);
+            repeated[m] = repeated_face(meshes[m], faces[m], mesh_normals(m));
         }
     struct Holder {
         const double* inverse;
@@ -310,9 +407,11 @@ inline std::vector<char> decide_expanded(const rt_shape_desc* shapes, uint32_t n
                     continue;
                 if (hs[b].instance >= 0) {
                     const uint32_t kb = (uint32_t)hs[b].instance, mb = instances[kb].mesh;
-                    if (ma == mb || share_face(meshes[ma], faces[ma], meshes[mb], faces[mb]))
+                    if (ma == mb ||
+                        share_face(meshes[ma], faces[ma], meshes[mb], faces[mb], mesh_normals(ma), mesh_normals(mb)))
                         expanded[ka] = expanded[kb] = 1;
-                } else if (has_face(meshes[ma], faces[ma], shapes[hs[b].shape])) {
+                } else if (has_face(meshes[ma], faces[ma], shapes[hs[b].shape], mesh_normals(ma),
+                                    ident::normals_of(plain_normals, hs[b].shape))) {
                     expanded[ka] = 1;
                 }
             }

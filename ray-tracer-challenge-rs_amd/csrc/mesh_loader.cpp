@@ -20,6 +20,11 @@ struct rt_mesh {
     std::vector<double> vertices;     // x, y, z per vertex
     std::vector<uint32_t> triangles;  // three 0-based vertex indices per triangle
     uint32_t ignored_lines = 0;
+    // RT_OBJ_NORMALS loads (rt_mesh_load_obj_ex); empty otherwise
+    std::vector<double> normals;             // x, y, z per vn line, as written
+    std::vector<uint32_t> triangle_normals;  // three 0-based normal indices per triangle, RT_NO_NORMAL x 3: a flat face
+    uint32_t n_smooth = 0;
+    bool with_normals = false;
 };
 
 namespace rtc {
@@ -66,7 +71,29 @@ uint32_t parse_index(const std::string& w, size_t n_vertices, size_t line_no) {
     return (uint32_t)at;
 }
 
-void parse_obj(const std::string& text, rt_mesh& m) {
+// the normal index of a face word (i//k, i/j/k), 0-based; RT_NO_NORMAL for a word without one
+uint32_t parse_normal_index(const std::string& w, size_t n_normals, size_t line_no) {
+    const size_t s1 = w.find('/');
+    if (s1 == std::string::npos) return RT_NO_NORMAL;
+    const size_t s2 = w.find('/', s1 + 1);
+    if (s2 == std::string::npos) return RT_NO_NORMAL;
+    const std::string tail = w.substr(s2 + 1);
+    if (tail.empty()) return RT_NO_NORMAL;
+    char* end = nullptr;
+    errno = 0;
+    const long long i = std::strtoll(tail.c_str(), &end, 10);
+    if (end != tail.c_str() + tail.size() || errno == ERANGE)
+        throw ObjError{"line " + std::to_string(line_no) + ": '" + w + "' is not a normal index"};
+    const long long at = i > 0 ? i - 1 : (long long)n_normals + i;  // negative: back from the normals so far
+    if (i == 0 || at < 0 || at >= (long long)n_normals)
+        throw ObjError{"line " + std::to_string(line_no) + ": normal index " + std::to_string(i) + " out of range (" +
+                       std::to_string(n_normals) + " normals so far)"};
+    return (uint32_t)at;
+}
+
+void parse_obj(const std::string& text, rt_mesh& m, uint32_t flags = 0) {
+    const bool with_normals = (flags & RT_OBJ_NORMALS) != 0;
+    m.with_normals = with_normals;
     size_t pos = 0, line_no = 0;
     while (pos < text.size()) {
         size_t eol = text.find('\n', pos);
@@ -81,12 +108,34 @@ void parse_obj(const std::string& text, rt_mesh& m) {
             for (int q = 1; q <= 3; ++q) m.vertices.push_back(parse_real(w[q], line_no));
         } else if (!w.empty() && w[0] == "f") {
             if (w.size() < 4) throw ObjError{"line " + std::to_string(line_no) + ": a face needs three vertices"};
-            std::vector<uint32_t> idx;
-            for (size_t q = 1; q < w.size(); ++q) idx.push_back(parse_index(w[q], m.vertices.size() / 3, line_no));
+            std::vector<uint32_t> idx, nidx;
+            bool smooth = with_normals;
+            for (size_t q = 1; q < w.size(); ++q) {
+                idx.push_back(parse_index(w[q], m.vertices.size() / 3, line_no));
+                if (with_normals) {
+                    nidx.push_back(parse_normal_index(w[q], m.normals.size() / 3, line_no));
+                    smooth = smooth && nidx.back() != RT_NO_NORMAL;  // every vertex names one, or the face is flat
+                }
+            }
             for (size_t k = 1; k + 1 < idx.size(); ++k) {  // the fan (1, k, k + 1)
                 m.triangles.push_back(idx[0]);
                 m.triangles.push_back(idx[k]);
                 m.triangles.push_back(idx[k + 1]);
+                if (with_normals) {
+                    m.triangle_normals.push_back(smooth ? nidx[0] : RT_NO_NORMAL);
+                    m.triangle_normals.push_back(smooth ? nidx[k] : RT_NO_NORMAL);
+                    m.triangle_normals.push_back(smooth ? nidx[k + 1] : RT_NO_NORMAL);
+                    m.n_smooth += smooth ? 1u : 0u;
+                }
+            }
+        } else if (with_normals && !w.empty() && w[0] == "vn") {
+            if (w.size() < 4) throw ObjError{"line " + std::to_string(line_no) + ": a normal needs three components"};
+            for (int q = 1; q <= 3; ++q) {
+                char* end = nullptr;
+                const double v = std::strtod(w[q].c_str(), &end);
+                if (w[q].empty() || end != w[q].c_str() + w[q].size())
+                    throw ObjError{"line " + std::to_string(line_no) + ": '" + w[q] + "' is not a number in a normal"};
+                m.normals.push_back(v);
             }
         } else {
             ++m.ignored_lines;
@@ -94,10 +143,10 @@ void parse_obj(const std::string& text, rt_mesh& m) {
     }
 }
 
-int load(const std::string& text, rt_mesh** out) {
+int load(const std::string& text, rt_mesh** out, uint32_t flags = 0) {
     try {
         auto m = std::make_unique<rt_mesh>();
-        parse_obj(text, *m);
+        parse_obj(text, *m, flags);
         *out = m.release();
         return RT_OK;
     } catch (const ObjError& e) {
@@ -105,6 +154,15 @@ int load(const std::string& text, rt_mesh** out) {
     } catch (const std::exception& e) {
         return set_error(RT_ERR_IO, std::string("OBJ: ") + e.what());
     }
+}
+
+int load_file(const char* path, rt_mesh** out, uint32_t flags) {
+    std::ifstream f(path, std::ios::binary);
+    if (!f) return set_error(RT_ERR_IO, std::string("cannot open ") + path + ": " + std::strerror(errno));
+    std::stringstream ss;
+    ss << f.rdbuf();
+    if (f.bad()) return set_error(RT_ERR_IO, std::string("cannot read ") + path);
+    return load(ss.str(), out, flags);
 }
 
 // Matrix<4> * Point (matrix.rs:332-346): per row a left fold from 0.0 over
@@ -130,12 +188,54 @@ int rt_mesh_load_obj_text(const char* text, rt_mesh** out) {
 
 int rt_mesh_load_obj(const char* path, rt_mesh** out) {
     if (!path || !out) return rtc::set_error(RT_ERR_INVALID, "rt_mesh_load_obj: null argument");
-    std::ifstream f(path, std::ios::binary);
-    if (!f) return rtc::set_error(RT_ERR_IO, std::string("cannot open ") + path + ": " + std::strerror(errno));
-    std::stringstream ss;
-    ss << f.rdbuf();
-    if (f.bad()) return rtc::set_error(RT_ERR_IO, std::string("cannot read ") + path);
-    return rtc::load(ss.str(), out);
+    return rtc::load_file(path, out, 0);
+}
+
+int rt_mesh_load_obj_ex(const char* path, const char* text, uint32_t flags, rt_mesh** out) {
+    if (!out || (path == nullptr) == (text == nullptr))
+        return rtc::set_error(RT_ERR_INVALID, "rt_mesh_load_obj_ex: give a path or a text (one of the two) and an output");
+    if (flags & ~RT_OBJ_NORMALS) return rtc::set_error(RT_ERR_INVALID, "rt_mesh_load_obj_ex: unknown flag");
+    return text ? rtc::load(text, out, flags) : rtc::load_file(path, out, flags);
+}
+
+int rt_mesh_normals_get(const rt_mesh* m, rt_mesh_normals_view* v) {
+    if (!m || !v) return rtc::set_error(RT_ERR_INVALID, "rt_mesh_normals_get: null argument");
+    *v = rt_mesh_normals_view{};
+    if (!m->with_normals) return RT_OK;
+    v->normals = m->normals.data();
+    v->n_normals = (uint32_t)(m->normals.size() / 3);
+    v->n_smooth = m->n_smooth;
+    v->triangle_normals = m->triangle_normals.data();
+    return RT_OK;
+}
+
+int rt_mesh_smooth_normals(const rt_mesh* m, const double* transform, int bake, rt_smooth_desc* out, uint32_t list,
+                           uint32_t* n_out) {
+    if (!m) return rtc::set_error(RT_ERR_INVALID, "rt_mesh_smooth_normals: null argument");
+    if (n_out) *n_out = m->n_smooth;
+    if (!out || !m->n_smooth) return RT_OK;
+    double inv[16];
+    const bool baked = transform && bake;
+    if (baked)
+        if (const int rc = rt_matrix_inverse(transform, inv)) return rc;
+    uint32_t at = 0;
+    const size_t n = m->triangle_normals.size() / 3;
+    for (size_t t = 0; t < n; ++t) {
+        const uint32_t* k = &m->triangle_normals[3 * t];
+        if (k[0] == RT_NO_NORMAL) continue;
+        rt_smooth_desc& d = out[at++];
+        std::memset(&d, 0, sizeof d);
+        d.list = list;
+        d.index = (uint32_t)t;
+        double* dst[3] = {d.normal_1, d.normal_2, d.normal_3};
+        for (int c = 0; c < 3; ++c) {
+            const double* src = &m->normals[3 * (size_t)k[c]];
+            // baked: transpose(inverse) * n, a left fold per row like Matrix<4> * Vector (matrix.rs:348-362), no FMA
+            for (int r = 0; r < 3; ++r)
+                dst[c][r] = baked ? ((0.0 + inv[r] * src[0]) + inv[4 + r] * src[1]) + inv[8 + r] * src[2] : src[r];
+        }
+    }
+    return RT_OK;
 }
 
 int rt_mesh_view_get(const rt_mesh* m, rt_mesh_view* v) {

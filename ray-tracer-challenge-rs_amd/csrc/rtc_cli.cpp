@@ -17,8 +17,11 @@
 // --instance FILE:tx,ty,tz[:s] (repeatable: a copy of the mesh scaled by s,
 // default 1, and moved by (tx, ty, tz), with Material::default, after every
 // shape and --obj triangle, in command-line order; each FILE is loaded once and
-// the world goes up through rt_scene_upload_instanced).  Pixels
-// are quantized on the device as canvas.rs:117-123 does.
+// the world goes up through rt_scene_upload_instanced),
+// --smooth (--obj and --instance read the files' vertex normals and the faces
+// that name three are smooth triangles: rt_scene_upload_smooth, DESIGN.md
+// §3.11; without it the output is what it was).  Pixels are quantized on the
+// device as canvas.rs:117-123 does.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -34,11 +37,13 @@ static int usage() {
     std::fprintf(stderr,
                  "usage: rtc <SCENE.yaml> <OUT.png|OUT.ppm> [-r serial|parallel|gpu] [-q] [--width W] [--height H]\n"
                  "           [--depth D] [--precision f32|f64] [--device N] [--gpus N] [--ppm-binary] [--timings]\n"
-                 "           [--samples N] [--obj MESH.obj]... [--instance MESH.obj:tx,ty,tz[:s]]...\n"
+                 "           [--samples N] [--obj MESH.obj]... [--instance MESH.obj:tx,ty,tz[:s]]... [--smooth]\n"
                  "  --obj MESH.obj appends the mesh's triangles (v and f lines; faces fan-triangulated) to the\n"
                  "  scene's shapes, with the default material and no transformation; repeatable.\n"
                  "  --instance MESH.obj:tx,ty,tz[:s] places a copy of the mesh, scaled by s (default 1) and moved by\n"
                  "  (tx, ty, tz), with the default material, after the shapes; repeatable, each file is read once.\n"
+                 "  --smooth makes --obj and --instance read the files' vertex normals (vn lines, f i//k and i/j/k):\n"
+                 "  a face whose vertices all name a normal is shaded with the interpolated normal.\n"
                  "  --samples N renders N x N samples per pixel (1..%d, default 1 = one ray per pixel centre) and\n"
                  "  averages them on the GPU.\n"
                  "  -r serial|parallel are accepted for the reference's command lines but render on the GPU like\n"
@@ -87,6 +92,7 @@ int main(int argc, char** argv) {
     uint32_t width = 0, height = 0, depth = RT_DEFAULT_MAX_DEPTH, precision = RT_PRECISION_F32;
     int device = 0, gpus = 1;
     uint32_t samples = 1;
+    bool smooth = false;
     std::vector<const char*> obj_paths;
     std::vector<Placement> placements;
     for (int i = 3; i < argc; ++i) {
@@ -95,6 +101,7 @@ int main(int argc, char** argv) {
         if (a == "-q" || a == "--quiet") quiet = true;
         else if (a == "--ppm-binary") ppm_binary = true;
         else if (a == "--timings") timings = true;
+        else if (a == "--smooth") smooth = true;
         else if (a == "-r" || a == "--rendering-mode") {
             const char* v = next();
             if (!v || (std::strcmp(v, "serial") && std::strcmp(v, "parallel") && std::strcmp(v, "gpu"))) return usage();
@@ -159,10 +166,22 @@ int main(int argc, char** argv) {
         m.pattern = -1;
         materials.push_back(m);
     }
+    // --smooth: the files' vertex normals, as rt_scene_upload_smooth's side list
+    std::vector<rt_smooth_desc> smooth_list;
+    const uint32_t obj_flags = smooth ? RT_OBJ_NORMALS : 0u;
+    auto add_normals = [&](const rt_mesh* mesh, uint32_t list, uint32_t first) {
+        uint32_t n = 0;
+        if (!smooth || rt_mesh_smooth_normals(mesh, nullptr, 0, nullptr, list, &n) != RT_OK || !n) return n;
+        const size_t at = smooth_list.size();
+        smooth_list.resize(at + n);
+        rt_mesh_smooth_normals(mesh, nullptr, 0, smooth_list.data() + at, list, &n);
+        for (size_t k = at; k < smooth_list.size(); ++k) smooth_list[k].index += first;
+        return n;
+    };
     for (const char* path : obj_paths) {
         rt_mesh* mesh = nullptr;
         rt_mesh_view mv;
-        if (rt_mesh_load_obj(path, &mesh) != RT_OK || rt_mesh_view_get(mesh, &mv) != RT_OK) {
+        if (rt_mesh_load_obj_ex(path, nullptr, obj_flags, &mesh) != RT_OK || rt_mesh_view_get(mesh, &mv) != RT_OK) {
             std::fprintf(stderr, "error: %s\n", rt_last_error());
             return 1;
         }
@@ -172,9 +191,11 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "error: %s\n", rt_last_error());
             return 1;
         }
+        const uint32_t n_smooth = add_normals(mesh, RT_SMOOTH_SHAPES, (uint32_t)at);
         if (!quiet)
             std::printf("%s: %u vertices, %u triangles, %u lines ignored\n", path, mv.n_vertices, mv.n_triangles,
                         mv.ignored_lines);
+        if (!quiet && smooth) std::printf("%s: %u smooth triangles\n", path, n_smooth);
         rt_mesh_free(mesh);
     }
     // --instance: each file's local triangles once, and one (mesh, inverse, material) per placement
@@ -186,7 +207,8 @@ int main(int argc, char** argv) {
         if (found == mesh_of.end()) {
             rt_mesh* mesh = nullptr;
             rt_mesh_view mv;
-            if (rt_mesh_load_obj(p.file.c_str(), &mesh) != RT_OK || rt_mesh_view_get(mesh, &mv) != RT_OK) {
+            if (rt_mesh_load_obj_ex(p.file.c_str(), nullptr, obj_flags, &mesh) != RT_OK ||
+                rt_mesh_view_get(mesh, &mv) != RT_OK) {
                 std::fprintf(stderr, "error: %s\n", rt_last_error());
                 return 1;
             }
@@ -198,6 +220,8 @@ int main(int argc, char** argv) {
             if (!quiet)
                 std::printf("%s: %u vertices, %u triangles, %u lines ignored\n", p.file.c_str(), mv.n_vertices,
                             mv.n_triangles, mv.ignored_lines);
+            const uint32_t n_smooth = add_normals(mesh, (uint32_t)mesh_triangles.size(), 0u);
+            if (!quiet && smooth) std::printf("%s: %u smooth triangles\n", p.file.c_str(), n_smooth);
             rt_mesh_free(mesh);
             found = mesh_of.emplace(p.file, (uint32_t)mesh_triangles.size()).first;
             mesh_triangles.push_back(std::move(tri));
@@ -221,10 +245,11 @@ int main(int argc, char** argv) {
     const double ctx_ms = ms_since(t_ctx);
     const auto t_up = clk::now();
     if (created != RT_OK ||
-        rt_scene_upload_instanced(ctx, shapes.data(), (uint32_t)shapes.size(), meshes.data(), (uint32_t)meshes.size(),
-                                  instances.data(), (uint32_t)instances.size(), materials.data(),
-                                  (uint32_t)materials.size(), v.patterns, v.n_patterns, v.lights,
-                                  v.n_lights) != RT_OK) {  // (no instances: rt_scene_upload itself)
+        rt_scene_upload_smooth(ctx, shapes.data(), (uint32_t)shapes.size(), meshes.data(), (uint32_t)meshes.size(),
+                               instances.data(), (uint32_t)instances.size(), smooth_list.data(),
+                               (uint32_t)smooth_list.size(), materials.data(), (uint32_t)materials.size(), v.patterns,
+                               v.n_patterns, v.lights,
+                               v.n_lights) != RT_OK) {  // (no smooth triangle: rt_scene_upload_instanced; no instances: rt_scene_upload)
         std::fprintf(stderr, "error: %s\n", rt_last_error());
         return 1;
     }

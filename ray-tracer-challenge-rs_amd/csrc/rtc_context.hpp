@@ -32,6 +32,13 @@ struct InstanceCounts {
     int32_t world_begin = 0;  // world indices from here on are instances' triangles
 };
 
+// Entries (nine reals each) of a world's smooth-triangle normal tables: one per
+// record of the triangle run and one per local record of the meshes, or zero
+// where that part holds no smooth triangle (rtc_internal.hpp kShapeSmooth).
+struct SmoothCounts {
+    uint32_t plain = 0, inst = 0;
+};
+
 template <typename R>
 struct DeviceWorld {
     DeviceBuffer<unsigned char> image;  // the allocation holding the four tables
@@ -49,6 +56,9 @@ struct DeviceWorld {
     DeviceBuffer<TriNode<R>> inst_nodes;    // every mesh's hierarchy
     DeviceBuffer<int32_t> inst_pos;         // local index -> record (InstRec::pos_begin)
     InstanceCounts inst_counts{};           // zeros: a world without instances
+    // Smooth triangles (rt_scene_upload_smooth): the plain part's entries, then the meshes', outside the LDS image
+    DeviceBuffer<R> smooth;
+    SmoothCounts smooth_counts{};           // zeros: a world without smooth triangles
     DevScene<R> scene{};
     // Point the tables into `image` for ns shapes, nm materials, np patterns.
     void carve(size_t ns, size_t nm, size_t np) {
@@ -93,6 +103,16 @@ struct DeviceWorld {
         inst_counts = c;
         return RT_OK;
     }
+    // Room for the normal tables of `c`; all zero: the world has no smooth triangle.
+    int allocate_smooth(const SmoothCounts& c) {
+        if (int rc = smooth.reserve(((size_t)c.plain + c.inst) * kSmoothReals)) return rc;
+        smooth_counts = c;
+        return RT_OK;
+    }
+    const R* smooth_plain() const { return smooth_counts.plain ? smooth.get() : nullptr; }
+    const R* smooth_inst() const {
+        return smooth_counts.inst ? smooth.get() + (size_t)smooth_counts.plain * kSmoothReals : nullptr;
+    }
 };
 
 // Does the world hold instances the kernels walk?  (A world whose instances
@@ -100,6 +120,12 @@ struct DeviceWorld {
 template <typename R>
 inline bool walked_instances(const DeviceWorld<R>& w) {
     return w.inst_counts.instances > 0;
+}
+// Does the world run the instance build's kernels (rtc::instanced::launch_trace*)?  They hold the instance
+// level and the smooth triangle's normal (rtc_kernels.hip prepare_hit); every other world runs the plain build.
+template <typename R>
+inline bool instance_build(const DeviceWorld<R>& w) {
+    return walked_instances(w) || w.smooth_counts.plain > 0 || w.smooth_counts.inst > 0;
 }
 
 struct CodeBuild;  // rtc_jit.cpp: one hipRTC build of a per-scene kernel, possibly in flight
@@ -267,6 +293,8 @@ struct rt_context {
     uint32_t duplicate_shapes = 0;  // shapes value-equal to an earlier one (one identity class)
     rt_tree_info tree_info{};       // the triangle hierarchy of the uploaded world (rt_scene_tree_info; zeros = none)
     rt_instance_info instance_info{};  // meshes and instances of the uploaded world (rt_scene_instance_info)
+    rt_smooth_info smooth_info{};      // smooth triangles of the uploaded world (rt_scene_smooth_info)
+    std::vector<uint8_t> smooth_shape; // by plain shape: a smooth triangle (rt_debug_normal refuses it); empty: none
     std::vector<int32_t> world_slot;  // world index -> slot | kind << 24 of the uploaded table
     // ray-pool overflow regions, one per resident workgroup; a ray batch's per-lane LIFOs (launch_rays)
     rtc::DeviceBuffer<unsigned char> d_spill;
@@ -334,6 +362,8 @@ struct InstancedLists {
     uint32_t n_meshes;
     const rt_instance_desc* instances;
     uint32_t n_instances;
+    const rt_smooth_desc* smooth = nullptr;  // rt_scene_upload_smooth's list
+    uint32_t n_smooth = 0;
 };
 int validate_scene_instanced(const rt_shape_desc* shapes, uint32_t ns, const InstancedLists& il,
                              const rt_material_desc* mats, uint32_t nm, const rt_pattern_desc* pats, uint32_t np,
@@ -345,7 +375,8 @@ int build_scene(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns, const
 int build_scene_instanced(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns, const rt_mesh_desc* meshes,
                           uint32_t n_meshes, const rt_instance_desc* instances, uint32_t n_inst,
                           const rt_material_desc* mats, uint32_t nm, const rt_pattern_desc* pats, uint32_t np,
-                          const rt_light_desc* lights, uint32_t nl);
+                          const rt_light_desc* lights, uint32_t nl, const rt_smooth_desc* smooth = nullptr,
+                          uint32_t n_smooth = 0);
 void scene_brightness(const rt_shape_desc* shapes, uint32_t ns, const rt_material_desc* mats, uint32_t nm,
                       const rt_pattern_desc* pats, uint32_t np,
                       const rt_light_desc* lights, uint32_t nl, double* bright_hit, double* bright_w);

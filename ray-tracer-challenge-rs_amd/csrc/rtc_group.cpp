@@ -60,6 +60,8 @@ struct SceneHeader {
     rt_tree_info tree_info;
     InstanceCounts inst;  // mesh instances (rt_scene_upload_instanced): zeros = none
     rt_instance_info instance_info;
+    SmoothCounts smooth;  // smooth triangles (rt_scene_upload_smooth): zeros = none
+    rt_smooth_info smooth_info;
 };
 
 // (device pointer, bytes) of every table of a member's world, in one order
@@ -73,6 +75,7 @@ void world_buffers(DeviceWorld<R>& w, const SceneHeader& h, std::vector<std::pai
     out.push_back({w.inst_shapes.get(), h.inst.records * sizeof(ShapeRec<R>)});
     out.push_back({w.inst_nodes.get(), h.inst.nodes * sizeof(TriNode<R>)});
     out.push_back({w.inst_pos.get(), h.inst.pos * sizeof(int32_t)});
+    out.push_back({w.smooth.get(), ((size_t)h.smooth.plain + h.smooth.inst) * kSmoothReals * sizeof(R)});
 }
 
 // Rank 0's `value` to every member of every rank, over RCCL (collective):
@@ -329,7 +332,7 @@ int group_scene_upload(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns
         if (!root_rc && hipSetDevice(ctx->device) != hipSuccess) root_rc = set_error(RT_ERR_HIP, "hipSetDevice");
         if (!root_rc)
             root_rc = il ? build_scene_instanced(ctx, shapes, ns, il->meshes, il->n_meshes, il->instances, il->n_instances,
-                                                 mats, nm, pats, np, lights, nl)
+                                                 mats, nm, pats, np, lights, nl, il->smooth, il->n_smooth)
                          : build_scene(ctx, shapes, ns, mats, nm, pats, np, lights, nl);
         if (root_rc) root_err = rt_last_error();
         root_h.status = root_rc;
@@ -338,6 +341,8 @@ int group_scene_upload(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns
         root_h.n_world_slots = (uint32_t)ctx->world_slot.size();
         root_h.inst = ctx->w32.inst_counts;
         root_h.instance_info = ctx->instance_info;
+        root_h.smooth = ctx->w32.smooth_counts;
+        root_h.smooth_info = ctx->smooth_info;
         root_h.ns = ns;
         root_h.nm = nm;
         root_h.np = np;
@@ -371,14 +376,16 @@ int group_scene_upload(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns
         else if (m->group.rank != 0) {
             const SceneHeader& h = hdr[i];
             // (worlds with and without instances run different kernels: the cached occupancies go)
-            if ((h.inst.instances > 0) != walked_instances(m->w32))
+            if ((h.inst.instances > 0 || h.smooth.plain > 0 || h.smooth.inst > 0) != instance_build(m->w32))
                 std::fill(std::begin(m->occ_blocks), std::end(m->occ_blocks), 0);
             if ((local_rc = m->w32.allocate(h.ns, h.nm, h.np, h.nl)) == RT_OK &&
                 (local_rc = m->w64.allocate(h.ns, h.nm, h.np, h.nl)) == RT_OK &&
                 (local_rc = m->w32.allocate_tree(h.n_tri_nodes, h.tri_flat_begin)) == RT_OK &&
                 (local_rc = m->w64.allocate_tree(h.n_tri_nodes, h.tri_flat_begin)) == RT_OK &&
-                (local_rc = m->w32.allocate_instances(h.inst)) == RT_OK)
-                local_rc = m->w64.allocate_instances(h.inst);
+                (local_rc = m->w32.allocate_instances(h.inst)) == RT_OK &&
+                (local_rc = m->w64.allocate_instances(h.inst)) == RT_OK &&
+                (local_rc = m->w32.allocate_smooth(h.smooth)) == RT_OK)
+                local_rc = m->w64.allocate_smooth(h.smooth);
         }
         if (local_rc) local_err = rt_last_error();
     }
@@ -414,6 +421,7 @@ int group_scene_upload(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns
         m->duplicate_shapes = h.duplicates;
         m->tree_info = h.tree_info;
         m->instance_info = h.instance_info;
+        m->smooth_info = h.smooth_info;
         m->have_scene = true;
         ++m->scene_gen;
     }

@@ -278,6 +278,7 @@ struct WorldIndices {
     const uint32_t* index = nullptr;  // world index of list entry i; null: i
     uint32_t n_plain = 0;             // with `index`: entries [0, n_plain) are the world's first shapes (world_slot's reach)
     std::vector<int32_t>* slot_of = nullptr;  // out: slot | kind << 24 of list entry i
+    ident::Normals normals = nullptr;  // vertex normals of list entry i, null for a flat shape (null: none is smooth)
     uint32_t of(uint32_t i) const { return index ? index[i] : i; }
     uint32_t plain(uint32_t ns) const { return index ? n_plain : ns; }
 };
@@ -332,7 +333,7 @@ int build_world(rt_context* ctx, DeviceWorld<R>& w, const rt_shape_desc* shapes,
             r.material = d.material;
             const bool class_end = next + 1 >= order.size() || cls[order[next + 1]] != cls[i];
             r.flags = (d.closed ? kShapeClosed : 0) | (class_end ? kShapeClassEnd : 0) | (similar ? kShapeSimilar : 0) | (aligned ? kShapeAxisAligned : 0) |
-                      (int32_t)(wi.of(cls[i]) << kShapeClassShift);
+                      (ident::normals_of(wi.normals, i) ? kShapeSmooth : 0) | (int32_t)(wi.of(cls[i]) << kShapeClassShift);
             r.casts_shadow = mats[d.material].casts_shadow ? 1 : 0;
             sh.push_back(r);
         }
@@ -442,7 +443,8 @@ int validate_scene_instanced(const rt_shape_desc* shapes, uint32_t ns, const Ins
                              const rt_material_desc* mats, uint32_t nm, const rt_pattern_desc* pats, uint32_t np,
                              const rt_light_desc* lights, uint32_t nl) {
     if (int rc = validate_scene(shapes, ns, mats, nm, pats, np, lights, nl)) return rc;
-    const std::string why = inst::validate(shapes, ns, il.meshes, il.n_meshes, il.instances, il.n_instances, nm);
+    std::string why = inst::validate(shapes, ns, il.meshes, il.n_meshes, il.instances, il.n_instances, nm);
+    if (why.empty()) why = inst::validate_smooth(shapes, ns, il.meshes, il.n_meshes, il.smooth, il.n_smooth);
     return why.empty() ? RT_OK : set_error(RT_ERR_INVALID, why);
 }
 
@@ -568,7 +570,7 @@ int blocks_per_cu(rt_context* ctx, bool pool, bool lds_world, size_t lds, int* p
     }
     int api = 0;
     // (a world with mesh instances runs the instance variant of every kernel; an upload that changes that clears the cache)
-    if (walked_instances(ctx->w32))
+    if (instance_build(ctx->w32))
         RT_HIP(ss ? instanced::occupancy_ss<R>(pool, lds_world, lds, &api)
                   : instanced::occupancy<R>(pool, lds_world, lds, &api));
     else
@@ -829,6 +831,8 @@ void set_instance_params(LaunchParams<R>& P, const DeviceWorld<R>& w) {
     P.inst_shapes = w.inst_shapes.get();
     P.inst_nodes = w.inst_nodes.get();
     P.inst_pos = w.inst_pos.get();
+    P.smooth_plain = w.smooth_plain();
+    P.smooth_inst = w.smooth_inst();
 }
 
 template <typename R>
@@ -892,10 +896,11 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
         const uint32_t generic_only =
             RT_FLAG_NO_SHADE | RT_FLAG_NO_TRACE | RT_FLAG_GENERATIONS | (ls.pool ? 0u : RT_FLAG_STAMPS);
         // (a world with a triangle hierarchy runs the generic kernels, which walk it)
-        const bool instanced = walked_instances(w);
-        const bool tree = w.n_tri_nodes > 0 || instanced;
+        const bool instanced = walked_instances(w), smooth = w.smooth_counts.plain || w.smooth_counts.inst;
+        const bool tree = w.n_tri_nodes > 0 || instanced || smooth;
         if (tree && ctx->jit.mode != RT_JIT_OFF && ctx->jit.log.empty())
-            ctx->jit.log = instanced
+            ctx->jit.log = smooth ? "no per-scene build: the world has smooth triangles, whose normals the generic kernels interpolate"
+                           : instanced
                                ? "no per-scene build: the world has mesh instances, which the generic kernels walk"
                                : "no per-scene build: the world has a triangle hierarchy, which the generic kernels walk";
         const bool want = cam && !dup && !tree && !(flags & generic_only) &&
@@ -968,7 +973,7 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
         if (w.scene.kind_begin[k + 1] > w.scene.kind_begin[k]) kinds |= 1u << k;
     // (supersampled launches: the all-kinds build only)
     const bool sp = sizeof(R) == 4 && ls.pool && ctx->knobs.kind_variants && (kinds & ~kKindsSp) == 0 && !dup && !ss &&
-                    !walked_instances(w);  // (instances are triangles)
+                    !instance_build(w);  // (instances are triangles)
     if (flags & RT_FLAG_FAIL_LAUNCH) return set_error(RT_ERR_HIP, "launch refused (RT_FLAG_FAIL_LAUNCH)");
     if constexpr (sizeof(R) == 4) {
         // The per-scene direct kernel's primary cull: each slot's screen
@@ -1058,7 +1063,7 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
         void* args[] = {&P, &sh, &mt, &pt, &lt};
         (void)hipGetLastError();
         RT_HIP(hipModuleLaunchKernel(jf, ls.grid, 1, 1, kBlock, 1, 1, (unsigned)ls.lds, stream, args, nullptr));
-    } else if (hipError_t e = walked_instances(w)
+    } else if (hipError_t e = instance_build(w)
                                   ? (ss ? instanced::launch_trace_ss<R>(P, ls.pool, dup, ls.grid, ls.lds, stream)
                                         : instanced::launch_trace<R>(P, ls.pool, dup, ls.grid, ls.lds, stream))
                               : ss ? launch_trace_ss<R>(P, ls.pool, dup, ls.grid, ls.lds, stream)
@@ -1071,6 +1076,7 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
                                          " B, pool " + std::to_string(ls.lcap) + "/" + std::to_string(ls.cap) +
                                          " rays in LDS): " + hipGetErrorString(e));
     if (dynamic) ctx->head_set ^= 1;
+    ctx->smooth_info.ran_smooth = !jf && (w.smooth_counts.plain || w.smooth_counts.inst) ? 1u : 0u;
     return RT_OK;
 }
 
@@ -1084,7 +1090,7 @@ int ray_blocks_per_cu(rt_context* ctx, bool lds_world, size_t lds, int* per_cu) 
         return RT_OK;
     }
     int api = 0;
-    if (walked_instances(ctx->w32)) RT_HIP(instanced::occupancy_rays<R>(lds_world, lds, &api));
+    if (instance_build(ctx->w32)) RT_HIP(instanced::occupancy_rays<R>(lds_world, lds, &api));
     else RT_HIP(occupancy_rays<R>(lds_world, lds, &api));
     *per_cu = cap_by_lds(api, lds);
     ctx->occ_lds[key] = lds;
@@ -1149,7 +1155,7 @@ int launch_rays(rt_context* ctx, DeviceWorld<R>& w, const void* d_rays, uint64_t
     }
     ctx->jit.used = false;
     if (o->flags & RT_FLAG_FAIL_LAUNCH) return set_error(RT_ERR_HIP, "launch refused (RT_FLAG_FAIL_LAUNCH)");
-    if (hipError_t e = walked_instances(w) ? instanced::launch_trace_rays<R>(P, ctx->duplicate_shapes > 0, ls.grid, ls.lds,
+    if (hipError_t e = instance_build(w) ? instanced::launch_trace_rays<R>(P, ctx->duplicate_shapes > 0, ls.grid, ls.lds,
                                                                              d_rays, d_rgb, d_hits, stream)
                                            : launch_trace_rays<R>(P, ctx->duplicate_shapes > 0, ls.grid, ls.lds, d_rays,
                                                                   d_rgb, d_hits, stream);
@@ -1157,6 +1163,7 @@ int launch_rays(rt_context* ctx, DeviceWorld<R>& w, const void* d_rays, uint64_t
         return set_error(RT_ERR_HIP, "launch of the ray-batch kernel (grid " + std::to_string(ls.grid) +
                                          ", dynamic LDS " + std::to_string(ls.lds) + " B, " + std::to_string(ls.cap) +
                                          " stack entries per lane): " + hipGetErrorString(e));
+    ctx->smooth_info.ran_smooth = w.smooth_counts.plain || w.smooth_counts.inst ? 1u : 0u;
     return RT_OK;
 }
 
@@ -1412,6 +1419,41 @@ int rt_scene_upload_instanced(rt_context* ctx, const rt_shape_desc* shapes, uint
     return build_scene_instanced(ctx, shapes, ns, meshes, n_meshes, instances, n_inst, mats, nm, pats, np, lights, nl);
 }
 
+int rt_scene_upload_smooth(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns, const rt_mesh_desc* meshes,
+                           uint32_t n_meshes, const rt_instance_desc* instances, uint32_t n_inst,
+                           const rt_smooth_desc* smooth, uint32_t n_smooth, const rt_material_desc* mats, uint32_t nm,
+                           const rt_pattern_desc* pats, uint32_t np, const rt_light_desc* lights, uint32_t nl) {
+    if (!n_smooth)  // rt_scene_upload_instanced itself
+        return rt_scene_upload_instanced(ctx, shapes, ns, meshes, n_meshes, instances, n_inst, mats, nm, pats, np, lights, nl);
+    const InstancedLists il{meshes, n_meshes, instances, n_inst, smooth, n_smooth};
+    // (the lists are checked before the context is looked at; a group's rank 0 checks its own)
+    if (!ctx || !ctx->group.comm)
+        if (int rc = validate_scene_instanced(shapes, ns, il, mats, nm, pats, np, lights, nl)) return rc;
+    if (!ctx) return set_error(RT_ERR_INVALID, "null context");
+    if (ctx->group.comm) return group_scene_upload(ctx, shapes, ns, mats, nm, pats, np, lights, nl, &il);
+    RT_HIP(hipSetDevice(ctx->device));
+    RT_HIP(hipDeviceSynchronize());  // launches on caller streams may still read the old tables
+    return build_scene_instanced(ctx, shapes, ns, meshes, n_meshes, instances, n_inst, mats, nm, pats, np, lights, nl,
+                                 smooth, n_smooth);
+}
+
+int rt_smooth_expand(const rt_shape_desc* shapes, uint32_t ns, const rt_mesh_desc* meshes, uint32_t n_meshes,
+                     const rt_instance_desc* instances, uint32_t n_inst, const rt_smooth_desc* smooth, uint32_t n_smooth,
+                     rt_smooth_desc* out, uint32_t* n_out) {
+    std::string why = inst::validate(shapes, ns, meshes, n_meshes, instances, n_inst, 0x7FFFFFFFu);
+    if (why.empty()) why = inst::validate_smooth(shapes, ns, meshes, n_meshes, smooth, n_smooth);
+    if (!why.empty()) return set_error(RT_ERR_INVALID, why);
+    const uint32_t n = inst::expand_smooth(ns, meshes, n_meshes, instances, n_inst, smooth, n_smooth, out);
+    if (n_out) *n_out = n;
+    return RT_OK;
+}
+
+int rt_scene_smooth_info(rt_context* ctx, rt_smooth_info* out) {
+    if (!ctx || !out) return set_error(RT_ERR_INVALID, "null argument");
+    *out = ctx->have_scene ? ctx->smooth_info : rt_smooth_info{};
+    return RT_OK;
+}
+
 int rt_instances_expand(const rt_shape_desc* shapes, uint32_t ns, const rt_mesh_desc* meshes, uint32_t n_meshes,
                         const rt_instance_desc* instances, uint32_t n_inst, rt_shape_desc* out) {
     // (materials are the upload's to check: any index passes here)
@@ -1535,7 +1577,7 @@ int build_plain_tables(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns
     int rc;
     ctx->have_scene = false;
     std::vector<uint32_t> cls;  // value-identity classes (shape_identity.hpp)
-    ctx->duplicate_shapes = ident::shape_classes(shapes, ns, mats, pats, cls);
+    ctx->duplicate_shapes = ident::shape_classes(shapes, ns, mats, pats, cls, wi.normals);
     std::vector<uint32_t> order = table_order(shapes, ns, cls);
     // A world the per-scene builds take whole (their records: up to
     // kJitRecordsMaxShapes shapes) keeps the flat triangle run and with it
@@ -1583,7 +1625,8 @@ struct InstancePlan {
 
 template <typename R>
 int upload_instances(rt_context* ctx, DeviceWorld<R>& w, const InstancePlan& ip, const rt_mesh_desc* meshes,
-                     const rt_instance_desc* instances, uint32_t n_inst, const rt_material_desc* mats) {
+                     const rt_instance_desc* instances, uint32_t n_inst, const rt_material_desc* mats,
+                     const inst::SmoothIndex* si) {
     int rc;
     if ((rc = w.allocate_instances(ip.counts))) return rc;
     std::vector<ShapeRec<R>> recs(ip.counts.records);
@@ -1609,7 +1652,7 @@ int upload_instances(rt_context* ctx, DeviceWorld<R>& w, const InstancePlan& ip,
                 r.tri[9 + q] = (R)d.normal[q];
             }
             r.world_index = (int32_t)j;  // the local index: for_instances adds the instance's base
-            r.flags = kShapeClassEnd;
+            r.flags = kShapeClassEnd | (si && ident::normals_of(si->of_mesh((uint32_t)m), j) ? kShapeSmooth : 0);
             recs[ip.rec_begin[m] + at] = r;
             pos[ip.pos_begin[m] + j] = (int32_t)(ip.rec_begin[m] + at);
         }
@@ -1664,30 +1707,79 @@ int upload_instances(rt_context* ctx, DeviceWorld<R>& w, const InstancePlan& ip,
     const int rs = hip_status(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");  // (host temporaries)
     return rc ? rc : rs;
 }
+
+// The normal tables of one precision (rtc_internal.hpp kShapeSmooth): an entry
+// per record of the triangle run when a plain record is smooth (list_normals:
+// by entry of the plain list, slot_of: build_world's), and an entry per local
+// record of the walked meshes when one of those is.  A flat record's entry is
+// zero and never read.
+template <typename R>
+int upload_smooth(rt_context* ctx, DeviceWorld<R>& w, const std::vector<const double*>& list_normals,
+                  const InstancePlan& ip, const inst::SmoothIndex& si) {
+    const int32_t tri0 = w.scene.kind_begin[RT_SHAPE_TRIANGLE], tri1 = w.scene.kind_begin[RT_SHAPE_TRIANGLE + 1];
+    SmoothCounts c;
+    if (std::any_of(list_normals.begin(), list_normals.end(), [](const double* p) { return p != nullptr; }))
+        c.plain = (uint32_t)(tri1 - tri0);
+    for (size_t m = 0; m < ip.meshes.size(); ++m)
+        if (!ip.meshes[m].order.empty() && si.smooth_in_mesh((uint32_t)m)) c.inst = ip.counts.records;
+    if (int rc = w.allocate_smooth(c)) return rc;
+    std::vector<R> host(((size_t)c.plain + c.inst) * kSmoothReals, (R)0);
+    if (c.plain)
+        for (size_t i = 0; i < list_normals.size(); ++i)
+            if (list_normals[i]) {
+                const int32_t slot = ip.slot_of[i] & 0xFFFFFF;
+                if (slot < tri0 || slot >= tri1) return set_error(RT_ERR_INVALID, "smooth triangle outside the triangle run");
+                for (int q = 0; q < kSmoothReals; ++q) host[(size_t)(slot - tri0) * kSmoothReals + q] = (R)list_normals[i][q];
+            }
+    if (c.inst)
+        for (size_t m = 0; m < ip.meshes.size(); ++m) {
+            const inst::MeshPlan& mp = ip.meshes[m];
+            const ident::Normals N = si.of_mesh((uint32_t)m);
+            for (uint32_t at = 0; N && at < mp.order.size(); ++at)
+                if (const double* n = N[mp.order[at]])
+                    for (int q = 0; q < kSmoothReals; ++q)
+                        host[((size_t)c.plain + ip.rec_begin[m] + at) * kSmoothReals + q] = (R)n[q];
+        }
+    if (host.empty()) return RT_OK;
+    const int rc = hip_status(hipMemcpyAsync(w.smooth.get(), host.data(), host.size() * sizeof(R), hipMemcpyHostToDevice,
+                                             ctx->stream), "hipMemcpyAsync");
+    const int rs = hip_status(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");  // (host temporary)
+    return rc ? rc : rs;
+}
 }  // namespace
 
 int build_scene(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns, const rt_material_desc* mats, uint32_t nm,
                 const rt_pattern_desc* pats, uint32_t np, const rt_light_desc* lights, uint32_t nl) {
     ctx->instance_info = rt_instance_info{};
-    if (walked_instances(ctx->w32)) std::fill(std::begin(ctx->occ_blocks), std::end(ctx->occ_blocks), 0);  // other kernels now
+    ctx->smooth_info = rt_smooth_info{};
+    ctx->smooth_shape.clear();
+    if (instance_build(ctx->w32)) std::fill(std::begin(ctx->occ_blocks), std::end(ctx->occ_blocks), 0);  // other kernels now
     ctx->w32.inst_counts = ctx->w64.inst_counts = InstanceCounts{};
+    ctx->w32.smooth_counts = ctx->w64.smooth_counts = SmoothCounts{};
     return build_plain_tables(ctx, shapes, ns, mats, nm, pats, np, lights, nl, WorldIndices{}, false);
 }
 
 int build_scene_instanced(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns, const rt_mesh_desc* meshes,
                           uint32_t n_meshes, const rt_instance_desc* instances, uint32_t n_inst,
                           const rt_material_desc* mats, uint32_t nm, const rt_pattern_desc* pats, uint32_t np,
-                          const rt_light_desc* lights, uint32_t nl) {
-    if (!n_inst) return build_scene(ctx, shapes, ns, mats, nm, pats, np, lights, nl);  // rt_scene_upload itself
+                          const rt_light_desc* lights, uint32_t nl, const rt_smooth_desc* smooth, uint32_t n_smooth) {
+    // (a world with a smooth triangle takes the general path whatever its instances: it runs the instance build)
+    if (!n_inst && !n_smooth) return build_scene(ctx, shapes, ns, mats, nm, pats, np, lights, nl);  // rt_scene_upload itself
     int rc;
     const auto t0 = std::chrono::steady_clock::now();
+    const inst::SmoothIndex si = inst::smooth_index(ns, meshes, n_meshes, smooth, n_smooth);
     InstancePlan ip;
-    ip.expanded = inst::decide_expanded(shapes, ns, meshes, n_meshes, instances, n_inst, mats, pats);
+    ip.expanded = inst::decide_expanded(shapes, ns, meshes, n_meshes, instances, n_inst, mats, pats, n_smooth ? &si : nullptr);
     ip.bases = inst::world_bases(ns, meshes, instances, n_inst);
     // the plain list: the shapes, then the triangles of the instances uploaded expanded
     std::vector<rt_shape_desc> list(shapes, shapes + ns);
     std::vector<uint32_t> index(ns);
     for (uint32_t i = 0; i < ns; ++i) index[i] = i;
+    std::vector<const double*> list_normals(ns, nullptr);  // by entry of the plain list: a smooth triangle's normals
+    for (uint32_t i = 0; i < (uint32_t)si.plain.size(); ++i) list_normals[i] = si.plain[i];
+    uint32_t smooth_triangles = (uint32_t)std::count_if(list_normals.begin(), list_normals.end(),
+                                                        [](const double* p) { return p != nullptr; });
+    for (uint32_t k = 0; k < n_inst; ++k) smooth_triangles += si.smooth_in_mesh(instances[k].mesh);
     ip.list_begin.assign(n_inst, 0);
     ip.expanded_pos.assign(n_inst, 0);
     uint32_t n_expanded = 0, walked_triangles = 0;
@@ -1703,9 +1795,12 @@ int build_scene_instanced(rt_context* ctx, const rt_shape_desc* shapes, uint32_t
         ip.list_begin[k] = (uint32_t)list.size();
         list.resize(list.size() + mesh.n_triangles);
         inst::expand_instance(mesh, instances[k], list.data() + ip.list_begin[k]);
-        for (uint32_t j = 0; j < mesh.n_triangles; ++j) index.push_back(ip.bases[k] + j);
+        for (uint32_t j = 0; j < mesh.n_triangles; ++j) {
+            index.push_back(ip.bases[k] + j);
+            list_normals.push_back(ident::normals_of(si.of_mesh(instances[k].mesh), j));
+        }
     }
-    if (n_expanded == n_inst) {
+    if (n_expanded == n_inst && !n_smooth) {
         // every instance has a value-equal partner: the plain list is the
         // expansion, uploaded as rt_scene_upload would (per-scene builds included)
         if ((rc = build_scene(ctx, list.data(), (uint32_t)list.size(), mats, nm, pats, np, lights, nl))) return rc;
@@ -1742,13 +1837,23 @@ int build_scene_instanced(rt_context* ctx, const rt_shape_desc* shapes, uint32_t
     wi.index = index.data();
     wi.n_plain = ns;
     wi.slot_of = &ip.slot_of;
+    wi.normals = n_smooth ? list_normals.data() : nullptr;
     if ((rc = build_plain_tables(ctx, list.data(), (uint32_t)list.size(), mats, nm, pats, np, lights, nl, wi, true)))
         return rc;
     ctx->have_scene = false;
-    if (!walked_instances(ctx->w32)) std::fill(std::begin(ctx->occ_blocks), std::end(ctx->occ_blocks), 0);  // other kernels now
-    if ((rc = upload_instances<float>(ctx, ctx->w32, ip, meshes, instances, n_inst, mats)) ||
-        (rc = upload_instances<double>(ctx, ctx->w64, ip, meshes, instances, n_inst, mats)))
+    if (!instance_build(ctx->w32)) std::fill(std::begin(ctx->occ_blocks), std::end(ctx->occ_blocks), 0);  // other kernels now
+    const inst::SmoothIndex* const sip = n_smooth ? &si : nullptr;
+    if ((rc = upload_instances<float>(ctx, ctx->w32, ip, meshes, instances, n_inst, mats, sip)) ||
+        (rc = upload_instances<double>(ctx, ctx->w64, ip, meshes, instances, n_inst, mats, sip)) ||
+        (rc = upload_smooth<float>(ctx, ctx->w32, list_normals, ip, si)) ||
+        (rc = upload_smooth<double>(ctx, ctx->w64, list_normals, ip, si)))
         return rc;
+    ctx->smooth_info = rt_smooth_info{};
+    ctx->smooth_info.smooth_triangles = smooth_triangles;
+    ctx->smooth_info.normal_bytes = ((uint64_t)ctx->w32.smooth_counts.plain + ctx->w32.smooth_counts.inst) * kSmoothReals *
+                                    (sizeof(float) + sizeof(double));
+    ctx->smooth_shape.assign(n_smooth ? ns : 0, 0);
+    for (uint32_t i = 0; i < (uint32_t)si.plain.size(); ++i) ctx->smooth_shape[i] = si.plain[i] != nullptr;
     // what the expansion's other tables would have come to: the triangle tests
     // of the flop model, and the brightness bound (a TestPattern's reach is
     // the object-space extent of the mesh, whatever the placement)
@@ -2314,6 +2419,9 @@ int debug_shape(rt_context* ctx, uint32_t shape, uint32_t mode, const double* in
     if (!in || !out) return set_error(RT_ERR_INVALID, "null input or output");
     if (precision > RT_PRECISION_F64) return set_error(RT_ERR_INVALID, "unknown precision");
     if (shape >= ctx->world_slot.size()) return set_error(RT_ERR_INVALID, "shape index out of range");
+    if (mode == 1 && shape < ctx->smooth_shape.size() && ctx->smooth_shape[shape])
+        return set_error(RT_ERR_INVALID, "rt_debug_normal: a smooth triangle's normal depends on the hit's u and v, "
+                                         "which a point does not give");
     if (n == 0) return RT_OK;
     if (n > 0xFFFFFFFFull) return set_error(RT_ERR_INVALID, "too many rays");
     RT_HIP(hipSetDevice(ctx->device));

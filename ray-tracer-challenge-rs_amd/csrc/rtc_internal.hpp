@@ -292,6 +292,13 @@ constexpr int32_t kShapeSimilar = 4;
 // over the axis's scale) and tri[9..11] the scale's signs, and the f32
 // kernels run its slab test in world space (rtc_kernels.hip cube_world).
 constexpr int32_t kShapeAxisAligned = 8;
+// A smooth triangle (rtc.h rt_scene_upload_smooth): its three vertex normals
+// are entry `slot - kind_begin[RT_SHAPE_TRIANGLE]` of LaunchParams::
+// smooth_plain (a record of the shape table) or entry `position` of
+// smooth_inst (a mesh's local record at that position of inst_shapes), nine
+// reals each.  Only the instance build's prepare_hit reads the bit.
+constexpr int32_t kShapeSmooth = 16;
+constexpr int kSmoothReals = 9;  // n1, n2, n3
 constexpr int kShapeClassShift = 8;
 
 template <typename R>
@@ -539,6 +546,13 @@ struct LaunchParams {
     const ShapeRec<R>* inst_shapes;    // every mesh's local records
     const TriNode<R>* inst_nodes;      // every mesh's hierarchy
     const int32_t* inst_pos;           // InstRec::pos_begin
+    // Smooth triangles (rt_scene_upload_smooth; null for every other world):
+    // the vertex normals of the triangle run and of the meshes' local records,
+    // dense and parallel to them (kShapeSmooth; a flat triangle's entry is
+    // never read).  Read per lane, once per shaded hit on a smooth triangle,
+    // by the instance build's prepare_hit; no other kernel loads them.
+    const R* smooth_plain;
+    const R* smooth_inst;
 };
 
 }  // namespace rtc

@@ -349,6 +349,31 @@ __device__ inline R sel(bool c, R a, R b) {
     return c ? a : b;
 }
 
+// Triangle::local_intersect (triangle.rs:39-56) on a local ray: the entry's t,
+// whether the reference pushes it, and the two barycentric values the
+// decision compared.  One definition for entries<RT_SHAPE_TRIANGLE> and for
+// the smooth triangle's normal (prepare_hit), which interpolates with the
+// bits the hit was accepted with.
+template <typename R>
+struct TriangleTest {
+    R t, u, v;
+    bool valid;
+};
+template <typename R>
+__device__ inline TriangleTest<R> triangle_test(const ShapeRec<R>& s, V3<R> o, V3<R> d) {
+    using T = Real<R>;
+    const V3<R> e1 = {s.tri[3], s.tri[4], s.tri[5]};
+    const V3<R> e2 = {s.tri[6], s.tri[7], s.tri[8]};
+    const V3<R> dce2 = cross(d, e2);
+    const R det = dot(e1, dce2);
+    const V3<R> v1o = vsub(o, V3<R>{s.tri[0], s.tri[1], s.tri[2]});
+    const R u = T::div(dot(v1o, dce2), det);
+    const V3<R> oce1 = cross(v1o, e1);
+    const R v = T::div(dot(d, oce1), det);
+    return {T::div(dot(e2, oce1), det), u, v,
+            !(T::fabs(det) < T::kEps) && (u >= (R)0 && u <= (R)1) && v > (R)0 && u + v < (R)1};
+}
+
 // kNearest: the caller only wants the nearest t >= 0 of this shape (the
 // closest-hit loop).  For a sphere or cube the two entries satisfy t1 <= t2
 // with one validity, so t2 can only be that t when t1 < 0: emit one
@@ -449,16 +474,8 @@ __device__ inline void entries(const ShapeRec<R>& s, V3<R> o, V3<R> d, F&& emit)
         z = T::rfma(d.z, t, o.z);
         emit(t, caps && x * x + z * z <= r_hi);
     } else {  // triangle.rs:39-56
-        const V3<R> e1 = {s.tri[3], s.tri[4], s.tri[5]};
-        const V3<R> e2 = {s.tri[6], s.tri[7], s.tri[8]};
-        const V3<R> dce2 = cross(d, e2);
-        const R det = dot(e1, dce2);
-        const V3<R> v1o = vsub(o, V3<R>{s.tri[0], s.tri[1], s.tri[2]});
-        const R u = T::div(dot(v1o, dce2), det);
-        const V3<R> oce1 = cross(v1o, e1);
-        const R v = T::div(dot(d, oce1), det);
-        emit(T::div(dot(e2, oce1), det),
-             !(T::fabs(det) < T::kEps) && (u >= (R)0 && u <= (R)1) && v > (R)0 && u + v < (R)1);
+        const TriangleTest<R> q = triangle_test(s, o, d);
+        emit(q.t, q.valid);
     }
 }
 
@@ -1921,7 +1938,7 @@ __device__ inline const MaterialRec<R>& prepare_hit(const DevScene<R>& sc, V3<R>
     }
 #endif
 #if !defined(RTC_JIT) && RTC_INSTANCES
-    if (kernarg_params<R>().n_instances) {  // wave-uniform (launch parameters)
+    if (kernarg_params<R>().n_instances || kernarg_params<R>().smooth_plain) {  // wave-uniform (launch parameters)
         // A world with mesh instances: a virtual triangle's record is put
         // together from its instance (inverse, material) and the mesh's local
         // record (the normal), the expansion's record field by field, so the
@@ -1934,7 +1951,23 @@ __device__ inline const MaterialRec<R>& prepare_hit(const DevScene<R>& sc, V3<R>
         const int material = *(virt ? &I->material : &g->material);
         const int kind = h.kind & 0xFF;
         q.p = along(o, d, h.t);
-        q.n = normalized(xform_normal(inv, local_normal(*g, kind, xform_point(inv, q.p))));  // normal_at
+        V3<R> ln;
+        if (kind == RT_SHAPE_TRIANGLE && (g->flags & kShapeSmooth)) {
+            // A smooth triangle (rtc.h rt_scene_upload_smooth): the triangle
+            // test once more on this one record with the lane's local ray, as
+            // the walk formed it, for the u and v the hit was accepted with;
+            // then n2 u + n3 v + n1 (1 - u - v), left to right, plain
+            // multiplies and adds.  Nine per-lane loads, once per shaded hit.
+            const R* const nn = virt ? P.smooth_inst + (size_t)h.slot * kSmoothReals
+                                     : P.smooth_plain + (size_t)(h.slot - sc.kind_begin[RT_SHAPE_TRIANGLE]) * kSmoothReals;
+            const TriangleTest<R> b = triangle_test(*g, xform_point(inv, o), xform_vector(inv, d));
+            const R w = ((R)1 - b.u) - b.v;
+            ln = {(nn[3] * b.u + nn[6] * b.v) + nn[0] * w, (nn[4] * b.u + nn[7] * b.v) + nn[1] * w,
+                  (nn[5] * b.u + nn[8] * b.v) + nn[2] * w};
+        } else {
+            ln = local_normal(*g, kind, xform_point(inv, q.p));
+        }
+        q.n = normalized(xform_normal(inv, ln));  // normal_at
         q.eye = vneg(d);
         if (dot(q.n, q.eye) < (R)0) q.n = vneg(q.n);
         q.mat = material;

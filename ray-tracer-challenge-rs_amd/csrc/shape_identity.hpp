@@ -56,13 +56,26 @@ inline bool material_eq(const rt_material_desc* M, const rt_pattern_desc* P, int
            (m.casts_shadow != 0) == (n.casts_shadow != 0) && pattern_eq(P, m.pattern, n.pattern);
 }
 
+// Smooth triangles (rtc.h rt_scene_upload_smooth) carry nine more values, the
+// vertex normals: `Normals` gives, per shape of a list, its nine doubles or
+// null for a flat shape (a null table: every shape is flat).  Two smooth
+// triangles are equal iff their flat parts and all nine components are; a
+// smooth and a flat triangle never are (another concrete type).
+using Normals = const double* const*;
+inline const double* normals_of(Normals N, uint32_t i) { return N ? N[i] : nullptr; }
+inline bool normals_eq(const double* a, const double* b) {
+    if (!a || !b) return !a && !b;
+    return reals_eq(a, b, 9);
+}
+
 // dyn Shape equality (shape.rs:34-38): same kind, then the derived field-wise
 // equality of that kind.  A triangle's vertex_2/vertex_3 are not in the
 // descriptor; they are compared through vertex_1 + edges.
 inline bool shape_eq(const rt_shape_desc* S, const rt_material_desc* M, const rt_pattern_desc* P, uint32_t a,
-                     uint32_t b) {
+                     uint32_t b, Normals N = nullptr) {
     if (a == b) return true;
     const rt_shape_desc &x = S[a], &y = S[b];
+    if (!normals_eq(normals_of(N, a), normals_of(N, b))) return false;
     if (x.kind != y.kind || !reals_eq(x.inverse, y.inverse, 16)) return false;
     if (x.kind == RT_SHAPE_CYLINDER || x.kind == RT_SHAPE_CONE)
         if (!(x.minimum == y.minimum && x.maximum == y.maximum && (x.closed != 0) == (y.closed != 0))) return false;
@@ -75,7 +88,7 @@ inline bool shape_eq(const rt_shape_desc* S, const rt_material_desc* M, const rt
 
 // Hash consistent with shape_eq's geometry part (-0 and +0 hash alike);
 // materials are compared exactly within a bucket.
-inline uint64_t geometry_hash(const rt_shape_desc& s) {
+inline uint64_t geometry_hash(const rt_shape_desc& s, const double* normals = nullptr) {
     uint64_t h = 1469598103934665603ull ^ (uint64_t)(uint32_t)s.kind;
     auto mix = [&h](double v) {
         if (v == 0.0) v = 0.0;  // -0 == +0
@@ -95,6 +108,8 @@ inline uint64_t geometry_hash(const rt_shape_desc& s) {
         for (double v : s.vertex_1) mix(v);
         for (double v : s.edge_1) mix(v);
         for (double v : s.edge_2) mix(v);
+        if (normals)
+            for (int q = 0; q < 9; ++q) mix(normals[q]);
     }
     return h;
 }
@@ -103,15 +118,15 @@ inline uint64_t geometry_hash(const rt_shape_desc& s) {
 // for a shape equal to no earlier one).  Returns the number of shapes that
 // equal an earlier one.
 inline uint32_t shape_classes(const rt_shape_desc* S, uint32_t n, const rt_material_desc* M,
-                              const rt_pattern_desc* P, std::vector<uint32_t>& cls) {
+                              const rt_pattern_desc* P, std::vector<uint32_t>& cls, Normals N = nullptr) {
     cls.resize(n);
     std::unordered_map<uint64_t, std::vector<uint32_t>> buckets;  // hash -> class representatives
     uint32_t dups = 0;
     for (uint32_t i = 0; i < n; ++i) {
         cls[i] = i;
-        auto& reps = buckets[geometry_hash(S[i])];
+        auto& reps = buckets[geometry_hash(S[i], normals_of(N, i))];
         for (uint32_t r : reps)
-            if (shape_eq(S, M, P, r, i)) {
+            if (shape_eq(S, M, P, r, i, N)) {
                 cls[i] = r;
                 ++dups;
                 break;

@@ -27,7 +27,7 @@ import numpy as np
 __all__ = [
     "RenderError", "lib_path", "abi_version", "device_count", "matrix_inverse", "camera_make",
     "camera_resize", "camera_set_transform", "camera_bound_rect", "load_scene", "load_scene_text", "SceneTables", "Context", "shard_rows",
-    "load_obj", "Mesh",
+    "load_obj", "Mesh", "SmoothDesc", "RT_SMOOTH_SHAPES", "RT_OBJ_NORMALS", "RT_NO_NORMAL",
     "RT_DEFAULT_MAX_DEPTH", "RT_TILE_H", "RT_TILE_W",
 ]
 
@@ -46,6 +46,9 @@ STATUS = {0: "RT_OK", -1: "RT_ERR_INVALID", -2: "RT_ERR_HIP", -3: "RT_ERR_NO_DEV
 RT_UNIQUE_ID_BYTES = 128
 RT_IPC_HANDLE_BYTES = 64
 RT_GATHER_RCCL, RT_GATHER_PEER = 0, 1
+RT_SMOOTH_SHAPES = 0xFFFFFFFF  # rt_smooth_desc.list: `index` counts the plain shapes
+RT_OBJ_NORMALS = 1             # rt_mesh_load_obj_ex: read vn lines and the faces' normal indices
+RT_NO_NORMAL = 0xFFFFFFFF      # rt_mesh_normals_view.triangle_normals of a flat face
 
 SHAPE_KINDS = {"sphere": 0, "plane": 1, "cube": 2, "cylinder": 3, "cone": 4, "triangle": 5}
 PATTERN_KINDS = {"stripe": 0, "gradient": 1, "ring": 2, "checker": 3, "complex": 4, "test": 5}
@@ -165,6 +168,20 @@ class InstanceInfo(C.Structure):
                 ("instanced_bytes", C.c_uint64), ("expansion_bytes", C.c_uint64), ("build_ms", C.c_double)]
 
 
+class SmoothDesc(C.Structure):
+    _fields_ = [("list", C.c_uint32), ("index", C.c_uint32), ("normal_1", C.c_double * 3),
+                ("normal_2", C.c_double * 3), ("normal_3", C.c_double * 3)]
+
+
+class SmoothInfo(C.Structure):
+    _fields_ = [("smooth_triangles", C.c_uint32), ("ran_smooth", C.c_uint32), ("normal_bytes", C.c_uint64)]
+
+
+class MeshNormalsView(C.Structure):
+    _fields_ = [("normals", C.POINTER(C.c_double)), ("n_normals", C.c_uint32), ("n_smooth", C.c_uint32),
+                ("triangle_normals", C.POINTER(C.c_uint32))]
+
+
 # --------------------------------------------------------------- library
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -242,6 +259,17 @@ def _load() -> C.CDLL:
         "rt_instances_expand": (C.c_int, [P(ShapeDesc), C.c_uint32, P(MeshDesc), C.c_uint32, P(InstanceDesc),
                                           C.c_uint32, P(ShapeDesc)]),
         "rt_scene_instance_info": (C.c_int, [C.c_void_p, P(InstanceInfo)]),
+        "rt_scene_upload_smooth": (C.c_int, [C.c_void_p, P(ShapeDesc), C.c_uint32, P(MeshDesc), C.c_uint32,
+                                             P(InstanceDesc), C.c_uint32, P(SmoothDesc), C.c_uint32,
+                                             P(MaterialDesc), C.c_uint32, P(PatternDesc), C.c_uint32, P(LightDesc),
+                                             C.c_uint32]),
+        "rt_smooth_expand": (C.c_int, [P(ShapeDesc), C.c_uint32, P(MeshDesc), C.c_uint32, P(InstanceDesc), C.c_uint32,
+                                       P(SmoothDesc), C.c_uint32, P(SmoothDesc), P(C.c_uint32)]),
+        "rt_scene_smooth_info": (C.c_int, [C.c_void_p, P(SmoothInfo)]),
+        "rt_mesh_load_obj_ex": (C.c_int, [C.c_char_p, C.c_char_p, C.c_uint32, P(C.c_void_p)]),
+        "rt_mesh_normals_get": (C.c_int, [C.c_void_p, P(MeshNormalsView)]),
+        "rt_mesh_smooth_normals": (C.c_int, [C.c_void_p, P(C.c_double), C.c_int, P(SmoothDesc), C.c_uint32,
+                                             P(C.c_uint32)]),
         "rt_image_write": (C.c_int, [C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint32]),
         "rt_image_write_format": (C.c_int, [C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int]),
         "rt_canvas_quantize": (C.c_int, [P(C.c_double), C.c_uint64, P(C.c_uint8)]),
@@ -304,6 +332,8 @@ EXPORTED_SYMBOLS = (
     "rt_mesh_load_obj", "rt_mesh_load_obj_text", "rt_mesh_view_get", "rt_mesh_free", "rt_mesh_triangles",
     "rt_scene_tree_info",
     "rt_scene_upload_instanced", "rt_instances_expand", "rt_scene_instance_info",
+    "rt_scene_upload_smooth", "rt_smooth_expand", "rt_scene_smooth_info",
+    "rt_mesh_load_obj_ex", "rt_mesh_normals_get", "rt_mesh_smooth_normals",
 )
 
 
@@ -441,10 +471,24 @@ class SceneTables:
     # identity inverse) and an array of InstanceDesc; None / empty = a plain world.
     meshes: list | None = None
     instances: C.Array | None = None
+    # Smooth triangles (rtc.h rt_scene_upload_smooth): an array of SmoothDesc naming triangles of `shapes`
+    # (list = RT_SMOOTH_SHAPES) or of a mesh, with their three vertex normals; None / empty = none.
+    smooth: C.Array | None = None
 
     @property
     def instanced(self) -> bool:
         return self.instances is not None and len(self.instances) > 0
+
+    @property
+    def smoothed(self) -> bool:
+        return self.smooth is not None and len(self.smooth) > 0
+
+    def smooth_args(self):
+        """rt_scene_upload_smooth's arguments after the context: instanced_args() with the smooth list
+        after the instances."""
+        a = self.instanced_args()
+        sm = self.smooth if self.smooth is not None else (SmoothDesc * 0)()
+        return a[:6] + (sm, len(sm)) + a[6:]
 
     def mesh_descs(self):
         """The MeshDesc array over `meshes` (it borrows their memory: keep the tables alive)."""
@@ -464,14 +508,22 @@ class SceneTables:
 
     def expanded(self) -> "SceneTables":
         """The flat world an instanced one means (rt_instances_expand): the shapes, then every instance's
-        triangles with its inverse and material; the other tables are shared.  A plain world: itself."""
+        triangles with its inverse and material; the other tables are shared.  A plain world: itself.
+        A smooth list is expanded with it (rt_smooth_expand): every entry then names a world index."""
         if not self.instanced:
             return self
         md, inst = self.mesh_descs(), self.instances
         total = len(self.shapes) + sum(len(self.meshes[i.mesh]) for i in inst if i.mesh < len(self.meshes))
         out = (ShapeDesc * total)()
         _check(_lib.rt_instances_expand(self.shapes, len(self.shapes), md, len(md), inst, len(inst), out))
-        return SceneTables(out, self.materials, self.patterns, self.lights, self.camera)
+        smooth = None
+        if self.smoothed:
+            n = C.c_uint32(0)
+            a = self.smooth_args()[:8]
+            _check(_lib.rt_smooth_expand(*a, None, C.byref(n)))
+            smooth = (SmoothDesc * n.value)()
+            _check(_lib.rt_smooth_expand(*a, smooth, C.byref(n)))
+        return SceneTables(out, self.materials, self.patterns, self.lights, self.camera, smooth=smooth)
 
     @property
     def counts(self):
@@ -530,6 +582,27 @@ class Mesh:
         self.triangles = np.ctypeslib.as_array(v.triangles, (v.n_triangles, 3)).copy() if v.n_triangles else \
             np.zeros((0, 3), dtype=np.uint32)
         self.ignored_lines = int(v.ignored_lines)
+        # load_obj(..., normals=True): the vn lines (k, 3) f64, per triangle its three 0-based normal
+        # indices (RT_NO_NORMAL x 3 for a flat face) and the number of smooth triangles; else empty / 0
+        nv = MeshNormalsView()
+        _check(_lib.rt_mesh_normals_get(self._h, C.byref(nv)))
+        self.normals = np.ctypeslib.as_array(nv.normals, (nv.n_normals, 3)).copy() if nv.n_normals else \
+            np.zeros((0, 3), dtype=np.float64)
+        self.triangle_normals = np.ctypeslib.as_array(nv.triangle_normals, (v.n_triangles, 3)).copy() \
+            if nv.triangle_normals and v.n_triangles else np.zeros((0, 3), dtype=np.uint32)
+        self.n_smooth = int(nv.n_smooth)
+
+    def smooth_descs(self, transform=None, bake: bool = False, list_index: int = RT_SMOOTH_SHAPES, first: int = 0):
+        """rt_mesh_smooth_normals: one SmoothDesc per smooth triangle, pairing with shape_descs(transform,
+        bake); `first` is added to every index (the triangles' position in their list)."""
+        out = (SmoothDesc * self.n_smooth)()
+        t = None if transform is None else (C.c_double * 16)(*np.asarray(transform, dtype=np.float64).reshape(16))
+        n = C.c_uint32(0)
+        _check(_lib.rt_mesh_smooth_normals(self._h, t, int(bool(bake)), out if self.n_smooth else None,
+                                           int(list_index), C.byref(n)))
+        for d in out:
+            d.index += first
+        return out
 
     def shape_descs(self, transform=None, bake: bool = False, material: int = 0):
         """rt_mesh_triangles: the faces as an array of ShapeDesc (Triangle::new per face)."""
@@ -547,11 +620,18 @@ class Mesh:
             pass
 
 
-def load_obj(path_or_text) -> Mesh:
+def load_obj(path_or_text, normals: bool = False) -> Mesh:
     """An OBJ file (a path: str without a newline, bytes or os.PathLike) or OBJ text (a str holding a
-    newline) -> Mesh.  Raises RenderError(RT_ERR_IO) with the line number for a bad v or f line."""
+    newline) -> Mesh.  Raises RenderError(RT_ERR_IO) with the line number for a bad v or f line.
+    normals=True also reads the vn lines and the faces' normal indices (Mesh.normals, triangle_normals,
+    n_smooth; rtc_scene.h rt_mesh_load_obj_ex)."""
     h = C.c_void_p()
-    if isinstance(path_or_text, str) and "\n" in path_or_text:
+    if normals:
+        if isinstance(path_or_text, str) and "\n" in path_or_text:
+            _check(_lib.rt_mesh_load_obj_ex(None, path_or_text.encode(), RT_OBJ_NORMALS, C.byref(h)))
+        else:
+            _check(_lib.rt_mesh_load_obj_ex(os.fsencode(path_or_text), None, RT_OBJ_NORMALS, C.byref(h)))
+    elif isinstance(path_or_text, str) and "\n" in path_or_text:
         _check(_lib.rt_mesh_load_obj_text(path_or_text.encode(), C.byref(h)))
     else:
         _check(_lib.rt_mesh_load_obj(os.fsencode(path_or_text), C.byref(h)))
@@ -677,11 +757,20 @@ class Context:
         _check(_lib.rt_scene_instance_info(self._h, C.byref(t)))
         return {name: getattr(t, name) for name, _ in t._fields_}
 
+    def smooth_info(self) -> dict:
+        """The uploaded world's smooth triangles (rtc.h rt_scene_smooth_info): how many, the device bytes of
+        the normal tables, whether the last launch ran the kernels that interpolate them."""
+        t = SmoothInfo()
+        _check(_lib.rt_scene_smooth_info(self._h, C.byref(t)))
+        return {name: getattr(t, name) for name, _ in t._fields_}
+
     def upload(self, scene: SceneTables | None) -> None:
-        """rt_scene_upload, or rt_scene_upload_instanced for tables with instances; on a non-zero rank of a
-        group, None (the scene comes from rank 0)."""
+        """rt_scene_upload, rt_scene_upload_instanced for tables with instances, or rt_scene_upload_smooth for
+        tables with smooth triangles; on a non-zero rank of a group, None (the scene comes from rank 0)."""
         if scene is None:
             _check(_lib.rt_scene_upload(self._h, None, 0, None, 0, None, 0, None, 0))
+        elif scene.smoothed:
+            _check(_lib.rt_scene_upload_smooth(self._h, *scene.smooth_args()))
         elif scene.instanced:
             _check(_lib.rt_scene_upload_instanced(self._h, *scene.instanced_args()))
         else:

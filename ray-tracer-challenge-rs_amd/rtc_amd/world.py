@@ -20,8 +20,8 @@ import ctypes as C
 import math
 from dataclasses import dataclass, field
 
-from . import (CameraDesc, InstanceDesc, LightDesc, MaterialDesc, PatternDesc, PATTERN_KINDS, SceneTables, ShapeDesc,
-               SHAPE_KINDS, camera_make, matrix_inverse)
+from . import (CameraDesc, InstanceDesc, LightDesc, MaterialDesc, PatternDesc, PATTERN_KINDS, RT_SMOOTH_SHAPES,
+               SceneTables, ShapeDesc, SHAPE_KINDS, SmoothDesc, camera_make, matrix_inverse)
 
 F64_MAX = 1.7976931348623157e308
 IDENTITY = [[1.0 if i == j else 0.0 for j in range(4)] for i in range(4)]
@@ -151,6 +151,7 @@ class Shape:
     maximum: float = F64_MAX
     closed: bool = False
     triangle: tuple | None = None  # (v1, e1, e2, normal)
+    normals: tuple | None = None   # a smooth triangle's (n1, n2, n3), used as given; None: flat
 
     def set_transformation(self, m):
         self.transformation_inverse = inverse(m)
@@ -208,10 +209,19 @@ def triangle(p1, p2, p3, material=None):
     return Shape("triangle", material or Material(), triangle=(tuple(map(float, p1)), e1, e2, n))
 
 
-def mesh(m, material=None, transform=None, bake=False):
+def smooth_triangle(p1, p2, p3, n1, n2, n3, material=None):
+    """The book's smooth triangle: triangle(p1, p2, p3) with the vertex normals n1, n2, n3 of p1, p2, p3, used
+    as given (rtc.h rt_scene_upload_smooth): the normal at a hit is n2 u + n3 v + n1 (1 - u - v)."""
+    s = triangle(p1, p2, p3, material)
+    s.normals = tuple(tuple(map(float, n)) for n in (n1, n2, n3))
+    return s
+
+
+def mesh(m, material=None, transform=None, bake=False, smooth=False):
     """The faces of a Mesh (rtc_amd.load_obj) as Triangle shapes sharing `material`, through the host's
     rt_mesh_triangles: Triangle::new per face; with `transform` either set_transformation on every triangle
-    (bake=False) or the vertices multiplied by it first (bake=True, identity inverse)."""
+    (bake=False) or the vertices multiplied by it first (bake=True, identity inverse).  smooth=True makes the
+    faces that name three normals (load_obj(..., normals=True)) smooth triangles; the others stay flat."""
     mat = material or Material()
     t = None if transform is None else [v for row in transform for v in row]
     out = []
@@ -219,6 +229,9 @@ def mesh(m, material=None, transform=None, bake=False):
         inv = [list(d.inverse[4 * i:4 * i + 4]) for i in range(4)]
         out.append(Shape("triangle", mat, transformation_inverse=inv,
                          triangle=(tuple(d.vertex_1), tuple(d.edge_1), tuple(d.edge_2), tuple(d.normal))))
+    if smooth:
+        for d in m.smooth_descs(t, bake):
+            out[d.index].normals = (tuple(d.normal_1), tuple(d.normal_2), tuple(d.normal_3))
     return out
 
 
@@ -229,12 +242,14 @@ class Instance:
     mesh: object
     material: Material = field(default_factory=Material)
     transformation_inverse: list = field(default_factory=lambda: [row[:] for row in IDENTITY])
+    smooth: bool = False  # the mesh's faces with three normals are smooth triangles (another mesh than its flat use)
 
 
-def instance(m, material=None, transform=None):
+def instance(m, material=None, transform=None, smooth=False):
     """A Mesh (rtc_amd.load_obj) placed by `transform` with `material`: an Instance for World.instances.
-    The device keeps the mesh's triangles once however many instances place it."""
-    i = Instance(m, material or Material())
+    The device keeps the mesh's triangles once however many instances place it.  smooth=True: the faces
+    that name three normals are smooth triangles and keep their local normals under the placement."""
+    i = Instance(m, material or Material(), smooth=smooth)
     if transform is not None:
         i.transformation_inverse = inverse(transform)
     return i
@@ -288,15 +303,18 @@ class World:
         # one material entry per shape, then one per instance
         mats = (MaterialDesc * (len(self.shapes) + len(self.instances)))()
         meshes, mesh_of, inst = [], [], (InstanceDesc * len(self.instances))()
+        smooth = []  # SmoothDesc entries: the meshes' in mesh order, then the shapes'
         for k, it in enumerate(self.instances):
             for j, seen in enumerate(mesh_of):
-                if seen is it.mesh:
+                if seen[0] is it.mesh and seen[1] == bool(it.smooth):
                     inst[k].mesh = j
                     break
             else:
                 inst[k].mesh = len(meshes)
-                mesh_of.append(it.mesh)
+                mesh_of.append((it.mesh, bool(it.smooth)))
                 meshes.append(it.mesh.shape_descs())  # local triangles: identity inverse
+                if it.smooth:
+                    smooth.extend(it.mesh.smooth_descs(list_index=inst[k].mesh))
             inst[k].material = len(self.shapes) + k
             inst[k].inverse[:] = [float(v) for row in it.transformation_inverse for v in row]
             put_material(mats[len(self.shapes) + k], it.material)
@@ -309,6 +327,10 @@ class World:
             if s.triangle:
                 d.vertex_1[:], d.edge_1[:], d.edge_2[:], d.normal[:] = [list(map(float, v)) for v in s.triangle]
             put_material(mats[i], s.material)
+            if s.normals is not None:
+                e = SmoothDesc(RT_SMOOTH_SHAPES, i)
+                e.normal_1[:], e.normal_2[:], e.normal_3[:] = [list(map(float, n)) for n in s.normals]
+                smooth.append(e)
         ptab = (PatternDesc * len(pats))()
         for i, p in enumerate(pats):
             d = ptab[i]
@@ -323,7 +345,8 @@ class World:
             lts[i].position[:] = list(map(float, lt.position))
             lts[i].intensity[:] = list(map(float, lt.intensity))
         return SceneTables(shapes, mats, ptab, lts, camera if camera is not None else CameraDesc(),
-                           meshes=meshes or None, instances=inst if len(inst) else None)
+                           meshes=meshes or None, instances=inst if len(inst) else None,
+                           smooth=(SmoothDesc * len(smooth))(*smooth) if smooth else None)
 
 
 def camera(width, height, fov, frm=(0, 0, 0), to=(0, 0, -1), up=(0, 1, 0)) -> CameraDesc:
