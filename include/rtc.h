@@ -85,7 +85,8 @@ typedef enum rt_pattern_kind {
     RT_PATTERN_RING = 2,     /* patterns/ring_pattern.rs     */
     RT_PATTERN_CHECKER = 3,  /* patterns/checker_pattern.rs  */
     RT_PATTERN_COMPLEX = 4,  /* patterns/complex_pattern.rs  */
-    RT_PATTERN_TEST = 5      /* patterns/pattern.rs:29-66    */
+    RT_PATTERN_TEST = 5,     /* patterns/pattern.rs:29-66    */
+    RT_PATTERN_IMAGE = 6     /* an image texture (rt_scene_upload_textured only; no reference) */
 } rt_pattern_kind;
 
 typedef enum rt_precision {
@@ -579,6 +580,119 @@ typedef struct rt_smooth_info {
     uint64_t normal_bytes;
 } rt_smooth_info;
 int rt_scene_smooth_info(rt_context* ctx, rt_smooth_info* out);
+
+/* Image textures (the book's bonus chapter "Texture
+ * mapping").  The reference has none of it, so this text is the contract.
+ *
+ * Texture: width x height RGB bytes, row 0 at the top, a host pointer read
+ * during the upload only.  Texel (x, y) has colour (R)byte / (R)255 per
+ * channel in the kernel's real type R (f64: (double)b / 255.0, an IEEE
+ * division).
+ *
+ * Image pattern: kind RT_PATTERN_IMAGE (6) of rt_pattern_desc, whose layout is
+ * untouched: sub_a = index into the upload's texture list, sub_b = -1,
+ * reserved = the filter (RT_FILTER_NEAREST 0, RT_FILTER_BILINEAR 1), color_a
+ * and color_b ignored, inverse = the pattern transform (planar map only).  It
+ * may be a material's pattern, never a sub-pattern of a complex pattern.
+ *
+ * (u, v) of a hit.  A triangle with texture coordinates t1, t2, t3 (of p1, p2,
+ * p3; the rt_uv_desc side list, built like rt_smooth_desc's):
+ *     uv = t2 * u_b + t3 * v_b + t1 * (1 - u_b - v_b)
+ * per component, left to right, plain multiplies and adds (no fused operation
+ * in the f64 path), u_b and v_b the two barycentric values
+ * Triangle::local_intersect compared for the accepted hit (the bits the
+ * smooth normal uses, from the one triangle test prepare_hit re-runs).  A
+ * component outside [0, 1] is wrapped by c - floor(c), one inside is used as
+ * is (exactly 1 stays 1).  The pattern's inverse is ignored for such hits, and
+ * an instanced mesh's triangles keep their coordinates under every placement.
+ * Any other hit (every shape kind, a triangle without coordinates included):
+ * the book's planar map of the pattern-space point
+ * pp = pattern.inverse * (shape.inverse * over_point), where the other
+ * pattern kinds sample: u = pp.x - floor(pp.x), v = pp.z - floor(pp.z).
+ *
+ * Sampling: x = u * (w - 1), y = (1 - v) * (h - 1) (the book's flip).
+ * Nearest: xi = floor(x) + (x - floor(x) >= 0.5 ? 1 : 0), the same for y
+ * (round half away from zero, written so both precisions decide alike; not
+ * floor(x + 0.5), not round-to-even).  Bilinear: x0 = floor(x),
+ * x1 = min(x0 + 1, w - 1), fx = x - x0, the same for y; per channel
+ *     (c00 * (1 - fx) + c10 * fx) * (1 - fy) + (c01 * (1 - fx) + c11 * fx) * fy
+ * with cXY the texel at (xX, yY), plain operations in that order.
+ * The sampled colour replaces the material's colour exactly where a pattern's
+ * does, once per hit; t, tie rules, normals, casts_shadow, bounding balls, the
+ * tree, the culls and the skips are untouched, and rt_stats.lit_patterned
+ * counts an image-patterned hit like any patterned hit.
+ *
+ * Value identity (the containers walk): two triangles with coordinates are
+ * equal iff their other parts and all six coordinate components are (== on
+ * doubles); one with and one without never are.  Two image patterns are equal
+ * iff their inverse, filter and textures' contents (width, height, bytes) are,
+ * whatever the textures' indices.  The brightness bound of an image pattern is
+ * its texture's largest channel / 255.
+ *
+ * rt_scene_upload_textured is rt_scene_upload_smooth's argument list plus the
+ * coordinate list and the texture list; with n_uvs = n_textures = 0 it is
+ * rt_scene_upload_smooth itself (which, like every older entry point, refuses
+ * pattern kind 6 as "unknown kind").  A world with an image pattern or a
+ * coordinate entry runs the generic kernels only, those of the texture build
+ * (the instance build plus the sampling code; rt_jit_status says so in its log).  rt_uv_expand pairs with
+ * rt_instances_expand / rt_smooth_expand (host only; out may be NULL to
+ * count).  RT_ERR_INVALID, each with its own rt_last_error text and checked
+ * before the context is looked at: a null list with a nonzero count, a list or
+ * triangle index out of range, a named record that is no triangle, the same
+ * triangle named twice, a coordinate that is not finite; a texture with null
+ * pixels, zero width or height, or width * height > 2^28; an image pattern
+ * with sub_a out of range, sub_b != -1, a filter other than 0 or 1, or used as
+ * a sub-pattern. */
+#define RT_FILTER_NEAREST 0
+#define RT_FILTER_BILINEAR 1
+#define RT_TEXTURE_MAX_TEXELS (1u << 28)
+typedef struct rt_texture_desc {
+    const uint8_t* rgb;   /* width * height * 3 bytes, row 0 at the top */
+    uint32_t width, height;
+} rt_texture_desc;
+typedef struct rt_uv_desc {   /* 56 bytes */
+    uint32_t list;    /* RT_SMOOTH_SHAPES: `index` counts the plain shapes; else an index into the mesh list */
+    uint32_t index;   /* the triangle in that list */
+    double uv_1[2], uv_2[2], uv_3[2];
+} rt_uv_desc;
+int rt_scene_upload_textured(rt_context* ctx,
+                             const rt_shape_desc* shapes, uint32_t n_shapes,
+                             const rt_mesh_desc* meshes, uint32_t n_meshes,
+                             const rt_instance_desc* instances, uint32_t n_instances,
+                             const rt_smooth_desc* smooth, uint32_t n_smooth,
+                             const rt_uv_desc* uvs, uint32_t n_uvs,
+                             const rt_texture_desc* textures, uint32_t n_textures,
+                             const rt_material_desc* materials, uint32_t n_materials,
+                             const rt_pattern_desc* patterns, uint32_t n_patterns,
+                             const rt_light_desc* lights, uint32_t n_lights);
+int rt_uv_expand(const rt_shape_desc* shapes, uint32_t n_shapes,
+                 const rt_mesh_desc* meshes, uint32_t n_meshes,
+                 const rt_instance_desc* instances, uint32_t n_instances,
+                 const rt_uv_desc* uvs, uint32_t n_uvs,
+                 rt_uv_desc* out, uint32_t* n_out);
+/* The textures of the last upload (zeros after any other upload): the
+ * triangles with coordinates as the world means them (an instance counts its
+ * mesh's once per placement), the texture count, the device bytes of both
+ * precisions' coordinate tables and of the texel storage (one packed RGBX
+ * dword per texel plus the per-texture table), and whether the last launch ran
+ * kernels that hold the texture code. */
+typedef struct rt_texture_info {
+    uint32_t textured_triangles;
+    uint32_t textures;
+    uint32_t ran_textured;
+    uint32_t reserved;
+    uint64_t uv_bytes;
+    uint64_t texel_bytes;
+} rt_texture_info;
+int rt_scene_texture_info(rt_context* ctx, rt_texture_info* out);
+/* Reads an image into width * height * 3 RGB bytes (row 0 at the top) that
+ * rt_image_free releases.  PPM P3 and P6: comments, any maxval <= 65535
+ * (samples scaled to bytes as round(v * 255 / maxval)), lines of any length.
+ * PNG (through zlib): 8-bit RGB or RGBA, non-interlaced, all five filter
+ * types; alpha is dropped.  Anything else is RT_ERR_IO with its own text.
+ * rt_image_read(rt_image_write(x)) == x for both formats.  Host only. */
+int rt_image_read(const char* path, uint8_t** rgb, uint32_t* width, uint32_t* height);
+void rt_image_free(uint8_t* rgb);
 
 /* Peer canvas: a frame assembled in place instead of gathered (SURVEY.md
  * §8e; the north star's "gather of framebuffer strips over xGMI" done as the

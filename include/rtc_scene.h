@@ -130,6 +130,38 @@ int rt_mesh_normals_get(const rt_mesh* mesh, rt_mesh_normals_view* view);
 int rt_mesh_smooth_normals(const rt_mesh* mesh, const double* transform, int bake, rt_smooth_desc* out,
                            uint32_t list, uint32_t* n_out);
 
+/* OBJ texture coordinates (image textures: rtc.h rt_scene_upload_textured).
+ * Under RT_OBJ_TEXCOORDS, which combines with RT_OBJ_NORMALS, rt_mesh_load_obj_ex
+ * also reads
+ *   vt u v [w]       a texture coordinate (u, v), kept as written (w is checked
+ *                    to be a number and dropped) and not counted in
+ *                    ignored_lines;
+ *   f i/j, i/j/k     the second index names the vertex's coordinate: 1-based,
+ *                    negative ones count back from the vt lines read so far.
+ * A face has coordinates iff every one of its vertices names one (i and i//k
+ * name none); the fan (1, k, k+1) carries each vertex's coordinate with it.
+ * RT_ERR_IO with the line number, each with its own text: a vt with fewer than
+ * two numbers, a vt with something that is not a number, a texture index that
+ * is no integer, a texture index out of range.  Without the flag nothing
+ * changes: vt lines are counted in ignored_lines.  The flag is 4, not 2:
+ * flags = 2 was the first unknown flag when RT_OBJ_NORMALS came, callers and
+ * tests were told it is refused, and it stays refused. */
+#define RT_OBJ_TEXCOORDS 4u
+#define RT_NO_TEXCOORD 0xFFFFFFFFu
+typedef struct rt_mesh_texcoords_view {
+    const double* texcoords;            /* n_texcoords x 2 */
+    uint32_t n_texcoords;
+    uint32_t n_textured;                /* triangles with three coordinates */
+    const uint32_t* triangle_texcoords; /* n_triangles x 3, 0-based; RT_NO_TEXCOORD x 3 for a face without */
+} rt_mesh_texcoords_view;
+/* all zero for a mesh loaded without RT_OBJ_TEXCOORDS */
+int rt_mesh_texcoords_get(const rt_mesh* mesh, rt_mesh_texcoords_view* view);
+/* One rt_uv_desc per triangle with coordinates, in triangle order, with `list`
+ * as given and index = the triangle's index in the mesh, like
+ * rt_mesh_smooth_normals.  Coordinates do not transform, so there is no bake.
+ * out may be NULL to count; *n_out = the mesh's n_textured.  Host only. */
+int rt_mesh_uvs(const rt_mesh* mesh, rt_uv_desc* out, uint32_t list, uint32_t* n_out);
+
 /* Camera::new(width, height, fov) + set_transformation(view_transform(...)) */
 int rt_camera_make(uint32_t width, uint32_t height, double field_of_view,
                    const double from[3], const double to[3], const double up[3],

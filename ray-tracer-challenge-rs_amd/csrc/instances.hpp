@@ -359,9 +359,123 @@ inline uint32_t expand_smooth(uint32_t ns, const rt_mesh_desc* meshes, uint32_t 
     return at;
 }
 
+// ---- image textures (rtc.h rt_scene_upload_textured) --------------------------
+// Empty when the texture list is well formed, else the reason (RT_ERR_INVALID).
+inline std::string validate_textures(const rt_texture_desc* textures, uint32_t n_textures) {
+    if (n_textures && !textures) return "rt_scene_upload_textured: null texture list with nonzero count";
+    for (uint32_t k = 0; k < n_textures; ++k) {
+        const rt_texture_desc& t = textures[k];
+        const std::string who = "texture " + std::to_string(k);
+        if (!t.rgb) return who + ": null pixels";
+        if (!t.width || !t.height) return who + ": zero width or height";
+        if ((uint64_t)t.width * t.height > (uint64_t)RT_TEXTURE_MAX_TEXELS) return who + ": more than 2^28 texels";
+    }
+    return "";
+}
+// The coordinate list against validated instanced lists, as validate_smooth.
+inline std::string validate_uvs(const rt_shape_desc* shapes, uint32_t ns, const rt_mesh_desc* meshes, uint32_t n_meshes,
+                                const rt_uv_desc* uvs, uint32_t n_uvs) {
+    if (n_uvs && !uvs) return "rt_scene_upload_textured: null uv list with nonzero count";
+    std::vector<std::vector<char>> seen(n_meshes + 1);  // [n_meshes]: the plain shapes
+    for (uint32_t k = 0; k < n_uvs; ++k) {
+        const rt_uv_desc& d = uvs[k];
+        const std::string who = "uv entry " + std::to_string(k);
+        if (d.list != RT_SMOOTH_SHAPES && d.list >= n_meshes) return who + ": list index out of range";
+        const bool plain = d.list == RT_SMOOTH_SHAPES;
+        const uint32_t n = plain ? ns : meshes[d.list].n_triangles;
+        if (d.index >= n) return who + ": triangle index out of range";
+        const rt_shape_desc& t = plain ? shapes[d.index] : meshes[d.list].triangles[d.index];
+        if (t.kind != RT_SHAPE_TRIANGLE) return who + ": the named record is not a triangle";
+        std::vector<char>& s = seen[plain ? n_meshes : d.list];
+        if (s.empty()) s.assign(n, 0);
+        if (s[d.index]) return who + ": the same triangle is named twice";
+        s[d.index] = 1;
+        for (const double* c : {d.uv_1, d.uv_2, d.uv_3})
+            for (int q = 0; q < 2; ++q)
+                if (!std::isfinite(c[q])) return who + ": a texture coordinate is not finite";
+    }
+    return "";
+}
+static_assert(sizeof(rt_uv_desc) == 56 && offsetof(rt_uv_desc, uv_1) == 8 &&
+                  offsetof(rt_uv_desc, uv_3) == 8 + 4 * sizeof(double),
+              "the six coordinate components are contiguous");
+// The coordinates of a validated list by triangle, in SmoothIndex's form: the entry's six doubles or null.
+inline SmoothIndex uv_index(uint32_t ns, const rt_mesh_desc* meshes, uint32_t n_meshes, const rt_uv_desc* uvs,
+                            uint32_t n_uvs) {
+    SmoothIndex ui;
+    ui.mesh.resize(n_meshes);
+    for (uint32_t k = 0; k < n_uvs; ++k) {
+        const rt_uv_desc& d = uvs[k];
+        std::vector<const double*>& v = d.list == RT_SMOOTH_SHAPES ? ui.plain : ui.mesh[d.list];
+        if (v.empty()) v.assign(d.list == RT_SMOOTH_SHAPES ? ns : meshes[d.list].n_triangles, nullptr);
+        v[d.index] = d.uv_1;
+    }
+    return ui;
+}
+// The coordinate list of the expansion, as expand_smooth: coordinates do not transform.
+inline uint32_t expand_uvs(uint32_t ns, const rt_mesh_desc* meshes, uint32_t n_meshes, const rt_instance_desc* instances,
+                           uint32_t n_inst, const rt_uv_desc* uvs, uint32_t n_uvs, rt_uv_desc* out) {
+    const SmoothIndex ui = uv_index(ns, meshes, n_meshes, uvs, n_uvs);
+    uint32_t at = 0;
+    auto put = [&](uint32_t world, const double* c) {
+        if (out) {
+            out[at].list = RT_SMOOTH_SHAPES;
+            out[at].index = world;
+            std::memcpy(out[at].uv_1, c, 6 * sizeof(double));
+        }
+        ++at;
+    };
+    for (uint32_t i = 0; i < (uint32_t)ui.plain.size(); ++i)
+        if (ui.plain[i]) put(i, ui.plain[i]);
+    uint32_t base = ns;
+    for (uint32_t k = 0; k < n_inst; ++k) {
+        const uint32_t m = instances[k].mesh;
+        for (uint32_t j = 0; j < (uint32_t)ui.mesh[m].size(); ++j)
+            if (ui.mesh[m][j]) put(base + j, ui.mesh[m][j]);
+        base += meshes[m].n_triangles;
+    }
+    return at;
+}
+// Do two textures hold the same picture (width, height, bytes)?
+inline bool texture_eq(const rt_texture_desc& a, const rt_texture_desc& b) {
+    return a.width == b.width && a.height == b.height &&
+           (a.rgb == b.rgb || std::memcmp(a.rgb, b.rgb, (size_t)a.width * a.height * 3) == 0);
+}
+// Image patterns compare by their textures' contents (shape_identity.hpp pattern_eq) and bound the brightness by
+// their largest channel (scene_brightness).  Rewrites validated patterns in place: an image pattern's sub_a
+// becomes the smallest index of a texture with the same picture, whichever patterns name which textures and in
+// what order, and its color_a and color_b (ignored otherwise) the largest channel / 255.
+inline void canonical_image_patterns(rt_pattern_desc* pats, uint32_t np, const rt_texture_desc* textures,
+                                     uint32_t n_textures) {
+    std::vector<int32_t> first(n_textures, -1);
+    std::vector<double> top(n_textures, 0.0);
+    for (uint32_t i = 0; i < np; ++i) {
+        rt_pattern_desc& p = pats[i];
+        if (p.kind != RT_PATTERN_IMAGE) continue;
+        const uint32_t t = (uint32_t)p.sub_a;
+        if (first[t] < 0) {
+            first[t] = (int32_t)t;
+            for (uint32_t e = 0; e < t; ++e)  // (every earlier texture, named by a pattern or not)
+                if (texture_eq(textures[e], textures[t])) {
+                    first[t] = (int32_t)e;
+                    break;
+                }
+            const size_t n = (size_t)textures[t].width * textures[t].height * 3;
+            top[t] = (double)*std::max_element(textures[t].rgb, textures[t].rgb + n) / 255.0;
+        }
+        p.sub_a = first[t];
+        for (int q = 0; q < 3; ++q) p.color_a[q] = p.color_b[q] = top[t];
+    }
+}
+
 // expanded[k] = 1: instance k has a triangle value-equal to another triangle
 // of the expansion and is uploaded as plain records.  si: the world's smooth
 // triangles (null: none), whose normals are part of a triangle's value.
+// Texture coordinates are left out of the faces' comparison here: two faces
+// equal but for their coordinates make their instances partners, which are
+// then uploaded as plain records, where shape_classes does compare the
+// coordinates.  The decision errs towards expanding, never towards a wrong
+// identity class.
 inline std::vector<char> decide_expanded(const rt_shape_desc* shapes, uint32_t ns, const rt_mesh_desc* meshes,
                                          uint32_t n_meshes, const rt_instance_desc* instances, uint32_t n_inst,
                                          const rt_material_desc* mats, const rt_pattern_desc* pats,

@@ -25,6 +25,11 @@ struct rt_mesh {
     std::vector<uint32_t> triangle_normals;  // three 0-based normal indices per triangle, RT_NO_NORMAL x 3: a flat face
     uint32_t n_smooth = 0;
     bool with_normals = false;
+    // RT_OBJ_TEXCOORDS loads; empty otherwise
+    std::vector<double> texcoords;             // u, v per vt line (a third component is read and dropped)
+    std::vector<uint32_t> triangle_texcoords;  // three 0-based vt indices per triangle, RT_NO_TEXCOORD x 3: none
+    uint32_t n_textured = 0;
+    bool with_texcoords = false;
 };
 
 namespace rtc {
@@ -91,9 +96,30 @@ uint32_t parse_normal_index(const std::string& w, size_t n_normals, size_t line_
     return (uint32_t)at;
 }
 
+// the texture index of a face word (i/j, i/j/k), 0-based; RT_NO_TEXCOORD for a word without one (i, i//k)
+uint32_t parse_texcoord_index(const std::string& w, size_t n_texcoords, size_t line_no) {
+    const size_t s1 = w.find('/');
+    if (s1 == std::string::npos) return RT_NO_TEXCOORD;
+    const size_t s2 = w.find('/', s1 + 1);
+    const std::string mid = w.substr(s1 + 1, s2 == std::string::npos ? std::string::npos : s2 - s1 - 1);
+    if (mid.empty()) return RT_NO_TEXCOORD;
+    char* end = nullptr;
+    errno = 0;
+    const long long i = std::strtoll(mid.c_str(), &end, 10);
+    if (end != mid.c_str() + mid.size() || errno == ERANGE)
+        throw ObjError{"line " + std::to_string(line_no) + ": '" + w + "' is not a texture index"};
+    const long long at = i > 0 ? i - 1 : (long long)n_texcoords + i;  // negative: back from the vt lines so far
+    if (i == 0 || at < 0 || at >= (long long)n_texcoords)
+        throw ObjError{"line " + std::to_string(line_no) + ": texture index " + std::to_string(i) + " out of range (" +
+                       std::to_string(n_texcoords) + " texture coordinates so far)"};
+    return (uint32_t)at;
+}
+
 void parse_obj(const std::string& text, rt_mesh& m, uint32_t flags = 0) {
     const bool with_normals = (flags & RT_OBJ_NORMALS) != 0;
+    const bool with_texcoords = (flags & RT_OBJ_TEXCOORDS) != 0;
     m.with_normals = with_normals;
+    m.with_texcoords = with_texcoords;
     size_t pos = 0, line_no = 0;
     while (pos < text.size()) {
         size_t eol = text.find('\n', pos);
@@ -108,13 +134,17 @@ void parse_obj(const std::string& text, rt_mesh& m, uint32_t flags = 0) {
             for (int q = 1; q <= 3; ++q) m.vertices.push_back(parse_real(w[q], line_no));
         } else if (!w.empty() && w[0] == "f") {
             if (w.size() < 4) throw ObjError{"line " + std::to_string(line_no) + ": a face needs three vertices"};
-            std::vector<uint32_t> idx, nidx;
-            bool smooth = with_normals;
+            std::vector<uint32_t> idx, nidx, tidx;
+            bool smooth = with_normals, mapped = with_texcoords;
             for (size_t q = 1; q < w.size(); ++q) {
                 idx.push_back(parse_index(w[q], m.vertices.size() / 3, line_no));
                 if (with_normals) {
                     nidx.push_back(parse_normal_index(w[q], m.normals.size() / 3, line_no));
                     smooth = smooth && nidx.back() != RT_NO_NORMAL;  // every vertex names one, or the face is flat
+                }
+                if (with_texcoords) {
+                    tidx.push_back(parse_texcoord_index(w[q], m.texcoords.size() / 2, line_no));
+                    mapped = mapped && tidx.back() != RT_NO_TEXCOORD;  // every vertex names one, or the face has none
                 }
             }
             for (size_t k = 1; k + 1 < idx.size(); ++k) {  // the fan (1, k, k + 1)
@@ -127,6 +157,12 @@ void parse_obj(const std::string& text, rt_mesh& m, uint32_t flags = 0) {
                     m.triangle_normals.push_back(smooth ? nidx[k + 1] : RT_NO_NORMAL);
                     m.n_smooth += smooth ? 1u : 0u;
                 }
+                if (with_texcoords) {
+                    m.triangle_texcoords.push_back(mapped ? tidx[0] : RT_NO_TEXCOORD);
+                    m.triangle_texcoords.push_back(mapped ? tidx[k] : RT_NO_TEXCOORD);
+                    m.triangle_texcoords.push_back(mapped ? tidx[k + 1] : RT_NO_TEXCOORD);
+                    m.n_textured += mapped ? 1u : 0u;
+                }
             }
         } else if (with_normals && !w.empty() && w[0] == "vn") {
             if (w.size() < 4) throw ObjError{"line " + std::to_string(line_no) + ": a normal needs three components"};
@@ -136,6 +172,17 @@ void parse_obj(const std::string& text, rt_mesh& m, uint32_t flags = 0) {
                 if (w[q].empty() || end != w[q].c_str() + w[q].size())
                     throw ObjError{"line " + std::to_string(line_no) + ": '" + w[q] + "' is not a number in a normal"};
                 m.normals.push_back(v);
+            }
+        } else if (with_texcoords && !w.empty() && w[0] == "vt") {
+            if (w.size() < 3)
+                throw ObjError{"line " + std::to_string(line_no) + ": a texture coordinate needs two components"};
+            for (size_t q = 1; q < w.size() && q <= 3; ++q) {  // u v [w]: the third is checked and dropped
+                char* end = nullptr;
+                const double v = std::strtod(w[q].c_str(), &end);
+                if (w[q].empty() || end != w[q].c_str() + w[q].size())
+                    throw ObjError{"line " + std::to_string(line_no) + ": '" + w[q] +
+                                   "' is not a number in a texture coordinate"};
+                if (q <= 2) m.texcoords.push_back(v);
             }
         } else {
             ++m.ignored_lines;
@@ -194,7 +241,8 @@ int rt_mesh_load_obj(const char* path, rt_mesh** out) {
 int rt_mesh_load_obj_ex(const char* path, const char* text, uint32_t flags, rt_mesh** out) {
     if (!out || (path == nullptr) == (text == nullptr))
         return rtc::set_error(RT_ERR_INVALID, "rt_mesh_load_obj_ex: give a path or a text (one of the two) and an output");
-    if (flags & ~RT_OBJ_NORMALS) return rtc::set_error(RT_ERR_INVALID, "rt_mesh_load_obj_ex: unknown flag");
+    if (flags & ~(RT_OBJ_NORMALS | RT_OBJ_TEXCOORDS))
+        return rtc::set_error(RT_ERR_INVALID, "rt_mesh_load_obj_ex: unknown flag");
     return text ? rtc::load(text, out, flags) : rtc::load_file(path, out, flags);
 }
 
@@ -206,6 +254,37 @@ int rt_mesh_normals_get(const rt_mesh* m, rt_mesh_normals_view* v) {
     v->n_normals = (uint32_t)(m->normals.size() / 3);
     v->n_smooth = m->n_smooth;
     v->triangle_normals = m->triangle_normals.data();
+    return RT_OK;
+}
+
+int rt_mesh_texcoords_get(const rt_mesh* m, rt_mesh_texcoords_view* v) {
+    if (!m || !v) return rtc::set_error(RT_ERR_INVALID, "rt_mesh_texcoords_get: null argument");
+    *v = rt_mesh_texcoords_view{};
+    if (!m->with_texcoords) return RT_OK;
+    v->texcoords = m->texcoords.data();
+    v->n_texcoords = (uint32_t)(m->texcoords.size() / 2);
+    v->n_textured = m->n_textured;
+    v->triangle_texcoords = m->triangle_texcoords.data();
+    return RT_OK;
+}
+
+int rt_mesh_uvs(const rt_mesh* m, rt_uv_desc* out, uint32_t list, uint32_t* n_out) {
+    if (!m) return rtc::set_error(RT_ERR_INVALID, "rt_mesh_uvs: null argument");
+    if (n_out) *n_out = m->n_textured;
+    if (!out || !m->n_textured) return RT_OK;
+    uint32_t at = 0;
+    const size_t n = m->triangle_texcoords.size() / 3;
+    for (size_t t = 0; t < n; ++t) {
+        const uint32_t* k = &m->triangle_texcoords[3 * t];
+        if (k[0] == RT_NO_TEXCOORD) continue;
+        rt_uv_desc& d = out[at++];
+        std::memset(&d, 0, sizeof d);
+        d.list = list;
+        d.index = (uint32_t)t;
+        double* dst[3] = {d.uv_1, d.uv_2, d.uv_3};
+        for (int c = 0; c < 3; ++c)
+            for (int q = 0; q < 2; ++q) dst[c][q] = m->texcoords[2 * (size_t)k[c] + q];
+    }
     return RT_OK;
 }
 

@@ -20,8 +20,10 @@
 // the world goes up through rt_scene_upload_instanced),
 // --smooth (--obj and --instance read the files' vertex normals and the faces
 // that name three are smooth triangles: rt_scene_upload_smooth, DESIGN.md
-// §3.11; without it the output is what it was).  Pixels are quantized on the
-// device as canvas.rs:117-123 does.
+// §3.11; without it the output is what it was), --texture IMAGE.ppm|png with
+// --texture-filter nearest|bilinear (the --obj and --instance meshes' material
+// gets an image pattern and their vt lines are read: rt_scene_upload_textured,
+// DESIGN.md §3.12).  Pixels are quantized on the device as canvas.rs:117-123 does.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -38,12 +40,16 @@ static int usage() {
                  "usage: rtc <SCENE.yaml> <OUT.png|OUT.ppm> [-r serial|parallel|gpu] [-q] [--width W] [--height H]\n"
                  "           [--depth D] [--precision f32|f64] [--device N] [--gpus N] [--ppm-binary] [--timings]\n"
                  "           [--samples N] [--obj MESH.obj]... [--instance MESH.obj:tx,ty,tz[:s]]... [--smooth]\n"
+                 "           [--texture IMAGE.ppm|png] [--texture-filter nearest|bilinear]\n"
                  "  --obj MESH.obj appends the mesh's triangles (v and f lines; faces fan-triangulated) to the\n"
                  "  scene's shapes, with the default material and no transformation; repeatable.\n"
                  "  --instance MESH.obj:tx,ty,tz[:s] places a copy of the mesh, scaled by s (default 1) and moved by\n"
                  "  (tx, ty, tz), with the default material, after the shapes; repeatable, each file is read once.\n"
                  "  --smooth makes --obj and --instance read the files' vertex normals (vn lines, f i//k and i/j/k):\n"
                  "  a face whose vertices all name a normal is shaded with the interpolated normal.\n"
+                 "  --texture IMAGE.ppm|png gives the --obj and --instance meshes' material that image as its pattern\n"
+                 "  and reads the files' texture coordinates (vt lines, f i/j and i/j/k); a face without them is\n"
+                 "  mapped by its x and z.  --texture-filter nearest|bilinear picks the filter (default bilinear).\n"
                  "  --samples N renders N x N samples per pixel (1..%d, default 1 = one ray per pixel centre) and\n"
                  "  averages them on the GPU.\n"
                  "  -r serial|parallel are accepted for the reference's command lines but render on the GPU like\n"
@@ -93,6 +99,8 @@ int main(int argc, char** argv) {
     int device = 0, gpus = 1;
     uint32_t samples = 1;
     bool smooth = false;
+    const char* texture_path = nullptr;
+    int texture_filter = RT_FILTER_BILINEAR;
     std::vector<const char*> obj_paths;
     std::vector<Placement> placements;
     for (int i = 3; i < argc; ++i) {
@@ -102,6 +110,12 @@ int main(int argc, char** argv) {
         else if (a == "--ppm-binary") ppm_binary = true;
         else if (a == "--timings") timings = true;
         else if (a == "--smooth") smooth = true;
+        else if (a == "--texture") { texture_path = next(); if (!texture_path) return usage(); }
+        else if (a == "--texture-filter") {
+            const char* v = next();
+            if (!v || (std::strcmp(v, "nearest") && std::strcmp(v, "bilinear"))) return usage();
+            texture_filter = std::strcmp(v, "nearest") == 0 ? RT_FILTER_NEAREST : RT_FILTER_BILINEAR;
+        }
         else if (a == "-r" || a == "--rendering-mode") {
             const char* v = next();
             if (!v || (std::strcmp(v, "serial") && std::strcmp(v, "parallel") && std::strcmp(v, "gpu"))) return usage();
@@ -154,6 +168,31 @@ int main(int argc, char** argv) {
     // (material.rs:157-161) appended to the materials
     std::vector<rt_shape_desc> shapes(v.shapes, v.shapes + v.n_shapes);
     std::vector<rt_material_desc> materials(v.materials, v.materials + v.n_materials);
+    // --texture: the image, one more pattern after the scene's, and the meshes' texture coordinates
+    std::vector<rt_pattern_desc> patterns(v.patterns, v.patterns + v.n_patterns);
+    std::vector<rt_uv_desc> uv_list;
+    rt_texture_desc texture = {};
+    uint8_t* texture_rgb = nullptr;
+    if (texture_path && obj_paths.empty() && placements.empty()) {
+        std::fprintf(stderr, "error: --texture needs a mesh to show on: give --obj or --instance\n");
+        return usage();
+    }
+    const bool textured = texture_path != nullptr;
+    if (textured) {
+        if (rt_image_read(texture_path, &texture_rgb, &texture.width, &texture.height) != RT_OK) {
+            std::fprintf(stderr, "error: %s\n", rt_last_error());
+            return 1;
+        }
+        texture.rgb = texture_rgb;
+        rt_pattern_desc p = {};
+        p.kind = RT_PATTERN_IMAGE;
+        p.sub_a = 0;
+        p.sub_b = -1;
+        p.reserved = texture_filter;
+        for (int q = 0; q < 4; ++q) p.inverse[5 * q] = 1.0;
+        patterns.push_back(p);
+        if (!quiet) std::printf("%s: %u x %u texels\n", texture_path, texture.width, texture.height);
+    }
     if (!obj_paths.empty() || !placements.empty()) {
         rt_material_desc m = {};
         m.color[0] = m.color[1] = m.color[2] = 1.0;
@@ -163,12 +202,21 @@ int main(int argc, char** argv) {
         m.shininess = 200.0;
         m.refractive_index = 1.0;
         m.casts_shadow = 1;
-        m.pattern = -1;
+        m.pattern = textured ? (int32_t)patterns.size() - 1 : -1;
         materials.push_back(m);
     }
     // --smooth: the files' vertex normals, as rt_scene_upload_smooth's side list
     std::vector<rt_smooth_desc> smooth_list;
-    const uint32_t obj_flags = smooth ? RT_OBJ_NORMALS : 0u;
+    const uint32_t obj_flags = (smooth ? RT_OBJ_NORMALS : 0u) | (textured ? RT_OBJ_TEXCOORDS : 0u);
+    auto add_uvs = [&](const rt_mesh* mesh, uint32_t list, uint32_t first) {
+        uint32_t n = 0;
+        if (!textured || rt_mesh_uvs(mesh, nullptr, list, &n) != RT_OK || !n) return n;
+        const size_t at = uv_list.size();
+        uv_list.resize(at + n);
+        rt_mesh_uvs(mesh, uv_list.data() + at, list, &n);
+        for (size_t k = at; k < uv_list.size(); ++k) uv_list[k].index += first;
+        return n;
+    };
     auto add_normals = [&](const rt_mesh* mesh, uint32_t list, uint32_t first) {
         uint32_t n = 0;
         if (!smooth || rt_mesh_smooth_normals(mesh, nullptr, 0, nullptr, list, &n) != RT_OK || !n) return n;
@@ -196,6 +244,8 @@ int main(int argc, char** argv) {
             std::printf("%s: %u vertices, %u triangles, %u lines ignored\n", path, mv.n_vertices, mv.n_triangles,
                         mv.ignored_lines);
         if (!quiet && smooth) std::printf("%s: %u smooth triangles\n", path, n_smooth);
+        const uint32_t n_uv = add_uvs(mesh, RT_SMOOTH_SHAPES, (uint32_t)at);
+        if (!quiet && textured) std::printf("%s: %u triangles with texture coordinates\n", path, n_uv);
         rt_mesh_free(mesh);
     }
     // --instance: each file's local triangles once, and one (mesh, inverse, material) per placement
@@ -222,6 +272,8 @@ int main(int argc, char** argv) {
                             mv.n_triangles, mv.ignored_lines);
             const uint32_t n_smooth = add_normals(mesh, (uint32_t)mesh_triangles.size(), 0u);
             if (!quiet && smooth) std::printf("%s: %u smooth triangles\n", p.file.c_str(), n_smooth);
+            const uint32_t n_uv = add_uvs(mesh, (uint32_t)mesh_triangles.size(), 0u);
+            if (!quiet && textured) std::printf("%s: %u triangles with texture coordinates\n", p.file.c_str(), n_uv);
             rt_mesh_free(mesh);
             found = mesh_of.emplace(p.file, (uint32_t)mesh_triangles.size()).first;
             mesh_triangles.push_back(std::move(tri));
@@ -245,14 +297,17 @@ int main(int argc, char** argv) {
     const double ctx_ms = ms_since(t_ctx);
     const auto t_up = clk::now();
     if (created != RT_OK ||
-        rt_scene_upload_smooth(ctx, shapes.data(), (uint32_t)shapes.size(), meshes.data(), (uint32_t)meshes.size(),
-                               instances.data(), (uint32_t)instances.size(), smooth_list.data(),
-                               (uint32_t)smooth_list.size(), materials.data(), (uint32_t)materials.size(), v.patterns,
-                               v.n_patterns, v.lights,
-                               v.n_lights) != RT_OK) {  // (no smooth triangle: rt_scene_upload_instanced; no instances: rt_scene_upload)
+        rt_scene_upload_textured(ctx, shapes.data(), (uint32_t)shapes.size(), meshes.data(), (uint32_t)meshes.size(),
+                                 instances.data(), (uint32_t)instances.size(), smooth_list.data(),
+                                 (uint32_t)smooth_list.size(), uv_list.data(), (uint32_t)uv_list.size(), &texture,
+                                 textured ? 1u : 0u, materials.data(), (uint32_t)materials.size(), patterns.data(),
+                                 (uint32_t)patterns.size(), v.lights,
+                                 v.n_lights) != RT_OK) {  // (no texture: rt_scene_upload_smooth; no smooth triangle: rt_scene_upload_instanced; no instances: rt_scene_upload)
+        rt_image_free(texture_rgb);
         std::fprintf(stderr, "error: %s\n", rt_last_error());
         return 1;
     }
+    rt_image_free(texture_rgb);  // (the upload copied the texels)
     // One frame: the default per-scene policy (RT_JIT_AUTO) starts a hipRTC
     // build only at a world's second large frame, so this render never
     // compiles.

@@ -39,6 +39,14 @@ struct SmoothCounts {
     uint32_t plain = 0, inst = 0;
 };
 
+// Texel storage of a world (rt_scene_upload_textured): the texture count and the texels of all of them; a
+// group's header carries them.  `on`: the world has an image pattern or a coordinate entry (it runs the
+// texture code even where it holds no texture).
+struct TextureCounts {
+    uint32_t textures = 0, on = 0;
+    uint64_t texels = 0;
+};
+
 template <typename R>
 struct DeviceWorld {
     DeviceBuffer<unsigned char> image;  // the allocation holding the four tables
@@ -59,6 +67,12 @@ struct DeviceWorld {
     // Smooth triangles (rt_scene_upload_smooth): the plain part's entries, then the meshes', outside the LDS image
     DeviceBuffer<R> smooth;
     SmoothCounts smooth_counts{};           // zeros: a world without smooth triangles
+    // Texture coordinates (rt_scene_upload_textured), laid out like `smooth` with six reals an entry; the texels
+    // and the per-texture table are the context's (rt_context::texels), one copy for both precisions
+    DeviceBuffer<R> uv;
+    SmoothCounts uv_counts{};               // zeros: no triangle with coordinates
+    const uint32_t* texels = nullptr;
+    const TexRec* tex_table = nullptr;      // non-null: the world runs the texture code
     DevScene<R> scene{};
     // Point the tables into `image` for ns shapes, nm materials, np patterns.
     void carve(size_t ns, size_t nm, size_t np) {
@@ -109,6 +123,14 @@ struct DeviceWorld {
         smooth_counts = c;
         return RT_OK;
     }
+    // Room for the coordinate tables of `c`; all zero: no triangle has coordinates.
+    int allocate_uv(const SmoothCounts& c) {
+        if (int rc = uv.reserve(((size_t)c.plain + c.inst) * kUVReals)) return rc;
+        uv_counts = c;
+        return RT_OK;
+    }
+    const R* uv_plain() const { return uv_counts.plain ? uv.get() : nullptr; }
+    const R* uv_inst() const { return uv_counts.inst ? uv.get() + (size_t)uv_counts.plain * kUVReals : nullptr; }
     const R* smooth_plain() const { return smooth_counts.plain ? smooth.get() : nullptr; }
     const R* smooth_inst() const {
         return smooth_counts.inst ? smooth.get() + (size_t)smooth_counts.plain * kSmoothReals : nullptr;
@@ -121,11 +143,18 @@ template <typename R>
 inline bool walked_instances(const DeviceWorld<R>& w) {
     return w.inst_counts.instances > 0;
 }
-// Does the world run the instance build's kernels (rtc::instanced::launch_trace*)?  They hold the instance
-// level and the smooth triangle's normal (rtc_kernels.hip prepare_hit); every other world runs the plain build.
+// Does the world hold an image pattern or a triangle with texture coordinates (rt_scene_upload_textured)?
+template <typename R>
+inline bool has_textures(const DeviceWorld<R>& w) {
+    return w.tex_table != nullptr;
+}
+// Does the world run the instance build's kernels (rtc::instanced::launch_trace*) or, when it is textured,
+// the texture build's (rtc::textured::launch_trace*: the instance build plus the texture code)?  They hold the
+// instance level and the smooth triangle's normal (rtc_kernels.hip prepare_hit); every other world runs the
+// plain build.
 template <typename R>
 inline bool instance_build(const DeviceWorld<R>& w) {
-    return walked_instances(w) || w.smooth_counts.plain > 0 || w.smooth_counts.inst > 0;
+    return walked_instances(w) || w.smooth_counts.plain > 0 || w.smooth_counts.inst > 0 || has_textures(w);
 }
 
 struct CodeBuild;  // rtc_jit.cpp: one hipRTC build of a per-scene kernel, possibly in flight
@@ -295,6 +324,12 @@ struct rt_context {
     rt_instance_info instance_info{};  // meshes and instances of the uploaded world (rt_scene_instance_info)
     rt_smooth_info smooth_info{};      // smooth triangles of the uploaded world (rt_scene_smooth_info)
     std::vector<uint8_t> smooth_shape; // by plain shape: a smooth triangle (rt_debug_normal refuses it); empty: none
+    // Image textures (rt_scene_upload_textured): the texels of every texture (a packed dword each) and the
+    // per-texture table, shared by both precisions' worlds (DeviceWorld::texels, tex_table)
+    rtc::DeviceBuffer<uint32_t> texels;
+    rtc::DeviceBuffer<rtc::TexRec> tex_table;
+    rtc::TextureCounts tex_counts{};
+    rt_texture_info texture_info{};    // rt_scene_texture_info
     std::vector<int32_t> world_slot;  // world index -> slot | kind << 24 of the uploaded table
     // ray-pool overflow regions, one per resident workgroup; a ray batch's per-lane LIFOs (launch_rays)
     rtc::DeviceBuffer<unsigned char> d_spill;
@@ -355,7 +390,8 @@ int order_after_last(rt_context* ctx, hipStream_t stream);  // cross-stream laun
 int copy_to_host(rt_context* ctx, void* out, size_t bytes);  // d_scratch -> caller host buffer, on ctx->stream
 uint32_t tile_rows_for(uint32_t height, uint32_t shards, uint32_t shard);
 int validate_scene(const rt_shape_desc* shapes, uint32_t ns, const rt_material_desc* mats, uint32_t nm,
-                   const rt_pattern_desc* pats, uint32_t np, const rt_light_desc* lights, uint32_t nl);
+                   const rt_pattern_desc* pats, uint32_t np, const rt_light_desc* lights, uint32_t nl,
+                   int64_t n_textures = -1);  // >= 0: rt_scene_upload_textured's count (image patterns are known)
 // The mesh and instance lists of rt_scene_upload_instanced
 struct InstancedLists {
     const rt_mesh_desc* meshes;
@@ -364,6 +400,12 @@ struct InstancedLists {
     uint32_t n_instances;
     const rt_smooth_desc* smooth = nullptr;  // rt_scene_upload_smooth's list
     uint32_t n_smooth = 0;
+    // rt_scene_upload_textured's lists; `textured`: the upload came through it (image patterns are known)
+    const rt_uv_desc* uvs = nullptr;
+    uint32_t n_uvs = 0;
+    const rt_texture_desc* textures = nullptr;
+    uint32_t n_textures = 0;
+    bool textured = false;
 };
 int validate_scene_instanced(const rt_shape_desc* shapes, uint32_t ns, const InstancedLists& il,
                              const rt_material_desc* mats, uint32_t nm, const rt_pattern_desc* pats, uint32_t np,
@@ -376,7 +418,7 @@ int build_scene_instanced(rt_context* ctx, const rt_shape_desc* shapes, uint32_t
                           uint32_t n_meshes, const rt_instance_desc* instances, uint32_t n_inst,
                           const rt_material_desc* mats, uint32_t nm, const rt_pattern_desc* pats, uint32_t np,
                           const rt_light_desc* lights, uint32_t nl, const rt_smooth_desc* smooth = nullptr,
-                          uint32_t n_smooth = 0);
+                          uint32_t n_smooth = 0, const InstancedLists* textured = nullptr);
 void scene_brightness(const rt_shape_desc* shapes, uint32_t ns, const rt_material_desc* mats, uint32_t nm,
                       const rt_pattern_desc* pats, uint32_t np,
                       const rt_light_desc* lights, uint32_t nl, double* bright_hit, double* bright_w);

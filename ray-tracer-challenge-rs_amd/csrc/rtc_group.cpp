@@ -62,6 +62,9 @@ struct SceneHeader {
     rt_instance_info instance_info;
     SmoothCounts smooth;  // smooth triangles (rt_scene_upload_smooth): zeros = none
     rt_smooth_info smooth_info;
+    SmoothCounts uv;      // image textures (rt_scene_upload_textured): zeros = none
+    TextureCounts tex;
+    rt_texture_info texture_info;
 };
 
 // (device pointer, bytes) of every table of a member's world, in one order
@@ -76,6 +79,7 @@ void world_buffers(DeviceWorld<R>& w, const SceneHeader& h, std::vector<std::pai
     out.push_back({w.inst_nodes.get(), h.inst.nodes * sizeof(TriNode<R>)});
     out.push_back({w.inst_pos.get(), h.inst.pos * sizeof(int32_t)});
     out.push_back({w.smooth.get(), ((size_t)h.smooth.plain + h.smooth.inst) * kSmoothReals * sizeof(R)});
+    out.push_back({w.uv.get(), ((size_t)h.uv.plain + h.uv.inst) * kUVReals * sizeof(R)});
 }
 
 // Rank 0's `value` to every member of every rank, over RCCL (collective):
@@ -332,7 +336,8 @@ int group_scene_upload(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns
         if (!root_rc && hipSetDevice(ctx->device) != hipSuccess) root_rc = set_error(RT_ERR_HIP, "hipSetDevice");
         if (!root_rc)
             root_rc = il ? build_scene_instanced(ctx, shapes, ns, il->meshes, il->n_meshes, il->instances, il->n_instances,
-                                                 mats, nm, pats, np, lights, nl, il->smooth, il->n_smooth)
+                                                 mats, nm, pats, np, lights, nl, il->smooth, il->n_smooth,
+                                                 il->textured ? il : nullptr)
                          : build_scene(ctx, shapes, ns, mats, nm, pats, np, lights, nl);
         if (root_rc) root_err = rt_last_error();
         root_h.status = root_rc;
@@ -343,6 +348,9 @@ int group_scene_upload(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns
         root_h.instance_info = ctx->instance_info;
         root_h.smooth = ctx->w32.smooth_counts;
         root_h.smooth_info = ctx->smooth_info;
+        root_h.uv = ctx->w32.uv_counts;
+        root_h.tex = ctx->tex_counts;
+        root_h.texture_info = ctx->texture_info;
         root_h.ns = ns;
         root_h.nm = nm;
         root_h.np = np;
@@ -376,7 +384,8 @@ int group_scene_upload(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns
         else if (m->group.rank != 0) {
             const SceneHeader& h = hdr[i];
             // (worlds with and without instances run different kernels: the cached occupancies go)
-            if ((h.inst.instances > 0 || h.smooth.plain > 0 || h.smooth.inst > 0) != instance_build(m->w32))
+            if ((h.inst.instances > 0 || h.smooth.plain > 0 || h.smooth.inst > 0 || h.tex.on) != instance_build(m->w32) ||
+                (h.tex.on != 0) != has_textures(m->w32))
                 std::fill(std::begin(m->occ_blocks), std::end(m->occ_blocks), 0);
             if ((local_rc = m->w32.allocate(h.ns, h.nm, h.np, h.nl)) == RT_OK &&
                 (local_rc = m->w64.allocate(h.ns, h.nm, h.np, h.nl)) == RT_OK &&
@@ -384,8 +393,15 @@ int group_scene_upload(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns
                 (local_rc = m->w64.allocate_tree(h.n_tri_nodes, h.tri_flat_begin)) == RT_OK &&
                 (local_rc = m->w32.allocate_instances(h.inst)) == RT_OK &&
                 (local_rc = m->w64.allocate_instances(h.inst)) == RT_OK &&
-                (local_rc = m->w32.allocate_smooth(h.smooth)) == RT_OK)
-                local_rc = m->w64.allocate_smooth(h.smooth);
+                (local_rc = m->w32.allocate_smooth(h.smooth)) == RT_OK &&
+                (local_rc = m->w64.allocate_smooth(h.smooth)) == RT_OK &&
+                (local_rc = m->w32.allocate_uv(h.uv)) == RT_OK && (local_rc = m->w64.allocate_uv(h.uv)) == RT_OK &&
+                (local_rc = m->texels.reserve(h.tex.on ? std::max<uint64_t>(h.tex.texels, 1) : 0)) == RT_OK)
+                local_rc = m->tex_table.reserve(h.tex.on ? std::max<uint32_t>(h.tex.textures, 1u) : 0);
+            // (the texels and the per-texture table: one copy a member, seen by both precisions' worlds)
+            m->tex_counts = h.tex;
+            m->w32.texels = m->w64.texels = h.tex.on && !local_rc ? m->texels.get() : nullptr;
+            m->w32.tex_table = m->w64.tex_table = h.tex.on && !local_rc ? m->tex_table.get() : nullptr;
         }
         if (local_rc) local_err = rt_last_error();
     }
@@ -396,6 +412,10 @@ int group_scene_upload(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns
         std::vector<std::pair<void*, size_t>> bufs;
         world_buffers(ms[i]->w32, hdr[i], bufs);
         world_buffers(ms[i]->w64, hdr[i], bufs);
+        if (hdr[i].tex.on) {
+            bufs.push_back({ms[i]->texels.get(), std::max<uint64_t>(hdr[i].tex.texels, 1) * sizeof(uint32_t)});
+            bufs.push_back({ms[i]->tex_table.get(), std::max<uint32_t>(hdr[i].tex.textures, 1u) * sizeof(TexRec)});
+        }
         for (auto& b : bufs)
             if (b.second) RT_NCCL(ncclBroadcast(b.first, b.first, b.second, ncclUint8, 0, ms[i]->group.comm, ms[i]->stream));
     }
@@ -422,6 +442,7 @@ int group_scene_upload(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns
         m->tree_info = h.tree_info;
         m->instance_info = h.instance_info;
         m->smooth_info = h.smooth_info;
+        m->texture_info = h.texture_info;
         m->have_scene = true;
         ++m->scene_gen;
     }

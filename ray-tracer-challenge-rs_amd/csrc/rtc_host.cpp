@@ -67,6 +67,23 @@ hipError_t launch_trace_ss(const LaunchParams<R>& P, bool pool, bool dup, uint32
 template <typename R>
 hipError_t occupancy_ss(bool pool, bool lds, size_t dyn_lds, int* blocks_per_cu);
 }  // namespace instanced
+namespace textured {  // rtc_kernels_tex*.o: the instance build plus the texture code, for worlds with textures
+template <typename R>
+hipError_t launch_trace(const LaunchParams<R>& P, bool pool, bool dup, uint32_t grid, size_t dyn_lds,
+                        hipStream_t stream);
+template <typename R>
+hipError_t occupancy(bool pool, bool lds, size_t dyn_lds, int* blocks_per_cu);
+template <typename R>
+hipError_t launch_trace_rays(const LaunchParams<R>& P, bool dup, uint32_t grid, size_t dyn_lds, const void* rays,
+                             void* rgb, void* hits, hipStream_t stream);
+template <typename R>
+hipError_t occupancy_rays(bool lds, size_t dyn_lds, int* blocks_per_cu);
+template <typename R>
+hipError_t launch_trace_ss(const LaunchParams<R>& P, bool pool, bool dup, uint32_t grid, size_t dyn_lds,
+                           hipStream_t stream);
+template <typename R>
+hipError_t occupancy_ss(bool pool, bool lds, size_t dyn_lds, int* blocks_per_cu);
+}  // namespace textured
 namespace sp {  // rtc_kernels_sp.o: the f32 pool kernel for worlds of spheres and planes only
 template <typename R>
 hipError_t launch_trace(const LaunchParams<R>& P, bool pool, bool dup, uint32_t grid, size_t dyn_lds,
@@ -279,6 +296,7 @@ struct WorldIndices {
     uint32_t n_plain = 0;             // with `index`: entries [0, n_plain) are the world's first shapes (world_slot's reach)
     std::vector<int32_t>* slot_of = nullptr;  // out: slot | kind << 24 of list entry i
     ident::Normals normals = nullptr;  // vertex normals of list entry i, null for a flat shape (null: none is smooth)
+    ident::Normals uvs = nullptr;      // texture coordinates of list entry i (six doubles), null for a shape without
     uint32_t of(uint32_t i) const { return index ? index[i] : i; }
     uint32_t plain(uint32_t ns) const { return index ? n_plain : ns; }
 };
@@ -333,7 +351,8 @@ int build_world(rt_context* ctx, DeviceWorld<R>& w, const rt_shape_desc* shapes,
             r.material = d.material;
             const bool class_end = next + 1 >= order.size() || cls[order[next + 1]] != cls[i];
             r.flags = (d.closed ? kShapeClosed : 0) | (class_end ? kShapeClassEnd : 0) | (similar ? kShapeSimilar : 0) | (aligned ? kShapeAxisAligned : 0) |
-                      (ident::normals_of(wi.normals, i) ? kShapeSmooth : 0) | (int32_t)(wi.of(cls[i]) << kShapeClassShift);
+                      (ident::normals_of(wi.normals, i) ? kShapeSmooth : 0) | (ident::normals_of(wi.uvs, i) ? kShapeUV : 0) |
+                      (int32_t)(wi.of(cls[i]) << kShapeClassShift);
             r.casts_shadow = mats[d.material].casts_shadow ? 1 : 0;
             sh.push_back(r);
         }
@@ -376,7 +395,7 @@ int build_world(rt_context* ctx, DeviceWorld<R>& w, const rt_shape_desc* shapes,
         for (int q = 0; q < 12; ++q) p.inv[q] = (R)d.inverse[q];
         p.kind = d.kind;
         p.sub_a = d.sub_a;
-        p.sub_b = d.sub_b;
+        p.sub_b = d.kind == RT_PATTERN_IMAGE ? d.reserved : d.sub_b;  // (an image pattern: its texture and its filter)
     }
     std::vector<LightRec<R>> lt(nl);
     for (uint32_t i = 0; i < nl; ++i)
@@ -442,14 +461,21 @@ int build_world(rt_context* ctx, DeviceWorld<R>& w, const rt_shape_desc* shapes,
 int validate_scene_instanced(const rt_shape_desc* shapes, uint32_t ns, const InstancedLists& il,
                              const rt_material_desc* mats, uint32_t nm, const rt_pattern_desc* pats, uint32_t np,
                              const rt_light_desc* lights, uint32_t nl) {
-    if (int rc = validate_scene(shapes, ns, mats, nm, pats, np, lights, nl)) return rc;
+    if (il.textured) {  // (the texture list first: the patterns are checked against it)
+        const std::string why = inst::validate_textures(il.textures, il.n_textures);
+        if (!why.empty()) return set_error(RT_ERR_INVALID, why);
+    }
+    if (int rc = validate_scene(shapes, ns, mats, nm, pats, np, lights, nl, il.textured ? (int64_t)il.n_textures : -1))
+        return rc;
     std::string why = inst::validate(shapes, ns, il.meshes, il.n_meshes, il.instances, il.n_instances, nm);
     if (why.empty()) why = inst::validate_smooth(shapes, ns, il.meshes, il.n_meshes, il.smooth, il.n_smooth);
+    if (why.empty() && il.textured) why = inst::validate_uvs(shapes, ns, il.meshes, il.n_meshes, il.uvs, il.n_uvs);
     return why.empty() ? RT_OK : set_error(RT_ERR_INVALID, why);
 }
 
 int validate_scene(const rt_shape_desc* shapes, uint32_t ns, const rt_material_desc* mats, uint32_t nm,
-                   const rt_pattern_desc* pats, uint32_t np, const rt_light_desc* lights, uint32_t nl) {
+                   const rt_pattern_desc* pats, uint32_t np, const rt_light_desc* lights, uint32_t nl,
+                   int64_t n_textures) {
     if ((ns && !shapes) || (nm && !mats) || (np && !pats) || (nl && !lights))
         return set_error(RT_ERR_INVALID, "rt_scene_upload: null table with nonzero count");
     for (uint32_t i = 0; i < ns; ++i) {
@@ -462,11 +488,23 @@ int validate_scene(const rt_shape_desc* shapes, uint32_t ns, const rt_material_d
         if (mats[i].pattern >= 0 && (uint32_t)mats[i].pattern >= np)
             return set_error(RT_ERR_INVALID, "material " + std::to_string(i) + ": pattern index out of range");
     for (uint32_t i = 0; i < np; ++i) {
-        if (pats[i].kind < 0 || pats[i].kind > RT_PATTERN_TEST)
+        // (an image pattern exists for rt_scene_upload_textured only: n_textures >= 0)
+        if (pats[i].kind < 0 || pats[i].kind > (n_textures >= 0 ? RT_PATTERN_IMAGE : RT_PATTERN_TEST))
             return set_error(RT_ERR_INVALID, "pattern " + std::to_string(i) + ": unknown kind");
         if (pats[i].kind == RT_PATTERN_COMPLEX &&
             (pats[i].sub_a < 0 || pats[i].sub_b < 0 || (uint32_t)pats[i].sub_a >= np || (uint32_t)pats[i].sub_b >= np))
             return set_error(RT_ERR_INVALID, "pattern " + std::to_string(i) + ": bad sub-pattern index");
+        if (n_textures >= 0 && pats[i].kind == RT_PATTERN_COMPLEX &&
+            (pats[pats[i].sub_a].kind == RT_PATTERN_IMAGE || pats[pats[i].sub_b].kind == RT_PATTERN_IMAGE))
+            return set_error(RT_ERR_INVALID, "pattern " + std::to_string(i) + ": an image pattern cannot be a sub-pattern");
+        if (pats[i].kind == RT_PATTERN_IMAGE) {
+            if (pats[i].sub_a < 0 || (int64_t)pats[i].sub_a >= n_textures)
+                return set_error(RT_ERR_INVALID, "pattern " + std::to_string(i) + ": texture index out of range");
+            if (pats[i].sub_b != -1)
+                return set_error(RT_ERR_INVALID, "pattern " + std::to_string(i) + ": an image pattern's sub_b must be -1");
+            if (pats[i].reserved != RT_FILTER_NEAREST && pats[i].reserved != RT_FILTER_BILINEAR)
+                return set_error(RT_ERR_INVALID, "pattern " + std::to_string(i) + ": unknown texture filter");
+        }
     }
     if (ns > 0xFFFFFF || nl > 0x7fffffff) return set_error(RT_ERR_INVALID, "table too large");
     return RT_OK;
@@ -570,7 +608,10 @@ int blocks_per_cu(rt_context* ctx, bool pool, bool lds_world, size_t lds, int* p
     }
     int api = 0;
     // (a world with mesh instances runs the instance variant of every kernel; an upload that changes that clears the cache)
-    if (instance_build(ctx->w32))
+    if (has_textures(ctx->w32))
+        RT_HIP(ss ? textured::occupancy_ss<R>(pool, lds_world, lds, &api)
+                  : textured::occupancy<R>(pool, lds_world, lds, &api));
+    else if (instance_build(ctx->w32))
         RT_HIP(ss ? instanced::occupancy_ss<R>(pool, lds_world, lds, &api)
                   : instanced::occupancy<R>(pool, lds_world, lds, &api));
     else
@@ -833,6 +874,10 @@ void set_instance_params(LaunchParams<R>& P, const DeviceWorld<R>& w) {
     P.inst_pos = w.inst_pos.get();
     P.smooth_plain = w.smooth_plain();
     P.smooth_inst = w.smooth_inst();
+    P.uv_plain = w.uv_plain();
+    P.uv_inst = w.uv_inst();
+    P.texels = w.texels;
+    P.textures = w.tex_table;
 }
 
 template <typename R>
@@ -897,9 +942,10 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
             RT_FLAG_NO_SHADE | RT_FLAG_NO_TRACE | RT_FLAG_GENERATIONS | (ls.pool ? 0u : RT_FLAG_STAMPS);
         // (a world with a triangle hierarchy runs the generic kernels, which walk it)
         const bool instanced = walked_instances(w), smooth = w.smooth_counts.plain || w.smooth_counts.inst;
-        const bool tree = w.n_tri_nodes > 0 || instanced || smooth;
+        const bool tree = w.n_tri_nodes > 0 || instanced || smooth || has_textures(w);
         if (tree && ctx->jit.mode != RT_JIT_OFF && ctx->jit.log.empty())
-            ctx->jit.log = smooth ? "no per-scene build: the world has smooth triangles, whose normals the generic kernels interpolate"
+            ctx->jit.log = has_textures(w) ? "no per-scene build: the world has textures, which the generic kernels sample"
+                           : smooth ? "no per-scene build: the world has smooth triangles, whose normals the generic kernels interpolate"
                            : instanced
                                ? "no per-scene build: the world has mesh instances, which the generic kernels walk"
                                : "no per-scene build: the world has a triangle hierarchy, which the generic kernels walk";
@@ -1063,7 +1109,10 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
         void* args[] = {&P, &sh, &mt, &pt, &lt};
         (void)hipGetLastError();
         RT_HIP(hipModuleLaunchKernel(jf, ls.grid, 1, 1, kBlock, 1, 1, (unsigned)ls.lds, stream, args, nullptr));
-    } else if (hipError_t e = instance_build(w)
+    } else if (hipError_t e = has_textures(w)
+                                  ? (ss ? textured::launch_trace_ss<R>(P, ls.pool, dup, ls.grid, ls.lds, stream)
+                                        : textured::launch_trace<R>(P, ls.pool, dup, ls.grid, ls.lds, stream))
+                              : instance_build(w)
                                   ? (ss ? instanced::launch_trace_ss<R>(P, ls.pool, dup, ls.grid, ls.lds, stream)
                                         : instanced::launch_trace<R>(P, ls.pool, dup, ls.grid, ls.lds, stream))
                               : ss ? launch_trace_ss<R>(P, ls.pool, dup, ls.grid, ls.lds, stream)
@@ -1077,6 +1126,7 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
                                          " rays in LDS): " + hipGetErrorString(e));
     if (dynamic) ctx->head_set ^= 1;
     ctx->smooth_info.ran_smooth = !jf && (w.smooth_counts.plain || w.smooth_counts.inst) ? 1u : 0u;
+    ctx->texture_info.ran_textured = !jf && has_textures(w) ? 1u : 0u;
     return RT_OK;
 }
 
@@ -1090,7 +1140,8 @@ int ray_blocks_per_cu(rt_context* ctx, bool lds_world, size_t lds, int* per_cu) 
         return RT_OK;
     }
     int api = 0;
-    if (instance_build(ctx->w32)) RT_HIP(instanced::occupancy_rays<R>(lds_world, lds, &api));
+    if (has_textures(ctx->w32)) RT_HIP(textured::occupancy_rays<R>(lds_world, lds, &api));
+    else if (instance_build(ctx->w32)) RT_HIP(instanced::occupancy_rays<R>(lds_world, lds, &api));
     else RT_HIP(occupancy_rays<R>(lds_world, lds, &api));
     *per_cu = cap_by_lds(api, lds);
     ctx->occ_lds[key] = lds;
@@ -1155,7 +1206,9 @@ int launch_rays(rt_context* ctx, DeviceWorld<R>& w, const void* d_rays, uint64_t
     }
     ctx->jit.used = false;
     if (o->flags & RT_FLAG_FAIL_LAUNCH) return set_error(RT_ERR_HIP, "launch refused (RT_FLAG_FAIL_LAUNCH)");
-    if (hipError_t e = instance_build(w) ? instanced::launch_trace_rays<R>(P, ctx->duplicate_shapes > 0, ls.grid, ls.lds,
+    if (hipError_t e = has_textures(w) ? textured::launch_trace_rays<R>(P, ctx->duplicate_shapes > 0, ls.grid, ls.lds,
+                                                                     d_rays, d_rgb, d_hits, stream)
+                       : instance_build(w) ? instanced::launch_trace_rays<R>(P, ctx->duplicate_shapes > 0, ls.grid, ls.lds,
                                                                              d_rays, d_rgb, d_hits, stream)
                                            : launch_trace_rays<R>(P, ctx->duplicate_shapes > 0, ls.grid, ls.lds, d_rays,
                                                                   d_rgb, d_hits, stream);
@@ -1164,6 +1217,7 @@ int launch_rays(rt_context* ctx, DeviceWorld<R>& w, const void* d_rays, uint64_t
                                          ", dynamic LDS " + std::to_string(ls.lds) + " B, " + std::to_string(ls.cap) +
                                          " stack entries per lane): " + hipGetErrorString(e));
     ctx->smooth_info.ran_smooth = w.smooth_counts.plain || w.smooth_counts.inst ? 1u : 0u;
+    ctx->texture_info.ran_textured = has_textures(w) ? 1u : 0u;
     return RT_OK;
 }
 
@@ -1448,6 +1502,53 @@ int rt_smooth_expand(const rt_shape_desc* shapes, uint32_t ns, const rt_mesh_des
     return RT_OK;
 }
 
+int rt_scene_upload_textured(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns, const rt_mesh_desc* meshes,
+                             uint32_t n_meshes, const rt_instance_desc* instances, uint32_t n_inst,
+                             const rt_smooth_desc* smooth, uint32_t n_smooth, const rt_uv_desc* uvs, uint32_t n_uvs,
+                             const rt_texture_desc* textures, uint32_t n_textures, const rt_material_desc* mats,
+                             uint32_t nm, const rt_pattern_desc* pats, uint32_t np, const rt_light_desc* lights,
+                             uint32_t nl) {
+    InstancedLists il{meshes, n_meshes, instances, n_inst, smooth, n_smooth};
+    il.uvs = uvs;
+    il.n_uvs = n_uvs;
+    il.textures = textures;
+    il.n_textures = n_textures;
+    il.textured = true;
+    // (the lists are checked before the context is looked at, here also for a group: the patterns are rewritten below)
+    if (int rc = validate_scene_instanced(shapes, ns, il, mats, nm, pats, np, lights, nl)) return rc;
+    bool images = false;
+    for (uint32_t i = 0; i < np; ++i) images = images || pats[i].kind == RT_PATTERN_IMAGE;
+    if (!n_uvs && !images)  // rt_scene_upload_smooth itself (textures no pattern names are not uploaded)
+        return rt_scene_upload_smooth(ctx, shapes, ns, meshes, n_meshes, instances, n_inst, smooth, n_smooth, mats, nm, pats,
+                                      np, lights, nl);
+    if (!ctx) return set_error(RT_ERR_INVALID, "null context");
+    // (patterns compare by their textures' contents: a copy with every image pattern's texture renumbered)
+    std::vector<rt_pattern_desc> cp(pats, pats + np);
+    inst::canonical_image_patterns(cp.data(), np, textures, n_textures);
+    if (ctx->group.comm) return group_scene_upload(ctx, shapes, ns, mats, nm, cp.data(), np, lights, nl, &il);
+    RT_HIP(hipSetDevice(ctx->device));
+    RT_HIP(hipDeviceSynchronize());  // launches on caller streams may still read the old tables
+    return build_scene_instanced(ctx, shapes, ns, meshes, n_meshes, instances, n_inst, mats, nm, cp.data(), np, lights, nl,
+                                 smooth, n_smooth, &il);
+}
+
+int rt_uv_expand(const rt_shape_desc* shapes, uint32_t ns, const rt_mesh_desc* meshes, uint32_t n_meshes,
+                 const rt_instance_desc* instances, uint32_t n_inst, const rt_uv_desc* uvs, uint32_t n_uvs,
+                 rt_uv_desc* out, uint32_t* n_out) {
+    std::string why = inst::validate(shapes, ns, meshes, n_meshes, instances, n_inst, 0x7FFFFFFFu);
+    if (why.empty()) why = inst::validate_uvs(shapes, ns, meshes, n_meshes, uvs, n_uvs);
+    if (!why.empty()) return set_error(RT_ERR_INVALID, why);
+    const uint32_t n = inst::expand_uvs(ns, meshes, n_meshes, instances, n_inst, uvs, n_uvs, out);
+    if (n_out) *n_out = n;
+    return RT_OK;
+}
+
+int rt_scene_texture_info(rt_context* ctx, rt_texture_info* out) {
+    if (!ctx || !out) return set_error(RT_ERR_INVALID, "null argument");
+    *out = ctx->have_scene ? ctx->texture_info : rt_texture_info{};
+    return RT_OK;
+}
+
 int rt_scene_smooth_info(rt_context* ctx, rt_smooth_info* out) {
     if (!ctx || !out) return set_error(RT_ERR_INVALID, "null argument");
     *out = ctx->have_scene ? ctx->smooth_info : rt_smooth_info{};
@@ -1577,7 +1678,7 @@ int build_plain_tables(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns
     int rc;
     ctx->have_scene = false;
     std::vector<uint32_t> cls;  // value-identity classes (shape_identity.hpp)
-    ctx->duplicate_shapes = ident::shape_classes(shapes, ns, mats, pats, cls, wi.normals);
+    ctx->duplicate_shapes = ident::shape_classes(shapes, ns, mats, pats, cls, wi.normals, wi.uvs);
     std::vector<uint32_t> order = table_order(shapes, ns, cls);
     // A world the per-scene builds take whole (their records: up to
     // kJitRecordsMaxShapes shapes) keeps the flat triangle run and with it
@@ -1626,7 +1727,7 @@ struct InstancePlan {
 template <typename R>
 int upload_instances(rt_context* ctx, DeviceWorld<R>& w, const InstancePlan& ip, const rt_mesh_desc* meshes,
                      const rt_instance_desc* instances, uint32_t n_inst, const rt_material_desc* mats,
-                     const inst::SmoothIndex* si) {
+                     const inst::SmoothIndex* si, const inst::SmoothIndex* ui) {
     int rc;
     if ((rc = w.allocate_instances(ip.counts))) return rc;
     std::vector<ShapeRec<R>> recs(ip.counts.records);
@@ -1652,7 +1753,8 @@ int upload_instances(rt_context* ctx, DeviceWorld<R>& w, const InstancePlan& ip,
                 r.tri[9 + q] = (R)d.normal[q];
             }
             r.world_index = (int32_t)j;  // the local index: for_instances adds the instance's base
-            r.flags = kShapeClassEnd | (si && ident::normals_of(si->of_mesh((uint32_t)m), j) ? kShapeSmooth : 0);
+            r.flags = kShapeClassEnd | (si && ident::normals_of(si->of_mesh((uint32_t)m), j) ? kShapeSmooth : 0) |
+                      (ui && ident::normals_of(ui->of_mesh((uint32_t)m), j) ? kShapeUV : 0);
             recs[ip.rec_begin[m] + at] = r;
             pos[ip.pos_begin[m] + j] = (int32_t)(ip.rec_begin[m] + at);
         }
@@ -1746,7 +1848,82 @@ int upload_smooth(rt_context* ctx, DeviceWorld<R>& w, const std::vector<const do
     const int rs = hip_status(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");  // (host temporary)
     return rc ? rc : rs;
 }
+
+// The coordinate tables of one precision (rtc_internal.hpp kShapeUV), built as upload_smooth builds the normal
+// tables: list_uvs by entry of the plain list, ui by mesh triangle.
+template <typename R>
+int upload_uvs(rt_context* ctx, DeviceWorld<R>& w, const std::vector<const double*>& list_uvs, const InstancePlan& ip,
+               const inst::SmoothIndex& ui) {
+    const int32_t tri0 = w.scene.kind_begin[RT_SHAPE_TRIANGLE], tri1 = w.scene.kind_begin[RT_SHAPE_TRIANGLE + 1];
+    SmoothCounts c;
+    if (std::any_of(list_uvs.begin(), list_uvs.end(), [](const double* p) { return p != nullptr; }))
+        c.plain = (uint32_t)(tri1 - tri0);
+    for (size_t m = 0; m < ip.meshes.size(); ++m)
+        if (!ip.meshes[m].order.empty() && ui.smooth_in_mesh((uint32_t)m)) c.inst = ip.counts.records;
+    if (int rc = w.allocate_uv(c)) return rc;
+    std::vector<R> host(((size_t)c.plain + c.inst) * kUVReals, (R)0);
+    if (c.plain)
+        for (size_t i = 0; i < list_uvs.size(); ++i)
+            if (list_uvs[i]) {
+                const int32_t slot = ip.slot_of[i] & 0xFFFFFF;
+                if (slot < tri0 || slot >= tri1) return set_error(RT_ERR_INVALID, "textured triangle outside the triangle run");
+                for (int q = 0; q < kUVReals; ++q) host[(size_t)(slot - tri0) * kUVReals + q] = (R)list_uvs[i][q];
+            }
+    if (c.inst)
+        for (size_t m = 0; m < ip.meshes.size(); ++m) {
+            const inst::MeshPlan& mp = ip.meshes[m];
+            const ident::Normals U = ui.of_mesh((uint32_t)m);
+            for (uint32_t at = 0; U && at < mp.order.size(); ++at)
+                if (const double* t = U[mp.order[at]])
+                    for (int q = 0; q < kUVReals; ++q) host[((size_t)c.plain + ip.rec_begin[m] + at) * kUVReals + q] = (R)t[q];
+        }
+    if (host.empty()) return RT_OK;
+    const int rc = hip_status(hipMemcpyAsync(w.uv.get(), host.data(), host.size() * sizeof(R), hipMemcpyHostToDevice,
+                                             ctx->stream), "hipMemcpyAsync");
+    const int rs = hip_status(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");  // (host temporary)
+    return rc ? rc : rs;
+}
+
+// The texels of every texture, one packed dword each (R | G << 8 | B << 16), and the per-texture table; a
+// world without a texture still gets a one-entry table, whose address marks the world as textured.
+int upload_textures(rt_context* ctx, const rt_texture_desc* textures, uint32_t n_textures) {
+    std::vector<TexRec> table(std::max<uint32_t>(n_textures, 1u), TexRec{0, 1, 1});
+    uint64_t total = 0;
+    for (uint32_t t = 0; t < n_textures; ++t) {
+        table[t] = TexRec{total, textures[t].width, textures[t].height};
+        total += (uint64_t)textures[t].width * textures[t].height;
+    }
+    int rc;
+    if ((rc = ctx->texels.reserve(std::max<uint64_t>(total, 1))) || (rc = ctx->tex_table.reserve(table.size()))) return rc;
+    std::vector<uint32_t> host(std::max<uint64_t>(total, 1), 0u);
+    for (uint32_t t = 0; t < n_textures; ++t) {
+        const uint8_t* src = textures[t].rgb;
+        uint32_t* dst = host.data() + table[t].offset;
+        const size_t n = (size_t)textures[t].width * textures[t].height;
+        for (size_t i = 0; i < n; ++i) dst[i] = (uint32_t)src[3 * i] | (uint32_t)src[3 * i + 1] << 8 | (uint32_t)src[3 * i + 2] << 16;
+    }
+    rc = hip_status(hipMemcpyAsync(ctx->texels.get(), host.data(), host.size() * sizeof(uint32_t), hipMemcpyHostToDevice,
+                                   ctx->stream), "hipMemcpyAsync");
+    if (!rc)
+        rc = hip_status(hipMemcpyAsync(ctx->tex_table.get(), table.data(), table.size() * sizeof(TexRec),
+                                       hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync");
+    const int rs = hip_status(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");  // (host temporaries)
+    if (rc || rs) return rc ? rc : rs;
+    ctx->tex_counts = TextureCounts{n_textures, 1u, total};
+    ctx->w32.texels = ctx->w64.texels = ctx->texels.get();
+    ctx->w32.tex_table = ctx->w64.tex_table = ctx->tex_table.get();
+    return RT_OK;
+}
 }  // namespace
+
+// The context holds no texture from here on (the buffers keep their room).
+static void clear_textures(rt_context* ctx) {
+    ctx->texture_info = rt_texture_info{};
+    ctx->tex_counts = TextureCounts{};
+    ctx->w32.uv_counts = ctx->w64.uv_counts = SmoothCounts{};
+    ctx->w32.texels = ctx->w64.texels = nullptr;
+    ctx->w32.tex_table = ctx->w64.tex_table = nullptr;
+}
 
 int build_scene(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns, const rt_material_desc* mats, uint32_t nm,
                 const rt_pattern_desc* pats, uint32_t np, const rt_light_desc* lights, uint32_t nl) {
@@ -1756,18 +1933,21 @@ int build_scene(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns, const
     if (instance_build(ctx->w32)) std::fill(std::begin(ctx->occ_blocks), std::end(ctx->occ_blocks), 0);  // other kernels now
     ctx->w32.inst_counts = ctx->w64.inst_counts = InstanceCounts{};
     ctx->w32.smooth_counts = ctx->w64.smooth_counts = SmoothCounts{};
+    clear_textures(ctx);
     return build_plain_tables(ctx, shapes, ns, mats, nm, pats, np, lights, nl, WorldIndices{}, false);
 }
 
 int build_scene_instanced(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns, const rt_mesh_desc* meshes,
                           uint32_t n_meshes, const rt_instance_desc* instances, uint32_t n_inst,
                           const rt_material_desc* mats, uint32_t nm, const rt_pattern_desc* pats, uint32_t np,
-                          const rt_light_desc* lights, uint32_t nl, const rt_smooth_desc* smooth, uint32_t n_smooth) {
-    // (a world with a smooth triangle takes the general path whatever its instances: it runs the instance build)
-    if (!n_inst && !n_smooth) return build_scene(ctx, shapes, ns, mats, nm, pats, np, lights, nl);  // rt_scene_upload itself
+                          const rt_light_desc* lights, uint32_t nl, const rt_smooth_desc* smooth, uint32_t n_smooth,
+                          const InstancedLists* tx) {
+    // (a world with a smooth triangle or a texture takes the general path whatever its instances: it runs the instance build)
+    if (!n_inst && !n_smooth && !tx) return build_scene(ctx, shapes, ns, mats, nm, pats, np, lights, nl);  // rt_scene_upload itself
     int rc;
     const auto t0 = std::chrono::steady_clock::now();
     const inst::SmoothIndex si = inst::smooth_index(ns, meshes, n_meshes, smooth, n_smooth);
+    const inst::SmoothIndex ui = inst::uv_index(ns, meshes, n_meshes, tx ? tx->uvs : nullptr, tx ? tx->n_uvs : 0);
     InstancePlan ip;
     ip.expanded = inst::decide_expanded(shapes, ns, meshes, n_meshes, instances, n_inst, mats, pats, n_smooth ? &si : nullptr);
     ip.bases = inst::world_bases(ns, meshes, instances, n_inst);
@@ -1780,6 +1960,11 @@ int build_scene_instanced(rt_context* ctx, const rt_shape_desc* shapes, uint32_t
     uint32_t smooth_triangles = (uint32_t)std::count_if(list_normals.begin(), list_normals.end(),
                                                         [](const double* p) { return p != nullptr; });
     for (uint32_t k = 0; k < n_inst; ++k) smooth_triangles += si.smooth_in_mesh(instances[k].mesh);
+    std::vector<const double*> list_uvs(ns, nullptr);  // by entry of the plain list: a triangle's texture coordinates
+    for (uint32_t i = 0; i < (uint32_t)ui.plain.size(); ++i) list_uvs[i] = ui.plain[i];
+    uint32_t textured_triangles = (uint32_t)std::count_if(list_uvs.begin(), list_uvs.end(),
+                                                          [](const double* p) { return p != nullptr; });
+    for (uint32_t k = 0; k < n_inst; ++k) textured_triangles += ui.smooth_in_mesh(instances[k].mesh);
     ip.list_begin.assign(n_inst, 0);
     ip.expanded_pos.assign(n_inst, 0);
     uint32_t n_expanded = 0, walked_triangles = 0;
@@ -1798,9 +1983,10 @@ int build_scene_instanced(rt_context* ctx, const rt_shape_desc* shapes, uint32_t
         for (uint32_t j = 0; j < mesh.n_triangles; ++j) {
             index.push_back(ip.bases[k] + j);
             list_normals.push_back(ident::normals_of(si.of_mesh(instances[k].mesh), j));
+            list_uvs.push_back(ident::normals_of(ui.of_mesh(instances[k].mesh), j));
         }
     }
-    if (n_expanded == n_inst && !n_smooth) {
+    if (n_expanded == n_inst && !n_smooth && !tx) {
         // every instance has a value-equal partner: the plain list is the
         // expansion, uploaded as rt_scene_upload would (per-scene builds included)
         if ((rc = build_scene(ctx, list.data(), (uint32_t)list.size(), mats, nm, pats, np, lights, nl))) return rc;
@@ -1838,13 +2024,28 @@ int build_scene_instanced(rt_context* ctx, const rt_shape_desc* shapes, uint32_t
     wi.n_plain = ns;
     wi.slot_of = &ip.slot_of;
     wi.normals = n_smooth ? list_normals.data() : nullptr;
+    wi.uvs = tx && tx->n_uvs ? list_uvs.data() : nullptr;
     if ((rc = build_plain_tables(ctx, list.data(), (uint32_t)list.size(), mats, nm, pats, np, lights, nl, wi, true)))
         return rc;
     ctx->have_scene = false;
-    if (!instance_build(ctx->w32)) std::fill(std::begin(ctx->occ_blocks), std::end(ctx->occ_blocks), 0);  // other kernels now
+    if (!instance_build(ctx->w32) || has_textures(ctx->w32) != (tx != nullptr))
+        std::fill(std::begin(ctx->occ_blocks), std::end(ctx->occ_blocks), 0);  // other kernels now
     const inst::SmoothIndex* const sip = n_smooth ? &si : nullptr;
-    if ((rc = upload_instances<float>(ctx, ctx->w32, ip, meshes, instances, n_inst, mats, sip)) ||
-        (rc = upload_instances<double>(ctx, ctx->w64, ip, meshes, instances, n_inst, mats, sip)) ||
+    const inst::SmoothIndex* const uip = tx && tx->n_uvs ? &ui : nullptr;
+    clear_textures(ctx);
+    if (tx) {
+        if ((rc = upload_uvs<float>(ctx, ctx->w32, list_uvs, ip, ui)) ||
+            (rc = upload_uvs<double>(ctx, ctx->w64, list_uvs, ip, ui)) ||
+            (rc = upload_textures(ctx, tx->textures, tx->n_textures)))
+            return rc;
+        ctx->texture_info.textured_triangles = textured_triangles;
+        ctx->texture_info.textures = tx->n_textures;
+        ctx->texture_info.uv_bytes = ((uint64_t)ctx->w32.uv_counts.plain + ctx->w32.uv_counts.inst) * kUVReals *
+                                     (sizeof(float) + sizeof(double));
+        ctx->texture_info.texel_bytes = ctx->tex_counts.texels * sizeof(uint32_t) + (uint64_t)tx->n_textures * sizeof(TexRec);
+    }
+    if ((rc = upload_instances<float>(ctx, ctx->w32, ip, meshes, instances, n_inst, mats, sip, uip)) ||
+        (rc = upload_instances<double>(ctx, ctx->w64, ip, meshes, instances, n_inst, mats, sip, uip)) ||
         (rc = upload_smooth<float>(ctx, ctx->w32, list_normals, ip, si)) ||
         (rc = upload_smooth<double>(ctx, ctx->w64, list_normals, ip, si)))
         return rc;

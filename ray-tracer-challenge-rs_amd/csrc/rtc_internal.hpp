@@ -299,6 +299,19 @@ constexpr int32_t kShapeAxisAligned = 8;
 // reals each.  Only the instance build's prepare_hit reads the bit.
 constexpr int32_t kShapeSmooth = 16;
 constexpr int kSmoothReals = 9;  // n1, n2, n3
+// A triangle with texture coordinates (rtc.h rt_scene_upload_textured): its
+// t1, t2, t3 are entry `slot - kind_begin[RT_SHAPE_TRIANGLE]` of LaunchParams::
+// uv_plain or entry `position` of uv_inst, six reals each, laid out like the
+// normal tables.  Only the texture build's prepare_hit reads the bit.
+constexpr int32_t kShapeUV = 32;
+constexpr int kUVReals = 6;  // t1, t2, t3
+// One texture of the upload: its first texel in LaunchParams::texels (one
+// packed dword per texel, R | G << 8 | B << 16, row 0 at the top) and its size.
+struct alignas(16) TexRec {
+    uint64_t offset;
+    uint32_t width, height;
+};
+static_assert(sizeof(TexRec) == 16);
 constexpr int kShapeClassShift = 8;
 
 template <typename R>
@@ -553,6 +566,17 @@ struct LaunchParams {
     // by the instance build's prepare_hit; no other kernel loads them.
     const R* smooth_plain;
     const R* smooth_inst;
+    // Image textures (rt_scene_upload_textured; null for every other world):
+    // the coordinate tables, laid out like the normal tables (kShapeUV), the
+    // texels of every texture in one allocation and the per-texture table.  A
+    // PatternRec of kind RT_PATTERN_IMAGE holds its texture in sub_a and its
+    // filter in sub_b.  `textures` is non-null exactly when the world has an
+    // image pattern or a coordinate entry (such a world runs the texture build,
+    // rtc::textured::launch_trace*); read by that build's prepare_hit only.
+    const R* uv_plain;
+    const R* uv_inst;
+    const uint32_t* texels;
+    const TexRec* textures;
 };
 
 }  // namespace rtc

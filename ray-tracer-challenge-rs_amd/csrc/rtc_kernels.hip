@@ -50,8 +50,19 @@
 // worlds without instances run the kernels they ran before: as a runtime
 // branch the instance level cost the f32 pool kernel 72 B/lane of scratch
 // against the 64 of tests/test_isa_budget.py.
+//
+// Texture variant: built with -DRTC_INSTANCES=1 -DRTC_TEXTURES=1
+// -DRTC_VARIANT=textured (one TU per precision), the instance variant plus the
+// texture code of prepare_hit (a textured triangle's coordinates, image_color)
+// as rtc::textured::launch_trace*, for worlds uploaded with an image pattern or
+// a texture coordinate (rt_scene_upload_textured).  Inside the instance variant
+// the same code, never run there, cost untextured instanced and smooth worlds
+// about 1 % a frame, so that variant compiles none of it.
 #ifndef RTC_INSTANCES
 #define RTC_INSTANCES 0
+#endif
+#ifndef RTC_TEXTURES
+#define RTC_TEXTURES 0
 #endif
 #if defined(RTC_VARIANT) && !RTC_INSTANCES
 #define RTC_POOL_ONLY 1  // a kind variant: the f32 pool kernel alone
@@ -1776,6 +1787,56 @@ __device__ inline V3<R> pattern_color(const DevScene<R>& sc, int pid, const Shap
     return pattern_color_obj(sc, pid, xform_point(s.inv, p));
 }
 
+#if !defined(RTC_JIT) && RTC_TEXTURES
+// An image pattern's colour (rtc.h rt_scene_upload_textured; the texture build
+// only).  (u, v): the hit's interpolated texture coordinates when `have_uv`,
+// wrapped where outside [0, 1]; else the planar map of the pattern-space point
+// of `obj`.  One dword per texel and lane for the nearest filter, four for the
+// bilinear one; the texture's record is read per lane by the pattern's index.
+// Inlined into prepare_hit: as a call it cost every kernel of the build a stack
+// frame (16 to 40 B of scratch a lane more).
+// Indices are clamped into the texture after the definition's arithmetic (a
+// NaN coordinate reads texel 0, nothing out of bounds).
+template <typename R>
+__device__ inline V3<R> texel_color(uint32_t t) {
+    using T = Real<R>;
+    return {T::div((R)(t & 0xFFu), (R)255), T::div((R)((t >> 8) & 0xFFu), (R)255), T::div((R)((t >> 16) & 0xFFu), (R)255)};
+}
+template <typename R>
+__device__ inline V3<R> image_color(const PatternRec<R>* pr, const uint32_t* texels,
+                                                        const TexRec* textures, bool have_uv, R u, R v, V3<R> obj) {
+    using T = Real<R>;
+    if (have_uv) {
+        if (!(u >= (R)0 && u <= (R)1)) u = u - T::floor(u);
+        if (!(v >= (R)0 && v <= (R)1)) v = v - T::floor(v);
+    } else {
+        const V3<R> pp = xform_point(pr->inv, obj);
+        u = pp.x - T::floor(pp.x);
+        v = pp.z - T::floor(pp.z);
+    }
+    const TexRec tr = textures[pr->sub_a];
+    const int w1 = (int)tr.width - 1, h1 = (int)tr.height - 1;
+    const uint32_t* const base = texels + tr.offset;
+    const R x = u * (R)w1, y = ((R)1 - v) * (R)h1;
+    const R xf = T::floor(x), yf = T::floor(y);
+    const R fx = x - xf, fy = y - yf;
+    const int x0 = min(max((int)xf, 0), w1), y0 = min(max((int)yf, 0), h1);
+    if (pr->sub_b == RT_FILTER_NEAREST) {
+        const int xi = min(x0 + (fx >= (R)0.5 ? 1 : 0), w1), yi = min(y0 + (fy >= (R)0.5 ? 1 : 0), h1);
+        return texel_color<R>(base[(size_t)yi * tr.width + xi]);
+    }
+    const int x1 = min(x0 + 1, w1), y1 = min(y0 + 1, h1);
+    const uint32_t* const r0 = base + (size_t)y0 * tr.width;
+    const uint32_t* const r1 = base + (size_t)y1 * tr.width;
+    const V3<R> c00 = texel_color<R>(r0[x0]), c10 = texel_color<R>(r0[x1]);
+    const V3<R> c01 = texel_color<R>(r1[x0]), c11 = texel_color<R>(r1[x1]);
+    const R gx = (R)1 - fx, gy = (R)1 - fy;
+    return {(c00.x * gx + c10.x * fx) * gy + (c01.x * gx + c11.x * fx) * fy,
+            (c00.y * gx + c10.y * fx) * gy + (c01.y * gx + c11.y * fx) * fy,
+            (c00.z * gx + c10.z * fx) * gy + (c01.z * gx + c11.z * fx) * fy};
+}
+#endif
+
 // Per-thread event counters (rt_stats order).
 // Event counters of one wave (rt_stats order), kept wave-uniform: each
 // event is counted as popcount(ballot(flag)) at a point every lane of the
@@ -1938,7 +1999,11 @@ __device__ inline const MaterialRec<R>& prepare_hit(const DevScene<R>& sc, V3<R>
     }
 #endif
 #if !defined(RTC_JIT) && RTC_INSTANCES
+#if RTC_TEXTURES
+    {  // (every world this build runs has instances, a smooth table or textures)
+#else
     if (kernarg_params<R>().n_instances || kernarg_params<R>().smooth_plain) {  // wave-uniform (launch parameters)
+#endif
         // A world with mesh instances: a virtual triangle's record is put
         // together from its instance (inverse, material) and the mesh's local
         // record (the normal), the expansion's record field by field, so the
@@ -1952,6 +2017,32 @@ __device__ inline const MaterialRec<R>& prepare_hit(const DevScene<R>& sc, V3<R>
         const int kind = h.kind & 0xFF;
         q.p = along(o, d, h.t);
         V3<R> ln;
+#if RTC_TEXTURES
+        R tu = (R)0, tv = (R)0;  // a textured triangle's interpolated coordinates (below)
+        bool have_uv = false;
+        if (kind == RT_SHAPE_TRIANGLE && (g->flags & kShapeUV)) {
+            // A triangle with texture coordinates (rtc.h rt_scene_upload_textured;
+            // the bit is set in textured worlds only): the triangle test once
+            // more for the u and v of the accepted hit, as for a smooth
+            // triangle, which it then serves too; t2 u + t3 v + t1 (1 - u - v)
+            // per component, left to right.  Six per-lane loads.
+            const R* const tt = virt ? P.uv_inst + (size_t)h.slot * kUVReals
+                                     : P.uv_plain + (size_t)(h.slot - sc.kind_begin[RT_SHAPE_TRIANGLE]) * kUVReals;
+            const TriangleTest<R> b = triangle_test(*g, xform_point(inv, o), xform_vector(inv, d));
+            const R w = ((R)1 - b.u) - b.v;
+            tu = (tt[2] * b.u + tt[4] * b.v) + tt[0] * w;
+            tv = (tt[3] * b.u + tt[5] * b.v) + tt[1] * w;
+            have_uv = true;
+            if (g->flags & kShapeSmooth) {
+                const R* const nn = virt ? P.smooth_inst + (size_t)h.slot * kSmoothReals
+                                         : P.smooth_plain + (size_t)(h.slot - sc.kind_begin[RT_SHAPE_TRIANGLE]) * kSmoothReals;
+                ln = {(nn[3] * b.u + nn[6] * b.v) + nn[0] * w, (nn[4] * b.u + nn[7] * b.v) + nn[1] * w,
+                      (nn[5] * b.u + nn[8] * b.v) + nn[2] * w};
+            } else {
+                ln = local_normal(*g, kind, xform_point(inv, q.p));
+            }
+        } else
+#endif
         if (kind == RT_SHAPE_TRIANGLE && (g->flags & kShapeSmooth)) {
             // A smooth triangle (rtc.h rt_scene_upload_smooth): the triangle
             // test once more on this one record with the lane's local ray, as
@@ -1976,7 +2067,18 @@ __device__ inline const MaterialRec<R>& prepare_hit(const DevScene<R>& sc, V3<R>
         q.over = along(q.p, q.n, q.off);
         q.base = {m.color[0], m.color[1], m.color[2]};
         patterned = m.pattern >= 0;
+#if RTC_TEXTURES
+        if (patterned) {
+            // (an image pattern exists in textured worlds only; its fetch stays out of line of every other path)
+            const PatternRec<R>* const pr = &sc.lpats[m.pattern];
+            if (P.textures && pr->kind == RT_PATTERN_IMAGE)
+                q.base = image_color<R>(pr, P.texels, P.textures, have_uv, tu, tv, xform_point(inv, q.over));
+            else
+                q.base = pattern_color_obj(sc, m.pattern, xform_point(inv, q.over));  // pattern_color
+        }
+#else
         if (patterned) q.base = pattern_color_obj(sc, m.pattern, xform_point(inv, q.over));  // pattern_color
+#endif
         return m;
     }
 #endif

@@ -43,6 +43,9 @@ inline bool pattern_eq(const rt_pattern_desc* P, int a, int b, int depth = 0) {
     if (x.kind == RT_PATTERN_COMPLEX)
         return pattern_eq(P, x.sub_a, y.sub_a, depth + 1) && pattern_eq(P, x.sub_b, y.sub_b, depth + 1);
     if (x.kind == RT_PATTERN_TEST) return true;  // pattern.rs:29-32: the transform only
+    // An image pattern (rtc.h rt_scene_upload_textured): its filter and its texture by content.  The upload
+    // renumbers sub_a to the first texture with the same width, height and bytes before any comparison.
+    if (x.kind == RT_PATTERN_IMAGE) return x.sub_a == y.sub_a && x.reserved == y.reserved;
     return reals_eq(x.color_a, y.color_a, 3) && reals_eq(x.color_b, y.color_b, 3);
 }
 
@@ -68,14 +71,24 @@ inline bool normals_eq(const double* a, const double* b) {
     return reals_eq(a, b, 9);
 }
 
+// Texture coordinates (rtc.h rt_scene_upload_textured) are six more values of
+// a triangle, given like the normals: per shape its six doubles or null.  Two
+// triangles with coordinates are equal iff their other parts and all six
+// components are; one with and one without never are.
+inline bool uvs_eq(const double* a, const double* b) {
+    if (!a || !b) return !a && !b;
+    return reals_eq(a, b, 6);
+}
+
 // dyn Shape equality (shape.rs:34-38): same kind, then the derived field-wise
 // equality of that kind.  A triangle's vertex_2/vertex_3 are not in the
 // descriptor; they are compared through vertex_1 + edges.
 inline bool shape_eq(const rt_shape_desc* S, const rt_material_desc* M, const rt_pattern_desc* P, uint32_t a,
-                     uint32_t b, Normals N = nullptr) {
+                     uint32_t b, Normals N = nullptr, Normals UV = nullptr) {
     if (a == b) return true;
     const rt_shape_desc &x = S[a], &y = S[b];
     if (!normals_eq(normals_of(N, a), normals_of(N, b))) return false;
+    if (!uvs_eq(normals_of(UV, a), normals_of(UV, b))) return false;
     if (x.kind != y.kind || !reals_eq(x.inverse, y.inverse, 16)) return false;
     if (x.kind == RT_SHAPE_CYLINDER || x.kind == RT_SHAPE_CONE)
         if (!(x.minimum == y.minimum && x.maximum == y.maximum && (x.closed != 0) == (y.closed != 0))) return false;
@@ -88,7 +101,7 @@ inline bool shape_eq(const rt_shape_desc* S, const rt_material_desc* M, const rt
 
 // Hash consistent with shape_eq's geometry part (-0 and +0 hash alike);
 // materials are compared exactly within a bucket.
-inline uint64_t geometry_hash(const rt_shape_desc& s, const double* normals = nullptr) {
+inline uint64_t geometry_hash(const rt_shape_desc& s, const double* normals = nullptr, const double* uv = nullptr) {
     uint64_t h = 1469598103934665603ull ^ (uint64_t)(uint32_t)s.kind;
     auto mix = [&h](double v) {
         if (v == 0.0) v = 0.0;  // -0 == +0
@@ -110,6 +123,8 @@ inline uint64_t geometry_hash(const rt_shape_desc& s, const double* normals = nu
         for (double v : s.edge_2) mix(v);
         if (normals)
             for (int q = 0; q < 9; ++q) mix(normals[q]);
+        if (uv)
+            for (int q = 0; q < 6; ++q) mix(uv[q]);
     }
     return h;
 }
@@ -118,15 +133,16 @@ inline uint64_t geometry_hash(const rt_shape_desc& s, const double* normals = nu
 // for a shape equal to no earlier one).  Returns the number of shapes that
 // equal an earlier one.
 inline uint32_t shape_classes(const rt_shape_desc* S, uint32_t n, const rt_material_desc* M,
-                              const rt_pattern_desc* P, std::vector<uint32_t>& cls, Normals N = nullptr) {
+                              const rt_pattern_desc* P, std::vector<uint32_t>& cls, Normals N = nullptr,
+                              Normals UV = nullptr) {
     cls.resize(n);
     std::unordered_map<uint64_t, std::vector<uint32_t>> buckets;  // hash -> class representatives
     uint32_t dups = 0;
     for (uint32_t i = 0; i < n; ++i) {
         cls[i] = i;
-        auto& reps = buckets[geometry_hash(S[i], normals_of(N, i))];
+        auto& reps = buckets[geometry_hash(S[i], normals_of(N, i), normals_of(UV, i))];
         for (uint32_t r : reps)
-            if (shape_eq(S, M, P, r, i, N)) {
+            if (shape_eq(S, M, P, r, i, N, UV)) {
                 cls[i] = r;
                 ++dups;
                 break;

@@ -28,6 +28,7 @@ __all__ = [
     "RenderError", "lib_path", "abi_version", "device_count", "matrix_inverse", "camera_make",
     "camera_resize", "camera_set_transform", "camera_bound_rect", "load_scene", "load_scene_text", "SceneTables", "Context", "shard_rows",
     "load_obj", "Mesh", "SmoothDesc", "RT_SMOOTH_SHAPES", "RT_OBJ_NORMALS", "RT_NO_NORMAL",
+    "UVDesc", "TextureDesc", "RT_OBJ_TEXCOORDS", "RT_NO_TEXCOORD", "TEXTURE_FILTERS", "read_image",
     "RT_DEFAULT_MAX_DEPTH", "RT_TILE_H", "RT_TILE_W",
 ]
 
@@ -49,9 +50,12 @@ RT_GATHER_RCCL, RT_GATHER_PEER = 0, 1
 RT_SMOOTH_SHAPES = 0xFFFFFFFF  # rt_smooth_desc.list: `index` counts the plain shapes
 RT_OBJ_NORMALS = 1             # rt_mesh_load_obj_ex: read vn lines and the faces' normal indices
 RT_NO_NORMAL = 0xFFFFFFFF      # rt_mesh_normals_view.triangle_normals of a flat face
+RT_OBJ_TEXCOORDS = 4           # rt_mesh_load_obj_ex: read vt lines and the faces' texture indices
+RT_NO_TEXCOORD = 0xFFFFFFFF    # rt_mesh_texcoords_view.triangle_texcoords of a face without coordinates
+TEXTURE_FILTERS = {"nearest": 0, "bilinear": 1}  # rt_pattern_desc.reserved of an image pattern
 
 SHAPE_KINDS = {"sphere": 0, "plane": 1, "cube": 2, "cylinder": 3, "cone": 4, "triangle": 5}
-PATTERN_KINDS = {"stripe": 0, "gradient": 1, "ring": 2, "checker": 3, "complex": 4, "test": 5}
+PATTERN_KINDS = {"stripe": 0, "gradient": 1, "ring": 2, "checker": 3, "complex": 4, "test": 5, "image": 6}
 PRECISIONS = {"f32": 0, "f64": 1}
 # rt_render_options.flags: diagnostic ablations (rtc.h); never in a parity or bench result
 RT_FLAG_NO_COUNTERS, RT_FLAG_NO_SHADE, RT_FLAG_NO_TRACE, RT_FLAG_STAMPS, RT_FLAG_FAIL_LAUNCH = 1, 2, 4, 8, 16
@@ -177,6 +181,25 @@ class SmoothInfo(C.Structure):
     _fields_ = [("smooth_triangles", C.c_uint32), ("ran_smooth", C.c_uint32), ("normal_bytes", C.c_uint64)]
 
 
+class UVDesc(C.Structure):
+    _fields_ = [("list", C.c_uint32), ("index", C.c_uint32), ("uv_1", C.c_double * 2), ("uv_2", C.c_double * 2),
+                ("uv_3", C.c_double * 2)]
+
+
+class TextureDesc(C.Structure):
+    _fields_ = [("rgb", C.POINTER(C.c_uint8)), ("width", C.c_uint32), ("height", C.c_uint32)]
+
+
+class TextureInfo(C.Structure):
+    _fields_ = [("textured_triangles", C.c_uint32), ("textures", C.c_uint32), ("ran_textured", C.c_uint32),
+                ("reserved", C.c_uint32), ("uv_bytes", C.c_uint64), ("texel_bytes", C.c_uint64)]
+
+
+class MeshTexcoordsView(C.Structure):
+    _fields_ = [("texcoords", C.POINTER(C.c_double)), ("n_texcoords", C.c_uint32), ("n_textured", C.c_uint32),
+                ("triangle_texcoords", C.POINTER(C.c_uint32))]
+
+
 class MeshNormalsView(C.Structure):
     _fields_ = [("normals", C.POINTER(C.c_double)), ("n_normals", C.c_uint32), ("n_smooth", C.c_uint32),
                 ("triangle_normals", C.POINTER(C.c_uint32))]
@@ -270,6 +293,17 @@ def _load() -> C.CDLL:
         "rt_mesh_normals_get": (C.c_int, [C.c_void_p, P(MeshNormalsView)]),
         "rt_mesh_smooth_normals": (C.c_int, [C.c_void_p, P(C.c_double), C.c_int, P(SmoothDesc), C.c_uint32,
                                              P(C.c_uint32)]),
+        "rt_scene_upload_textured": (C.c_int, [C.c_void_p, P(ShapeDesc), C.c_uint32, P(MeshDesc), C.c_uint32,
+                                               P(InstanceDesc), C.c_uint32, P(SmoothDesc), C.c_uint32, P(UVDesc),
+                                               C.c_uint32, P(TextureDesc), C.c_uint32, P(MaterialDesc), C.c_uint32,
+                                               P(PatternDesc), C.c_uint32, P(LightDesc), C.c_uint32]),
+        "rt_uv_expand": (C.c_int, [P(ShapeDesc), C.c_uint32, P(MeshDesc), C.c_uint32, P(InstanceDesc), C.c_uint32,
+                                   P(UVDesc), C.c_uint32, P(UVDesc), P(C.c_uint32)]),
+        "rt_scene_texture_info": (C.c_int, [C.c_void_p, P(TextureInfo)]),
+        "rt_mesh_texcoords_get": (C.c_int, [C.c_void_p, P(MeshTexcoordsView)]),
+        "rt_mesh_uvs": (C.c_int, [C.c_void_p, P(UVDesc), C.c_uint32, P(C.c_uint32)]),
+        "rt_image_read": (C.c_int, [C.c_char_p, P(P(C.c_uint8)), P(C.c_uint32), P(C.c_uint32)]),
+        "rt_image_free": (None, [P(C.c_uint8)]),
         "rt_image_write": (C.c_int, [C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint32]),
         "rt_image_write_format": (C.c_int, [C.c_char_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int]),
         "rt_canvas_quantize": (C.c_int, [P(C.c_double), C.c_uint64, P(C.c_uint8)]),
@@ -334,6 +368,8 @@ EXPORTED_SYMBOLS = (
     "rt_scene_upload_instanced", "rt_instances_expand", "rt_scene_instance_info",
     "rt_scene_upload_smooth", "rt_smooth_expand", "rt_scene_smooth_info",
     "rt_mesh_load_obj_ex", "rt_mesh_normals_get", "rt_mesh_smooth_normals",
+    "rt_scene_upload_textured", "rt_uv_expand", "rt_scene_texture_info", "rt_mesh_texcoords_get", "rt_mesh_uvs",
+    "rt_image_read", "rt_image_free",
 )
 
 
@@ -427,6 +463,17 @@ def write_image(path, image: np.ndarray, fmt: str = "auto") -> None:
                                       img.shape[0], IMAGE_FORMATS[fmt]))
 
 
+def read_image(path) -> np.ndarray:
+    """rt_image_read: a PPM (P3, P6) or PNG (8-bit RGB / RGBA, alpha dropped) file as a uint8 array of shape
+    (H, W, 3), row 0 at the top: what world.image_pattern takes."""
+    rgb, w, h = C.POINTER(C.c_uint8)(), C.c_uint32(0), C.c_uint32(0)
+    _check(_lib.rt_image_read(os.fsencode(path), C.byref(rgb), C.byref(w), C.byref(h)))
+    try:
+        return np.ctypeslib.as_array(rgb, (h.value, w.value, 3)).copy()
+    finally:
+        _lib.rt_image_free(rgb)
+
+
 def canvas_quantize(image: np.ndarray) -> np.ndarray:
     """canvas.rs:81, 117-123 on the host: round(clamp(c, 0, 1) * 255) as u8 of an f64 canvas."""
     src = np.ascontiguousarray(image, dtype=np.float64)
@@ -474,6 +521,36 @@ class SceneTables:
     # Smooth triangles (rtc.h rt_scene_upload_smooth): an array of SmoothDesc naming triangles of `shapes`
     # (list = RT_SMOOTH_SHAPES) or of a mesh, with their three vertex normals; None / empty = none.
     smooth: C.Array | None = None
+    # Image textures (rtc.h rt_scene_upload_textured): an array of UVDesc naming triangles like `smooth` with
+    # their three texture coordinates, and the textures image patterns index (pattern.sub_a): uint8 arrays
+    # of shape (H, W, 3); None / empty = none.
+    uvs: C.Array | None = None
+    textures: list | None = None
+
+    @property
+    def textured(self) -> bool:
+        return (self.uvs is not None and len(self.uvs) > 0) or bool(self.textures) or \
+            any(p.kind == PATTERN_KINDS["image"] for p in self.patterns)
+
+    def texture_descs(self):
+        """The TextureDesc array over `textures` (it borrows their memory: keep the tables alive)."""
+        tex = [np.ascontiguousarray(t, dtype=np.uint8) for t in (self.textures or [])]
+        arr = (TextureDesc * len(tex))()
+        for i, t in enumerate(tex):
+            if t.ndim != 3 or t.shape[2] != 3:
+                raise ValueError("a texture is a uint8 array of shape (H, W, 3)")
+            arr[i].rgb = t.ctypes.data_as(C.POINTER(C.c_uint8))
+            arr[i].width, arr[i].height = t.shape[1], t.shape[0]
+        arr._keep = tex
+        return arr
+
+    def textured_args(self):
+        """rt_scene_upload_textured's arguments after the context: smooth_args() with the coordinate list
+        and the texture list after the smooth list."""
+        a = self.smooth_args()
+        uv = self.uvs if self.uvs is not None else (UVDesc * 0)()
+        td = self.texture_descs()
+        return a[:8] + (uv, len(uv), td, len(td)) + a[8:]
 
     @property
     def instanced(self) -> bool:
@@ -523,7 +600,15 @@ class SceneTables:
             _check(_lib.rt_smooth_expand(*a, None, C.byref(n)))
             smooth = (SmoothDesc * n.value)()
             _check(_lib.rt_smooth_expand(*a, smooth, C.byref(n)))
-        return SceneTables(out, self.materials, self.patterns, self.lights, self.camera, smooth=smooth)
+        uvs = None
+        if self.uvs is not None and len(self.uvs):
+            n = C.c_uint32(0)
+            a = self.instanced_args()[:6] + (self.uvs, len(self.uvs))
+            _check(_lib.rt_uv_expand(*a, None, C.byref(n)))
+            uvs = (UVDesc * n.value)()
+            _check(_lib.rt_uv_expand(*a, uvs, C.byref(n)))
+        return SceneTables(out, self.materials, self.patterns, self.lights, self.camera, smooth=smooth, uvs=uvs,
+                           textures=self.textures)
 
     @property
     def counts(self):
@@ -591,6 +676,25 @@ class Mesh:
         self.triangle_normals = np.ctypeslib.as_array(nv.triangle_normals, (v.n_triangles, 3)).copy() \
             if nv.triangle_normals and v.n_triangles else np.zeros((0, 3), dtype=np.uint32)
         self.n_smooth = int(nv.n_smooth)
+        # load_obj(..., texcoords=True): the vt lines (k, 2) f64 (u, v), per triangle its three 0-based
+        # indices (RT_NO_TEXCOORD x 3 for a face without) and the number of triangles with coordinates
+        tv = MeshTexcoordsView()
+        _check(_lib.rt_mesh_texcoords_get(self._h, C.byref(tv)))
+        self.texcoords = np.ctypeslib.as_array(tv.texcoords, (tv.n_texcoords, 2)).copy() if tv.n_texcoords else \
+            np.zeros((0, 2), dtype=np.float64)
+        self.triangle_texcoords = np.ctypeslib.as_array(tv.triangle_texcoords, (v.n_triangles, 3)).copy() \
+            if tv.triangle_texcoords and v.n_triangles else np.zeros((0, 3), dtype=np.uint32)
+        self.n_textured = int(tv.n_textured)
+
+    def uv_descs(self, list_index: int = RT_SMOOTH_SHAPES, first: int = 0):
+        """rt_mesh_uvs: one UVDesc per triangle with texture coordinates, pairing with shape_descs(); `first`
+        is added to every index.  Coordinates do not transform: there is no bake."""
+        out = (UVDesc * self.n_textured)()
+        n = C.c_uint32(0)
+        _check(_lib.rt_mesh_uvs(self._h, out if self.n_textured else None, int(list_index), C.byref(n)))
+        for d in out:
+            d.index += first
+        return out
 
     def smooth_descs(self, transform=None, bake: bool = False, list_index: int = RT_SMOOTH_SHAPES, first: int = 0):
         """rt_mesh_smooth_normals: one SmoothDesc per smooth triangle, pairing with shape_descs(transform,
@@ -620,17 +724,19 @@ class Mesh:
             pass
 
 
-def load_obj(path_or_text, normals: bool = False) -> Mesh:
+def load_obj(path_or_text, normals: bool = False, texcoords: bool = False) -> Mesh:
     """An OBJ file (a path: str without a newline, bytes or os.PathLike) or OBJ text (a str holding a
     newline) -> Mesh.  Raises RenderError(RT_ERR_IO) with the line number for a bad v or f line.
     normals=True also reads the vn lines and the faces' normal indices (Mesh.normals, triangle_normals,
-    n_smooth; rtc_scene.h rt_mesh_load_obj_ex)."""
+    n_smooth; rtc_scene.h rt_mesh_load_obj_ex); texcoords=True the vt lines and the faces' texture indices
+    (Mesh.texcoords, triangle_texcoords, n_textured)."""
     h = C.c_void_p()
-    if normals:
+    flags = (RT_OBJ_NORMALS if normals else 0) | (RT_OBJ_TEXCOORDS if texcoords else 0)
+    if flags:
         if isinstance(path_or_text, str) and "\n" in path_or_text:
-            _check(_lib.rt_mesh_load_obj_ex(None, path_or_text.encode(), RT_OBJ_NORMALS, C.byref(h)))
+            _check(_lib.rt_mesh_load_obj_ex(None, path_or_text.encode(), flags, C.byref(h)))
         else:
-            _check(_lib.rt_mesh_load_obj_ex(os.fsencode(path_or_text), None, RT_OBJ_NORMALS, C.byref(h)))
+            _check(_lib.rt_mesh_load_obj_ex(os.fsencode(path_or_text), None, flags, C.byref(h)))
     elif isinstance(path_or_text, str) and "\n" in path_or_text:
         _check(_lib.rt_mesh_load_obj_text(path_or_text.encode(), C.byref(h)))
     else:
@@ -764,11 +870,21 @@ class Context:
         _check(_lib.rt_scene_smooth_info(self._h, C.byref(t)))
         return {name: getattr(t, name) for name, _ in t._fields_}
 
+    def texture_info(self) -> dict:
+        """The uploaded world's textures (rtc.h rt_scene_texture_info): triangles with coordinates, textures,
+        the device bytes of the coordinate tables and the texels, whether the last launch ran the texture code."""
+        t = TextureInfo()
+        _check(_lib.rt_scene_texture_info(self._h, C.byref(t)))
+        return {name: getattr(t, name) for name, _ in t._fields_ if name != "reserved"}
+
     def upload(self, scene: SceneTables | None) -> None:
-        """rt_scene_upload, rt_scene_upload_instanced for tables with instances, or rt_scene_upload_smooth for
-        tables with smooth triangles; on a non-zero rank of a group, None (the scene comes from rank 0)."""
+        """rt_scene_upload, rt_scene_upload_instanced for tables with instances, rt_scene_upload_smooth for
+        tables with smooth triangles, or rt_scene_upload_textured for tables with texture coordinates or
+        textures; on a non-zero rank of a group, None (the scene comes from rank 0)."""
         if scene is None:
             _check(_lib.rt_scene_upload(self._h, None, 0, None, 0, None, 0, None, 0))
+        elif scene.textured:
+            _check(_lib.rt_scene_upload_textured(self._h, *scene.textured_args()))
         elif scene.smoothed:
             _check(_lib.rt_scene_upload_smooth(self._h, *scene.smooth_args()))
         elif scene.instanced:

@@ -21,7 +21,7 @@ import math
 from dataclasses import dataclass, field
 
 from . import (CameraDesc, InstanceDesc, LightDesc, MaterialDesc, PatternDesc, PATTERN_KINDS, RT_SMOOTH_SHAPES,
-               SceneTables, ShapeDesc, SHAPE_KINDS, SmoothDesc, camera_make, matrix_inverse)
+               SceneTables, ShapeDesc, SHAPE_KINDS, SmoothDesc, TEXTURE_FILTERS, UVDesc, camera_make, matrix_inverse)
 
 F64_MAX = 1.7976931348623157e308
 IDENTITY = [[1.0 if i == j else 0.0 for j in range(4)] for i in range(4)]
@@ -93,6 +93,10 @@ class Pattern:
     transformation_inverse: list = field(default_factory=lambda: [row[:] for row in IDENTITY])
     sub_a: "Pattern | None" = None
     sub_b: "Pattern | None" = None
+    # an image pattern (rtc.h rt_scene_upload_textured): a uint8 array of shape (H, W, 3), row 0 at the top, and
+    # the filter (TEXTURE_FILTERS); two patterns that hold the same array object share one texture of the upload
+    image: object = field(default=None, compare=False)
+    filter: int = 0
 
     def set_transformation(self, m):
         self.transformation_inverse = inverse(m)
@@ -117,6 +121,17 @@ def checker_pattern(a, b):
 
 def complex_pattern(a: Pattern, b: Pattern):
     return Pattern("complex", sub_a=a, sub_b=b)
+
+
+def image_pattern(image, filter="nearest"):
+    """An image texture as a material's pattern (rtc.h rt_scene_upload_textured): `image` is a uint8 array of
+    shape (H, W, 3), row 0 at the top (rtc_amd.read_image); a triangle with texture coordinates samples it at
+    the interpolated (u, v), every other hit through the planar map of the pattern-space point."""
+    import numpy as np
+    img = np.ascontiguousarray(image, dtype=np.uint8)
+    if img.ndim != 3 or img.shape[2] != 3 or not img.size:
+        raise ValueError("image_pattern takes a uint8 array of shape (H, W, 3)")
+    return Pattern("image", image=img, filter=TEXTURE_FILTERS[filter])
 
 
 def test_pattern():
@@ -152,6 +167,7 @@ class Shape:
     closed: bool = False
     triangle: tuple | None = None  # (v1, e1, e2, normal)
     normals: tuple | None = None   # a smooth triangle's (n1, n2, n3), used as given; None: flat
+    uvs: tuple | None = None       # a triangle's texture coordinates (t1, t2, t3) of p1, p2, p3; None: none
 
     def set_transformation(self, m):
         self.transformation_inverse = inverse(m)
@@ -217,11 +233,20 @@ def smooth_triangle(p1, p2, p3, n1, n2, n3, material=None):
     return s
 
 
-def mesh(m, material=None, transform=None, bake=False, smooth=False):
+def textured_triangle(p1, p2, p3, t1, t2, t3, material=None):
+    """triangle(p1, p2, p3) with the texture coordinates t1, t2, t3 of p1, p2, p3 (rtc.h
+    rt_scene_upload_textured): an image pattern is sampled at t2 u + t3 v + t1 (1 - u - v)."""
+    s = triangle(p1, p2, p3, material)
+    s.uvs = tuple(tuple(map(float, t)) for t in (t1, t2, t3))
+    return s
+
+
+def mesh(m, material=None, transform=None, bake=False, smooth=False, textured=False):
     """The faces of a Mesh (rtc_amd.load_obj) as Triangle shapes sharing `material`, through the host's
     rt_mesh_triangles: Triangle::new per face; with `transform` either set_transformation on every triangle
     (bake=False) or the vertices multiplied by it first (bake=True, identity inverse).  smooth=True makes the
-    faces that name three normals (load_obj(..., normals=True)) smooth triangles; the others stay flat."""
+    faces that name three normals (load_obj(..., normals=True)) smooth triangles; the others stay flat.
+    textured=True gives the faces that name three texture coordinates (load_obj(..., texcoords=True)) theirs."""
     mat = material or Material()
     t = None if transform is None else [v for row in transform for v in row]
     out = []
@@ -232,6 +257,9 @@ def mesh(m, material=None, transform=None, bake=False, smooth=False):
     if smooth:
         for d in m.smooth_descs(t, bake):
             out[d.index].normals = (tuple(d.normal_1), tuple(d.normal_2), tuple(d.normal_3))
+    if textured:
+        for d in m.uv_descs():
+            out[d.index].uvs = (tuple(d.uv_1), tuple(d.uv_2), tuple(d.uv_3))
     return out
 
 
@@ -243,13 +271,15 @@ class Instance:
     material: Material = field(default_factory=Material)
     transformation_inverse: list = field(default_factory=lambda: [row[:] for row in IDENTITY])
     smooth: bool = False  # the mesh's faces with three normals are smooth triangles (another mesh than its flat use)
+    textured: bool = False  # the mesh's faces with three texture coordinates carry them (another mesh again)
 
 
-def instance(m, material=None, transform=None, smooth=False):
+def instance(m, material=None, transform=None, smooth=False, textured=False):
     """A Mesh (rtc_amd.load_obj) placed by `transform` with `material`: an Instance for World.instances.
     The device keeps the mesh's triangles once however many instances place it.  smooth=True: the faces
-    that name three normals are smooth triangles and keep their local normals under the placement."""
-    i = Instance(m, material or Material(), smooth=smooth)
+    that name three normals are smooth triangles and keep their local normals under the placement;
+    textured=True: the faces that name three texture coordinates keep them under every placement."""
+    i = Instance(m, material or Material(), smooth=smooth, textured=textured)
     if transform is not None:
         i.transformation_inverse = inverse(transform)
     return i
@@ -304,17 +334,21 @@ class World:
         mats = (MaterialDesc * (len(self.shapes) + len(self.instances)))()
         meshes, mesh_of, inst = [], [], (InstanceDesc * len(self.instances))()
         smooth = []  # SmoothDesc entries: the meshes' in mesh order, then the shapes'
+        uvs = []     # UVDesc entries, in the same order
+        textures = []  # the image patterns' arrays, one entry per array object
         for k, it in enumerate(self.instances):
             for j, seen in enumerate(mesh_of):
-                if seen[0] is it.mesh and seen[1] == bool(it.smooth):
+                if seen[0] is it.mesh and seen[1] == (bool(it.smooth), bool(it.textured)):
                     inst[k].mesh = j
                     break
             else:
                 inst[k].mesh = len(meshes)
-                mesh_of.append((it.mesh, bool(it.smooth)))
+                mesh_of.append((it.mesh, (bool(it.smooth), bool(it.textured))))
                 meshes.append(it.mesh.shape_descs())  # local triangles: identity inverse
                 if it.smooth:
                     smooth.extend(it.mesh.smooth_descs(list_index=inst[k].mesh))
+                if it.textured:
+                    uvs.extend(it.mesh.uv_descs(list_index=inst[k].mesh))
             inst[k].material = len(self.shapes) + k
             inst[k].inverse[:] = [float(v) for row in it.transformation_inverse for v in row]
             put_material(mats[len(self.shapes) + k], it.material)
@@ -331,6 +365,10 @@ class World:
                 e = SmoothDesc(RT_SMOOTH_SHAPES, i)
                 e.normal_1[:], e.normal_2[:], e.normal_3[:] = [list(map(float, n)) for n in s.normals]
                 smooth.append(e)
+            if s.uvs is not None:
+                e = UVDesc(RT_SMOOTH_SHAPES, i)
+                e.uv_1[:], e.uv_2[:], e.uv_3[:] = [list(map(float, t)) for t in s.uvs]
+                uvs.append(e)
         ptab = (PatternDesc * len(pats))()
         for i, p in enumerate(pats):
             d = ptab[i]
@@ -340,13 +378,23 @@ class World:
             d.inverse[:] = [float(v) for row in p.transformation_inverse for v in row]
             d.sub_a = pats.index(p.sub_a) if p.sub_a is not None else -1
             d.sub_b = pats.index(p.sub_b) if p.sub_b is not None else -1
+            if p.kind == "image":
+                for j, t in enumerate(textures):
+                    if t is p.image:
+                        d.sub_a = j
+                        break
+                else:
+                    d.sub_a = len(textures)
+                    textures.append(p.image)
+                d.reserved = int(p.filter)
         lts = (LightDesc * len(self.lights))()
         for i, lt in enumerate(self.lights):
             lts[i].position[:] = list(map(float, lt.position))
             lts[i].intensity[:] = list(map(float, lt.intensity))
         return SceneTables(shapes, mats, ptab, lts, camera if camera is not None else CameraDesc(),
                            meshes=meshes or None, instances=inst if len(inst) else None,
-                           smooth=(SmoothDesc * len(smooth))(*smooth) if smooth else None)
+                           smooth=(SmoothDesc * len(smooth))(*smooth) if smooth else None,
+                           uvs=(UVDesc * len(uvs))(*uvs) if uvs else None, textures=textures or None)
 
 
 def camera(width, height, fov, frm=(0, 0, 0), to=(0, 0, -1), up=(0, 1, 0)) -> CameraDesc:
