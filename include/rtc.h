@@ -694,6 +694,108 @@ int rt_scene_texture_info(rt_context* ctx, rt_texture_info* out);
 int rt_image_read(const char* path, uint8_t** rgb, uint32_t* width, uint32_t* height);
 void rt_image_free(uint8_t* rgb);
 
+/* Area lights (the book's bonus chapter "Soft shadows").  The
+ * reference has none of it, so this text is the contract.
+ *
+ * An area light is a parallelogram: `corner`, the two full edges and a grid
+ * of usteps x vsteps cells, one sample per cell.
+ *
+ * Sample positions.  uvec = full_uvec / usteps and vvec = full_vvec / vsteps:
+ * IEEE divisions per component by the count as a double, done once on the
+ * host; the kernels read corner, uvec and vvec rounded once to their real
+ * type.  Cell (i, j), i < usteps, j < vsteps, has index k = j * usteps + i and
+ * the sample, per component,
+ *     pos = (corner + uvec * (i + ju)) + vvec * (j + jv)
+ * with plain multiplies and adds, left to right, in the kernel's real type.
+ * RT_JITTER_NONE: ju = jv = 0.5 (the cell's centre).
+ *
+ * Lighting.  An area light MEANS its expansion into N = usteps * vsteps point
+ * lights at those positions, each of intensity `intensity` / N, and the
+ * world's light list means
+ *     lights ++ E(area 0) ++ E(area 1) ++ ...
+ * in the idiom of rt_instances_expand.  Per area light and hit the kernels
+ * compute eff = base * intensity and ambient = eff * m.ambient once, then
+ * sum = the samples' diffuse + specular terms in ascending k, where sample k
+ * contributes only where light . normal >= 0 and is_shadowed(over_point,
+ * pos_k) is false (calculate_lighting's arithmetic with pos_k for the light's
+ * position; its specular only where reflect . eye > 0), and
+ *     colour = ambient + sum / N.
+ * That is the expansion's colour up to rounding.  It departs from the book on
+ * purpose: the book multiplies the mean unshadowed lighting by the visible
+ * fraction; weighting each sample by its own shadow test is the Monte-Carlo
+ * estimator, and the form an expansion can check.
+ *
+ * Counters are the expansion's, exactly: rt_stats.shadow counts N per area
+ * light per shaded hit, lit_patterned N per area light per patterned hit; the
+ * pattern or texture colour is evaluated once per hit, as before.
+ *
+ * The brightness bound of the fixed-point pixel sums counts an area light as
+ * a point light of `intensity`: a world rt_render* refuses with a point light
+ * is refused with the equal area light.
+ *
+ * Hashed jitter (RT_JITTER_HASHED) is precision-independent.  With uint32_t
+ * wraparound,
+ *     mix(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16
+ *     key = mix(mix(mix(seed ^ ray_id) ^ remaining) ^ ((area_index << 8) | k))
+ *     ju  = (key >> 8) * 2^-24
+ *     jv  = (mix(key ^ 0x9E3779B9) >> 8) * 2^-24
+ * both exact in f32 and f64.  `remaining` is that of the ray being shaded,
+ * area_index the light's place in the area list.  ray_id: for frames
+ * y * W + x in WHOLE-image coordinates (a shard, a canvas render and every
+ * rank of a group produce the whole frame's pixels); for supersampled frames
+ * the sample's pixel index in the sample camera Cn, (grid y + j)(grid W) +
+ * grid x + i; for rt_color_at and rt_trace_rays* the ray's index in the batch
+ * modulo 2^32.  A secondary ray keeps its primary ray's ray_id.  Results stay
+ * bit-reproducible.
+ *
+ * rt_scene_upload_lit is rt_scene_upload_textured's argument list plus the
+ * area list; with n_area = 0 it is rt_scene_upload_textured itself.  A world
+ * with an area light runs the generic kernels only, those of the area build
+ * (the texture build plus the sample loop; rt_jit_status says so in its log),
+ * whatever else it holds.  rt_lights_expand writes the expansion's light list
+ * (host only; `out` holds n_lights + the sum of the sample counts, *n_out the
+ * number written, out may be NULL to count); a hashed light, whose samples
+ * depend on the ray, is RT_ERR_INVALID there.  rt_area_light_sample gives the
+ * f64 position of one sample for either jitter mode (host only).
+ * RT_ERR_INVALID, each with its own rt_last_error text and checked before the
+ * context is looked at: a null list with a nonzero count, a step count of 0
+ * or above RT_LIGHT_MAX_STEPS, a jitter other than 0 or 1, a component that
+ * is not finite.  Zero-length edges are allowed (all samples coincide). */
+#define RT_LIGHT_MAX_STEPS 16          /* per axis: at most 256 samples */
+#define RT_JITTER_NONE   0             /* cell centres */
+#define RT_JITTER_HASHED 1             /* per ray, above */
+typedef struct rt_area_light_desc {    /* 112 bytes */
+    double corner[3], full_uvec[3], full_vvec[3], intensity[3];
+    uint32_t usteps, vsteps, jitter, seed;
+} rt_area_light_desc;
+int rt_scene_upload_lit(rt_context* ctx,
+                        const rt_shape_desc* shapes, uint32_t n_shapes,
+                        const rt_mesh_desc* meshes, uint32_t n_meshes,
+                        const rt_instance_desc* instances, uint32_t n_instances,
+                        const rt_smooth_desc* smooth, uint32_t n_smooth,
+                        const rt_uv_desc* uvs, uint32_t n_uvs,
+                        const rt_texture_desc* textures, uint32_t n_textures,
+                        const rt_material_desc* materials, uint32_t n_materials,
+                        const rt_pattern_desc* patterns, uint32_t n_patterns,
+                        const rt_light_desc* lights, uint32_t n_lights,
+                        const rt_area_light_desc* area, uint32_t n_area);
+int rt_lights_expand(const rt_light_desc* lights, uint32_t n_lights,
+                     const rt_area_light_desc* area, uint32_t n_area,
+                     rt_light_desc* out, uint32_t* n_out);
+int rt_area_light_sample(const rt_area_light_desc* desc, uint32_t area_index, uint32_t ray_id,
+                         uint32_t remaining, uint32_t k, double pos[3]);
+/* The area lights of the last upload (zeros after any other upload): how many,
+ * the sum of their sample counts, the device bytes of both precisions'
+ * records, and whether the last launch ran kernels that hold the sample loop. */
+typedef struct rt_light_info {
+    uint32_t area_lights;
+    uint32_t samples;
+    uint32_t ran_area;
+    uint32_t reserved;
+    uint64_t area_bytes;
+} rt_light_info;
+int rt_scene_light_info(rt_context* ctx, rt_light_info* out);
+
 /* Peer canvas: a frame assembled in place instead of gathered (SURVEY.md
  * §8e; the north star's "gather of framebuffer strips over xGMI" done as the
  * shards' own stores into rank 0's image).  The owner creates a device canvas

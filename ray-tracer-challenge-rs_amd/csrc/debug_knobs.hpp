@@ -7,6 +7,7 @@
 //   lds_world=0                   world tables not staged in LDS
 //   cull=0                        every shape uploaded unbounded (no wave cull)
 //   tri_tree=0                    no triangle hierarchy (every triangle record visited); read at upload
+//   area_cull=0                   area lights: no light-level caster cull (every sample culls for itself)
 //   tri_min=N | tri_leaf=N        the sweep's values of tri_tree.hpp's kTriTreeMin and kTriLeaf
 //   kind_variants=0               no sphere/plane-only pool kernel
 //   pool_lds_rays=N               LDS-resident LIFO slots (else sized for occupancy)

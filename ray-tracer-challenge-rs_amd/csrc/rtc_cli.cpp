@@ -23,7 +23,10 @@
 // §3.11; without it the output is what it was), --texture IMAGE.ppm|png with
 // --texture-filter nearest|bilinear (the --obj and --instance meshes' material
 // gets an image pattern and their vt lines are read: rt_scene_upload_textured,
-// DESIGN.md §3.12).  Pixels are quantized on the device as canvas.rs:117-123 does.
+// DESIGN.md §3.12), --area-light cx,cy,cz:ux,uy,uz:vx,vy,vz:USTEPSxVSTEPS
+// [:r,g,b][:jitter[=SEED]] (repeatable: an area light added to the scene's
+// lights, rt_scene_upload_lit).  Pixels are quantized on the
+// device as canvas.rs:117-123 does.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -41,6 +44,7 @@ static int usage() {
                  "           [--depth D] [--precision f32|f64] [--device N] [--gpus N] [--ppm-binary] [--timings]\n"
                  "           [--samples N] [--obj MESH.obj]... [--instance MESH.obj:tx,ty,tz[:s]]... [--smooth]\n"
                  "           [--texture IMAGE.ppm|png] [--texture-filter nearest|bilinear]\n"
+                 "           [--area-light cx,cy,cz:ux,uy,uz:vx,vy,vz:USTEPSxVSTEPS[:r,g,b][:jitter[=SEED]]]...\n"
                  "  --obj MESH.obj appends the mesh's triangles (v and f lines; faces fan-triangulated) to the\n"
                  "  scene's shapes, with the default material and no transformation; repeatable.\n"
                  "  --instance MESH.obj:tx,ty,tz[:s] places a copy of the mesh, scaled by s (default 1) and moved by\n"
@@ -50,12 +54,54 @@ static int usage() {
                  "  --texture IMAGE.ppm|png gives the --obj and --instance meshes' material that image as its pattern\n"
                  "  and reads the files' texture coordinates (vt lines, f i/j and i/j/k); a face without them is\n"
                  "  mapped by its x and z.  --texture-filter nearest|bilinear picks the filter (default bilinear).\n"
+                 "  --area-light adds an area light to the scene's lights: the parallelogram from corner c along the\n"
+                 "  full edges u and v, USTEPS x VSTEPS samples (1..%d each), intensity r,g,b (default 1,1,1), sampled\n"
+                 "  at the cell centres or, with jitter, at hashed positions per ray (seed SEED, default 0); repeatable.\n"
                  "  --samples N renders N x N samples per pixel (1..%d, default 1 = one ray per pixel centre) and\n"
                  "  averages them on the GPU.\n"
                  "  -r serial|parallel are accepted for the reference's command lines but render on the GPU like\n"
                  "  -r gpu: this build ships no CPU renderer (Camera::render / render_parallel are not in it).\n",
-                 RT_MAX_SAMPLE_GRID);
+                 RT_LIGHT_MAX_STEPS, RT_MAX_SAMPLE_GRID);
     return 2;
+}
+
+// One --area-light argument: cx,cy,cz:ux,uy,uz:vx,vy,vz:USTEPSxVSTEPS[:r,g,b][:jitter[=SEED]]
+static bool parse_area_light(const std::string& a, rt_area_light_desc* out) {
+    std::vector<std::string> part;
+    for (size_t at = 0;;) {
+        const size_t c = a.find(':', at);
+        part.push_back(a.substr(at, c == std::string::npos ? c : c - at));
+        if (c == std::string::npos) break;
+        at = c + 1;
+    }
+    auto triple = [](const std::string& v, double t[3]) {
+        char tail = 0;
+        return std::sscanf(v.c_str(), "%lf,%lf,%lf%c", &t[0], &t[1], &t[2], &tail) == 3;
+    };
+    if (part.size() < 4 || part.size() > 6) return false;
+    *out = rt_area_light_desc{};
+    if (!triple(part[0], out->corner) || !triple(part[1], out->full_uvec) || !triple(part[2], out->full_vvec)) return false;
+    char tail = 0;
+    if (std::sscanf(part[3].c_str(), "%ux%u%c", &out->usteps, &out->vsteps, &tail) != 2) return false;
+    out->intensity[0] = out->intensity[1] = out->intensity[2] = 1.0;
+    out->jitter = RT_JITTER_NONE;
+    size_t at = 4;
+    if (at < part.size() && triple(part[at], out->intensity)) ++at;
+    if (at < part.size()) {
+        if (part[at] == "jitter") {
+            out->jitter = RT_JITTER_HASHED;
+        } else if (part[at].rfind("jitter=", 0) == 0) {
+            char* end = nullptr;
+            const unsigned long seed = std::strtoul(part[at].c_str() + 7, &end, 0);
+            if (end == part[at].c_str() + 7 || *end || seed > 0xFFFFFFFFul) return false;
+            out->jitter = RT_JITTER_HASHED;
+            out->seed = (uint32_t)seed;
+        } else {
+            return false;
+        }
+        ++at;
+    }
+    return at == part.size();
 }
 
 // One --instance argument: FILE:tx,ty,tz[:s]
@@ -103,6 +149,7 @@ int main(int argc, char** argv) {
     int texture_filter = RT_FILTER_BILINEAR;
     std::vector<const char*> obj_paths;
     std::vector<Placement> placements;
+    std::vector<rt_area_light_desc> area_lights;
     for (int i = 3; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> const char* { return i + 1 < argc ? argv[++i] : nullptr; };
@@ -143,6 +190,15 @@ int main(int argc, char** argv) {
                 return usage();
             }
             placements.push_back(p);
+        }
+        else if (a == "--area-light") {
+            const char* v = next();
+            rt_area_light_desc d;
+            if (!v || !parse_area_light(v, &d)) {
+                std::fprintf(stderr, "error: --area-light takes cx,cy,cz:ux,uy,uz:vx,vy,vz:USTEPSxVSTEPS[:r,g,b][:jitter[=SEED]]\n");
+                return usage();
+            }
+            area_lights.push_back(d);
         }
         else if (a == "--device") { const char* v = next(); if (!v) return usage(); device = std::atoi(v); }
         else if (a == "--precision") {
@@ -297,12 +353,13 @@ int main(int argc, char** argv) {
     const double ctx_ms = ms_since(t_ctx);
     const auto t_up = clk::now();
     if (created != RT_OK ||
-        rt_scene_upload_textured(ctx, shapes.data(), (uint32_t)shapes.size(), meshes.data(), (uint32_t)meshes.size(),
+        rt_scene_upload_lit(ctx, shapes.data(), (uint32_t)shapes.size(), meshes.data(), (uint32_t)meshes.size(),
                                  instances.data(), (uint32_t)instances.size(), smooth_list.data(),
                                  (uint32_t)smooth_list.size(), uv_list.data(), (uint32_t)uv_list.size(), &texture,
                                  textured ? 1u : 0u, materials.data(), (uint32_t)materials.size(), patterns.data(),
                                  (uint32_t)patterns.size(), v.lights,
-                                 v.n_lights) != RT_OK) {  // (no texture: rt_scene_upload_smooth; no smooth triangle: rt_scene_upload_instanced; no instances: rt_scene_upload)
+                                 v.n_lights, area_lights.data(),
+                                 (uint32_t)area_lights.size()) != RT_OK) {  // (no area light: rt_scene_upload_textured; no texture: rt_scene_upload_smooth; no smooth triangle: rt_scene_upload_instanced; no instances: rt_scene_upload)
         rt_image_free(texture_rgb);
         std::fprintf(stderr, "error: %s\n", rt_last_error());
         return 1;

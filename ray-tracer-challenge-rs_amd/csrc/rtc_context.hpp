@@ -73,6 +73,10 @@ struct DeviceWorld {
     SmoothCounts uv_counts{};               // zeros: no triangle with coordinates
     const uint32_t* texels = nullptr;
     const TexRec* tex_table = nullptr;      // non-null: the world runs the texture code
+    // Area lights (rt_scene_upload_lit; rtc_internal.hpp AreaLightRec), outside the LDS image
+    DeviceBuffer<AreaLightRec<R>> area;
+    uint32_t n_area = 0;                    // 0: a world without area lights
+    uint32_t area_samples = 0;              // the sum of their sample counts
     DevScene<R> scene{};
     // Point the tables into `image` for ns shapes, nm materials, np patterns.
     void carve(size_t ns, size_t nm, size_t np) {
@@ -129,6 +133,13 @@ struct DeviceWorld {
         uv_counts = c;
         return RT_OK;
     }
+    // Room for n area lights of `samples` samples in all; n = 0: the world has none.
+    int allocate_area(uint32_t n, uint32_t samples) {
+        if (int rc = area.reserve(n)) return rc;
+        n_area = n;
+        area_samples = n ? samples : 0u;
+        return RT_OK;
+    }
     const R* uv_plain() const { return uv_counts.plain ? uv.get() : nullptr; }
     const R* uv_inst() const { return uv_counts.inst ? uv.get() + (size_t)uv_counts.plain * kUVReals : nullptr; }
     const R* smooth_plain() const { return smooth_counts.plain ? smooth.get() : nullptr; }
@@ -147,6 +158,12 @@ inline bool walked_instances(const DeviceWorld<R>& w) {
 template <typename R>
 inline bool has_textures(const DeviceWorld<R>& w) {
     return w.tex_table != nullptr;
+}
+// Does the world hold an area light (rt_scene_upload_lit)?  It then runs the area build's kernels
+// (rtc::area::launch_trace*: the texture build plus the sample loop) and is uploaded as a textured world.
+template <typename R>
+inline bool has_area(const DeviceWorld<R>& w) {
+    return w.n_area > 0;
 }
 // Does the world run the instance build's kernels (rtc::instanced::launch_trace*) or, when it is textured,
 // the texture build's (rtc::textured::launch_trace*: the instance build plus the texture code)?  They hold the
@@ -181,6 +198,7 @@ struct rt_context {
         bool lds_world = true;      // RTC_DEBUG=lds_world=0 gathers shade data from global memory
         bool cull = true;  // RTC_DEBUG=cull=0 uploads every shape as unbounded (no wave cull; exactness tests)
         bool tri_tree = true;  // RTC_DEBUG=tri_tree=0 uploads without a triangle hierarchy (flat triangle loop)
+        bool area_cull = true;  // RTC_DEBUG=area_cull=0: area lights' samples without the light-level caster cull
         // RTC_DEBUG=tri_min=N,tri_leaf=N: the sweep's values of tri_tree.hpp's kTriTreeMin and kTriLeaf (0 = those)
         uint32_t tri_min = 0, tri_leaf = 0;
         bool kind_variants = true;  // RTC_DEBUG=kind_variants=0: always the all-kinds kernels
@@ -330,6 +348,7 @@ struct rt_context {
     rtc::DeviceBuffer<rtc::TexRec> tex_table;
     rtc::TextureCounts tex_counts{};
     rt_texture_info texture_info{};    // rt_scene_texture_info
+    rt_light_info light_info{};        // area lights of the uploaded world (rt_scene_light_info)
     std::vector<int32_t> world_slot;  // world index -> slot | kind << 24 of the uploaded table
     // ray-pool overflow regions, one per resident workgroup; a ray batch's per-lane LIFOs (launch_rays)
     rtc::DeviceBuffer<unsigned char> d_spill;
@@ -406,6 +425,9 @@ struct InstancedLists {
     const rt_texture_desc* textures = nullptr;
     uint32_t n_textures = 0;
     bool textured = false;
+    // rt_scene_upload_lit's list (it uploads as a textured world: `textured` is set with it)
+    const rt_area_light_desc* area = nullptr;
+    uint32_t n_area = 0;
 };
 int validate_scene_instanced(const rt_shape_desc* shapes, uint32_t ns, const InstancedLists& il,
                              const rt_material_desc* mats, uint32_t nm, const rt_pattern_desc* pats, uint32_t np,
@@ -421,7 +443,8 @@ int build_scene_instanced(rt_context* ctx, const rt_shape_desc* shapes, uint32_t
                           uint32_t n_smooth = 0, const InstancedLists* textured = nullptr);
 void scene_brightness(const rt_shape_desc* shapes, uint32_t ns, const rt_material_desc* mats, uint32_t nm,
                       const rt_pattern_desc* pats, uint32_t np,
-                      const rt_light_desc* lights, uint32_t nl, double* bright_hit, double* bright_w);
+                      const rt_light_desc* lights, uint32_t nl, double* bright_hit, double* bright_w,
+                      double extra_intensity = 0.0);  // the area lights': each counts as a point light of its intensity
 // One frame (or shard strip) of this device into `out_device` on `stream`.
 int capture_jit_table(rt_context* ctx);  // the f32 table of the uploaded world, for rtc_jit.cpp
 int fetch_jit_tables(rt_context* ctx);   // build_world<float>'s host tables read back (a group's other ranks)

@@ -65,6 +65,8 @@ struct SceneHeader {
     SmoothCounts uv;      // image textures (rt_scene_upload_textured): zeros = none
     TextureCounts tex;
     rt_texture_info texture_info;
+    uint32_t n_area, area_samples;  // area lights (rt_scene_upload_lit): zeros = none
+    rt_light_info light_info;
 };
 
 // (device pointer, bytes) of every table of a member's world, in one order
@@ -80,6 +82,7 @@ void world_buffers(DeviceWorld<R>& w, const SceneHeader& h, std::vector<std::pai
     out.push_back({w.inst_pos.get(), h.inst.pos * sizeof(int32_t)});
     out.push_back({w.smooth.get(), ((size_t)h.smooth.plain + h.smooth.inst) * kSmoothReals * sizeof(R)});
     out.push_back({w.uv.get(), ((size_t)h.uv.plain + h.uv.inst) * kUVReals * sizeof(R)});
+    out.push_back({w.area.get(), (size_t)h.n_area * sizeof(AreaLightRec<R>)});
 }
 
 // Rank 0's `value` to every member of every rank, over RCCL (collective):
@@ -351,6 +354,9 @@ int group_scene_upload(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns
         root_h.uv = ctx->w32.uv_counts;
         root_h.tex = ctx->tex_counts;
         root_h.texture_info = ctx->texture_info;
+        root_h.n_area = ctx->w32.n_area;
+        root_h.area_samples = ctx->w32.area_samples;
+        root_h.light_info = ctx->light_info;
         root_h.ns = ns;
         root_h.nm = nm;
         root_h.np = np;
@@ -385,7 +391,7 @@ int group_scene_upload(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns
             const SceneHeader& h = hdr[i];
             // (worlds with and without instances run different kernels: the cached occupancies go)
             if ((h.inst.instances > 0 || h.smooth.plain > 0 || h.smooth.inst > 0 || h.tex.on) != instance_build(m->w32) ||
-                (h.tex.on != 0) != has_textures(m->w32))
+                (h.tex.on != 0) != has_textures(m->w32) || (h.n_area != 0) != has_area(m->w32))
                 std::fill(std::begin(m->occ_blocks), std::end(m->occ_blocks), 0);
             if ((local_rc = m->w32.allocate(h.ns, h.nm, h.np, h.nl)) == RT_OK &&
                 (local_rc = m->w64.allocate(h.ns, h.nm, h.np, h.nl)) == RT_OK &&
@@ -396,6 +402,8 @@ int group_scene_upload(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns
                 (local_rc = m->w32.allocate_smooth(h.smooth)) == RT_OK &&
                 (local_rc = m->w64.allocate_smooth(h.smooth)) == RT_OK &&
                 (local_rc = m->w32.allocate_uv(h.uv)) == RT_OK && (local_rc = m->w64.allocate_uv(h.uv)) == RT_OK &&
+                (local_rc = m->w32.allocate_area(h.n_area, h.area_samples)) == RT_OK &&
+                (local_rc = m->w64.allocate_area(h.n_area, h.area_samples)) == RT_OK &&
                 (local_rc = m->texels.reserve(h.tex.on ? std::max<uint64_t>(h.tex.texels, 1) : 0)) == RT_OK)
                 local_rc = m->tex_table.reserve(h.tex.on ? std::max<uint32_t>(h.tex.textures, 1u) : 0);
             // (the texels and the per-texture table: one copy a member, seen by both precisions' worlds)
@@ -435,7 +443,7 @@ int group_scene_upload(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns
         if ((rc = fetch_jit_tables(m)) || (rc = capture_jit_table(m))) return rc;
         m->flops = FlopScene{};
         m->flops.per_ray = h.flops_per_ray;
-        m->flops.n_lights = h.nl;
+        m->flops.n_lights = h.nl + h.area_samples;
         m->bright_hit = h.bright_hit;
         m->bright_w = h.bright_w;
         m->duplicate_shapes = h.duplicates;
@@ -443,6 +451,7 @@ int group_scene_upload(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns
         m->instance_info = h.instance_info;
         m->smooth_info = h.smooth_info;
         m->texture_info = h.texture_info;
+        m->light_info = h.light_info;
         m->have_scene = true;
         ++m->scene_gen;
     }

@@ -84,6 +84,23 @@ hipError_t launch_trace_ss(const LaunchParams<R>& P, bool pool, bool dup, uint32
 template <typename R>
 hipError_t occupancy_ss(bool pool, bool lds, size_t dyn_lds, int* blocks_per_cu);
 }  // namespace textured
+namespace area {  // rtc_kernels_area*.o: the texture build plus the area lights' sample loop, for worlds with an area light
+template <typename R>
+hipError_t launch_trace(const LaunchParams<R>& P, bool pool, bool dup, uint32_t grid, size_t dyn_lds,
+                        hipStream_t stream);
+template <typename R>
+hipError_t occupancy(bool pool, bool lds, size_t dyn_lds, int* blocks_per_cu);
+template <typename R>
+hipError_t launch_trace_rays(const LaunchParams<R>& P, bool dup, uint32_t grid, size_t dyn_lds, const void* rays,
+                             void* rgb, void* hits, hipStream_t stream);
+template <typename R>
+hipError_t occupancy_rays(bool lds, size_t dyn_lds, int* blocks_per_cu);
+template <typename R>
+hipError_t launch_trace_ss(const LaunchParams<R>& P, bool pool, bool dup, uint32_t grid, size_t dyn_lds,
+                           hipStream_t stream);
+template <typename R>
+hipError_t occupancy_ss(bool pool, bool lds, size_t dyn_lds, int* blocks_per_cu);
+}  // namespace area
 namespace sp {  // rtc_kernels_sp.o: the f32 pool kernel for worlds of spheres and planes only
 template <typename R>
 hipError_t launch_trace(const LaunchParams<R>& P, bool pool, bool dup, uint32_t grid, size_t dyn_lds,
@@ -608,7 +625,9 @@ int blocks_per_cu(rt_context* ctx, bool pool, bool lds_world, size_t lds, int* p
     }
     int api = 0;
     // (a world with mesh instances runs the instance variant of every kernel; an upload that changes that clears the cache)
-    if (has_textures(ctx->w32))
+    if (has_area(ctx->w32))
+        RT_HIP(ss ? area::occupancy_ss<R>(pool, lds_world, lds, &api) : area::occupancy<R>(pool, lds_world, lds, &api));
+    else if (has_textures(ctx->w32))
         RT_HIP(ss ? textured::occupancy_ss<R>(pool, lds_world, lds, &api)
                   : textured::occupancy<R>(pool, lds_world, lds, &api));
     else if (instance_build(ctx->w32))
@@ -878,6 +897,10 @@ void set_instance_params(LaunchParams<R>& P, const DeviceWorld<R>& w) {
     P.uv_inst = w.uv_inst();
     P.texels = w.texels;
     P.textures = w.tex_table;
+    P.area = w.n_area ? w.area.get() : nullptr;
+    P.n_area = w.n_area;
+    P.area_samples = w.area_samples;
+    P.area_cull = 1u;  // (the callers clear it under RTC_DEBUG=area_cull=0)
 }
 
 template <typename R>
@@ -893,6 +916,7 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
     P.n_tri_nodes = w.n_tri_nodes;
     P.tri_flat_begin = w.tri_flat_begin;
     set_instance_params(P, w);
+    if (!ctx->knobs.area_cull) P.area_cull = 0u;
     if (cam) {
         for (int q = 0; q < 12; ++q) P.cam.inv[q] = (R)cam->inverse[q];
         for (int q = 0; q < 3; ++q) P.cam.origin[q] = (R)cam->origin[q];
@@ -944,7 +968,8 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
         const bool instanced = walked_instances(w), smooth = w.smooth_counts.plain || w.smooth_counts.inst;
         const bool tree = w.n_tri_nodes > 0 || instanced || smooth || has_textures(w);
         if (tree && ctx->jit.mode != RT_JIT_OFF && ctx->jit.log.empty())
-            ctx->jit.log = has_textures(w) ? "no per-scene build: the world has textures, which the generic kernels sample"
+            ctx->jit.log = has_area(w) ? "no per-scene build: the world has area lights, which the generic kernels sample"
+                           : has_textures(w) ? "no per-scene build: the world has textures, which the generic kernels sample"
                            : smooth ? "no per-scene build: the world has smooth triangles, whose normals the generic kernels interpolate"
                            : instanced
                                ? "no per-scene build: the world has mesh instances, which the generic kernels walk"
@@ -1109,7 +1134,10 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
         void* args[] = {&P, &sh, &mt, &pt, &lt};
         (void)hipGetLastError();
         RT_HIP(hipModuleLaunchKernel(jf, ls.grid, 1, 1, kBlock, 1, 1, (unsigned)ls.lds, stream, args, nullptr));
-    } else if (hipError_t e = has_textures(w)
+    } else if (hipError_t e = has_area(w)
+                                  ? (ss ? area::launch_trace_ss<R>(P, ls.pool, dup, ls.grid, ls.lds, stream)
+                                        : area::launch_trace<R>(P, ls.pool, dup, ls.grid, ls.lds, stream))
+                              : has_textures(w)
                                   ? (ss ? textured::launch_trace_ss<R>(P, ls.pool, dup, ls.grid, ls.lds, stream)
                                         : textured::launch_trace<R>(P, ls.pool, dup, ls.grid, ls.lds, stream))
                               : instance_build(w)
@@ -1127,6 +1155,7 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
     if (dynamic) ctx->head_set ^= 1;
     ctx->smooth_info.ran_smooth = !jf && (w.smooth_counts.plain || w.smooth_counts.inst) ? 1u : 0u;
     ctx->texture_info.ran_textured = !jf && has_textures(w) ? 1u : 0u;
+    ctx->light_info.ran_area = !jf && has_area(w) ? 1u : 0u;
     return RT_OK;
 }
 
@@ -1140,7 +1169,8 @@ int ray_blocks_per_cu(rt_context* ctx, bool lds_world, size_t lds, int* per_cu) 
         return RT_OK;
     }
     int api = 0;
-    if (has_textures(ctx->w32)) RT_HIP(textured::occupancy_rays<R>(lds_world, lds, &api));
+    if (has_area(ctx->w32)) RT_HIP(area::occupancy_rays<R>(lds_world, lds, &api));
+    else if (has_textures(ctx->w32)) RT_HIP(textured::occupancy_rays<R>(lds_world, lds, &api));
     else if (instance_build(ctx->w32)) RT_HIP(instanced::occupancy_rays<R>(lds_world, lds, &api));
     else RT_HIP(occupancy_rays<R>(lds_world, lds, &api));
     *per_cu = cap_by_lds(api, lds);
@@ -1183,6 +1213,7 @@ int launch_rays(rt_context* ctx, DeviceWorld<R>& w, const void* d_rays, uint64_t
     P.n_tri_nodes = w.n_tri_nodes;
     P.tri_flat_begin = w.tri_flat_begin;
     set_instance_params(P, w);
+    if (!ctx->knobs.area_cull) P.area_cull = 0u;
     P.n_rays = n;
     P.n_tiles = (uint32_t)((n + kBlock - 1) / kBlock);
     P.max_depth = o->max_depth;
@@ -1206,7 +1237,9 @@ int launch_rays(rt_context* ctx, DeviceWorld<R>& w, const void* d_rays, uint64_t
     }
     ctx->jit.used = false;
     if (o->flags & RT_FLAG_FAIL_LAUNCH) return set_error(RT_ERR_HIP, "launch refused (RT_FLAG_FAIL_LAUNCH)");
-    if (hipError_t e = has_textures(w) ? textured::launch_trace_rays<R>(P, ctx->duplicate_shapes > 0, ls.grid, ls.lds,
+    if (hipError_t e = has_area(w) ? area::launch_trace_rays<R>(P, ctx->duplicate_shapes > 0, ls.grid, ls.lds, d_rays, d_rgb,
+                                                                d_hits, stream)
+                       : has_textures(w) ? textured::launch_trace_rays<R>(P, ctx->duplicate_shapes > 0, ls.grid, ls.lds,
                                                                      d_rays, d_rgb, d_hits, stream)
                        : instance_build(w) ? instanced::launch_trace_rays<R>(P, ctx->duplicate_shapes > 0, ls.grid, ls.lds,
                                                                              d_rays, d_rgb, d_hits, stream)
@@ -1218,6 +1251,7 @@ int launch_rays(rt_context* ctx, DeviceWorld<R>& w, const void* d_rays, uint64_t
                                          " stack entries per lane): " + hipGetErrorString(e));
     ctx->smooth_info.ran_smooth = w.smooth_counts.plain || w.smooth_counts.inst ? 1u : 0u;
     ctx->texture_info.ran_textured = has_textures(w) ? 1u : 0u;
+    ctx->light_info.ran_area = has_area(w) ? 1u : 0u;
     return RT_OK;
 }
 
@@ -1364,6 +1398,7 @@ rt_context::Knobs read_knobs() {
     if (debug_knob("lds_world", &v)) k.lds_world = v != "0";
     if (debug_knob("cull", &v)) k.cull = v != "0";
     if (debug_knob("tri_tree", &v)) k.tri_tree = v != "0";
+    if (debug_knob("area_cull", &v)) k.area_cull = v != "0";
     if (debug_knob("tri_min", &v)) k.tri_min = (uint32_t)std::max(0, std::atoi(v.c_str()));
     if (debug_knob("tri_leaf", &v)) k.tri_leaf = (uint32_t)std::max(0, std::atoi(v.c_str()));
     if (debug_knob("kind_variants", &v)) k.kind_variants = v != "0";
@@ -1549,6 +1584,128 @@ int rt_scene_texture_info(rt_context* ctx, rt_texture_info* out) {
     return RT_OK;
 }
 
+// rt_scene_upload_lit's list; empty: valid.  Each refusal has a text of its own (rtc.h).
+static std::string validate_area(const rt_area_light_desc* area, uint32_t n_area) {
+    if (n_area && !area) return "rt_scene_upload_lit: null area light list with nonzero count";
+    for (uint32_t a = 0; a < n_area; ++a) {
+        const rt_area_light_desc& d = area[a];
+        const std::string who = "area light " + std::to_string(a);
+        if (d.usteps == 0 || d.vsteps == 0) return who + ": a step count of 0";
+        if (d.usteps > RT_LIGHT_MAX_STEPS || d.vsteps > RT_LIGHT_MAX_STEPS)
+            return who + ": a step count above RT_LIGHT_MAX_STEPS";
+        if (d.jitter != RT_JITTER_NONE && d.jitter != RT_JITTER_HASHED) return who + ": unknown jitter mode";
+        for (int q = 0; q < 3; ++q)
+            if (!std::isfinite(d.corner[q]) || !std::isfinite(d.full_uvec[q]) || !std::isfinite(d.full_vvec[q]) ||
+                !std::isfinite(d.intensity[q]))
+                return who + ": a component that is not finite";
+    }
+    return std::string();
+}
+
+static uint32_t area_mix(uint32_t x) {  // rtc.h "Hashed jitter"
+    x ^= x >> 16;
+    x *= 0x7feb352du;
+    x ^= x >> 15;
+    x *= 0x846ca68bu;
+    x ^= x >> 16;
+    return x;
+}
+
+// Sample k of a valid light, in f64 (the kernels' arithmetic in R = double).
+static void area_sample(const rt_area_light_desc& d, uint32_t area_index, uint32_t ray_id, uint32_t remaining, uint32_t k,
+                        double pos[3]) {
+    const uint32_t i = k % d.usteps, j = k / d.usteps;
+    double ju = 0.5, jv = 0.5;
+    if (d.jitter == RT_JITTER_HASHED) {
+        const uint32_t key = area_mix(area_mix(area_mix(d.seed ^ ray_id) ^ remaining) ^ ((area_index << 8) | k));
+        ju = (double)(key >> 8) * 0x1p-24;
+        jv = (double)(area_mix(key ^ 0x9E3779B9u) >> 8) * 0x1p-24;
+    }
+    const double fu = (double)i + ju, fv = (double)j + jv;
+    for (int q = 0; q < 3; ++q) {
+        const double u = d.full_uvec[q] / (double)d.usteps, v = d.full_vvec[q] / (double)d.vsteps;
+        pos[q] = (d.corner[q] + u * fu) + v * fv;
+    }
+}
+
+int rt_area_light_sample(const rt_area_light_desc* desc, uint32_t area_index, uint32_t ray_id, uint32_t remaining,
+                         uint32_t k, double pos[3]) {
+    if (!desc || !pos) return set_error(RT_ERR_INVALID, "null argument");
+    const std::string why = validate_area(desc, 1);
+    if (!why.empty()) return set_error(RT_ERR_INVALID, why);
+    if (k >= desc->usteps * desc->vsteps) return set_error(RT_ERR_INVALID, "rt_area_light_sample: sample index out of range");
+    area_sample(*desc, area_index, ray_id, remaining, k, pos);
+    return RT_OK;
+}
+
+int rt_lights_expand(const rt_light_desc* lights, uint32_t nl, const rt_area_light_desc* area, uint32_t n_area,
+                     rt_light_desc* out, uint32_t* n_out) {
+    if (nl && !lights) return set_error(RT_ERR_INVALID, "rt_lights_expand: null light list with nonzero count");
+    const std::string why = validate_area(area, n_area);
+    if (!why.empty()) return set_error(RT_ERR_INVALID, why);
+    uint64_t n = nl;
+    for (uint32_t a = 0; a < n_area; ++a) {
+        if (area[a].jitter == RT_JITTER_HASHED)
+            return set_error(RT_ERR_INVALID, "area light " + std::to_string(a) +
+                                                 ": a hashed light has no expansion (its samples depend on the ray)");
+        n += area[a].usteps * area[a].vsteps;
+    }
+    if (n > 0x7fffffffull) return set_error(RT_ERR_INVALID, "table too large");
+    if (out) {
+        for (uint32_t l = 0; l < nl; ++l) out[l] = lights[l];
+        uint32_t at = nl;
+        for (uint32_t a = 0; a < n_area; ++a) {
+            const uint32_t N = area[a].usteps * area[a].vsteps;
+            for (uint32_t k = 0; k < N; ++k, ++at) {
+                area_sample(area[a], a, 0, 0, k, out[at].position);
+                for (int q = 0; q < 3; ++q) out[at].intensity[q] = area[a].intensity[q] / (double)N;
+            }
+        }
+    }
+    if (n_out) *n_out = (uint32_t)n;
+    return RT_OK;
+}
+
+int rt_scene_upload_lit(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns, const rt_mesh_desc* meshes,
+                        uint32_t n_meshes, const rt_instance_desc* instances, uint32_t n_inst,
+                        const rt_smooth_desc* smooth, uint32_t n_smooth, const rt_uv_desc* uvs, uint32_t n_uvs,
+                        const rt_texture_desc* textures, uint32_t n_textures, const rt_material_desc* mats, uint32_t nm,
+                        const rt_pattern_desc* pats, uint32_t np, const rt_light_desc* lights, uint32_t nl,
+                        const rt_area_light_desc* area, uint32_t n_area) {
+    // (the area list is checked before the context is looked at, and before the other lists)
+    const std::string why = validate_area(area, n_area);
+    if (!why.empty()) return set_error(RT_ERR_INVALID, why);
+    if (!n_area)  // rt_scene_upload_textured itself
+        return rt_scene_upload_textured(ctx, shapes, ns, meshes, n_meshes, instances, n_inst, smooth, n_smooth, uvs, n_uvs,
+                                        textures, n_textures, mats, nm, pats, np, lights, nl);
+    InstancedLists il{meshes, n_meshes, instances, n_inst, smooth, n_smooth};
+    il.uvs = uvs;
+    il.n_uvs = n_uvs;
+    il.textures = textures;
+    il.n_textures = n_textures;
+    il.textured = true;  // (a world with an area light is uploaded as a textured world: the area build holds that code)
+    il.area = area;
+    il.n_area = n_area;
+    if (int rc = validate_scene_instanced(shapes, ns, il, mats, nm, pats, np, lights, nl)) return rc;
+    uint64_t total = nl;
+    for (uint32_t a = 0; a < n_area; ++a) total += area[a].usteps * area[a].vsteps;
+    if (total > 0x7fffffffull) return set_error(RT_ERR_INVALID, "table too large");
+    if (!ctx) return set_error(RT_ERR_INVALID, "null context");
+    std::vector<rt_pattern_desc> cp(pats, pats + np);
+    inst::canonical_image_patterns(cp.data(), np, textures, n_textures);
+    if (ctx->group.comm) return group_scene_upload(ctx, shapes, ns, mats, nm, cp.data(), np, lights, nl, &il);
+    RT_HIP(hipSetDevice(ctx->device));
+    RT_HIP(hipDeviceSynchronize());  // launches on caller streams may still read the old tables
+    return build_scene_instanced(ctx, shapes, ns, meshes, n_meshes, instances, n_inst, mats, nm, cp.data(), np, lights, nl,
+                                 smooth, n_smooth, &il);
+}
+
+int rt_scene_light_info(rt_context* ctx, rt_light_info* out) {
+    if (!ctx || !out) return set_error(RT_ERR_INVALID, "null argument");
+    *out = ctx->have_scene ? ctx->light_info : rt_light_info{};
+    return RT_OK;
+}
+
 int rt_scene_smooth_info(rt_context* ctx, rt_smooth_info* out) {
     if (!ctx || !out) return set_error(RT_ERR_INVALID, "null argument");
     *out = ctx->have_scene ? ctx->smooth_info : rt_smooth_info{};
@@ -1609,7 +1766,7 @@ double object_extent(const rt_shape_desc& d) {
 // lights' intensities and the Phong coefficients.
 void scene_brightness(const rt_shape_desc* shapes, uint32_t ns, const rt_material_desc* mats, uint32_t nm,
                       const rt_pattern_desc* pats, uint32_t np, const rt_light_desc* lights, uint32_t nl,
-                      double* bright_hit, double* bright_w) {
+                      double* bright_hit, double* bright_w, double extra_intensity) {
     // per material: the colours its pattern chain may return, and whether a
     // TestPattern is among them
     std::vector<double> col(nm, 0.0);
@@ -1658,7 +1815,7 @@ void scene_brightness(const rt_shape_desc* shapes, uint32_t ns, const rt_materia
         w = std::max(w, mixed ? std::max(m.reflectiveness, m.transparency) * (1.0 + 1e-6)
                               : std::fabs(m.reflectiveness) + std::fabs(m.transparency));
     }
-    double hit = 0.0;
+    double hit = extra_intensity * per_light;
     for (uint32_t l = 0; l < nl; ++l) {
         double in = 0.0;
         for (int k = 0; k < 3; ++k) in = std::max(in, std::fabs(lights[l].intensity[k]));
@@ -1925,8 +2082,46 @@ static void clear_textures(rt_context* ctx) {
     ctx->w32.tex_table = ctx->w64.tex_table = nullptr;
 }
 
+// The context holds no area light from here on (the buffers keep their room).
+static void clear_area(rt_context* ctx) {
+    if (has_area(ctx->w32)) std::fill(std::begin(ctx->occ_blocks), std::end(ctx->occ_blocks), 0);  // other kernels now
+    ctx->light_info = rt_light_info{};
+    ctx->w32.n_area = ctx->w64.n_area = 0;
+    ctx->w32.area_samples = ctx->w64.area_samples = 0;
+}
+
+// The area light records of one precision (rtc_internal.hpp AreaLightRec): the cell edges are the full edges
+// divided by the step counts in f64 (rtc.h "Sample positions"), then everything is rounded once to R.
+template <typename R>
+static int upload_area(rt_context* ctx, DeviceWorld<R>& w, const rt_area_light_desc* area, uint32_t n_area) {
+    uint32_t samples = 0;
+    std::vector<AreaLightRec<R>> host(n_area);
+    for (uint32_t a = 0; a < n_area; ++a) {
+        const rt_area_light_desc& d = area[a];
+        AreaLightRec<R>& r = host[a];
+        for (int q = 0; q < 3; ++q) {
+            r.corner[q] = (R)d.corner[q];
+            r.uvec[q] = (R)(d.full_uvec[q] / (double)d.usteps);
+            r.vvec[q] = (R)(d.full_vvec[q] / (double)d.vsteps);
+            r.intensity[q] = (R)d.intensity[q];
+        }
+        r.usteps = d.usteps;
+        r.vsteps = d.vsteps;
+        r.jitter = d.jitter;
+        r.seed = d.seed;
+        samples += d.usteps * d.vsteps;
+    }
+    if (int rc = w.allocate_area(n_area, samples)) return rc;
+    if (!n_area) return RT_OK;
+    const int rc = hip_status(hipMemcpyAsync(w.area.get(), host.data(), host.size() * sizeof(host[0]), hipMemcpyHostToDevice,
+                                             ctx->stream), "hipMemcpyAsync");
+    const int rs = hip_status(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");  // (host temporary)
+    return rc ? rc : rs;
+}
+
 int build_scene(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns, const rt_material_desc* mats, uint32_t nm,
                 const rt_pattern_desc* pats, uint32_t np, const rt_light_desc* lights, uint32_t nl) {
+    clear_area(ctx);
     ctx->instance_info = rt_instance_info{};
     ctx->smooth_info = rt_smooth_info{};
     ctx->smooth_shape.clear();
@@ -1945,6 +2140,9 @@ int build_scene_instanced(rt_context* ctx, const rt_shape_desc* shapes, uint32_t
     // (a world with a smooth triangle or a texture takes the general path whatever its instances: it runs the instance build)
     if (!n_inst && !n_smooth && !tx) return build_scene(ctx, shapes, ns, mats, nm, pats, np, lights, nl);  // rt_scene_upload itself
     int rc;
+    const uint32_t n_area = tx ? tx->n_area : 0u;
+    if (has_area(ctx->w32) != (n_area > 0)) std::fill(std::begin(ctx->occ_blocks), std::end(ctx->occ_blocks), 0);  // other kernels now
+    clear_area(ctx);
     const auto t0 = std::chrono::steady_clock::now();
     const inst::SmoothIndex si = inst::smooth_index(ns, meshes, n_meshes, smooth, n_smooth);
     const inst::SmoothIndex ui = inst::uv_index(ns, meshes, n_meshes, tx ? tx->uvs : nullptr, tx ? tx->n_uvs : 0);
@@ -2074,8 +2272,24 @@ int build_scene_instanced(rt_context* ctx, const rt_shape_desc* shapes, uint32_t
                 for (int q = 0; q < 3; ++q) d.vertex_1[q] = extent[instances[k].mesh];
                 reach.push_back(d);
             }
+        // (an area light counts as a point light of its intensity: its samples' weights sum to 1)
+        double area_intensity = 0.0;
+        for (uint32_t a = 0; a < n_area; ++a) {
+            double in = 0.0;
+            for (int q = 0; q < 3; ++q) in = std::max(in, std::fabs(tx->area[a].intensity[q]));
+            area_intensity += in;
+        }
         scene_brightness(reach.data(), (uint32_t)reach.size(), mats, nm, pats, np, lights, nl, &ctx->bright_hit,
-                         &ctx->bright_w);
+                         &ctx->bright_w, area_intensity);
+    }
+    if (n_area) {
+        if ((rc = upload_area<float>(ctx, ctx->w32, tx->area, n_area)) ||
+            (rc = upload_area<double>(ctx, ctx->w64, tx->area, n_area)))
+            return rc;
+        ctx->light_info.area_lights = n_area;
+        ctx->light_info.samples = ctx->w32.area_samples;
+        ctx->light_info.area_bytes = (uint64_t)n_area * (sizeof(AreaLightRec<float>) + sizeof(AreaLightRec<double>));
+        ctx->flops.n_lights += ctx->w32.area_samples;  // the expansion's light count
     }
     rt_instance_info& info = ctx->instance_info;
     info = rt_instance_info{};

@@ -368,6 +368,20 @@ struct alignas(16) LightRec {
     R intensity[3];
 };
 
+// An area light (rtc.h rt_scene_upload_lit): a parallelogram of usteps x vsteps
+// cells, each sampled once per shaded hit; uvec and vvec are the cell edges
+// (the full edges divided by the step counts on the host, then rounded to R).
+// Read wave-uniformly by the area build's shade_ray; no other kernel loads it.
+template <typename R>
+struct alignas(16) AreaLightRec {
+    R corner[3];
+    R uvec[3];
+    R vvec[3];
+    R intensity[3];
+    uint32_t usteps, vsteps, jitter, seed;
+};
+static_assert(sizeof(AreaLightRec<float>) == 64 && sizeof(AreaLightRec<double>) == 112);
+
 template <typename R>
 struct CameraRec {
     R inv[12];
@@ -577,6 +591,14 @@ struct LaunchParams {
     const R* uv_inst;
     const uint32_t* texels;
     const TexRec* textures;
+    // Area lights (rt_scene_upload_lit; null / 0 for every other world): the
+    // records in list order and the sum of their sample counts (what the event
+    // counters add to n_lights per shaded hit).  A world with one runs the area
+    // build (rtc::area::launch_trace*); read by that build's shade_ray only.
+    const AreaLightRec<R>* area;
+    uint32_t n_area;
+    uint32_t area_samples;
+    uint32_t area_cull;  // 1: the light-level caster cull runs (rtc_kernels.hip area_pass_mask); RTC_DEBUG=area_cull=0 clears it
 };
 
 }  // namespace rtc

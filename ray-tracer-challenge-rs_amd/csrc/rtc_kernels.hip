@@ -58,8 +58,19 @@
 // a texture coordinate (rt_scene_upload_textured).  Inside the instance variant
 // the same code, never run there, cost untextured instanced and smooth worlds
 // about 1 % a frame, so that variant compiles none of it.
+//
+// Area variant: built with -DRTC_INSTANCES=1 -DRTC_TEXTURES=1
+// -DRTC_AREA_LIGHTS=1 -DRTC_VARIANT=area (one TU per precision), the texture
+// variant plus the area lights' sample loop of shade_ray and the ray identity
+// its hashed jitter needs (Shaded::ray_id, set by every tracer kernel) as
+// rtc::area::launch_trace*, for worlds uploaded with an area light
+// (rt_scene_upload_lit).  Every line of it sits behind RTC_AREA_LIGHTS, so the
+// other builds compile to what they compiled to before.
 #ifndef RTC_INSTANCES
 #define RTC_INSTANCES 0
+#endif
+#ifndef RTC_AREA_LIGHTS
+#define RTC_AREA_LIGHTS 0
 #endif
 #ifndef RTC_TEXTURES
 #define RTC_TEXTURES 0
@@ -1859,6 +1870,9 @@ struct Shaded {
     bool patterned = false;  // each light evaluation samples a pattern
     bool refr_eval = false;  // refracted_color past the opaque/depth check
     bool schlick = false;    // schlicks_approximation evaluated
+#if RTC_AREA_LIGHTS
+    uint32_t ray_id = 0;     // in: the primary ray this ray descends from (rtc.h "Hashed jitter")
+#endif
 };
 
 // Children are handed to push(origin, direction, weight) where they are
@@ -1892,6 +1906,9 @@ __device__ inline void count_generations(unsigned long long* gc, bool traced, bo
 // `primary` rays entering the path, `hit` = shade_ray's result.
 template <typename R>
 __device__ inline void count_events(Counts& k, bool primary, bool hit, const Shaded<R>& sh, int n_lights) {
+#if RTC_AREA_LIGHTS
+    n_lights += (int)kernarg_params<R>().area_samples;  // the expansion's lights: one per sample
+#endif
     k.c[0] += wave_count(primary);
     const uint32_t shaded = wave_count(hit);
     k.c[4] += shaded;
@@ -2177,6 +2194,120 @@ __device__ __attribute__((always_inline)) inline LightSide<R> light_side(const D
     return {ld, ldn, shadowed};
 }
 
+#if RTC_AREA_LIGHTS
+// The jitter hash of rtc.h ("Hashed jitter"), uint32_t wraparound.
+__device__ inline uint32_t area_mix(uint32_t x) {
+    x ^= x >> 16;
+    x *= 0x7feb352du;
+    x ^= x >> 15;
+    x *= 0x846ca68bu;
+    x ^= x >> 16;
+    return x;
+}
+
+// Light-level caster cull (acceleration only).  Every shadow
+// segment of an area light at a hit runs from the lane's over point to a point
+// of the light's parallelogram, which lies in the ball (lc, lr): lc its centre,
+// lr = (|U| + |V|) / 2 >= both half diagonals.  The point at parameter s of the
+// segment to a point q of that ball is within s |q - lc| <= lr of the point at
+// s of the segment to lc, so a caster's ball (c, r) the segment over -> lc
+// stays farther than r + lr from is met by no sample's segment.  Once per area
+// light and wave: bit `slot` of the result is set when that holds for every
+// active lane, for the first 64 records of the shape table (planes, unbounded
+// records, mesh instances and records beyond 64 keep their own per-sample
+// culls).  any_hit passes such a record by on one scalar bit test per sample.
+// The margins (0.1 % of the limit, 1e-4 of the squared lengths involved, far
+// above the rounding of either precision and of the f32 reciprocal) keep the
+// test conservative; a lane whose terms are not numbers keeps the record.
+struct AreaPassBits {
+    static constexpr bool kOn = true;
+    unsigned long long pass;
+    __device__ inline bool skips(int slot) const { return slot >= 0 && slot < 64 && ((pass >> slot) & 1ull); }
+    __device__ inline bool skips_every_ball() const { return false; }
+};
+template <typename R>
+__device__ inline unsigned long long area_pass_mask(const DevScene<R>& sc, const AreaLightRec<R>& A, uint32_t us,
+                                                    uint32_t vs, V3<R> over) {
+    const R fu = (R)us, fv = (R)vs;
+    const V3<R> U = {A.uvec[0] * fu, A.uvec[1] * fu, A.uvec[2] * fu};
+    const V3<R> V = {A.vvec[0] * fv, A.vvec[1] * fv, A.vvec[2] * fv};
+    const V3<R> lc = {A.corner[0] + (U.x + V.x) * (R)0.5, A.corner[1] + (U.y + V.y) * (R)0.5,
+                      A.corner[2] + (U.z + V.z) * (R)0.5};
+    const R lr = (magnitude(U) + magnitude(V)) * (R)0.5;
+    const V3<R> w = vsub(lc, over);
+    const R ww = dot(w, w), rww = recip(ww);
+    const int n_slots = sc.kind_begin[kNumKinds] < 64 ? sc.kind_begin[kNumKinds] : 64;
+    unsigned long long pass = 0;
+    for (int slot = 0; slot < n_slots; ++slot) {
+        const ShapeRec<R>* s = &sc.shapes[slot];  // wave-uniform: the ball alone is loaded
+        const R r2 = s->bound[3];
+        if (!(r2 >= (R)0) || !(r2 < Real<R>::kInf)) continue;  // a plane or an unbounded record
+        const R reach = Real<R>::sqrt(r2) + lr;
+        const V3<R> v = {s->bound[0] - over.x, s->bound[1] - over.y, s->bound[2] - over.z};
+        const R vv = dot(v, v);
+        R t = dot(v, w) * rww;
+        t = t < (R)0 ? (R)0 : (t > (R)1 ? (R)1 : t);  // (not a number: kept, and so is the record below)
+        const V3<R> e = {v.x - t * w.x, v.y - t * w.y, v.z - t * w.z};
+        const bool far = dot(e, e) > (reach * reach) * (R)1.001 + (R)1e-4 * (vv + ww);
+        if (!wave_any(!far)) pass |= 1ull << slot;
+    }
+    return pass;
+}
+
+// One area light at a hit (rtc.h "Lighting"): the expansion's usteps x vsteps
+// point lights of intensity / N, with the base colour, eff and the ambient
+// term worked out once and the samples' diffuse and specular terms summed in
+// ascending k, then divided by N.  The record and both trip counts are
+// wave-uniform; ray_id and remaining are the lane's.
+template <typename R, bool kDirect>
+__device__ inline V3<R> area_light_term(const DevScene<R>& sc, const AreaLightRec<R>& A, uint32_t area_index,
+                                        uint32_t ray_id, uint32_t remaining, const MaterialRec<R>& m, V3<R> base,
+                                        V3<R> n, V3<R> eye, V3<R> over) {
+    // (the host refuses counts outside 1..RT_LIGHT_MAX_STEPS; the clamp bounds the loop whatever the record holds)
+    const uint32_t us = A.usteps < (uint32_t)RT_LIGHT_MAX_STEPS ? A.usteps : (uint32_t)RT_LIGHT_MAX_STEPS;
+    const uint32_t vs = A.vsteps < (uint32_t)RT_LIGHT_MAX_STEPS ? A.vsteps : (uint32_t)RT_LIGHT_MAX_STEPS;
+    const V3<R> eff = {base.x * A.intensity[0], base.y * A.intensity[1], base.z * A.intensity[2]};
+    const V3<R> kd = {eff.x * m.diffuse, eff.y * m.diffuse, eff.z * m.diffuse};
+    const V3<R> ks = {A.intensity[0] * m.specular, A.intensity[1] * m.specular, A.intensity[2] * m.specular};
+    const uint32_t key0 = area_mix(area_mix(A.seed ^ ray_id) ^ remaining);
+    // (the launch's flags and switches: wave-uniform)
+    const AreaPassBits sb{kernarg_params<R>().area_cull && skips_on(sc) ? area_pass_mask(sc, A, us, vs, over) : 0ull};
+    V3<R> sum = {(R)0, (R)0, (R)0};
+    uint32_t k = 0;
+    for (uint32_t j = 0; j < vs; ++j) {
+        for (uint32_t i = 0; i < us; ++i, ++k) {
+            R ju = (R)0.5, jv = (R)0.5;
+            if (A.jitter == RT_JITTER_HASHED) {  // wave-uniform
+                const uint32_t key = area_mix(key0 ^ ((area_index << 8) | k));
+                ju = (R)(key >> 8) * (R)5.9604644775390625e-8;  // 2^-24: exact in both precisions
+                jv = (R)(area_mix(key ^ 0x9E3779B9u) >> 8) * (R)5.9604644775390625e-8;
+            }
+            const R fu = (R)i + ju, fv = (R)j + jv;
+            LightRec<R> L;
+            for (int q = 0; q < 3; ++q) {
+                L.position[q] = (A.corner[q] + A.uvec[q] * fu) + A.vvec[q] * fv;
+                L.intensity[q] = A.intensity[q];
+            }
+            const LightSide<R> s = light_side<R, kDirect, AreaPassBits>(sc, L, over, n, sb);
+            if (!s.shadowed && !(s.ldn < (R)0)) {
+                V3<R> c = {kd.x * s.ldn, kd.y * s.ldn, kd.z * s.ldn};
+                if (m.specular != (R)0) {
+                    const R rde = dot(reflect(vneg(s.ld), n), eye);
+                    if (!(rde <= (R)0)) {
+                        const R f = Real<R>::pow(rde, m.shininess);
+                        c = {c.x + ks.x * f, c.y + ks.y * f, c.z + ks.z * f};
+                    }
+                }
+                sum = {sum.x + c.x, sum.y + c.y, sum.z + c.z};
+            }
+        }
+    }
+    const R nn = (R)(us * vs);
+    return {eff.x * m.ambient + Real<R>::div(sum.x, nn), eff.y * m.ambient + Real<R>::div(sum.y, nn),
+            eff.z * m.ambient + Real<R>::div(sum.z, nn)};
+}
+#endif
+
 #ifdef RTC_JIT
 // the lights again, each with the shadow bits of (light, plane kPlane) in the block's word w
 template <int I, int E, int kPlane, typename F>
@@ -2261,6 +2392,18 @@ __device__ inline bool shade_ray(const DevScene<R>& sc, V3<R> o, V3<R> d, uint32
         const V3<R> c = lighting_term(L, m, base, n, eye, s.ld, s.ldn, s.shadowed);
         surface = {surface.x + c.x, surface.y + c.y, surface.z + c.z};
     });
+#if RTC_AREA_LIGHTS
+    {
+        // the area lights follow the point lights, as their expansions do in the world's light list
+        const LaunchParams<R>& AP = kernarg_params<R>();
+        const uint32_t n_area = AP.area ? AP.n_area : 0u;  // wave-uniform (launch parameters)
+        for (uint32_t ai = 0; ai < n_area; ++ai) {
+            const AreaLightRec<R> A = ld_const(&AP.area[ai]);  // wave-uniform: scalar loads, as ld_uniform(&sc.lights[li])
+            const V3<R> c = area_light_term<R, B::kOn>(sc, A, ai, out.ray_id, remaining, m, base, n, eye, over);
+            surface = {surface.x + c.x, surface.y + c.y, surface.z + c.z};
+        }
+    }
+#endif
     out.surface = surface;
     out.refl_child = out.refr_child = false;
     // shade_hit evaluates Schlick whenever the material is both (world.rs:59-60)
@@ -2427,6 +2570,32 @@ __device__ inline void load_primary(const LaunchParams<R>& P, uint32_t t, uint32
         if (valid) camera_ray(P.cam, x, y, o, d);
     }
 }
+
+#if RTC_AREA_LIGHTS
+// The identity of the primary ray of thread `lane` of tile t (rtc.h "Hashed
+// jitter"): its index in a color_at batch, else its pixel index y * W + x in
+// whole-image coordinates (tile_pixel's y is the image row whatever the shard),
+// so shards, canvases and ranks hash what the whole frame hashes.  A pool
+// entry names its pixel by the lane of its tile, so a secondary ray finds its
+// primary ray's identity from the tile and that lane alone.
+template <typename R>
+__device__ inline uint32_t primary_ray_id(const LaunchParams<R>& P, uint32_t t, uint32_t lane) {
+    if (P.rays) return (uint32_t)((uint64_t)t * kBlock + lane);
+    uint32_t x, y;
+    uint64_t out_idx;
+    (void)tile_pixel(P, t, lane, x, y, out_idx);
+    return y * P.width + x;
+}
+// Sample (i, j) of that pixel in a supersampled frame of grid n: its pixel index in the sample camera.
+template <typename R>
+__device__ inline uint32_t sample_ray_id(const LaunchParams<R>& P, uint32_t t, uint32_t lane, uint32_t n, uint32_t i,
+                                         uint32_t j) {
+    uint32_t x, y;
+    uint64_t out_idx;
+    (void)tile_pixel(P, t, lane, x, y, out_idx);
+    return (n * y + j) * (n * P.width) + n * x + i;
+}
+#endif
 
 // The workgroup's counters into its counter shard: each wave's lane 0 puts
 // the wave's (uniform) counts in LDS, and after one barrier lanes 0..7 of
@@ -2609,6 +2778,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(sizeof(R
         V3<R> c = {(R)0, (R)0, (R)0};
         Shaded<R> sh;
         bool hit = false;
+#if RTC_AREA_LIGHTS
+        sh.ray_id = primary_ray_id(P, t, tid);
+#endif
         if (valid) {
             if (kDiag && (P.flags & (RT_FLAG_NO_SHADE | RT_FLAG_NO_TRACE))) {
                 if (P.flags & RT_FLAG_NO_TRACE) {
@@ -2619,6 +2791,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(sizeof(R
                 }
 #ifdef RTC_JIT  // (camera frames only: load_primary above)
             } else if (shade_ray<R, false>(sc, o, d, 0, sh, NoPush{}, wave_pixel_block(P, t))) {
+#elif RTC_AREA_LIGHTS  // (the jitter hashes the ray's `remaining`: the primary ray's, though no child is made here)
+            } else if (shade_ray<R, false>(sc, o, d, P.max_depth, sh)) {
 #else
             } else if (shade_ray<R, false>(sc, o, d, 0, sh)) {
 #endif
@@ -2921,6 +3095,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(sizeof(R
                 if (slot < (int)cap) pool_put(pl, slot, co, cd, rw * cw, child_meta);
                 else atomicOr(P.error_flag, kErrPoolOverflow);
             };
+#if RTC_AREA_LIGHTS
+            sh.ray_id = primary_ray_id(P, t, pix);
+#endif
             if (active) hit = shade_ray<R, true, kDup>(sc, ro, rd, meta >> 8, sh, push);
             count_events(k, false, hit, sh, sc.n_lights);
 #ifndef RTC_JIT  // (per-scene builds never take RT_FLAG_GENERATIONS launches)
@@ -3018,7 +3195,12 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(sizeof(R
                 if (valid) {
                     V3<R> o, d;
                     camera_ray(P.cam, n * x + i, n * y + j, o, d);
+#if RTC_AREA_LIGHTS
+                    sh.ray_id = (n * y + j) * (n * P.width) + n * x + i;
+                    if (shade_ray<R, false>(sc, o, d, P.max_depth, sh)) {
+#else
                     if (shade_ray<R, false>(sc, o, d, 0, sh)) {
+#endif
                         hit = true;
                         c = {c.x + sh.surface.x, c.y + sh.surface.y, c.z + sh.surface.z};
                     }
@@ -3160,6 +3342,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(sizeof(R
                     if (slot < (int)cap) pool_put(pl, slot, co, cd, rw * cw, child_meta);
                     else atomicOr(P.error_flag, kErrPoolOverflow);
                 };
+#if RTC_AREA_LIGHTS
+                // (one sample's rays at a time in the pool: the sample is the loop's, the pixel the entry's)
+                sh.ray_id = sample_ray_id(P, t, pix, n, sample - (sample / n) * n, sample / n);
+#endif
                 if (active) hit = shade_ray<R, true, kDup>(sc, ro, rd, meta >> 8, sh, push);
                 count_events(k, false, hit, sh, sc.n_lights);
                 if (hit) {
@@ -3284,6 +3470,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(sizeof(R
                     atomicOr(P.error_flag, kErrPoolOverflow);
                 }
             };
+#if RTC_AREA_LIGHTS
+            sh.ray_id = (uint32_t)r;  // the ray's index in the batch, modulo 2^32; its children keep it
+#endif
             if (active) hit = shade_ray<R, true, kDup>(sc, o, d, rem, sh, push);
             count_events(k, primary, hit, sh, sc.n_lights);
             if (P.gen_counts) count_generations(P.gen_counts, active, hit, rem);

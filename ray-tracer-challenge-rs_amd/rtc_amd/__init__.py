@@ -28,6 +28,7 @@ __all__ = [
     "RenderError", "lib_path", "abi_version", "device_count", "matrix_inverse", "camera_make",
     "camera_resize", "camera_set_transform", "camera_bound_rect", "load_scene", "load_scene_text", "SceneTables", "Context", "shard_rows",
     "load_obj", "Mesh", "SmoothDesc", "RT_SMOOTH_SHAPES", "RT_OBJ_NORMALS", "RT_NO_NORMAL",
+    "AreaLightDesc", "RT_LIGHT_MAX_STEPS", "RT_JITTER_NONE", "RT_JITTER_HASHED", "area_light_sample",
     "UVDesc", "TextureDesc", "RT_OBJ_TEXCOORDS", "RT_NO_TEXCOORD", "TEXTURE_FILTERS", "read_image",
     "RT_DEFAULT_MAX_DEPTH", "RT_TILE_H", "RT_TILE_W",
 ]
@@ -53,6 +54,8 @@ RT_NO_NORMAL = 0xFFFFFFFF      # rt_mesh_normals_view.triangle_normals of a flat
 RT_OBJ_TEXCOORDS = 4           # rt_mesh_load_obj_ex: read vt lines and the faces' texture indices
 RT_NO_TEXCOORD = 0xFFFFFFFF    # rt_mesh_texcoords_view.triangle_texcoords of a face without coordinates
 TEXTURE_FILTERS = {"nearest": 0, "bilinear": 1}  # rt_pattern_desc.reserved of an image pattern
+RT_LIGHT_MAX_STEPS = 16                 # rt_area_light_desc: steps per axis
+RT_JITTER_NONE, RT_JITTER_HASHED = 0, 1  # rt_area_light_desc.jitter
 
 SHAPE_KINDS = {"sphere": 0, "plane": 1, "cube": 2, "cylinder": 3, "cone": 4, "triangle": 5}
 PATTERN_KINDS = {"stripe": 0, "gradient": 1, "ring": 2, "checker": 3, "complex": 4, "test": 5, "image": 6}
@@ -195,6 +198,17 @@ class TextureInfo(C.Structure):
                 ("reserved", C.c_uint32), ("uv_bytes", C.c_uint64), ("texel_bytes", C.c_uint64)]
 
 
+class AreaLightDesc(C.Structure):
+    _fields_ = [("corner", C.c_double * 3), ("full_uvec", C.c_double * 3), ("full_vvec", C.c_double * 3),
+                ("intensity", C.c_double * 3), ("usteps", C.c_uint32), ("vsteps", C.c_uint32),
+                ("jitter", C.c_uint32), ("seed", C.c_uint32)]
+
+
+class LightInfo(C.Structure):
+    _fields_ = [("area_lights", C.c_uint32), ("samples", C.c_uint32), ("ran_area", C.c_uint32),
+                ("reserved", C.c_uint32), ("area_bytes", C.c_uint64)]
+
+
 class MeshTexcoordsView(C.Structure):
     _fields_ = [("texcoords", C.POINTER(C.c_double)), ("n_texcoords", C.c_uint32), ("n_textured", C.c_uint32),
                 ("triangle_texcoords", C.POINTER(C.c_uint32))]
@@ -300,6 +314,16 @@ def _load() -> C.CDLL:
         "rt_uv_expand": (C.c_int, [P(ShapeDesc), C.c_uint32, P(MeshDesc), C.c_uint32, P(InstanceDesc), C.c_uint32,
                                    P(UVDesc), C.c_uint32, P(UVDesc), P(C.c_uint32)]),
         "rt_scene_texture_info": (C.c_int, [C.c_void_p, P(TextureInfo)]),
+        "rt_scene_upload_lit": (C.c_int, [C.c_void_p, P(ShapeDesc), C.c_uint32, P(MeshDesc), C.c_uint32,
+                                          P(InstanceDesc), C.c_uint32, P(SmoothDesc), C.c_uint32, P(UVDesc),
+                                          C.c_uint32, P(TextureDesc), C.c_uint32, P(MaterialDesc), C.c_uint32,
+                                          P(PatternDesc), C.c_uint32, P(LightDesc), C.c_uint32, P(AreaLightDesc),
+                                          C.c_uint32]),
+        "rt_lights_expand": (C.c_int, [P(LightDesc), C.c_uint32, P(AreaLightDesc), C.c_uint32, P(LightDesc),
+                                       P(C.c_uint32)]),
+        "rt_area_light_sample": (C.c_int, [P(AreaLightDesc), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                           P(C.c_double)]),
+        "rt_scene_light_info": (C.c_int, [C.c_void_p, P(LightInfo)]),
         "rt_mesh_texcoords_get": (C.c_int, [C.c_void_p, P(MeshTexcoordsView)]),
         "rt_mesh_uvs": (C.c_int, [C.c_void_p, P(UVDesc), C.c_uint32, P(C.c_uint32)]),
         "rt_image_read": (C.c_int, [C.c_char_p, P(P(C.c_uint8)), P(C.c_uint32), P(C.c_uint32)]),
@@ -370,6 +394,7 @@ EXPORTED_SYMBOLS = (
     "rt_mesh_load_obj_ex", "rt_mesh_normals_get", "rt_mesh_smooth_normals",
     "rt_scene_upload_textured", "rt_uv_expand", "rt_scene_texture_info", "rt_mesh_texcoords_get", "rt_mesh_uvs",
     "rt_image_read", "rt_image_free",
+    "rt_scene_upload_lit", "rt_lights_expand", "rt_area_light_sample", "rt_scene_light_info",
 )
 
 
@@ -474,6 +499,13 @@ def read_image(path) -> np.ndarray:
         _lib.rt_image_free(rgb)
 
 
+def area_light_sample(desc: "AreaLightDesc", area_index: int, ray_id: int, remaining: int, k: int) -> np.ndarray:
+    """rt_area_light_sample: the f64 position of sample k of an area light, for either jitter mode."""
+    pos = (C.c_double * 3)()
+    _check(_lib.rt_area_light_sample(C.byref(desc), area_index, ray_id, remaining, k, pos))
+    return np.array(pos[:], dtype=np.float64)
+
+
 def canvas_quantize(image: np.ndarray) -> np.ndarray:
     """canvas.rs:81, 117-123 on the host: round(clamp(c, 0, 1) * 255) as u8 of an f64 canvas."""
     src = np.ascontiguousarray(image, dtype=np.float64)
@@ -526,6 +558,29 @@ class SceneTables:
     # of shape (H, W, 3); None / empty = none.
     uvs: C.Array | None = None
     textures: list | None = None
+    # Area lights (rtc.h rt_scene_upload_lit): an array of AreaLightDesc; None / empty = none.
+    area_lights: C.Array | None = None
+
+    @property
+    def lit(self) -> bool:
+        return self.area_lights is not None and len(self.area_lights) > 0
+
+    def lit_args(self):
+        """rt_scene_upload_lit's arguments after the context: textured_args() with the area list at the end."""
+        al = self.area_lights if self.area_lights is not None else (AreaLightDesc * 0)()
+        return self.textured_args() + (al, len(al))
+
+    def expanded_lights(self):
+        """The light list the world means (rt_lights_expand): the point lights, then every area light's
+        samples as point lights of intensity / N.  A hashed light has no expansion (RenderError)."""
+        if not self.lit:
+            return self.lights
+        n = C.c_uint32(0)
+        a = (self.lights, len(self.lights), self.area_lights, len(self.area_lights))
+        _check(_lib.rt_lights_expand(*a, None, C.byref(n)))
+        out = (LightDesc * n.value)()
+        _check(_lib.rt_lights_expand(*a, out, C.byref(n)))
+        return out
 
     @property
     def textured(self) -> bool:
@@ -586,9 +641,13 @@ class SceneTables:
     def expanded(self) -> "SceneTables":
         """The flat world an instanced one means (rt_instances_expand): the shapes, then every instance's
         triangles with its inverse and material; the other tables are shared.  A plain world: itself.
-        A smooth list is expanded with it (rt_smooth_expand): every entry then names a world index."""
+        A smooth list is expanded with it (rt_smooth_expand): every entry then names a world index.
+        Area lights are expanded too (rt_lights_expand): the result holds point lights only."""
         if not self.instanced:
-            return self
+            if not self.lit:
+                return self
+            return SceneTables(self.shapes, self.materials, self.patterns, self.expanded_lights(), self.camera,
+                               self.duplicate_shapes, smooth=self.smooth, uvs=self.uvs, textures=self.textures)
         md, inst = self.mesh_descs(), self.instances
         total = len(self.shapes) + sum(len(self.meshes[i.mesh]) for i in inst if i.mesh < len(self.meshes))
         out = (ShapeDesc * total)()
@@ -607,8 +666,8 @@ class SceneTables:
             _check(_lib.rt_uv_expand(*a, None, C.byref(n)))
             uvs = (UVDesc * n.value)()
             _check(_lib.rt_uv_expand(*a, uvs, C.byref(n)))
-        return SceneTables(out, self.materials, self.patterns, self.lights, self.camera, smooth=smooth, uvs=uvs,
-                           textures=self.textures)
+        return SceneTables(out, self.materials, self.patterns, self.expanded_lights(), self.camera, smooth=smooth,
+                           uvs=uvs, textures=self.textures)
 
     @property
     def counts(self):
@@ -877,12 +936,22 @@ class Context:
         _check(_lib.rt_scene_texture_info(self._h, C.byref(t)))
         return {name: getattr(t, name) for name, _ in t._fields_ if name != "reserved"}
 
+    def light_info(self) -> dict:
+        """The uploaded world's area lights (rtc.h rt_scene_light_info): how many, their samples in all, the
+        device bytes of their records, whether the last launch ran the kernels that hold the sample loop."""
+        t = LightInfo()
+        _check(_lib.rt_scene_light_info(self._h, C.byref(t)))
+        return {name: getattr(t, name) for name, _ in t._fields_ if name != "reserved"}
+
     def upload(self, scene: SceneTables | None) -> None:
         """rt_scene_upload, rt_scene_upload_instanced for tables with instances, rt_scene_upload_smooth for
-        tables with smooth triangles, or rt_scene_upload_textured for tables with texture coordinates or
-        textures; on a non-zero rank of a group, None (the scene comes from rank 0)."""
+        tables with smooth triangles, rt_scene_upload_textured for tables with texture coordinates or
+        textures, or rt_scene_upload_lit for tables with area lights; on a non-zero rank of a group, None
+        (the scene comes from rank 0)."""
         if scene is None:
             _check(_lib.rt_scene_upload(self._h, None, 0, None, 0, None, 0, None, 0))
+        elif scene.lit:
+            _check(_lib.rt_scene_upload_lit(self._h, *scene.lit_args()))
         elif scene.textured:
             _check(_lib.rt_scene_upload_textured(self._h, *scene.textured_args()))
         elif scene.smoothed:

@@ -20,7 +20,7 @@ import ctypes as C
 import math
 from dataclasses import dataclass, field
 
-from . import (CameraDesc, InstanceDesc, LightDesc, MaterialDesc, PatternDesc, PATTERN_KINDS, RT_SMOOTH_SHAPES,
+from . import (AreaLightDesc, CameraDesc, InstanceDesc, LightDesc, MaterialDesc, PatternDesc, PATTERN_KINDS, RT_SMOOTH_SHAPES,
                SceneTables, ShapeDesc, SHAPE_KINDS, SmoothDesc, TEXTURE_FILTERS, UVDesc, camera_make, matrix_inverse)
 
 F64_MAX = 1.7976931348623157e308
@@ -292,10 +292,36 @@ class Light:
 
 
 @dataclass
+class AreaLight:
+    """An area light (rtc.h rt_scene_upload_lit): the parallelogram corner + s full_uvec + t full_vvec, cut
+    into usteps x vsteps cells with one sample each; jitter False = the cells' centres, True = hashed per ray
+    with `seed`.  It means usteps * vsteps point lights of intensity / (usteps * vsteps)."""
+    corner: tuple
+    full_uvec: tuple
+    full_vvec: tuple
+    usteps: int = 1
+    vsteps: int = 1
+    intensity: tuple = (1.0, 1.0, 1.0)
+    jitter: bool = False
+    seed: int = 0
+
+    def desc(self) -> AreaLightDesc:
+        d = AreaLightDesc()
+        d.corner[:] = list(map(float, self.corner))
+        d.full_uvec[:] = list(map(float, self.full_uvec))
+        d.full_vvec[:] = list(map(float, self.full_vvec))
+        d.intensity[:] = list(map(float, self.intensity))
+        d.usteps, d.vsteps = int(self.usteps), int(self.vsteps)
+        d.jitter, d.seed = int(self.jitter), int(self.seed) & 0xFFFFFFFF
+        return d
+
+
+@dataclass
 class World:
     lights: list = field(default_factory=list)
     shapes: list = field(default_factory=list)
     instances: list = field(default_factory=list)  # of Instance: their triangles follow the shapes in world order
+    area_lights: list = field(default_factory=list)  # of AreaLight: their samples follow the lights in the light list
 
     @staticmethod
     def default() -> "World":
@@ -394,7 +420,9 @@ class World:
         return SceneTables(shapes, mats, ptab, lts, camera if camera is not None else CameraDesc(),
                            meshes=meshes or None, instances=inst if len(inst) else None,
                            smooth=(SmoothDesc * len(smooth))(*smooth) if smooth else None,
-                           uvs=(UVDesc * len(uvs))(*uvs) if uvs else None, textures=textures or None)
+                           uvs=(UVDesc * len(uvs))(*uvs) if uvs else None, textures=textures or None,
+                           area_lights=(AreaLightDesc * len(self.area_lights))(*[a.desc() for a in self.area_lights])
+                           if self.area_lights else None)
 
 
 def camera(width, height, fov, frm=(0, 0, 0), to=(0, 0, -1), up=(0, 1, 0)) -> CameraDesc:
