@@ -12,7 +12,10 @@
 //   decide_expanded() which instances have a value-equal partner and are
 //                   uploaded as plain records (the containers walk identifies
 //                   shapes by value: shape_identity.hpp);
-//   world_bases()   the world index of each instance's first triangle.
+//   world_bases()   the world index of each instance's first triangle;
+//   validate_side(), side_index(), expand_side()
+//                   the per-triangle side lists (vertex normals, texture
+//                   coordinates): one implementation, two uses.
 #pragma once
 
 #include <algorithm>
@@ -278,16 +281,47 @@ inline bool share_face(const rt_mesh_desc& a, const FaceIndex& fa, const rt_mesh
     return false;
 }
 
-// ---- smooth triangles (rtc.h rt_scene_upload_smooth) -------------------------
+// ---- per-triangle side lists (rtc.h rt_scene_upload_smooth, rt_scene_upload_textured) ----
+// Vertex normals and texture coordinates are both lists of entries that name a
+// triangle (a plain shape, or a mesh's local record) and give it a run of
+// reals.  What differs is here; the code below is written once for both.
+struct SmoothSide {  // rt_scene_upload_smooth's list: nine normal components an entry
+    using Desc = rt_smooth_desc;
+    static constexpr int kReals = 9;
+    static constexpr const char* kEntry = "smooth entry ";
+    static constexpr const char* kNullList = "rt_scene_upload_smooth: null smooth list with nonzero count";
+    static constexpr const char* kNotFinite = ": a normal component is not finite";
+    static constexpr const char* kOutsideRun = "smooth triangle outside the triangle run";
+    static const double* reals(const Desc& d) { return d.normal_1; }
+    static double* reals(Desc& d) { return d.normal_1; }
+};
+static_assert(sizeof(rt_smooth_desc) == 80 && offsetof(rt_smooth_desc, normal_1) == 8 &&
+                  offsetof(rt_smooth_desc, normal_3) == 8 + 6 * sizeof(double),
+              "the nine normal components are contiguous");
+struct UVSide {  // rt_scene_upload_textured's coordinate list: six components an entry
+    using Desc = rt_uv_desc;
+    static constexpr int kReals = 6;
+    static constexpr const char* kEntry = "uv entry ";
+    static constexpr const char* kNullList = "rt_scene_upload_textured: null uv list with nonzero count";
+    static constexpr const char* kNotFinite = ": a texture coordinate is not finite";
+    static constexpr const char* kOutsideRun = "textured triangle outside the triangle run";
+    static const double* reals(const Desc& d) { return d.uv_1; }
+    static double* reals(Desc& d) { return d.uv_1; }
+};
+static_assert(sizeof(rt_uv_desc) == 56 && offsetof(rt_uv_desc, uv_1) == 8 &&
+                  offsetof(rt_uv_desc, uv_3) == 8 + 4 * sizeof(double),
+              "the six coordinate components are contiguous");
+
 // Empty when the list is well formed against validated instanced lists, else
 // the reason (RT_ERR_INVALID), each with its own text.
-inline std::string validate_smooth(const rt_shape_desc* shapes, uint32_t ns, const rt_mesh_desc* meshes,
-                                   uint32_t n_meshes, const rt_smooth_desc* smooth, uint32_t n_smooth) {
-    if (n_smooth && !smooth) return "rt_scene_upload_smooth: null smooth list with nonzero count";
+template <typename Side>
+inline std::string validate_side(const rt_shape_desc* shapes, uint32_t ns, const rt_mesh_desc* meshes, uint32_t n_meshes,
+                                 const typename Side::Desc* list, uint32_t n_list) {
+    if (n_list && !list) return Side::kNullList;
     std::vector<std::vector<char>> seen(n_meshes + 1);  // [n_meshes]: the plain shapes
-    for (uint32_t k = 0; k < n_smooth; ++k) {
-        const rt_smooth_desc& d = smooth[k];
-        const std::string who = "smooth entry " + std::to_string(k);
+    for (uint32_t k = 0; k < n_list; ++k) {
+        const typename Side::Desc& d = list[k];
+        const std::string who = Side::kEntry + std::to_string(k);
         if (d.list != RT_SMOOTH_SHAPES && d.list >= n_meshes) return who + ": list index out of range";
         const bool plain = d.list == RT_SMOOTH_SHAPES;
         const uint32_t n = plain ? ns : meshes[d.list].n_triangles;
@@ -298,52 +332,50 @@ inline std::string validate_smooth(const rt_shape_desc* shapes, uint32_t ns, con
         if (s.empty()) s.assign(n, 0);
         if (s[d.index]) return who + ": the same triangle is named twice";
         s[d.index] = 1;
-        for (const double* n : {d.normal_1, d.normal_2, d.normal_3})
-            for (int q = 0; q < 3; ++q)
-                if (!std::isfinite(n[q])) return who + ": a normal component is not finite";
+        for (int q = 0; q < Side::kReals; ++q)
+            if (!std::isfinite(Side::reals(d)[q])) return who + Side::kNotFinite;
     }
     return "";
 }
-static_assert(sizeof(rt_smooth_desc) == 80 && offsetof(rt_smooth_desc, normal_1) == 8 &&
-                  offsetof(rt_smooth_desc, normal_3) == 8 + 6 * sizeof(double),
-              "the nine normal components are contiguous");
 
-// The normals of a validated smooth list by triangle: per plain shape and per
-// mesh triangle the entry's nine doubles, or null for a flat one.
-struct SmoothIndex {
-    std::vector<const double*> plain;              // by shape; empty: none is smooth
+// The reals of a validated side list by triangle: per plain shape and per mesh
+// triangle the entry's reals, or null for a triangle the list does not name.
+struct SideIndex {
+    std::vector<const double*> plain;              // by shape; empty: none is named
     std::vector<std::vector<const double*>> mesh;  // by mesh, by local index; empty: none of the mesh's is
     ident::Normals of_plain() const { return plain.empty() ? nullptr : plain.data(); }
     ident::Normals of_mesh(uint32_t m) const { return mesh[m].empty() ? nullptr : mesh[m].data(); }
-    uint32_t smooth_in_mesh(uint32_t m) const {
+    uint32_t named_in_mesh(uint32_t m) const {
         return (uint32_t)std::count_if(mesh[m].begin(), mesh[m].end(), [](const double* p) { return p != nullptr; });
     }
 };
-inline SmoothIndex smooth_index(uint32_t ns, const rt_mesh_desc* meshes, uint32_t n_meshes, const rt_smooth_desc* smooth,
-                                uint32_t n_smooth) {
-    SmoothIndex si;
+template <typename Side>
+inline SideIndex side_index(uint32_t ns, const rt_mesh_desc* meshes, uint32_t n_meshes, const typename Side::Desc* list,
+                            uint32_t n_list) {
+    SideIndex si;
     si.mesh.resize(n_meshes);
-    for (uint32_t k = 0; k < n_smooth; ++k) {
-        const rt_smooth_desc& d = smooth[k];
+    for (uint32_t k = 0; k < n_list; ++k) {
+        const typename Side::Desc& d = list[k];
         std::vector<const double*>& v = d.list == RT_SMOOTH_SHAPES ? si.plain : si.mesh[d.list];
         if (v.empty()) v.assign(d.list == RT_SMOOTH_SHAPES ? ns : meshes[d.list].n_triangles, nullptr);
-        v[d.index] = d.normal_1;
+        v[d.index] = Side::reals(d);
     }
     return si;
 }
-// The smooth list of the expansion (expand()): the plain entries, then per
+// The side list of the expansion (expand()): the plain entries, then per
 // instance its mesh's entries at the instance's world indices, every entry with
-// RT_SMOOTH_SHAPES, in ascending world index.  Returns the count; out may be null.
-inline uint32_t expand_smooth(uint32_t ns, const rt_mesh_desc* meshes, uint32_t n_meshes,
-                              const rt_instance_desc* instances, uint32_t n_inst, const rt_smooth_desc* smooth,
-                              uint32_t n_smooth, rt_smooth_desc* out) {
-    const SmoothIndex si = smooth_index(ns, meshes, n_meshes, smooth, n_smooth);
+// RT_SMOOTH_SHAPES, in ascending world index (the reals do not transform).
+// Returns the count; out may be null.
+template <typename Side>
+inline uint32_t expand_side(uint32_t ns, const rt_mesh_desc* meshes, uint32_t n_meshes, const rt_instance_desc* instances,
+                            uint32_t n_inst, const typename Side::Desc* list, uint32_t n_list, typename Side::Desc* out) {
+    const SideIndex si = side_index<Side>(ns, meshes, n_meshes, list, n_list);
     uint32_t at = 0;
-    auto put = [&](uint32_t world, const double* n) {
+    auto put = [&](uint32_t world, const double* reals) {
         if (out) {
             out[at].list = RT_SMOOTH_SHAPES;
             out[at].index = world;
-            std::memcpy(out[at].normal_1, n, 9 * sizeof(double));
+            std::memcpy(Side::reals(out[at]), reals, Side::kReals * sizeof(double));
         }
         ++at;
     };
@@ -371,70 +403,6 @@ inline std::string validate_textures(const rt_texture_desc* textures, uint32_t n
         if ((uint64_t)t.width * t.height > (uint64_t)RT_TEXTURE_MAX_TEXELS) return who + ": more than 2^28 texels";
     }
     return "";
-}
-// The coordinate list against validated instanced lists, as validate_smooth.
-inline std::string validate_uvs(const rt_shape_desc* shapes, uint32_t ns, const rt_mesh_desc* meshes, uint32_t n_meshes,
-                                const rt_uv_desc* uvs, uint32_t n_uvs) {
-    if (n_uvs && !uvs) return "rt_scene_upload_textured: null uv list with nonzero count";
-    std::vector<std::vector<char>> seen(n_meshes + 1);  // [n_meshes]: the plain shapes
-    for (uint32_t k = 0; k < n_uvs; ++k) {
-        const rt_uv_desc& d = uvs[k];
-        const std::string who = "uv entry " + std::to_string(k);
-        if (d.list != RT_SMOOTH_SHAPES && d.list >= n_meshes) return who + ": list index out of range";
-        const bool plain = d.list == RT_SMOOTH_SHAPES;
-        const uint32_t n = plain ? ns : meshes[d.list].n_triangles;
-        if (d.index >= n) return who + ": triangle index out of range";
-        const rt_shape_desc& t = plain ? shapes[d.index] : meshes[d.list].triangles[d.index];
-        if (t.kind != RT_SHAPE_TRIANGLE) return who + ": the named record is not a triangle";
-        std::vector<char>& s = seen[plain ? n_meshes : d.list];
-        if (s.empty()) s.assign(n, 0);
-        if (s[d.index]) return who + ": the same triangle is named twice";
-        s[d.index] = 1;
-        for (const double* c : {d.uv_1, d.uv_2, d.uv_3})
-            for (int q = 0; q < 2; ++q)
-                if (!std::isfinite(c[q])) return who + ": a texture coordinate is not finite";
-    }
-    return "";
-}
-static_assert(sizeof(rt_uv_desc) == 56 && offsetof(rt_uv_desc, uv_1) == 8 &&
-                  offsetof(rt_uv_desc, uv_3) == 8 + 4 * sizeof(double),
-              "the six coordinate components are contiguous");
-// The coordinates of a validated list by triangle, in SmoothIndex's form: the entry's six doubles or null.
-inline SmoothIndex uv_index(uint32_t ns, const rt_mesh_desc* meshes, uint32_t n_meshes, const rt_uv_desc* uvs,
-                            uint32_t n_uvs) {
-    SmoothIndex ui;
-    ui.mesh.resize(n_meshes);
-    for (uint32_t k = 0; k < n_uvs; ++k) {
-        const rt_uv_desc& d = uvs[k];
-        std::vector<const double*>& v = d.list == RT_SMOOTH_SHAPES ? ui.plain : ui.mesh[d.list];
-        if (v.empty()) v.assign(d.list == RT_SMOOTH_SHAPES ? ns : meshes[d.list].n_triangles, nullptr);
-        v[d.index] = d.uv_1;
-    }
-    return ui;
-}
-// The coordinate list of the expansion, as expand_smooth: coordinates do not transform.
-inline uint32_t expand_uvs(uint32_t ns, const rt_mesh_desc* meshes, uint32_t n_meshes, const rt_instance_desc* instances,
-                           uint32_t n_inst, const rt_uv_desc* uvs, uint32_t n_uvs, rt_uv_desc* out) {
-    const SmoothIndex ui = uv_index(ns, meshes, n_meshes, uvs, n_uvs);
-    uint32_t at = 0;
-    auto put = [&](uint32_t world, const double* c) {
-        if (out) {
-            out[at].list = RT_SMOOTH_SHAPES;
-            out[at].index = world;
-            std::memcpy(out[at].uv_1, c, 6 * sizeof(double));
-        }
-        ++at;
-    };
-    for (uint32_t i = 0; i < (uint32_t)ui.plain.size(); ++i)
-        if (ui.plain[i]) put(i, ui.plain[i]);
-    uint32_t base = ns;
-    for (uint32_t k = 0; k < n_inst; ++k) {
-        const uint32_t m = instances[k].mesh;
-        for (uint32_t j = 0; j < (uint32_t)ui.mesh[m].size(); ++j)
-            if (ui.mesh[m][j]) put(base + j, ui.mesh[m][j]);
-        base += meshes[m].n_triangles;
-    }
-    return at;
 }
 // Do two textures hold the same picture (width, height, bytes)?
 inline bool texture_eq(const rt_texture_desc& a, const rt_texture_desc& b) {
@@ -479,7 +447,7 @@ inline void canonical_image_patterns(rt_pattern_desc* pats, uint32_t np, const r
 inline std::vector<char> decide_expanded(const rt_shape_desc* shapes, uint32_t ns, const rt_mesh_desc* meshes,
                                          uint32_t n_meshes, const rt_instance_desc* instances, uint32_t n_inst,
                                          const rt_material_desc* mats, const rt_pattern_desc* pats,
-                                         const SmoothIndex* si = nullptr) {
+                                         const SideIndex* si = nullptr) {
     auto mesh_normals = [&](uint32_t m) { return si ? si->of_mesh(m) : nullptr; };
     const ident::Normals plain_normals = si ? si->of_plain() : nullptr;
     std::vector<char> expanded(n_inst, 0);

@@ -32,11 +32,39 @@ struct InstanceCounts {
     int32_t world_begin = 0;  // world indices from here on are instances' triangles
 };
 
-// Entries (nine reals each) of a world's smooth-triangle normal tables: one per
-// record of the triangle run and one per local record of the meshes, or zero
-// where that part holds no smooth triangle (rtc_internal.hpp kShapeSmooth).
+// Entries of a world's per-triangle side table (the smooth triangles' normals,
+// the texture coordinates): one per record of the triangle run and one per
+// local record of the meshes, or zero where that part holds no such triangle
+// (rtc_internal.hpp kShapeSmooth, kShapeUV).
 struct SmoothCounts {
     uint32_t plain = 0, inst = 0;
+};
+
+// A side table of one precision, kReals reals an entry: the plain part's
+// entries, then the meshes', outside the LDS image.
+template <typename R, int kReals>
+struct SideTable {
+    DeviceBuffer<R> reals;
+    SmoothCounts counts{};  // zeros: the world has no such triangle
+    // Room for the entries of `c`.
+    int allocate(const SmoothCounts& c) {
+        if (int rc = reals.reserve(((size_t)c.plain + c.inst) * kReals)) return rc;
+        counts = c;
+        return RT_OK;
+    }
+    size_t bytes() const { return ((size_t)counts.plain + counts.inst) * kReals * sizeof(R); }
+    const R* plain() const { return counts.plain ? reals.get() : nullptr; }
+    const R* inst() const { return counts.inst ? reals.get() + (size_t)counts.plain * kReals : nullptr; }
+};
+
+// Which build of the tracer kernels a world runs (rtc_host.cpp kLaunchers): every
+// build holds the code of the ones before it.  Stored in rt_context::kernel_build
+// by set_kernel_build and nowhere re-derived.
+enum class KernelBuild : uint32_t {
+    plain,      // rtc::launch_trace*: worlds of shapes alone
+    instanced,  // rtc::instanced::*: the instance level and the smooth triangle's normal (rtc_kernels.hip prepare_hit)
+    textured,   // rtc::textured::*: ... plus the texture code, for an image pattern or a coordinate entry
+    area,       // rtc::area::*: ... plus the area lights' sample loop
 };
 
 // Texel storage of a world (rt_scene_upload_textured): the texture count and the texels of all of them; a
@@ -64,13 +92,10 @@ struct DeviceWorld {
     DeviceBuffer<TriNode<R>> inst_nodes;    // every mesh's hierarchy
     DeviceBuffer<int32_t> inst_pos;         // local index -> record (InstRec::pos_begin)
     InstanceCounts inst_counts{};           // zeros: a world without instances
-    // Smooth triangles (rt_scene_upload_smooth): the plain part's entries, then the meshes', outside the LDS image
-    DeviceBuffer<R> smooth;
-    SmoothCounts smooth_counts{};           // zeros: a world without smooth triangles
-    // Texture coordinates (rt_scene_upload_textured), laid out like `smooth` with six reals an entry; the texels
-    // and the per-texture table are the context's (rt_context::texels), one copy for both precisions
-    DeviceBuffer<R> uv;
-    SmoothCounts uv_counts{};               // zeros: no triangle with coordinates
+    SideTable<R, kSmoothReals> smooth;  // smooth triangles (rt_scene_upload_smooth): the vertex normals
+    // Texture coordinates (rt_scene_upload_textured); the texels and the per-texture table are the context's
+    // (rt_context::texels), one copy for both precisions
+    SideTable<R, kUVReals> uv;
     const uint32_t* texels = nullptr;
     const TexRec* tex_table = nullptr;      // non-null: the world runs the texture code
     // Area lights (rt_scene_upload_lit; rtc_internal.hpp AreaLightRec), outside the LDS image
@@ -121,30 +146,12 @@ struct DeviceWorld {
         inst_counts = c;
         return RT_OK;
     }
-    // Room for the normal tables of `c`; all zero: the world has no smooth triangle.
-    int allocate_smooth(const SmoothCounts& c) {
-        if (int rc = smooth.reserve(((size_t)c.plain + c.inst) * kSmoothReals)) return rc;
-        smooth_counts = c;
-        return RT_OK;
-    }
-    // Room for the coordinate tables of `c`; all zero: no triangle has coordinates.
-    int allocate_uv(const SmoothCounts& c) {
-        if (int rc = uv.reserve(((size_t)c.plain + c.inst) * kUVReals)) return rc;
-        uv_counts = c;
-        return RT_OK;
-    }
     // Room for n area lights of `samples` samples in all; n = 0: the world has none.
     int allocate_area(uint32_t n, uint32_t samples) {
         if (int rc = area.reserve(n)) return rc;
         n_area = n;
         area_samples = n ? samples : 0u;
         return RT_OK;
-    }
-    const R* uv_plain() const { return uv_counts.plain ? uv.get() : nullptr; }
-    const R* uv_inst() const { return uv_counts.inst ? uv.get() + (size_t)uv_counts.plain * kUVReals : nullptr; }
-    const R* smooth_plain() const { return smooth_counts.plain ? smooth.get() : nullptr; }
-    const R* smooth_inst() const {
-        return smooth_counts.inst ? smooth.get() + (size_t)smooth_counts.plain * kSmoothReals : nullptr;
     }
 };
 
@@ -154,24 +161,21 @@ template <typename R>
 inline bool walked_instances(const DeviceWorld<R>& w) {
     return w.inst_counts.instances > 0;
 }
-// Does the world hold an image pattern or a triangle with texture coordinates (rt_scene_upload_textured)?
+// Does the world hold the texture tables (an image pattern, a triangle with texture coordinates or an area
+// light: rt_scene_upload_textured, rt_scene_upload_lit)?
 template <typename R>
 inline bool has_textures(const DeviceWorld<R>& w) {
     return w.tex_table != nullptr;
 }
-// Does the world hold an area light (rt_scene_upload_lit)?  It then runs the area build's kernels
-// (rtc::area::launch_trace*: the texture build plus the sample loop) and is uploaded as a textured world.
+// Does the world hold an area light (rt_scene_upload_lit)?
 template <typename R>
 inline bool has_area(const DeviceWorld<R>& w) {
     return w.n_area > 0;
 }
-// Does the world run the instance build's kernels (rtc::instanced::launch_trace*) or, when it is textured,
-// the texture build's (rtc::textured::launch_trace*: the instance build plus the texture code)?  They hold the
-// instance level and the smooth triangle's normal (rtc_kernels.hip prepare_hit); every other world runs the
-// plain build.
+// Does the world hold a smooth triangle (rt_scene_upload_smooth)?
 template <typename R>
-inline bool instance_build(const DeviceWorld<R>& w) {
-    return walked_instances(w) || w.smooth_counts.plain > 0 || w.smooth_counts.inst > 0 || has_textures(w);
+inline bool has_smooth(const DeviceWorld<R>& w) {
+    return w.smooth.counts.plain > 0 || w.smooth.counts.inst > 0;
 }
 
 struct CodeBuild;  // rtc_jit.cpp: one hipRTC build of a per-scene kernel, possibly in flight
@@ -309,8 +313,9 @@ struct rt_context {
     int device = 0;
     int cu_count = 0;
     size_t lds_per_block = 64 * 1024;
-    size_t occ_lds[20] = {};    // occupancy cache: {direct,pool} x {f32,f64} x {global,LDS world},
-    int occ_blocks[20] = {};    // then the ray-batch kernel's {f32,f64} x {global,LDS world},
+    rtc::KernelBuild kernel_build = rtc::KernelBuild::plain;  // the uploaded world's (set_kernel_build)
+    size_t occ_lds[20] = {};    // occupancy cache of kernel_build's kernels: {direct,pool} x {f32,f64} x
+    int occ_blocks[20] = {};    // {global,LDS world}, then the ray-batch kernel's {f32,f64} x {global,LDS world},
                                 // then the supersampled kernels' (as the first eight)
     Knobs knobs;
     rtc::Stream stream;
@@ -408,43 +413,43 @@ int check_pool_error(rt_context* ctx);
 int order_after_last(rt_context* ctx, hipStream_t stream);  // cross-stream launch order (rtc.h)
 int copy_to_host(rt_context* ctx, void* out, size_t bytes);  // d_scratch -> caller host buffer, on ctx->stream
 uint32_t tile_rows_for(uint32_t height, uint32_t shards, uint32_t shard);
-int validate_scene(const rt_shape_desc* shapes, uint32_t ns, const rt_material_desc* mats, uint32_t nm,
-                   const rt_pattern_desc* pats, uint32_t np, const rt_light_desc* lights, uint32_t nl,
-                   int64_t n_textures = -1);  // >= 0: rt_scene_upload_textured's count (image patterns are known)
-// The mesh and instance lists of rt_scene_upload_instanced
-struct InstancedLists {
-    const rt_mesh_desc* meshes;
-    uint32_t n_meshes;
-    const rt_instance_desc* instances;
-    uint32_t n_instances;
+// Every list an upload can carry (rtc.h rt_scene_upload ... rt_scene_upload_lit): an entry point fills the
+// ones it takes and leaves the others empty.
+struct WorldLists {
+    const rt_shape_desc* shapes = nullptr;
+    uint32_t n_shapes = 0;
+    const rt_material_desc* materials = nullptr;
+    uint32_t n_materials = 0;
+    const rt_pattern_desc* patterns = nullptr;
+    uint32_t n_patterns = 0;
+    const rt_light_desc* lights = nullptr;
+    uint32_t n_lights = 0;
+    const rt_mesh_desc* meshes = nullptr;  // rt_scene_upload_instanced's lists
+    uint32_t n_meshes = 0;
+    const rt_instance_desc* instances = nullptr;
+    uint32_t n_instances = 0;
     const rt_smooth_desc* smooth = nullptr;  // rt_scene_upload_smooth's list
     uint32_t n_smooth = 0;
-    // rt_scene_upload_textured's lists; `textured`: the upload came through it (image patterns are known)
-    const rt_uv_desc* uvs = nullptr;
+    const rt_uv_desc* uvs = nullptr;  // rt_scene_upload_textured's lists
     uint32_t n_uvs = 0;
     const rt_texture_desc* textures = nullptr;
     uint32_t n_textures = 0;
-    bool textured = false;
-    // rt_scene_upload_lit's list (it uploads as a textured world: `textured` is set with it)
-    const rt_area_light_desc* area = nullptr;
+    const rt_area_light_desc* area = nullptr;  // rt_scene_upload_lit's list
     uint32_t n_area = 0;
+    // the upload came through rt_scene_upload_textured or rt_scene_upload_lit: image patterns are known and
+    // checked against `textures` (the older entry points refuse pattern kind 6)
+    bool image_patterns = false;
 };
-int validate_scene_instanced(const rt_shape_desc* shapes, uint32_t ns, const InstancedLists& il,
-                             const rt_material_desc* mats, uint32_t nm, const rt_pattern_desc* pats, uint32_t np,
-                             const rt_light_desc* lights, uint32_t nl);
-// Flatten and upload the world tables to this device (no validation, no sync).
-int build_scene(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns, const rt_material_desc* mats, uint32_t nm,
-                const rt_pattern_desc* pats, uint32_t np, const rt_light_desc* lights, uint32_t nl);
-// ... of an instanced world (rtc.h rt_scene_upload_instanced; validated lists)
-int build_scene_instanced(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns, const rt_mesh_desc* meshes,
-                          uint32_t n_meshes, const rt_instance_desc* instances, uint32_t n_inst,
-                          const rt_material_desc* mats, uint32_t nm, const rt_pattern_desc* pats, uint32_t np,
-                          const rt_light_desc* lights, uint32_t nl, const rt_smooth_desc* smooth = nullptr,
-                          uint32_t n_smooth = 0, const InstancedLists* textured = nullptr);
-void scene_brightness(const rt_shape_desc* shapes, uint32_t ns, const rt_material_desc* mats, uint32_t nm,
-                      const rt_pattern_desc* pats, uint32_t np,
-                      const rt_light_desc* lights, uint32_t nl, double* bright_hit, double* bright_w,
-                      double extra_intensity = 0.0);  // the area lights': each counts as a point light of its intensity
+// Every refusal of rtc.h for these lists, in the entry points' order: the area list, the texture list, the
+// base tables, the mesh and instance lists, the smooth list, the uv list, the lights' total.
+int validate_scene(const WorldLists& wl);
+// Flatten and upload the validated lists to this device (no sync): the plain tables alone, or with the
+// instance, side, texture and area tables, by what the lists hold; then set_kernel_build.
+int build_scene(rt_context* ctx, const WorldLists& wl);
+// The one place that stores which build of the kernels the context's world runs and that clears the
+// occupancy cache (when the build changes): the end of a successful build_scene, and from the header on a
+// group's other ranks.
+void set_kernel_build(rt_context* ctx, KernelBuild build);
 // One frame (or shard strip) of this device into `out_device` on `stream`.
 int capture_jit_table(rt_context* ctx);  // the f32 table of the uploaded world, for rtc_jit.cpp
 int fetch_jit_tables(rt_context* ctx);   // build_world<float>'s host tables read back (a group's other ranks)
@@ -472,9 +477,7 @@ int jit_wait(rt_context* ctx, double timeout_ms, int* pending);
 const std::string& device_arch(rt_context* ctx);  // rtc_jit.cpp: the device's gfx target, read once
 
 // rtc_group.cpp: the same entry points on a multi-GPU context
-int group_scene_upload(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns, const rt_material_desc* mats,
-                       uint32_t nm, const rt_pattern_desc* pats, uint32_t np, const rt_light_desc* lights,
-                       uint32_t nl, const InstancedLists* il = nullptr);  // il: rt_scene_upload_instanced's lists
+int group_scene_upload(rt_context* ctx, const WorldLists& wl);
 int group_render_device(rt_context* ctx, const rt_camera_desc* cam, const rt_render_options* o, void* out_device,
                         hipStream_t stream);
 int group_render(rt_context* ctx, const rt_camera_desc* cam, const rt_render_options* o, void* out_host,

@@ -6,7 +6,7 @@
 // caller just calls render_parallel (camera.rs:97-112), so the split lives
 // here, not in the caller:
 //
-//   rt_scene_upload   rank 0 flattens the World (rtc_host.cpp build_scene)
+//   rt_scene_upload*  rank 0 flattens the World (rtc_host.cpp build_scene)
 //                     and ncclBroadcasts a header plus the four device
 //                     buffers (per precision: the table image, the lights)
 //                     (f32 and f64 records) to every other GPU.
@@ -48,6 +48,7 @@ namespace {
 // ranks can allocate them.
 struct SceneHeader {
     int32_t status;  // rank 0's validation/upload result: the others fail with it too
+    KernelBuild build;  // the kernels the world runs (rank 0's build_scene chose them)
     uint32_t ns, nm, np, nl;
     uint32_t n_world_slots;  // world indices world_slot answers for (ns, but for an instanced world)
     int32_t kind_begin[kNumKinds + 1];
@@ -80,8 +81,8 @@ void world_buffers(DeviceWorld<R>& w, const SceneHeader& h, std::vector<std::pai
     out.push_back({w.inst_shapes.get(), h.inst.records * sizeof(ShapeRec<R>)});
     out.push_back({w.inst_nodes.get(), h.inst.nodes * sizeof(TriNode<R>)});
     out.push_back({w.inst_pos.get(), h.inst.pos * sizeof(int32_t)});
-    out.push_back({w.smooth.get(), ((size_t)h.smooth.plain + h.smooth.inst) * kSmoothReals * sizeof(R)});
-    out.push_back({w.uv.get(), ((size_t)h.uv.plain + h.uv.inst) * kUVReals * sizeof(R)});
+    out.push_back({w.smooth.reals.get(), w.smooth.bytes()});  // (allocated for the header's counts)
+    out.push_back({w.uv.reals.get(), w.uv.bytes()});
     out.push_back({w.area.get(), (size_t)h.n_area * sizeof(AreaLightRec<R>)});
 }
 
@@ -318,9 +319,7 @@ int agree_status(const std::vector<rt_context*>& ms, int local) {
     return RT_OK;
 }
 
-int group_scene_upload(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns, const rt_material_desc* mats,
-                       uint32_t nm, const rt_pattern_desc* pats, uint32_t np, const rt_light_desc* lights,
-                       uint32_t nl, const InstancedLists* il) {
+int group_scene_upload(rt_context* ctx, const WorldLists& wl) {
     const std::vector<rt_context*> ms = members(ctx);
     int rc;
     SceneHeader root_h{};
@@ -334,33 +333,28 @@ int group_scene_upload(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns
     if (ctx->group.rank == 0) {  // only rank 0's tables are used (rtc.h)
         // a failure here still takes part in the header broadcast, so the
         // other ranks return it instead of waiting in the table broadcast
-        root_rc = il ? validate_scene_instanced(shapes, ns, *il, mats, nm, pats, np, lights, nl)
-                     : validate_scene(shapes, ns, mats, nm, pats, np, lights, nl);
+        root_rc = validate_scene(wl);
         if (!root_rc && hipSetDevice(ctx->device) != hipSuccess) root_rc = set_error(RT_ERR_HIP, "hipSetDevice");
-        if (!root_rc)
-            root_rc = il ? build_scene_instanced(ctx, shapes, ns, il->meshes, il->n_meshes, il->instances, il->n_instances,
-                                                 mats, nm, pats, np, lights, nl, il->smooth, il->n_smooth,
-                                                 il->textured ? il : nullptr)
-                         : build_scene(ctx, shapes, ns, mats, nm, pats, np, lights, nl);
+        if (!root_rc) root_rc = build_scene(ctx, wl);
         if (root_rc) root_err = rt_last_error();
         root_h.status = root_rc;
-        // (the shape table's size: an instanced world's also holds the instances uploaded expanded)
-        ns = root_rc ? ns : (uint32_t)ctx->w32.scene.kind_begin[kNumKinds];
+        root_h.build = ctx->kernel_build;
         root_h.n_world_slots = (uint32_t)ctx->world_slot.size();
         root_h.inst = ctx->w32.inst_counts;
         root_h.instance_info = ctx->instance_info;
-        root_h.smooth = ctx->w32.smooth_counts;
+        root_h.smooth = ctx->w32.smooth.counts;
         root_h.smooth_info = ctx->smooth_info;
-        root_h.uv = ctx->w32.uv_counts;
+        root_h.uv = ctx->w32.uv.counts;
         root_h.tex = ctx->tex_counts;
         root_h.texture_info = ctx->texture_info;
         root_h.n_area = ctx->w32.n_area;
         root_h.area_samples = ctx->w32.area_samples;
         root_h.light_info = ctx->light_info;
-        root_h.ns = ns;
-        root_h.nm = nm;
-        root_h.np = np;
-        root_h.nl = nl;
+        // (the shape table's size: an instanced world's also holds the instances uploaded expanded)
+        root_h.ns = root_rc ? wl.n_shapes : (uint32_t)ctx->w32.scene.kind_begin[kNumKinds];
+        root_h.nm = wl.n_materials;
+        root_h.np = wl.n_patterns;
+        root_h.nl = wl.n_lights;
         for (int k = 0; k <= kNumKinds; ++k) root_h.kind_begin[k] = ctx->w32.scene.kind_begin[k];
         root_h.any_secondary = ctx->w32.scene.any_secondary;
         root_h.duplicates = ctx->duplicate_shapes;
@@ -389,19 +383,15 @@ int group_scene_upload(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns
         if (hipSetDevice(m->device) != hipSuccess) local_rc = set_error(RT_ERR_HIP, "hipSetDevice");
         else if (m->group.rank != 0) {
             const SceneHeader& h = hdr[i];
-            // (worlds with and without instances run different kernels: the cached occupancies go)
-            if ((h.inst.instances > 0 || h.smooth.plain > 0 || h.smooth.inst > 0 || h.tex.on) != instance_build(m->w32) ||
-                (h.tex.on != 0) != has_textures(m->w32) || (h.n_area != 0) != has_area(m->w32))
-                std::fill(std::begin(m->occ_blocks), std::end(m->occ_blocks), 0);
             if ((local_rc = m->w32.allocate(h.ns, h.nm, h.np, h.nl)) == RT_OK &&
                 (local_rc = m->w64.allocate(h.ns, h.nm, h.np, h.nl)) == RT_OK &&
                 (local_rc = m->w32.allocate_tree(h.n_tri_nodes, h.tri_flat_begin)) == RT_OK &&
                 (local_rc = m->w64.allocate_tree(h.n_tri_nodes, h.tri_flat_begin)) == RT_OK &&
                 (local_rc = m->w32.allocate_instances(h.inst)) == RT_OK &&
                 (local_rc = m->w64.allocate_instances(h.inst)) == RT_OK &&
-                (local_rc = m->w32.allocate_smooth(h.smooth)) == RT_OK &&
-                (local_rc = m->w64.allocate_smooth(h.smooth)) == RT_OK &&
-                (local_rc = m->w32.allocate_uv(h.uv)) == RT_OK && (local_rc = m->w64.allocate_uv(h.uv)) == RT_OK &&
+                (local_rc = m->w32.smooth.allocate(h.smooth)) == RT_OK &&
+                (local_rc = m->w64.smooth.allocate(h.smooth)) == RT_OK &&
+                (local_rc = m->w32.uv.allocate(h.uv)) == RT_OK && (local_rc = m->w64.uv.allocate(h.uv)) == RT_OK &&
                 (local_rc = m->w32.allocate_area(h.n_area, h.area_samples)) == RT_OK &&
                 (local_rc = m->w64.allocate_area(h.n_area, h.area_samples)) == RT_OK &&
                 (local_rc = m->texels.reserve(h.tex.on ? std::max<uint64_t>(h.tex.texels, 1) : 0)) == RT_OK)
@@ -452,6 +442,7 @@ int group_scene_upload(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns
         m->smooth_info = h.smooth_info;
         m->texture_info = h.texture_info;
         m->light_info = h.light_info;
+        set_kernel_build(m, h.build);  // (the header's: this rank built nothing)
         m->have_scene = true;
         ++m->scene_gen;
     }

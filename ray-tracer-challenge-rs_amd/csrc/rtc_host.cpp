@@ -33,80 +33,58 @@
 
 namespace rtc {
 
-template <typename R>
-hipError_t launch_trace(const LaunchParams<R>& P, bool pool, bool dup, uint32_t grid, size_t dyn_lds,
-                        hipStream_t stream);
-template <typename R>
-hipError_t occupancy(bool pool, bool lds, size_t dyn_lds, int* blocks_per_cu);
-template <typename R>
-hipError_t launch_trace_rays(const LaunchParams<R>& P, bool dup, uint32_t grid, size_t dyn_lds, const void* rays,
-                             void* rgb, void* hits, hipStream_t stream);
-template <typename R>
-hipError_t occupancy_rays(bool lds, size_t dyn_lds, int* blocks_per_cu);
-// the supersampled frame kernels (trace_direct_ss, trace_pool_ss)
-template <typename R>
-hipError_t launch_trace_ss(const LaunchParams<R>& P, bool pool, bool dup, uint32_t grid, size_t dyn_lds,
-                           hipStream_t stream);
-template <typename R>
-hipError_t occupancy_ss(bool pool, bool lds, size_t dyn_lds, int* blocks_per_cu);
-
-namespace instanced {  // rtc_kernels_inst*.o: every tracer kernel with the instance level, for worlds with mesh instances
-template <typename R>
-hipError_t launch_trace(const LaunchParams<R>& P, bool pool, bool dup, uint32_t grid, size_t dyn_lds,
-                        hipStream_t stream);
-template <typename R>
-hipError_t occupancy(bool pool, bool lds, size_t dyn_lds, int* blocks_per_cu);
-template <typename R>
-hipError_t launch_trace_rays(const LaunchParams<R>& P, bool dup, uint32_t grid, size_t dyn_lds, const void* rays,
-                             void* rgb, void* hits, hipStream_t stream);
-template <typename R>
-hipError_t occupancy_rays(bool lds, size_t dyn_lds, int* blocks_per_cu);
-template <typename R>
-hipError_t launch_trace_ss(const LaunchParams<R>& P, bool pool, bool dup, uint32_t grid, size_t dyn_lds,
-                           hipStream_t stream);
-template <typename R>
-hipError_t occupancy_ss(bool pool, bool lds, size_t dyn_lds, int* blocks_per_cu);
-}  // namespace instanced
-namespace textured {  // rtc_kernels_tex*.o: the instance build plus the texture code, for worlds with textures
-template <typename R>
-hipError_t launch_trace(const LaunchParams<R>& P, bool pool, bool dup, uint32_t grid, size_t dyn_lds,
-                        hipStream_t stream);
-template <typename R>
-hipError_t occupancy(bool pool, bool lds, size_t dyn_lds, int* blocks_per_cu);
-template <typename R>
-hipError_t launch_trace_rays(const LaunchParams<R>& P, bool dup, uint32_t grid, size_t dyn_lds, const void* rays,
-                             void* rgb, void* hits, hipStream_t stream);
-template <typename R>
-hipError_t occupancy_rays(bool lds, size_t dyn_lds, int* blocks_per_cu);
-template <typename R>
-hipError_t launch_trace_ss(const LaunchParams<R>& P, bool pool, bool dup, uint32_t grid, size_t dyn_lds,
-                           hipStream_t stream);
-template <typename R>
-hipError_t occupancy_ss(bool pool, bool lds, size_t dyn_lds, int* blocks_per_cu);
-}  // namespace textured
-namespace area {  // rtc_kernels_area*.o: the texture build plus the area lights' sample loop, for worlds with an area light
-template <typename R>
-hipError_t launch_trace(const LaunchParams<R>& P, bool pool, bool dup, uint32_t grid, size_t dyn_lds,
-                        hipStream_t stream);
-template <typename R>
-hipError_t occupancy(bool pool, bool lds, size_t dyn_lds, int* blocks_per_cu);
-template <typename R>
-hipError_t launch_trace_rays(const LaunchParams<R>& P, bool dup, uint32_t grid, size_t dyn_lds, const void* rays,
-                             void* rgb, void* hits, hipStream_t stream);
-template <typename R>
-hipError_t occupancy_rays(bool lds, size_t dyn_lds, int* blocks_per_cu);
-template <typename R>
-hipError_t launch_trace_ss(const LaunchParams<R>& P, bool pool, bool dup, uint32_t grid, size_t dyn_lds,
-                           hipStream_t stream);
-template <typename R>
-hipError_t occupancy_ss(bool pool, bool lds, size_t dyn_lds, int* blocks_per_cu);
-}  // namespace area
+// The six launchers every build of the tracer kernels (rtc_kernels.hip, RTC_VARIANT) defines in its own
+// namespace: the frame kernels, the ray-batch kernel and the supersampled frame kernels (trace_direct_ss,
+// trace_pool_ss), each with its occupancy query.
+#define RTC_KERNEL_LAUNCHERS                                                                                          \
+    template <typename R>                                                                                             \
+    hipError_t launch_trace(const LaunchParams<R>& P, bool pool, bool dup, uint32_t grid, size_t dyn_lds,             \
+                            hipStream_t stream);                                                                      \
+    template <typename R>                                                                                             \
+    hipError_t occupancy(bool pool, bool lds, size_t dyn_lds, int* blocks_per_cu);                                    \
+    template <typename R>                                                                                             \
+    hipError_t launch_trace_rays(const LaunchParams<R>& P, bool dup, uint32_t grid, size_t dyn_lds, const void* rays, \
+                                 void* rgb, void* hits, hipStream_t stream);                                          \
+    template <typename R>                                                                                             \
+    hipError_t occupancy_rays(bool lds, size_t dyn_lds, int* blocks_per_cu);                                          \
+    template <typename R>                                                                                             \
+    hipError_t launch_trace_ss(const LaunchParams<R>& P, bool pool, bool dup, uint32_t grid, size_t dyn_lds,          \
+                               hipStream_t stream);                                                                   \
+    template <typename R>                                                                                             \
+    hipError_t occupancy_ss(bool pool, bool lds, size_t dyn_lds, int* blocks_per_cu);
+RTC_KERNEL_LAUNCHERS                          // rtc_kernels*.o: the plain build
+namespace instanced { RTC_KERNEL_LAUNCHERS }  // rtc_kernels_inst*.o: with the instance level, for worlds with mesh instances
+namespace textured { RTC_KERNEL_LAUNCHERS }   // rtc_kernels_tex*.o: the instance build plus the texture code
+namespace area { RTC_KERNEL_LAUNCHERS }       // rtc_kernels_area*.o: the texture build plus the area lights' sample loop
+#undef RTC_KERNEL_LAUNCHERS
 namespace sp {  // rtc_kernels_sp.o: the f32 pool kernel for worlds of spheres and planes only
 template <typename R>
 hipError_t launch_trace(const LaunchParams<R>& P, bool pool, bool dup, uint32_t grid, size_t dyn_lds,
                         hipStream_t stream);
 }  // namespace sp
 constexpr uint32_t kKindsSp = (1u << RT_SHAPE_SPHERE) | (1u << RT_SHAPE_PLANE);
+
+// The launchers of each build, by KernelBuild: the one place that maps a world's stored build
+// (rt_context::kernel_build) to kernels.
+template <typename R>
+struct Launchers {
+    decltype(&launch_trace<R>) launch_trace;
+    decltype(&occupancy<R>) occupancy;
+    decltype(&launch_trace_rays<R>) launch_trace_rays;
+    decltype(&occupancy_rays<R>) occupancy_rays;
+    decltype(&launch_trace_ss<R>) launch_trace_ss;
+    decltype(&occupancy_ss<R>) occupancy_ss;
+};
+#define RTC_BUILD(ns)                                                                                    \
+    {ns launch_trace<R>, ns occupancy<R>, ns launch_trace_rays<R>, ns occupancy_rays<R>, ns launch_trace_ss<R>, \
+     ns occupancy_ss<R>}
+template <typename R>
+constexpr Launchers<R> kLaunchers[] = {RTC_BUILD(rtc::), RTC_BUILD(instanced::), RTC_BUILD(textured::), RTC_BUILD(area::)};
+#undef RTC_BUILD
+template <typename R>
+const Launchers<R>& launchers(const rt_context* ctx) {
+    return kLaunchers<R>[(uint32_t)ctx->kernel_build];
+}
 
 hipError_t launch_order_tiles(uint32_t* cost, uint32_t* order, uint32_t n, uint32_t* n_items, float split_per_cost,
                               uint32_t max_split_log2, float urgent_per_cost, uint32_t graded, uint32_t min_split_log2,
@@ -318,11 +296,23 @@ struct WorldIndices {
     uint32_t plain(uint32_t ns) const { return index ? n_plain : ns; }
 };
 
+// What both precisions' plain tables of one upload share (build_plain_tables).
+struct PlainPlan {
+    std::vector<uint32_t> cls;    // value-identity classes (shape_identity.hpp)
+    std::vector<uint32_t> order;  // table_order's, the tree's triangles moved to the front of their run
+    TrianglePlan triangles;
+};
+// The plain tables of `wl` (its shapes, materials, patterns and lights) in R on the device.
 template <typename R>
-int build_world(rt_context* ctx, DeviceWorld<R>& w, const rt_shape_desc* shapes, uint32_t ns,
-                const rt_material_desc* mats, uint32_t nm, const rt_pattern_desc* pats, uint32_t np,
-                const rt_light_desc* lights, uint32_t nl, const std::vector<uint32_t>& cls,
-                const std::vector<uint32_t>& order, const TrianglePlan& plan, const WorldIndices& wi = WorldIndices{}) {
+int build_world(rt_context* ctx, DeviceWorld<R>& w, const WorldLists& wl, const PlainPlan& pp, const WorldIndices& wi) {
+    const rt_shape_desc* shapes = wl.shapes;
+    const rt_material_desc* mats = wl.materials;
+    const rt_pattern_desc* pats = wl.patterns;
+    const rt_light_desc* lights = wl.lights;
+    const uint32_t ns = wl.n_shapes, nm = wl.n_materials, np = wl.n_patterns, nl = wl.n_lights;
+    const std::vector<uint32_t>& cls = pp.cls;
+    const std::vector<uint32_t>& order = pp.order;
+    const TrianglePlan& plan = pp.triangles;
     std::vector<ShapeRec<R>> sh;
     std::vector<int32_t> begin(kNumKinds + 1, 0);
     size_t next = 0;
@@ -475,25 +465,33 @@ int build_world(rt_context* ctx, DeviceWorld<R>& w, const rt_shape_desc* shapes,
     return RT_OK;
 }
 
-int validate_scene_instanced(const rt_shape_desc* shapes, uint32_t ns, const InstancedLists& il,
-                             const rt_material_desc* mats, uint32_t nm, const rt_pattern_desc* pats, uint32_t np,
-                             const rt_light_desc* lights, uint32_t nl) {
-    if (il.textured) {  // (the texture list first: the patterns are checked against it)
-        const std::string why = inst::validate_textures(il.textures, il.n_textures);
-        if (!why.empty()) return set_error(RT_ERR_INVALID, why);
+// rt_scene_upload_lit's list; empty: valid.  Each refusal has a text of its own (rtc.h).
+static std::string validate_area(const rt_area_light_desc* area, uint32_t n_area) {
+    if (n_area && !area) return "rt_scene_upload_lit: null area light list with nonzero count";
+    for (uint32_t a = 0; a < n_area; ++a) {
+        const rt_area_light_desc& d = area[a];
+        const std::string who = "area light " + std::to_string(a);
+        if (d.usteps == 0 || d.vsteps == 0) return who + ": a step count of 0";
+        if (d.usteps > RT_LIGHT_MAX_STEPS || d.vsteps > RT_LIGHT_MAX_STEPS)
+            return who + ": a step count above RT_LIGHT_MAX_STEPS";
+        if (d.jitter != RT_JITTER_NONE && d.jitter != RT_JITTER_HASHED) return who + ": unknown jitter mode";
+        for (int q = 0; q < 3; ++q)
+            if (!std::isfinite(d.corner[q]) || !std::isfinite(d.full_uvec[q]) || !std::isfinite(d.full_vvec[q]) ||
+                !std::isfinite(d.intensity[q]))
+                return who + ": a component that is not finite";
     }
-    if (int rc = validate_scene(shapes, ns, mats, nm, pats, np, lights, nl, il.textured ? (int64_t)il.n_textures : -1))
-        return rc;
-    std::string why = inst::validate(shapes, ns, il.meshes, il.n_meshes, il.instances, il.n_instances, nm);
-    if (why.empty()) why = inst::validate_smooth(shapes, ns, il.meshes, il.n_meshes, il.smooth, il.n_smooth);
-    if (why.empty() && il.textured) why = inst::validate_uvs(shapes, ns, il.meshes, il.n_meshes, il.uvs, il.n_uvs);
-    return why.empty() ? RT_OK : set_error(RT_ERR_INVALID, why);
+    return std::string();
 }
 
-int validate_scene(const rt_shape_desc* shapes, uint32_t ns, const rt_material_desc* mats, uint32_t nm,
-                   const rt_pattern_desc* pats, uint32_t np, const rt_light_desc* lights, uint32_t nl,
-                   int64_t n_textures) {
-    if ((ns && !shapes) || (nm && !mats) || (np && !pats) || (nl && !lights))
+// The base tables of `wl`: shapes, materials, patterns, lights.
+static int validate_base(const WorldLists& wl) {
+    const rt_shape_desc* shapes = wl.shapes;
+    const rt_material_desc* mats = wl.materials;
+    const rt_pattern_desc* pats = wl.patterns;
+    const uint32_t ns = wl.n_shapes, nm = wl.n_materials, np = wl.n_patterns, nl = wl.n_lights;
+    // (an image pattern exists for rt_scene_upload_textured and _lit only, checked against their texture count)
+    const int64_t n_textures = wl.image_patterns ? (int64_t)wl.n_textures : -1;
+    if ((ns && !shapes) || (nm && !mats) || (np && !pats) || (nl && !wl.lights))
         return set_error(RT_ERR_INVALID, "rt_scene_upload: null table with nonzero count");
     for (uint32_t i = 0; i < ns; ++i) {
         if (shapes[i].kind < 0 || shapes[i].kind >= kNumKinds)
@@ -505,7 +503,6 @@ int validate_scene(const rt_shape_desc* shapes, uint32_t ns, const rt_material_d
         if (mats[i].pattern >= 0 && (uint32_t)mats[i].pattern >= np)
             return set_error(RT_ERR_INVALID, "material " + std::to_string(i) + ": pattern index out of range");
     for (uint32_t i = 0; i < np; ++i) {
-        // (an image pattern exists for rt_scene_upload_textured only: n_textures >= 0)
         if (pats[i].kind < 0 || pats[i].kind > (n_textures >= 0 ? RT_PATTERN_IMAGE : RT_PATTERN_TEST))
             return set_error(RT_ERR_INVALID, "pattern " + std::to_string(i) + ": unknown kind");
         if (pats[i].kind == RT_PATTERN_COMPLEX &&
@@ -525,6 +522,22 @@ int validate_scene(const rt_shape_desc* shapes, uint32_t ns, const rt_material_d
     }
     if (ns > 0xFFFFFF || nl > 0x7fffffff) return set_error(RT_ERR_INVALID, "table too large");
     return RT_OK;
+}
+
+int validate_scene(const WorldLists& wl) {
+    std::string why = validate_area(wl.area, wl.n_area);
+    // (the texture list before the base tables: the patterns are checked against it)
+    if (why.empty() && wl.image_patterns) why = inst::validate_textures(wl.textures, wl.n_textures);
+    if (!why.empty()) return set_error(RT_ERR_INVALID, why);
+    if (int rc = validate_base(wl)) return rc;
+    why = inst::validate(wl.shapes, wl.n_shapes, wl.meshes, wl.n_meshes, wl.instances, wl.n_instances, wl.n_materials);
+    if (why.empty())
+        why = inst::validate_side<inst::SmoothSide>(wl.shapes, wl.n_shapes, wl.meshes, wl.n_meshes, wl.smooth, wl.n_smooth);
+    if (why.empty()) why = inst::validate_side<inst::UVSide>(wl.shapes, wl.n_shapes, wl.meshes, wl.n_meshes, wl.uvs, wl.n_uvs);
+    uint64_t total = wl.n_lights;  // the expansion's lights: the point lights and every area light's samples
+    for (uint32_t a = 0; why.empty() && a < wl.n_area; ++a) total += wl.area[a].usteps * wl.area[a].vsteps;
+    if (why.empty() && total > 0x7fffffffull) why = "table too large";
+    return why.empty() ? RT_OK : set_error(RT_ERR_INVALID, why);
 }
 
 uint32_t tile_rows_for(uint32_t height, uint32_t shards, uint32_t shard) {
@@ -613,9 +626,10 @@ int cap_by_lds(int api, size_t lds) {
     return std::min(api, (int)(kLdsPerCu / per_block));
 }
 
-// Cached occupancy (workgroups per CU) of one kernel instantiation at a
-// given dynamic LDS size (cap_by_lds).  ss: the supersampled kernels (keys
-// 12..19 of the same table).
+// Cached occupancy (workgroups per CU) of one kernel instantiation of the
+// world's build at a given dynamic LDS size (cap_by_lds); an upload that
+// changes the build clears the cache (set_kernel_build).  ss: the
+// supersampled kernels (keys 12..19 of the same table).
 template <typename R>
 int blocks_per_cu(rt_context* ctx, bool pool, bool lds_world, size_t lds, int* per_cu, bool ss = false) {
     const int key = (pool ? 1 : 0) + (sizeof(R) == 8 ? 2 : 0) + (lds_world ? 4 : 0) + (ss ? 12 : 0);
@@ -624,17 +638,8 @@ int blocks_per_cu(rt_context* ctx, bool pool, bool lds_world, size_t lds, int* p
         return RT_OK;
     }
     int api = 0;
-    // (a world with mesh instances runs the instance variant of every kernel; an upload that changes that clears the cache)
-    if (has_area(ctx->w32))
-        RT_HIP(ss ? area::occupancy_ss<R>(pool, lds_world, lds, &api) : area::occupancy<R>(pool, lds_world, lds, &api));
-    else if (has_textures(ctx->w32))
-        RT_HIP(ss ? textured::occupancy_ss<R>(pool, lds_world, lds, &api)
-                  : textured::occupancy<R>(pool, lds_world, lds, &api));
-    else if (instance_build(ctx->w32))
-        RT_HIP(ss ? instanced::occupancy_ss<R>(pool, lds_world, lds, &api)
-                  : instanced::occupancy<R>(pool, lds_world, lds, &api));
-    else
-        RT_HIP(ss ? occupancy_ss<R>(pool, lds_world, lds, &api) : occupancy<R>(pool, lds_world, lds, &api));
+    const Launchers<R>& k = launchers<R>(ctx);
+    RT_HIP(ss ? k.occupancy_ss(pool, lds_world, lds, &api) : k.occupancy(pool, lds_world, lds, &api));
     *per_cu = cap_by_lds(api, lds);
     ctx->occ_lds[key] = lds;
     ctx->occ_blocks[key] = *per_cu;
@@ -891,10 +896,10 @@ void set_instance_params(LaunchParams<R>& P, const DeviceWorld<R>& w) {
     P.inst_shapes = w.inst_shapes.get();
     P.inst_nodes = w.inst_nodes.get();
     P.inst_pos = w.inst_pos.get();
-    P.smooth_plain = w.smooth_plain();
-    P.smooth_inst = w.smooth_inst();
-    P.uv_plain = w.uv_plain();
-    P.uv_inst = w.uv_inst();
+    P.smooth_plain = w.smooth.plain();
+    P.smooth_inst = w.smooth.inst();
+    P.uv_plain = w.uv.plain();
+    P.uv_inst = w.uv.inst();
     P.texels = w.texels;
     P.textures = w.tex_table;
     P.area = w.n_area ? w.area.get() : nullptr;
@@ -965,7 +970,7 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
         const uint32_t generic_only =
             RT_FLAG_NO_SHADE | RT_FLAG_NO_TRACE | RT_FLAG_GENERATIONS | (ls.pool ? 0u : RT_FLAG_STAMPS);
         // (a world with a triangle hierarchy runs the generic kernels, which walk it)
-        const bool instanced = walked_instances(w), smooth = w.smooth_counts.plain || w.smooth_counts.inst;
+        const bool instanced = walked_instances(w), smooth = has_smooth(w);
         const bool tree = w.n_tri_nodes > 0 || instanced || smooth || has_textures(w);
         if (tree && ctx->jit.mode != RT_JIT_OFF && ctx->jit.log.empty())
             ctx->jit.log = has_area(w) ? "no per-scene build: the world has area lights, which the generic kernels sample"
@@ -1044,7 +1049,7 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
         if (w.scene.kind_begin[k + 1] > w.scene.kind_begin[k]) kinds |= 1u << k;
     // (supersampled launches: the all-kinds build only)
     const bool sp = sizeof(R) == 4 && ls.pool && ctx->knobs.kind_variants && (kinds & ~kKindsSp) == 0 && !dup && !ss &&
-                    !instance_build(w);  // (instances are triangles)
+                    ctx->kernel_build == KernelBuild::plain;  // (the other builds' worlds hold triangles)
     if (flags & RT_FLAG_FAIL_LAUNCH) return set_error(RT_ERR_HIP, "launch refused (RT_FLAG_FAIL_LAUNCH)");
     if constexpr (sizeof(R) == 4) {
         // The per-scene direct kernel's primary cull: each slot's screen
@@ -1134,18 +1139,9 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
         void* args[] = {&P, &sh, &mt, &pt, &lt};
         (void)hipGetLastError();
         RT_HIP(hipModuleLaunchKernel(jf, ls.grid, 1, 1, kBlock, 1, 1, (unsigned)ls.lds, stream, args, nullptr));
-    } else if (hipError_t e = has_area(w)
-                                  ? (ss ? area::launch_trace_ss<R>(P, ls.pool, dup, ls.grid, ls.lds, stream)
-                                        : area::launch_trace<R>(P, ls.pool, dup, ls.grid, ls.lds, stream))
-                              : has_textures(w)
-                                  ? (ss ? textured::launch_trace_ss<R>(P, ls.pool, dup, ls.grid, ls.lds, stream)
-                                        : textured::launch_trace<R>(P, ls.pool, dup, ls.grid, ls.lds, stream))
-                              : instance_build(w)
-                                  ? (ss ? instanced::launch_trace_ss<R>(P, ls.pool, dup, ls.grid, ls.lds, stream)
-                                        : instanced::launch_trace<R>(P, ls.pool, dup, ls.grid, ls.lds, stream))
-                              : ss ? launch_trace_ss<R>(P, ls.pool, dup, ls.grid, ls.lds, stream)
+    } else if (hipError_t e = ss   ? launchers<R>(ctx).launch_trace_ss(P, ls.pool, dup, ls.grid, ls.lds, stream)
                               : sp ? sp::launch_trace<R>(P, ls.pool, dup, ls.grid, ls.lds, stream)
-                                   : launch_trace<R>(P, ls.pool, dup, ls.grid, ls.lds, stream);
+                                   : launchers<R>(ctx).launch_trace(P, ls.pool, dup, ls.grid, ls.lds, stream);
                e != hipSuccess)
         return set_error(RT_ERR_HIP, std::string("launch of the ") + (ss ? "supersampled " : "") +
                                          (ls.pool ? "pool" : "direct") + " kernel (grid " +
@@ -1153,7 +1149,7 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
                                          " B, pool " + std::to_string(ls.lcap) + "/" + std::to_string(ls.cap) +
                                          " rays in LDS): " + hipGetErrorString(e));
     if (dynamic) ctx->head_set ^= 1;
-    ctx->smooth_info.ran_smooth = !jf && (w.smooth_counts.plain || w.smooth_counts.inst) ? 1u : 0u;
+    ctx->smooth_info.ran_smooth = !jf && has_smooth(w) ? 1u : 0u;
     ctx->texture_info.ran_textured = !jf && has_textures(w) ? 1u : 0u;
     ctx->light_info.ran_area = !jf && has_area(w) ? 1u : 0u;
     return RT_OK;
@@ -1169,10 +1165,7 @@ int ray_blocks_per_cu(rt_context* ctx, bool lds_world, size_t lds, int* per_cu) 
         return RT_OK;
     }
     int api = 0;
-    if (has_area(ctx->w32)) RT_HIP(area::occupancy_rays<R>(lds_world, lds, &api));
-    else if (has_textures(ctx->w32)) RT_HIP(textured::occupancy_rays<R>(lds_world, lds, &api));
-    else if (instance_build(ctx->w32)) RT_HIP(instanced::occupancy_rays<R>(lds_world, lds, &api));
-    else RT_HIP(occupancy_rays<R>(lds_world, lds, &api));
+    RT_HIP(launchers<R>(ctx).occupancy_rays(lds_world, lds, &api));
     *per_cu = cap_by_lds(api, lds);
     ctx->occ_lds[key] = lds;
     ctx->occ_blocks[key] = *per_cu;
@@ -1237,19 +1230,13 @@ int launch_rays(rt_context* ctx, DeviceWorld<R>& w, const void* d_rays, uint64_t
     }
     ctx->jit.used = false;
     if (o->flags & RT_FLAG_FAIL_LAUNCH) return set_error(RT_ERR_HIP, "launch refused (RT_FLAG_FAIL_LAUNCH)");
-    if (hipError_t e = has_area(w) ? area::launch_trace_rays<R>(P, ctx->duplicate_shapes > 0, ls.grid, ls.lds, d_rays, d_rgb,
-                                                                d_hits, stream)
-                       : has_textures(w) ? textured::launch_trace_rays<R>(P, ctx->duplicate_shapes > 0, ls.grid, ls.lds,
-                                                                     d_rays, d_rgb, d_hits, stream)
-                       : instance_build(w) ? instanced::launch_trace_rays<R>(P, ctx->duplicate_shapes > 0, ls.grid, ls.lds,
-                                                                             d_rays, d_rgb, d_hits, stream)
-                                           : launch_trace_rays<R>(P, ctx->duplicate_shapes > 0, ls.grid, ls.lds, d_rays,
-                                                                  d_rgb, d_hits, stream);
+    if (hipError_t e = launchers<R>(ctx).launch_trace_rays(P, ctx->duplicate_shapes > 0, ls.grid, ls.lds, d_rays, d_rgb,
+                                                           d_hits, stream);
         e != hipSuccess)
         return set_error(RT_ERR_HIP, "launch of the ray-batch kernel (grid " + std::to_string(ls.grid) +
                                          ", dynamic LDS " + std::to_string(ls.lds) + " B, " + std::to_string(ls.cap) +
                                          " stack entries per lane): " + hipGetErrorString(e));
-    ctx->smooth_info.ran_smooth = w.smooth_counts.plain || w.smooth_counts.inst ? 1u : 0u;
+    ctx->smooth_info.ran_smooth = has_smooth(w) ? 1u : 0u;
     ctx->texture_info.ran_textured = has_textures(w) ? 1u : 0u;
     ctx->light_info.ran_area = has_area(w) ? 1u : 0u;
     return RT_OK;
@@ -1479,62 +1466,63 @@ rt_context::~rt_context() {
     if (group.comm) (void)ncclCommDestroy(group.comm);
 }
 
+// Every rt_scene_upload* entry point after it has filled `in`: the lists are checked before the context is
+// looked at (rtc.h), except that a group's rank 0 checks its own (group_scene_upload) -- unless image patterns
+// are known, which are rewritten here and so are checked here on every rank.
+static int upload_world(rt_context* ctx, const WorldLists& in) {
+    const bool group = ctx && ctx->group.comm;
+    if (!group || in.image_patterns)
+        if (int rc = validate_scene(in)) return rc;
+    if (!ctx) return set_error(RT_ERR_INVALID, "null context");
+    WorldLists wl = in;
+    // (patterns compare by their textures' contents: a copy with every image pattern's texture renumbered)
+    std::vector<rt_pattern_desc> cp;
+    if (wl.image_patterns) {
+        cp.assign(wl.patterns, wl.patterns + wl.n_patterns);
+        inst::canonical_image_patterns(cp.data(), wl.n_patterns, wl.textures, wl.n_textures);
+        wl.patterns = cp.data();
+    }
+    if (group) return group_scene_upload(ctx, wl);
+    RT_HIP(hipSetDevice(ctx->device));
+    RT_HIP(hipDeviceSynchronize());  // launches on caller streams may still read the old tables
+    return build_scene(ctx, wl);
+}
+
+// rt_smooth_expand and rt_uv_expand: the side list of the expansion.
+template <typename Side>
+static int expand_side_list(const WorldLists& wl, const typename Side::Desc* list, uint32_t n_list,
+                            typename Side::Desc* out, uint32_t* n_out) {
+    // (materials are the upload's to check: any index passes here)
+    std::string why = inst::validate(wl.shapes, wl.n_shapes, wl.meshes, wl.n_meshes, wl.instances, wl.n_instances, 0x7FFFFFFFu);
+    if (why.empty()) why = inst::validate_side<Side>(wl.shapes, wl.n_shapes, wl.meshes, wl.n_meshes, list, n_list);
+    if (!why.empty()) return set_error(RT_ERR_INVALID, why);
+    const uint32_t n = inst::expand_side<Side>(wl.n_shapes, wl.meshes, wl.n_meshes, wl.instances, wl.n_instances, list, n_list, out);
+    if (n_out) *n_out = n;
+    return RT_OK;
+}
+
 extern "C" {
 
 int rt_scene_upload(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns, const rt_material_desc* mats,
                     uint32_t nm, const rt_pattern_desc* pats, uint32_t np, const rt_light_desc* lights,
                     uint32_t nl) {
-    if (!ctx) return set_error(RT_ERR_INVALID, "null context");
-    if (ctx->group.comm) return group_scene_upload(ctx, shapes, ns, mats, nm, pats, np, lights, nl);
-    int rc = validate_scene(shapes, ns, mats, nm, pats, np, lights, nl);
-    if (rc) return rc;
-    RT_HIP(hipSetDevice(ctx->device));
-    RT_HIP(hipDeviceSynchronize());  // launches on caller streams may still read the old tables
-    return build_scene(ctx, shapes, ns, mats, nm, pats, np, lights, nl);
+    if (!ctx) return set_error(RT_ERR_INVALID, "null context");  // (this entry point looks at the context first)
+    return upload_world(ctx, WorldLists{shapes, ns, mats, nm, pats, np, lights, nl});
 }
 
 int rt_scene_upload_instanced(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns, const rt_mesh_desc* meshes,
                               uint32_t n_meshes, const rt_instance_desc* instances, uint32_t n_inst,
                               const rt_material_desc* mats, uint32_t nm, const rt_pattern_desc* pats, uint32_t np,
                               const rt_light_desc* lights, uint32_t nl) {
-    const InstancedLists il{meshes, n_meshes, instances, n_inst};
-    // (the lists are checked before the context is looked at; a group's rank 0 checks its own)
-    if (!ctx || !ctx->group.comm)
-        if (int rc = validate_scene_instanced(shapes, ns, il, mats, nm, pats, np, lights, nl)) return rc;
-    if (!ctx) return set_error(RT_ERR_INVALID, "null context");
-    if (ctx->group.comm) return group_scene_upload(ctx, shapes, ns, mats, nm, pats, np, lights, nl, &il);
-    RT_HIP(hipSetDevice(ctx->device));
-    RT_HIP(hipDeviceSynchronize());  // launches on caller streams may still read the old tables
-    return build_scene_instanced(ctx, shapes, ns, meshes, n_meshes, instances, n_inst, mats, nm, pats, np, lights, nl);
+    return upload_world(ctx, WorldLists{shapes, ns, mats, nm, pats, np, lights, nl, meshes, n_meshes, instances, n_inst});
 }
 
 int rt_scene_upload_smooth(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns, const rt_mesh_desc* meshes,
                            uint32_t n_meshes, const rt_instance_desc* instances, uint32_t n_inst,
                            const rt_smooth_desc* smooth, uint32_t n_smooth, const rt_material_desc* mats, uint32_t nm,
                            const rt_pattern_desc* pats, uint32_t np, const rt_light_desc* lights, uint32_t nl) {
-    if (!n_smooth)  // rt_scene_upload_instanced itself
-        return rt_scene_upload_instanced(ctx, shapes, ns, meshes, n_meshes, instances, n_inst, mats, nm, pats, np, lights, nl);
-    const InstancedLists il{meshes, n_meshes, instances, n_inst, smooth, n_smooth};
-    // (the lists are checked before the context is looked at; a group's rank 0 checks its own)
-    if (!ctx || !ctx->group.comm)
-        if (int rc = validate_scene_instanced(shapes, ns, il, mats, nm, pats, np, lights, nl)) return rc;
-    if (!ctx) return set_error(RT_ERR_INVALID, "null context");
-    if (ctx->group.comm) return group_scene_upload(ctx, shapes, ns, mats, nm, pats, np, lights, nl, &il);
-    RT_HIP(hipSetDevice(ctx->device));
-    RT_HIP(hipDeviceSynchronize());  // launches on caller streams may still read the old tables
-    return build_scene_instanced(ctx, shapes, ns, meshes, n_meshes, instances, n_inst, mats, nm, pats, np, lights, nl,
-                                 smooth, n_smooth);
-}
-
-int rt_smooth_expand(const rt_shape_desc* shapes, uint32_t ns, const rt_mesh_desc* meshes, uint32_t n_meshes,
-                     const rt_instance_desc* instances, uint32_t n_inst, const rt_smooth_desc* smooth, uint32_t n_smooth,
-                     rt_smooth_desc* out, uint32_t* n_out) {
-    std::string why = inst::validate(shapes, ns, meshes, n_meshes, instances, n_inst, 0x7FFFFFFFu);
-    if (why.empty()) why = inst::validate_smooth(shapes, ns, meshes, n_meshes, smooth, n_smooth);
-    if (!why.empty()) return set_error(RT_ERR_INVALID, why);
-    const uint32_t n = inst::expand_smooth(ns, meshes, n_meshes, instances, n_inst, smooth, n_smooth, out);
-    if (n_out) *n_out = n;
-    return RT_OK;
+    return upload_world(ctx, WorldLists{shapes, ns, mats, nm, pats, np, lights, nl, meshes, n_meshes, instances, n_inst,
+                                        smooth, n_smooth});
 }
 
 int rt_scene_upload_textured(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns, const rt_mesh_desc* meshes,
@@ -1543,63 +1531,40 @@ int rt_scene_upload_textured(rt_context* ctx, const rt_shape_desc* shapes, uint3
                              const rt_texture_desc* textures, uint32_t n_textures, const rt_material_desc* mats,
                              uint32_t nm, const rt_pattern_desc* pats, uint32_t np, const rt_light_desc* lights,
                              uint32_t nl) {
-    InstancedLists il{meshes, n_meshes, instances, n_inst, smooth, n_smooth};
-    il.uvs = uvs;
-    il.n_uvs = n_uvs;
-    il.textures = textures;
-    il.n_textures = n_textures;
-    il.textured = true;
-    // (the lists are checked before the context is looked at, here also for a group: the patterns are rewritten below)
-    if (int rc = validate_scene_instanced(shapes, ns, il, mats, nm, pats, np, lights, nl)) return rc;
-    bool images = false;
-    for (uint32_t i = 0; i < np; ++i) images = images || pats[i].kind == RT_PATTERN_IMAGE;
-    if (!n_uvs && !images)  // rt_scene_upload_smooth itself (textures no pattern names are not uploaded)
-        return rt_scene_upload_smooth(ctx, shapes, ns, meshes, n_meshes, instances, n_inst, smooth, n_smooth, mats, nm, pats,
-                                      np, lights, nl);
-    if (!ctx) return set_error(RT_ERR_INVALID, "null context");
-    // (patterns compare by their textures' contents: a copy with every image pattern's texture renumbered)
-    std::vector<rt_pattern_desc> cp(pats, pats + np);
-    inst::canonical_image_patterns(cp.data(), np, textures, n_textures);
-    if (ctx->group.comm) return group_scene_upload(ctx, shapes, ns, mats, nm, cp.data(), np, lights, nl, &il);
-    RT_HIP(hipSetDevice(ctx->device));
-    RT_HIP(hipDeviceSynchronize());  // launches on caller streams may still read the old tables
-    return build_scene_instanced(ctx, shapes, ns, meshes, n_meshes, instances, n_inst, mats, nm, cp.data(), np, lights, nl,
-                                 smooth, n_smooth, &il);
+    return upload_world(ctx, WorldLists{shapes, ns, mats, nm, pats, np, lights, nl, meshes, n_meshes, instances, n_inst,
+                                        smooth, n_smooth, uvs, n_uvs, textures, n_textures, nullptr, 0, true});
+}
+
+int rt_scene_upload_lit(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns, const rt_mesh_desc* meshes,
+                        uint32_t n_meshes, const rt_instance_desc* instances, uint32_t n_inst,
+                        const rt_smooth_desc* smooth, uint32_t n_smooth, const rt_uv_desc* uvs, uint32_t n_uvs,
+                        const rt_texture_desc* textures, uint32_t n_textures, const rt_material_desc* mats, uint32_t nm,
+                        const rt_pattern_desc* pats, uint32_t np, const rt_light_desc* lights, uint32_t nl,
+                        const rt_area_light_desc* area, uint32_t n_area) {
+    return upload_world(ctx, WorldLists{shapes, ns, mats, nm, pats, np, lights, nl, meshes, n_meshes, instances, n_inst,
+                                        smooth, n_smooth, uvs, n_uvs, textures, n_textures, area, n_area, true});
+}
+
+int rt_smooth_expand(const rt_shape_desc* shapes, uint32_t ns, const rt_mesh_desc* meshes, uint32_t n_meshes,
+                     const rt_instance_desc* instances, uint32_t n_inst, const rt_smooth_desc* smooth, uint32_t n_smooth,
+                     rt_smooth_desc* out, uint32_t* n_out) {
+    const WorldLists wl{.shapes = shapes, .n_shapes = ns, .meshes = meshes, .n_meshes = n_meshes, .instances = instances,
+                        .n_instances = n_inst};
+    return expand_side_list<inst::SmoothSide>(wl, smooth, n_smooth, out, n_out);
 }
 
 int rt_uv_expand(const rt_shape_desc* shapes, uint32_t ns, const rt_mesh_desc* meshes, uint32_t n_meshes,
                  const rt_instance_desc* instances, uint32_t n_inst, const rt_uv_desc* uvs, uint32_t n_uvs,
                  rt_uv_desc* out, uint32_t* n_out) {
-    std::string why = inst::validate(shapes, ns, meshes, n_meshes, instances, n_inst, 0x7FFFFFFFu);
-    if (why.empty()) why = inst::validate_uvs(shapes, ns, meshes, n_meshes, uvs, n_uvs);
-    if (!why.empty()) return set_error(RT_ERR_INVALID, why);
-    const uint32_t n = inst::expand_uvs(ns, meshes, n_meshes, instances, n_inst, uvs, n_uvs, out);
-    if (n_out) *n_out = n;
-    return RT_OK;
+    const WorldLists wl{.shapes = shapes, .n_shapes = ns, .meshes = meshes, .n_meshes = n_meshes, .instances = instances,
+                        .n_instances = n_inst};
+    return expand_side_list<inst::UVSide>(wl, uvs, n_uvs, out, n_out);
 }
 
 int rt_scene_texture_info(rt_context* ctx, rt_texture_info* out) {
     if (!ctx || !out) return set_error(RT_ERR_INVALID, "null argument");
     *out = ctx->have_scene ? ctx->texture_info : rt_texture_info{};
     return RT_OK;
-}
-
-// rt_scene_upload_lit's list; empty: valid.  Each refusal has a text of its own (rtc.h).
-static std::string validate_area(const rt_area_light_desc* area, uint32_t n_area) {
-    if (n_area && !area) return "rt_scene_upload_lit: null area light list with nonzero count";
-    for (uint32_t a = 0; a < n_area; ++a) {
-        const rt_area_light_desc& d = area[a];
-        const std::string who = "area light " + std::to_string(a);
-        if (d.usteps == 0 || d.vsteps == 0) return who + ": a step count of 0";
-        if (d.usteps > RT_LIGHT_MAX_STEPS || d.vsteps > RT_LIGHT_MAX_STEPS)
-            return who + ": a step count above RT_LIGHT_MAX_STEPS";
-        if (d.jitter != RT_JITTER_NONE && d.jitter != RT_JITTER_HASHED) return who + ": unknown jitter mode";
-        for (int q = 0; q < 3; ++q)
-            if (!std::isfinite(d.corner[q]) || !std::isfinite(d.full_uvec[q]) || !std::isfinite(d.full_vvec[q]) ||
-                !std::isfinite(d.intensity[q]))
-                return who + ": a component that is not finite";
-    }
-    return std::string();
 }
 
 static uint32_t area_mix(uint32_t x) {  // rtc.h "Hashed jitter"
@@ -1666,40 +1631,6 @@ int rt_lights_expand(const rt_light_desc* lights, uint32_t nl, const rt_area_lig
     return RT_OK;
 }
 
-int rt_scene_upload_lit(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns, const rt_mesh_desc* meshes,
-                        uint32_t n_meshes, const rt_instance_desc* instances, uint32_t n_inst,
-                        const rt_smooth_desc* smooth, uint32_t n_smooth, const rt_uv_desc* uvs, uint32_t n_uvs,
-                        const rt_texture_desc* textures, uint32_t n_textures, const rt_material_desc* mats, uint32_t nm,
-                        const rt_pattern_desc* pats, uint32_t np, const rt_light_desc* lights, uint32_t nl,
-                        const rt_area_light_desc* area, uint32_t n_area) {
-    // (the area list is checked before the context is looked at, and before the other lists)
-    const std::string why = validate_area(area, n_area);
-    if (!why.empty()) return set_error(RT_ERR_INVALID, why);
-    if (!n_area)  // rt_scene_upload_textured itself
-        return rt_scene_upload_textured(ctx, shapes, ns, meshes, n_meshes, instances, n_inst, smooth, n_smooth, uvs, n_uvs,
-                                        textures, n_textures, mats, nm, pats, np, lights, nl);
-    InstancedLists il{meshes, n_meshes, instances, n_inst, smooth, n_smooth};
-    il.uvs = uvs;
-    il.n_uvs = n_uvs;
-    il.textures = textures;
-    il.n_textures = n_textures;
-    il.textured = true;  // (a world with an area light is uploaded as a textured world: the area build holds that code)
-    il.area = area;
-    il.n_area = n_area;
-    if (int rc = validate_scene_instanced(shapes, ns, il, mats, nm, pats, np, lights, nl)) return rc;
-    uint64_t total = nl;
-    for (uint32_t a = 0; a < n_area; ++a) total += area[a].usteps * area[a].vsteps;
-    if (total > 0x7fffffffull) return set_error(RT_ERR_INVALID, "table too large");
-    if (!ctx) return set_error(RT_ERR_INVALID, "null context");
-    std::vector<rt_pattern_desc> cp(pats, pats + np);
-    inst::canonical_image_patterns(cp.data(), np, textures, n_textures);
-    if (ctx->group.comm) return group_scene_upload(ctx, shapes, ns, mats, nm, cp.data(), np, lights, nl, &il);
-    RT_HIP(hipSetDevice(ctx->device));
-    RT_HIP(hipDeviceSynchronize());  // launches on caller streams may still read the old tables
-    return build_scene_instanced(ctx, shapes, ns, meshes, n_meshes, instances, n_inst, mats, nm, cp.data(), np, lights, nl,
-                                 smooth, n_smooth, &il);
-}
-
 int rt_scene_light_info(rt_context* ctx, rt_light_info* out) {
     if (!ctx || !out) return set_error(RT_ERR_INVALID, "null argument");
     *out = ctx->have_scene ? ctx->light_info : rt_light_info{};
@@ -1763,10 +1694,13 @@ double object_extent(const rt_shape_desc& d) {
 // pattern reaches, and for a TestPattern, pattern.rs:55-58, the pattern-space
 // point itself: bounded by the surface's object-space extent through the
 // material's pattern transform, +inf on an unbounded surface), times the
-// lights' intensities and the Phong coefficients.
-void scene_brightness(const rt_shape_desc* shapes, uint32_t ns, const rt_material_desc* mats, uint32_t nm,
-                      const rt_pattern_desc* pats, uint32_t np, const rt_light_desc* lights, uint32_t nl,
-                      double* bright_hit, double* bright_w, double extra_intensity) {
+// lights' intensities and the Phong coefficients.  An area light counts as a
+// point light of its intensity: its samples' weights sum to 1.
+static void scene_brightness(const WorldLists& wl, double* bright_hit, double* bright_w) {
+    const rt_shape_desc* shapes = wl.shapes;
+    const rt_material_desc* mats = wl.materials;
+    const rt_pattern_desc* pats = wl.patterns;
+    const uint32_t ns = wl.n_shapes, nm = wl.n_materials, np = wl.n_patterns;
     // per material: the colours its pattern chain may return, and whether a
     // TestPattern is among them
     std::vector<double> col(nm, 0.0);
@@ -1815,10 +1749,16 @@ void scene_brightness(const rt_shape_desc* shapes, uint32_t ns, const rt_materia
         w = std::max(w, mixed ? std::max(m.reflectiveness, m.transparency) * (1.0 + 1e-6)
                               : std::fabs(m.reflectiveness) + std::fabs(m.transparency));
     }
-    double hit = extra_intensity * per_light;
-    for (uint32_t l = 0; l < nl; ++l) {
+    double area_intensity = 0.0;
+    for (uint32_t a = 0; a < wl.n_area; ++a) {
         double in = 0.0;
-        for (int k = 0; k < 3; ++k) in = std::max(in, std::fabs(lights[l].intensity[k]));
+        for (int q = 0; q < 3; ++q) in = std::max(in, std::fabs(wl.area[a].intensity[q]));
+        area_intensity += in;
+    }
+    double hit = area_intensity * per_light;
+    for (uint32_t l = 0; l < wl.n_lights; ++l) {
+        double in = 0.0;
+        for (int k = 0; k < 3; ++k) in = std::max(in, std::fabs(wl.lights[l].intensity[k]));
         hit += in * per_light;
     }
     *bright_hit = std::isfinite(hit) ? hit : std::numeric_limits<double>::infinity();
@@ -1826,24 +1766,26 @@ void scene_brightness(const rt_shape_desc* shapes, uint32_t ns, const rt_materia
 }
 
 namespace {
-// build_scene for a shape list with the world indices `wi`; generic_only: the
-// world also has instances the generic kernels walk, so no per-scene build
-// will run and the plain triangle run gets its tree at any world size.
-int build_plain_tables(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns, const rt_material_desc* mats,
-                       uint32_t nm, const rt_pattern_desc* pats, uint32_t np, const rt_light_desc* lights, uint32_t nl,
-                       const WorldIndices& wi, bool generic_only) {
+// The plain tables of `wl` (shapes, materials, patterns, lights; its other
+// lists are the caller's to upload), the shapes with the world indices `wi`;
+// generic_only: the world also has instances the generic kernels walk, so no
+// per-scene build will run and the plain triangle run gets its tree at any
+// world size.
+int build_plain_tables(rt_context* ctx, const WorldLists& wl, const WorldIndices& wi, bool generic_only) {
     int rc;
-    ctx->have_scene = false;
-    std::vector<uint32_t> cls;  // value-identity classes (shape_identity.hpp)
-    ctx->duplicate_shapes = ident::shape_classes(shapes, ns, mats, pats, cls, wi.normals, wi.uvs);
-    std::vector<uint32_t> order = table_order(shapes, ns, cls);
+    const rt_shape_desc* shapes = wl.shapes;
+    const uint32_t ns = wl.n_shapes;
+    PlainPlan pp;
+    ctx->duplicate_shapes = ident::shape_classes(shapes, ns, wl.materials, wl.patterns, pp.cls, wi.normals, wi.uvs);
+    pp.order = table_order(shapes, ns, pp.cls);
     // A world the per-scene builds take whole (their records: up to
     // kJitRecordsMaxShapes shapes) keeps the flat triangle run and with it
     // its per-scene kernels, which measured faster for f32 frames up to that
     // size than the generic kernels with a tree (a tree inside
     // per-scene builds is future work).  RTC_DEBUG=tri_min=N overrides.
     const bool per_scene_world = (int64_t)ns <= (int64_t)kJitRecordsMaxShapes && !ctx->knobs.tri_min && !generic_only;
-    const TrianglePlan plan = per_scene_world ? TrianglePlan{} : plan_triangles(ctx->knobs, shapes, order, cls);
+    if (!per_scene_world) pp.triangles = plan_triangles(ctx->knobs, shapes, pp.order, pp.cls);
+    const TrianglePlan& plan = pp.triangles;
     ctx->tree_info = rt_tree_info{};
     if (!plan.tree.nodes.empty()) {
         uint32_t triangles = 0;
@@ -1851,22 +1793,26 @@ int build_plain_tables(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns
         ctx->tree_info = {(uint32_t)plan.tree.nodes.size(), plan.tree.leaves, plan.tree.depth, plan.in_tree,
                           triangles - plan.in_tree, 0u, plan.build_ms};
     }
-    if ((rc = build_world<float>(ctx, ctx->w32, shapes, ns, mats, nm, pats, np, lights, nl, cls, order, plan, wi)))
-        return rc;
-    if ((rc = capture_jit_table(ctx))) return rc;
-    if ((rc = build_world<double>(ctx, ctx->w64, shapes, ns, mats, nm, pats, np, lights, nl, cls, order, plan, wi)))
+    if ((rc = build_world<float>(ctx, ctx->w32, wl, pp, wi)) || (rc = capture_jit_table(ctx)) ||
+        (rc = build_world<double>(ctx, ctx->w64, wl, pp, wi)))
         return rc;
     ctx->flops = FlopScene{};
     for (uint32_t i = 0; i < ns; ++i) {
         const rt_shape_desc& d = shapes[i];
         ctx->flops.per_ray += shape_test_flops(d.kind, d.closed != 0);
     }
-    ctx->flops.n_lights = nl;
-    scene_brightness(shapes, ns, mats, nm, pats, np, lights, nl, &ctx->bright_hit, &ctx->bright_w);
-    ctx->have_scene = true;
+    ctx->flops.n_lights = wl.n_lights;
+    scene_brightness(wl, &ctx->bright_hit, &ctx->bright_w);
     ++ctx->scene_gen;  // invalidates the recorded tile costs
     return RT_OK;
 }
+
+// One per-triangle side list of an upload (inst::SmoothSide, inst::UVSide) as the build holds it.
+struct SideList {
+    inst::SideIndex index;            // by plain shape and by mesh triangle
+    std::vector<const double*> list;  // by entry of the plain list: the triangle's reals, or null
+    uint32_t triangles = 0;           // triangles of the expansion the list names
+};
 
 // The instance tables of one precision (rtc_internal.hpp InstRec), from the
 // plans of the meshes in use and the per-instance decisions.
@@ -1879,12 +1825,25 @@ struct InstancePlan {
     std::vector<int32_t> slot_of;                   // build_world's, by entry of the plain list
     std::vector<uint32_t> list_begin;               // by instance: its first entry of the plain list (expanded ones)
     InstanceCounts counts;
+    SideList normals, uvs;                          // the smooth list and the uv list
 };
 
+// A side list of `wl` in the build's terms, before the expanded instances' entries are appended to `list`.
+template <typename Side>
+SideList side_list(const WorldLists& wl, const typename Side::Desc* descs, uint32_t n_descs) {
+    SideList s;
+    s.index = inst::side_index<Side>(wl.n_shapes, wl.meshes, wl.n_meshes, descs, n_descs);
+    s.list.assign(wl.n_shapes, nullptr);
+    for (uint32_t i = 0; i < (uint32_t)s.index.plain.size(); ++i) s.list[i] = s.index.plain[i];
+    s.triangles = (uint32_t)std::count_if(s.list.begin(), s.list.end(), [](const double* p) { return p != nullptr; });
+    for (uint32_t k = 0; k < wl.n_instances; ++k) s.triangles += s.index.named_in_mesh(wl.instances[k].mesh);
+    return s;
+}
+
 template <typename R>
-int upload_instances(rt_context* ctx, DeviceWorld<R>& w, const InstancePlan& ip, const rt_mesh_desc* meshes,
-                     const rt_instance_desc* instances, uint32_t n_inst, const rt_material_desc* mats,
-                     const inst::SmoothIndex* si, const inst::SmoothIndex* ui) {
+int upload_instances(rt_context* ctx, DeviceWorld<R>& w, const InstancePlan& ip, const WorldLists& wl) {
+    const rt_mesh_desc* meshes = wl.meshes;
+    const uint32_t n_inst = wl.n_instances;
     int rc;
     if ((rc = w.allocate_instances(ip.counts))) return rc;
     std::vector<ShapeRec<R>> recs(ip.counts.records);
@@ -1910,8 +1869,8 @@ int upload_instances(rt_context* ctx, DeviceWorld<R>& w, const InstancePlan& ip,
                 r.tri[9 + q] = (R)d.normal[q];
             }
             r.world_index = (int32_t)j;  // the local index: for_instances adds the instance's base
-            r.flags = kShapeClassEnd | (si && ident::normals_of(si->of_mesh((uint32_t)m), j) ? kShapeSmooth : 0) |
-                      (ui && ident::normals_of(ui->of_mesh((uint32_t)m), j) ? kShapeUV : 0);
+            r.flags = kShapeClassEnd | (ident::normals_of(ip.normals.index.of_mesh((uint32_t)m), j) ? kShapeSmooth : 0) |
+                      (ident::normals_of(ip.uvs.index.of_mesh((uint32_t)m), j) ? kShapeUV : 0);
             recs[ip.rec_begin[m] + at] = r;
             pos[ip.pos_begin[m] + j] = (int32_t)(ip.rec_begin[m] + at);
         }
@@ -1926,14 +1885,14 @@ int upload_instances(rt_context* ctx, DeviceWorld<R>& w, const InstancePlan& ip,
     }
     std::vector<InstRec<R>> ir(n_inst);
     for (uint32_t k = 0; k < n_inst; ++k) {
-        const rt_instance_desc& d = instances[k];
+        const rt_instance_desc& d = wl.instances[k];
         const uint32_t m = d.mesh;
         InstRec<R>& r = ir[k];
         r = InstRec<R>{};
         for (int q = 0; q < 12; ++q) r.inv[q] = (R)d.inverse[q];
         r.ball[3] = (R)-1;
         r.world_base = (int32_t)ip.bases[k];
-        r.casts_shadow = mats[d.material].casts_shadow ? 1 : 0;
+        r.casts_shadow = wl.materials[d.material].casts_shadow ? 1 : 0;
         r.material = d.material;
         r.n_triangles = (int32_t)meshes[m].n_triangles;
         if (ip.expanded[k]) {
@@ -1967,83 +1926,51 @@ int upload_instances(rt_context* ctx, DeviceWorld<R>& w, const InstancePlan& ip,
     return rc ? rc : rs;
 }
 
-// The normal tables of one precision (rtc_internal.hpp kShapeSmooth): an entry
-// per record of the triangle run when a plain record is smooth (list_normals:
-// by entry of the plain list, slot_of: build_world's), and an entry per local
-// record of the walked meshes when one of those is.  A flat record's entry is
-// zero and never read.
-template <typename R>
-int upload_smooth(rt_context* ctx, DeviceWorld<R>& w, const std::vector<const double*>& list_normals,
-                  const InstancePlan& ip, const inst::SmoothIndex& si) {
+// A side table of one precision (rtc_internal.hpp kShapeSmooth, kShapeUV): an
+// entry per record of the triangle run when a plain record is named (side.list:
+// by entry of the plain list, ip.slot_of: build_world's), and an entry per
+// local record of the walked meshes when one of those is.  An entry of a
+// record the list does not name is zero and never read.
+template <typename Side, typename R>
+int upload_side(rt_context* ctx, const DeviceWorld<R>& w, SideTable<R, Side::kReals>& table, const InstancePlan& ip,
+                const SideList& side) {
+    constexpr int kReals = Side::kReals;
     const int32_t tri0 = w.scene.kind_begin[RT_SHAPE_TRIANGLE], tri1 = w.scene.kind_begin[RT_SHAPE_TRIANGLE + 1];
     SmoothCounts c;
-    if (std::any_of(list_normals.begin(), list_normals.end(), [](const double* p) { return p != nullptr; }))
+    if (std::any_of(side.list.begin(), side.list.end(), [](const double* p) { return p != nullptr; }))
         c.plain = (uint32_t)(tri1 - tri0);
     for (size_t m = 0; m < ip.meshes.size(); ++m)
-        if (!ip.meshes[m].order.empty() && si.smooth_in_mesh((uint32_t)m)) c.inst = ip.counts.records;
-    if (int rc = w.allocate_smooth(c)) return rc;
-    std::vector<R> host(((size_t)c.plain + c.inst) * kSmoothReals, (R)0);
+        if (!ip.meshes[m].order.empty() && side.index.named_in_mesh((uint32_t)m)) c.inst = ip.counts.records;
+    if (int rc = table.allocate(c)) return rc;
+    std::vector<R> host(((size_t)c.plain + c.inst) * kReals, (R)0);
     if (c.plain)
-        for (size_t i = 0; i < list_normals.size(); ++i)
-            if (list_normals[i]) {
+        for (size_t i = 0; i < side.list.size(); ++i)
+            if (side.list[i]) {
                 const int32_t slot = ip.slot_of[i] & 0xFFFFFF;
-                if (slot < tri0 || slot >= tri1) return set_error(RT_ERR_INVALID, "smooth triangle outside the triangle run");
-                for (int q = 0; q < kSmoothReals; ++q) host[(size_t)(slot - tri0) * kSmoothReals + q] = (R)list_normals[i][q];
+                if (slot < tri0 || slot >= tri1) return set_error(RT_ERR_INVALID, Side::kOutsideRun);
+                for (int q = 0; q < kReals; ++q) host[(size_t)(slot - tri0) * kReals + q] = (R)side.list[i][q];
             }
     if (c.inst)
         for (size_t m = 0; m < ip.meshes.size(); ++m) {
             const inst::MeshPlan& mp = ip.meshes[m];
-            const ident::Normals N = si.of_mesh((uint32_t)m);
+            const ident::Normals N = side.index.of_mesh((uint32_t)m);
             for (uint32_t at = 0; N && at < mp.order.size(); ++at)
                 if (const double* n = N[mp.order[at]])
-                    for (int q = 0; q < kSmoothReals; ++q)
-                        host[((size_t)c.plain + ip.rec_begin[m] + at) * kSmoothReals + q] = (R)n[q];
+                    for (int q = 0; q < kReals; ++q) host[((size_t)c.plain + ip.rec_begin[m] + at) * kReals + q] = (R)n[q];
         }
     if (host.empty()) return RT_OK;
-    const int rc = hip_status(hipMemcpyAsync(w.smooth.get(), host.data(), host.size() * sizeof(R), hipMemcpyHostToDevice,
+    const int rc = hip_status(hipMemcpyAsync(table.reals.get(), host.data(), host.size() * sizeof(R), hipMemcpyHostToDevice,
                                              ctx->stream), "hipMemcpyAsync");
     const int rs = hip_status(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");  // (host temporary)
     return rc ? rc : rs;
 }
-
-// The coordinate tables of one precision (rtc_internal.hpp kShapeUV), built as upload_smooth builds the normal
-// tables: list_uvs by entry of the plain list, ui by mesh triangle.
-template <typename R>
-int upload_uvs(rt_context* ctx, DeviceWorld<R>& w, const std::vector<const double*>& list_uvs, const InstancePlan& ip,
-               const inst::SmoothIndex& ui) {
-    const int32_t tri0 = w.scene.kind_begin[RT_SHAPE_TRIANGLE], tri1 = w.scene.kind_begin[RT_SHAPE_TRIANGLE + 1];
-    SmoothCounts c;
-    if (std::any_of(list_uvs.begin(), list_uvs.end(), [](const double* p) { return p != nullptr; }))
-        c.plain = (uint32_t)(tri1 - tri0);
-    for (size_t m = 0; m < ip.meshes.size(); ++m)
-        if (!ip.meshes[m].order.empty() && ui.smooth_in_mesh((uint32_t)m)) c.inst = ip.counts.records;
-    if (int rc = w.allocate_uv(c)) return rc;
-    std::vector<R> host(((size_t)c.plain + c.inst) * kUVReals, (R)0);
-    if (c.plain)
-        for (size_t i = 0; i < list_uvs.size(); ++i)
-            if (list_uvs[i]) {
-                const int32_t slot = ip.slot_of[i] & 0xFFFFFF;
-                if (slot < tri0 || slot >= tri1) return set_error(RT_ERR_INVALID, "textured triangle outside the triangle run");
-                for (int q = 0; q < kUVReals; ++q) host[(size_t)(slot - tri0) * kUVReals + q] = (R)list_uvs[i][q];
-            }
-    if (c.inst)
-        for (size_t m = 0; m < ip.meshes.size(); ++m) {
-            const inst::MeshPlan& mp = ip.meshes[m];
-            const ident::Normals U = ui.of_mesh((uint32_t)m);
-            for (uint32_t at = 0; U && at < mp.order.size(); ++at)
-                if (const double* t = U[mp.order[at]])
-                    for (int q = 0; q < kUVReals; ++q) host[((size_t)c.plain + ip.rec_begin[m] + at) * kUVReals + q] = (R)t[q];
-        }
-    if (host.empty()) return RT_OK;
-    const int rc = hip_status(hipMemcpyAsync(w.uv.get(), host.data(), host.size() * sizeof(R), hipMemcpyHostToDevice,
-                                             ctx->stream), "hipMemcpyAsync");
-    const int rs = hip_status(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");  // (host temporary)
-    return rc ? rc : rs;
-}
+static_assert(inst::SmoothSide::kReals == kSmoothReals && inst::UVSide::kReals == kUVReals, "the device tables' entry sizes");
 
 // The texels of every texture, one packed dword each (R | G << 8 | B << 16), and the per-texture table; a
 // world without a texture still gets a one-entry table, whose address marks the world as textured.
-int upload_textures(rt_context* ctx, const rt_texture_desc* textures, uint32_t n_textures) {
+int upload_textures(rt_context* ctx, const WorldLists& wl) {
+    const rt_texture_desc* textures = wl.textures;
+    const uint32_t n_textures = wl.n_textures;
     std::vector<TexRec> table(std::max<uint32_t>(n_textures, 1u), TexRec{0, 1, 1});
     uint64_t total = 0;
     for (uint32_t t = 0; t < n_textures; ++t) {
@@ -2071,33 +1998,15 @@ int upload_textures(rt_context* ctx, const rt_texture_desc* textures, uint32_t n
     ctx->w32.tex_table = ctx->w64.tex_table = ctx->tex_table.get();
     return RT_OK;
 }
-}  // namespace
-
-// The context holds no texture from here on (the buffers keep their room).
-static void clear_textures(rt_context* ctx) {
-    ctx->texture_info = rt_texture_info{};
-    ctx->tex_counts = TextureCounts{};
-    ctx->w32.uv_counts = ctx->w64.uv_counts = SmoothCounts{};
-    ctx->w32.texels = ctx->w64.texels = nullptr;
-    ctx->w32.tex_table = ctx->w64.tex_table = nullptr;
-}
-
-// The context holds no area light from here on (the buffers keep their room).
-static void clear_area(rt_context* ctx) {
-    if (has_area(ctx->w32)) std::fill(std::begin(ctx->occ_blocks), std::end(ctx->occ_blocks), 0);  // other kernels now
-    ctx->light_info = rt_light_info{};
-    ctx->w32.n_area = ctx->w64.n_area = 0;
-    ctx->w32.area_samples = ctx->w64.area_samples = 0;
-}
 
 // The area light records of one precision (rtc_internal.hpp AreaLightRec): the cell edges are the full edges
 // divided by the step counts in f64 (rtc.h "Sample positions"), then everything is rounded once to R.
 template <typename R>
-static int upload_area(rt_context* ctx, DeviceWorld<R>& w, const rt_area_light_desc* area, uint32_t n_area) {
+int upload_area(rt_context* ctx, DeviceWorld<R>& w, const WorldLists& wl) {
     uint32_t samples = 0;
-    std::vector<AreaLightRec<R>> host(n_area);
-    for (uint32_t a = 0; a < n_area; ++a) {
-        const rt_area_light_desc& d = area[a];
+    std::vector<AreaLightRec<R>> host(wl.n_area);
+    for (uint32_t a = 0; a < wl.n_area; ++a) {
+        const rt_area_light_desc& d = wl.area[a];
         AreaLightRec<R>& r = host[a];
         for (int q = 0; q < 3; ++q) {
             r.corner[q] = (R)d.corner[q];
@@ -2111,58 +2020,54 @@ static int upload_area(rt_context* ctx, DeviceWorld<R>& w, const rt_area_light_d
         r.seed = d.seed;
         samples += d.usteps * d.vsteps;
     }
-    if (int rc = w.allocate_area(n_area, samples)) return rc;
-    if (!n_area) return RT_OK;
+    if (int rc = w.allocate_area(wl.n_area, samples)) return rc;
+    if (!wl.n_area) return RT_OK;
     const int rc = hip_status(hipMemcpyAsync(w.area.get(), host.data(), host.size() * sizeof(host[0]), hipMemcpyHostToDevice,
                                              ctx->stream), "hipMemcpyAsync");
     const int rs = hip_status(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");  // (host temporary)
     return rc ? rc : rs;
 }
 
-int build_scene(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns, const rt_material_desc* mats, uint32_t nm,
-                const rt_pattern_desc* pats, uint32_t np, const rt_light_desc* lights, uint32_t nl) {
-    clear_area(ctx);
+// The context holds no instance, smooth triangle, texture or area light from here on (the buffers keep
+// their room): a build fills in what its world has.
+void clear_lists(rt_context* ctx) {
     ctx->instance_info = rt_instance_info{};
     ctx->smooth_info = rt_smooth_info{};
+    ctx->texture_info = rt_texture_info{};
+    ctx->light_info = rt_light_info{};
     ctx->smooth_shape.clear();
-    if (instance_build(ctx->w32)) std::fill(std::begin(ctx->occ_blocks), std::end(ctx->occ_blocks), 0);  // other kernels now
-    ctx->w32.inst_counts = ctx->w64.inst_counts = InstanceCounts{};
-    ctx->w32.smooth_counts = ctx->w64.smooth_counts = SmoothCounts{};
-    clear_textures(ctx);
-    return build_plain_tables(ctx, shapes, ns, mats, nm, pats, np, lights, nl, WorldIndices{}, false);
+    ctx->tex_counts = TextureCounts{};
+    auto clear = [](auto& w) {
+        w.inst_counts = InstanceCounts{};
+        w.smooth.counts = w.uv.counts = SmoothCounts{};
+        w.texels = nullptr;
+        w.tex_table = nullptr;
+        w.n_area = w.area_samples = 0;
+    };
+    clear(ctx->w32);
+    clear(ctx->w64);
 }
 
-int build_scene_instanced(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns, const rt_mesh_desc* meshes,
-                          uint32_t n_meshes, const rt_instance_desc* instances, uint32_t n_inst,
-                          const rt_material_desc* mats, uint32_t nm, const rt_pattern_desc* pats, uint32_t np,
-                          const rt_light_desc* lights, uint32_t nl, const rt_smooth_desc* smooth, uint32_t n_smooth,
-                          const InstancedLists* tx) {
-    // (a world with a smooth triangle or a texture takes the general path whatever its instances: it runs the instance build)
-    if (!n_inst && !n_smooth && !tx) return build_scene(ctx, shapes, ns, mats, nm, pats, np, lights, nl);  // rt_scene_upload itself
+// The general path of build_scene: the plain list (the shapes, then the triangles of the instances uploaded
+// expanded), the tables of the meshes the kernels walk, the side tables, and for a `textured` world the
+// texture tables and the area lights.  *plain_only: every instance has a value-equal partner and the world
+// has nothing else, so the plain list, the expansion, was uploaded as rt_scene_upload would (per-scene
+// builds included) and nothing more.
+int build_general(rt_context* ctx, const WorldLists& wl, bool textured, bool* plain_only) {
     int rc;
-    const uint32_t n_area = tx ? tx->n_area : 0u;
-    if (has_area(ctx->w32) != (n_area > 0)) std::fill(std::begin(ctx->occ_blocks), std::end(ctx->occ_blocks), 0);  // other kernels now
-    clear_area(ctx);
+    const rt_mesh_desc* meshes = wl.meshes;
+    const rt_instance_desc* instances = wl.instances;
+    const uint32_t ns = wl.n_shapes, n_meshes = wl.n_meshes, n_inst = wl.n_instances;
     const auto t0 = std::chrono::steady_clock::now();
-    const inst::SmoothIndex si = inst::smooth_index(ns, meshes, n_meshes, smooth, n_smooth);
-    const inst::SmoothIndex ui = inst::uv_index(ns, meshes, n_meshes, tx ? tx->uvs : nullptr, tx ? tx->n_uvs : 0);
     InstancePlan ip;
-    ip.expanded = inst::decide_expanded(shapes, ns, meshes, n_meshes, instances, n_inst, mats, pats, n_smooth ? &si : nullptr);
+    ip.normals = side_list<inst::SmoothSide>(wl, wl.smooth, wl.n_smooth);
+    ip.uvs = side_list<inst::UVSide>(wl, wl.uvs, wl.n_uvs);
+    ip.expanded = inst::decide_expanded(wl.shapes, ns, meshes, n_meshes, instances, n_inst, wl.materials, wl.patterns,
+                                        wl.n_smooth ? &ip.normals.index : nullptr);
     ip.bases = inst::world_bases(ns, meshes, instances, n_inst);
-    // the plain list: the shapes, then the triangles of the instances uploaded expanded
-    std::vector<rt_shape_desc> list(shapes, shapes + ns);
+    std::vector<rt_shape_desc> list(wl.shapes, wl.shapes + ns);
     std::vector<uint32_t> index(ns);
     for (uint32_t i = 0; i < ns; ++i) index[i] = i;
-    std::vector<const double*> list_normals(ns, nullptr);  // by entry of the plain list: a smooth triangle's normals
-    for (uint32_t i = 0; i < (uint32_t)si.plain.size(); ++i) list_normals[i] = si.plain[i];
-    uint32_t smooth_triangles = (uint32_t)std::count_if(list_normals.begin(), list_normals.end(),
-                                                        [](const double* p) { return p != nullptr; });
-    for (uint32_t k = 0; k < n_inst; ++k) smooth_triangles += si.smooth_in_mesh(instances[k].mesh);
-    std::vector<const double*> list_uvs(ns, nullptr);  // by entry of the plain list: a triangle's texture coordinates
-    for (uint32_t i = 0; i < (uint32_t)ui.plain.size(); ++i) list_uvs[i] = ui.plain[i];
-    uint32_t textured_triangles = (uint32_t)std::count_if(list_uvs.begin(), list_uvs.end(),
-                                                          [](const double* p) { return p != nullptr; });
-    for (uint32_t k = 0; k < n_inst; ++k) textured_triangles += ui.smooth_in_mesh(instances[k].mesh);
     ip.list_begin.assign(n_inst, 0);
     ip.expanded_pos.assign(n_inst, 0);
     uint32_t n_expanded = 0, walked_triangles = 0;
@@ -2180,14 +2085,16 @@ int build_scene_instanced(rt_context* ctx, const rt_shape_desc* shapes, uint32_t
         inst::expand_instance(mesh, instances[k], list.data() + ip.list_begin[k]);
         for (uint32_t j = 0; j < mesh.n_triangles; ++j) {
             index.push_back(ip.bases[k] + j);
-            list_normals.push_back(ident::normals_of(si.of_mesh(instances[k].mesh), j));
-            list_uvs.push_back(ident::normals_of(ui.of_mesh(instances[k].mesh), j));
+            ip.normals.list.push_back(ident::normals_of(ip.normals.index.of_mesh(instances[k].mesh), j));
+            ip.uvs.list.push_back(ident::normals_of(ip.uvs.index.of_mesh(instances[k].mesh), j));
         }
     }
-    if (n_expanded == n_inst && !n_smooth && !tx) {
-        // every instance has a value-equal partner: the plain list is the
-        // expansion, uploaded as rt_scene_upload would (per-scene builds included)
-        if ((rc = build_scene(ctx, list.data(), (uint32_t)list.size(), mats, nm, pats, np, lights, nl))) return rc;
+    WorldLists plain = wl;  // (build_plain_tables reads the base tables alone)
+    plain.shapes = list.data();
+    plain.n_shapes = (uint32_t)list.size();
+    *plain_only = n_expanded == n_inst && !wl.n_smooth && !textured;
+    if (*plain_only) {
+        if ((rc = build_plain_tables(ctx, plain, WorldIndices{}, false))) return rc;
         ctx->instance_info.meshes = n_meshes;
         ctx->instance_info.instances = ctx->instance_info.expanded = n_inst;
         ctx->instance_info.build_ms =
@@ -2221,38 +2128,26 @@ int build_scene_instanced(rt_context* ctx, const rt_shape_desc* shapes, uint32_t
     wi.index = index.data();
     wi.n_plain = ns;
     wi.slot_of = &ip.slot_of;
-    wi.normals = n_smooth ? list_normals.data() : nullptr;
-    wi.uvs = tx && tx->n_uvs ? list_uvs.data() : nullptr;
-    if ((rc = build_plain_tables(ctx, list.data(), (uint32_t)list.size(), mats, nm, pats, np, lights, nl, wi, true)))
-        return rc;
-    ctx->have_scene = false;
-    if (!instance_build(ctx->w32) || has_textures(ctx->w32) != (tx != nullptr))
-        std::fill(std::begin(ctx->occ_blocks), std::end(ctx->occ_blocks), 0);  // other kernels now
-    const inst::SmoothIndex* const sip = n_smooth ? &si : nullptr;
-    const inst::SmoothIndex* const uip = tx && tx->n_uvs ? &ui : nullptr;
-    clear_textures(ctx);
-    if (tx) {
-        if ((rc = upload_uvs<float>(ctx, ctx->w32, list_uvs, ip, ui)) ||
-            (rc = upload_uvs<double>(ctx, ctx->w64, list_uvs, ip, ui)) ||
-            (rc = upload_textures(ctx, tx->textures, tx->n_textures)))
+    wi.normals = wl.n_smooth ? ip.normals.list.data() : nullptr;
+    wi.uvs = wl.n_uvs ? ip.uvs.list.data() : nullptr;
+    if ((rc = build_plain_tables(ctx, plain, wi, true))) return rc;
+    if (textured) {
+        if ((rc = upload_side<inst::UVSide>(ctx, ctx->w32, ctx->w32.uv, ip, ip.uvs)) ||
+            (rc = upload_side<inst::UVSide>(ctx, ctx->w64, ctx->w64.uv, ip, ip.uvs)) || (rc = upload_textures(ctx, wl)))
             return rc;
-        ctx->texture_info.textured_triangles = textured_triangles;
-        ctx->texture_info.textures = tx->n_textures;
-        ctx->texture_info.uv_bytes = ((uint64_t)ctx->w32.uv_counts.plain + ctx->w32.uv_counts.inst) * kUVReals *
-                                     (sizeof(float) + sizeof(double));
-        ctx->texture_info.texel_bytes = ctx->tex_counts.texels * sizeof(uint32_t) + (uint64_t)tx->n_textures * sizeof(TexRec);
+        ctx->texture_info.textured_triangles = ip.uvs.triangles;
+        ctx->texture_info.textures = wl.n_textures;
+        ctx->texture_info.uv_bytes = ctx->w32.uv.bytes() + ctx->w64.uv.bytes();
+        ctx->texture_info.texel_bytes = ctx->tex_counts.texels * sizeof(uint32_t) + (uint64_t)wl.n_textures * sizeof(TexRec);
     }
-    if ((rc = upload_instances<float>(ctx, ctx->w32, ip, meshes, instances, n_inst, mats, sip, uip)) ||
-        (rc = upload_instances<double>(ctx, ctx->w64, ip, meshes, instances, n_inst, mats, sip, uip)) ||
-        (rc = upload_smooth<float>(ctx, ctx->w32, list_normals, ip, si)) ||
-        (rc = upload_smooth<double>(ctx, ctx->w64, list_normals, ip, si)))
+    if ((rc = upload_instances<float>(ctx, ctx->w32, ip, wl)) || (rc = upload_instances<double>(ctx, ctx->w64, ip, wl)) ||
+        (rc = upload_side<inst::SmoothSide>(ctx, ctx->w32, ctx->w32.smooth, ip, ip.normals)) ||
+        (rc = upload_side<inst::SmoothSide>(ctx, ctx->w64, ctx->w64.smooth, ip, ip.normals)))
         return rc;
-    ctx->smooth_info = rt_smooth_info{};
-    ctx->smooth_info.smooth_triangles = smooth_triangles;
-    ctx->smooth_info.normal_bytes = ((uint64_t)ctx->w32.smooth_counts.plain + ctx->w32.smooth_counts.inst) * kSmoothReals *
-                                    (sizeof(float) + sizeof(double));
-    ctx->smooth_shape.assign(n_smooth ? ns : 0, 0);
-    for (uint32_t i = 0; i < (uint32_t)si.plain.size(); ++i) ctx->smooth_shape[i] = si.plain[i] != nullptr;
+    ctx->smooth_info.smooth_triangles = ip.normals.triangles;
+    ctx->smooth_info.normal_bytes = ctx->w32.smooth.bytes() + ctx->w64.smooth.bytes();
+    ctx->smooth_shape.assign(wl.n_smooth ? ns : 0, 0);
+    for (uint32_t i = 0; i < (uint32_t)ip.normals.index.plain.size(); ++i) ctx->smooth_shape[i] = ip.normals.index.plain[i] != nullptr;
     // what the expansion's other tables would have come to: the triangle tests
     // of the flop model, and the brightness bound (a TestPattern's reach is
     // the object-space extent of the mesh, whatever the placement)
@@ -2272,27 +2167,18 @@ int build_scene_instanced(rt_context* ctx, const rt_shape_desc* shapes, uint32_t
                 for (int q = 0; q < 3; ++q) d.vertex_1[q] = extent[instances[k].mesh];
                 reach.push_back(d);
             }
-        // (an area light counts as a point light of its intensity: its samples' weights sum to 1)
-        double area_intensity = 0.0;
-        for (uint32_t a = 0; a < n_area; ++a) {
-            double in = 0.0;
-            for (int q = 0; q < 3; ++q) in = std::max(in, std::fabs(tx->area[a].intensity[q]));
-            area_intensity += in;
-        }
-        scene_brightness(reach.data(), (uint32_t)reach.size(), mats, nm, pats, np, lights, nl, &ctx->bright_hit,
-                         &ctx->bright_w, area_intensity);
+        plain.shapes = reach.data();
+        plain.n_shapes = (uint32_t)reach.size();
+        scene_brightness(plain, &ctx->bright_hit, &ctx->bright_w);
     }
-    if (n_area) {
-        if ((rc = upload_area<float>(ctx, ctx->w32, tx->area, n_area)) ||
-            (rc = upload_area<double>(ctx, ctx->w64, tx->area, n_area)))
-            return rc;
-        ctx->light_info.area_lights = n_area;
+    if (wl.n_area) {
+        if ((rc = upload_area<float>(ctx, ctx->w32, wl)) || (rc = upload_area<double>(ctx, ctx->w64, wl))) return rc;
+        ctx->light_info.area_lights = wl.n_area;
         ctx->light_info.samples = ctx->w32.area_samples;
-        ctx->light_info.area_bytes = (uint64_t)n_area * (sizeof(AreaLightRec<float>) + sizeof(AreaLightRec<double>));
+        ctx->light_info.area_bytes = (uint64_t)wl.n_area * (sizeof(AreaLightRec<float>) + sizeof(AreaLightRec<double>));
         ctx->flops.n_lights += ctx->w32.area_samples;  // the expansion's light count
     }
     rt_instance_info& info = ctx->instance_info;
-    info = rt_instance_info{};
     info.meshes = n_meshes;
     info.instances = n_inst;
     info.expanded = n_expanded;
@@ -2307,6 +2193,36 @@ int build_scene_instanced(rt_context* ctx, const rt_shape_desc* shapes, uint32_t
     info.expansion_bytes = (uint64_t)walked_triangles * (sizeof(ShapeRec<float>) + sizeof(ShapeRec<double>) + 2 * sizeof(int32_t)) +
                            (uint64_t)(walked_triangles / 4) * (sizeof(TriNode<float>) + sizeof(TriNode<double>));
     info.build_ms = plan_ms;
+    return RT_OK;
+}
+}  // namespace
+
+void set_kernel_build(rt_context* ctx, KernelBuild build) {
+    if (build != ctx->kernel_build) std::fill(std::begin(ctx->occ_blocks), std::end(ctx->occ_blocks), 0);  // other kernels now
+    ctx->kernel_build = build;
+}
+
+// Which path an upload takes, and which build of the kernels its world runs, is decided here, by what the
+// validated lists hold:
+//   an area light                             the general path, the area build (with the texture tables);
+//   else a coordinate entry or image pattern  the general path, the texture build (no other world uploads textures);
+//   else a smooth entry                       the general path, the instance build;
+//   else instances                            the general path and the instance build, unless every instance has a
+//                                             value-equal partner: then the plain path with the expansion;
+//   else                                      the plain path (per-scene builds allowed), the plain build.
+int build_scene(rt_context* ctx, const WorldLists& wl) {
+    ctx->have_scene = false;
+    clear_lists(ctx);
+    bool images = false;
+    for (uint32_t i = 0; i < wl.n_patterns; ++i) images = images || wl.patterns[i].kind == RT_PATTERN_IMAGE;
+    const bool textured = wl.n_area || wl.n_uvs || images;
+    bool plain_only = !wl.n_instances && !wl.n_smooth && !textured;
+    if (int rc = plain_only ? build_plain_tables(ctx, wl, WorldIndices{}, false) : build_general(ctx, wl, textured, &plain_only))
+        return rc;
+    set_kernel_build(ctx, wl.n_area ? KernelBuild::area
+                          : textured ? KernelBuild::textured
+                          : plain_only ? KernelBuild::plain
+                                       : KernelBuild::instanced);
     ctx->have_scene = true;
     return RT_OK;
 }

@@ -1,5 +1,5 @@
 // CPU checks of the host side of smooth triangles (csrc/instances.hpp
-// validate_smooth / smooth_index / expand_smooth / decide_expanded and
+// validate_side / side_index / expand_side over SmoothSide, decide_expanded and
 // csrc/shape_identity.hpp with normals), compiled stand-alone by
 // tests/test_smooth_cpu.py, with the address and undefined-behaviour sanitizers
 // where the compiler has them.  Prints one line per check and "ok".
@@ -73,10 +73,10 @@ int main() {
         const std::vector<rt_shape_desc> mixed = {shapes[0], sphere};
         const rt_mesh_desc meshes[1] = {{a.data(), (uint32_t)a.size(), 0}};
         auto why = [&](const std::vector<rt_shape_desc>& s, std::vector<rt_smooth_desc> list) {
-            return inst::validate_smooth(s.data(), (uint32_t)s.size(), meshes, 1, list.data(), (uint32_t)list.size());
+            return inst::validate_side<inst::SmoothSide>(s.data(), (uint32_t)s.size(), meshes, 1, list.data(), (uint32_t)list.size());
         };
         CHECK(why(shapes, {smooth(RT_SMOOTH_SHAPES, 2), smooth(0, 3)}).empty(), "a well-formed list passes");
-        CHECK(inst::validate_smooth(shapes.data(), 3, meshes, 1, nullptr, 2).find("null smooth list") != std::string::npos,
+        CHECK(inst::validate_side<inst::SmoothSide>(shapes.data(), 3, meshes, 1, nullptr, 2).find("null smooth list") != std::string::npos,
               "null list");
         CHECK(why(shapes, {smooth(1, 0)}).find("list index out of range") != std::string::npos, "list index");
         CHECK(why(shapes, {smooth(RT_SMOOTH_SHAPES, 3)}).find("triangle index out of range") != std::string::npos, "index");
@@ -98,9 +98,9 @@ int main() {
         const rt_mesh_desc meshes[2] = {{a.data(), 4, 0}, {b.data(), 2, 0}};
         const std::vector<rt_instance_desc> in = {place(0, 0, 1.0), place(1, 0, 2.0), place(0, 1, 3.0)};
         const std::vector<rt_smooth_desc> list = {smooth(0, 3), smooth(RT_SMOOTH_SHAPES, 1), smooth(0, 0), smooth(1, 1)};
-        const uint32_t n = inst::expand_smooth(3, meshes, 2, in.data(), 3, list.data(), 4, nullptr);
+        const uint32_t n = inst::expand_side<inst::SmoothSide>(3, meshes, 2, in.data(), 3, list.data(), 4, nullptr);
         std::vector<rt_smooth_desc> out(n);
-        inst::expand_smooth(3, meshes, 2, in.data(), 3, list.data(), 4, out.data());
+        inst::expand_side<inst::SmoothSide>(3, meshes, 2, in.data(), 3, list.data(), 4, out.data());
         const uint32_t want_index[6] = {1, 3 + 0, 3 + 3, 7 + 1, 9 + 0, 9 + 3};
         const int from[6] = {1, 2, 0, 3, 2, 0};
         CHECK(n == 6, "1 plain + 2 + 1 + 2 entries, got %u", n);
@@ -121,7 +121,7 @@ int main() {
         std::memcpy(n2.normal_1, n0.normal_1, 9 * sizeof(double));
         n2.normal_2[1] += 1e-9;
         const std::vector<rt_smooth_desc> list = {n0, n1, n2};
-        const inst::SmoothIndex si = inst::smooth_index(5, nullptr, 0, list.data(), 3);
+        const inst::SideIndex si = inst::side_index<inst::SmoothSide>(5, nullptr, 0, list.data(), 3);
         std::vector<uint32_t> cls;
         const uint32_t dups = ident::shape_classes(s.data(), 5, mats.data(), nullptr, cls, si.of_plain());
         CHECK(cls == (std::vector<uint32_t>{0, 0, 2, 3, 3}) && dups == 2, "classes %u %u %u %u %u", cls[0], cls[1], cls[2],
@@ -131,7 +131,7 @@ int main() {
         z.index = 1;
         z.normal_1[1] = -0.0;
         const std::vector<rt_smooth_desc> lz = {n0, z};
-        const inst::SmoothIndex sz = inst::smooth_index(5, nullptr, 0, lz.data(), 2);
+        const inst::SideIndex sz = inst::side_index<inst::SmoothSide>(5, nullptr, 0, lz.data(), 2);
         ident::shape_classes(s.data(), 2, mats.data(), nullptr, cls, sz.of_plain());
         CHECK(cls[1] == 0, "-0 == +0");
         // without a normal table the old answer: all five one class
@@ -151,10 +151,10 @@ int main() {
         std::memcpy(m1f2.normal_1, smooth(0, 2).normal_1, 9 * sizeof(double));
         m1f2.normal_1[1] = 0.5;
         const std::vector<rt_smooth_desc> list = {smooth(0, 0), smooth(0, 2), m1f2};
-        const inst::SmoothIndex si = inst::smooth_index(0, meshes, 3, list.data(), 3);
+        const inst::SideIndex si = inst::side_index<inst::SmoothSide>(0, meshes, 3, list.data(), 3);
         auto decide = [&](const std::vector<rt_shape_desc>& shapes, const std::vector<rt_instance_desc>& in,
                           const std::vector<rt_smooth_desc>& l) {
-            const inst::SmoothIndex x = inst::smooth_index((uint32_t)shapes.size(), meshes, 3, l.data(), (uint32_t)l.size());
+            const inst::SideIndex x = inst::side_index<inst::SmoothSide>((uint32_t)shapes.size(), meshes, 3, l.data(), (uint32_t)l.size());
             return inst::decide_expanded(shapes.data(), (uint32_t)shapes.size(), meshes, 3, in.data(), (uint32_t)in.size(),
                                          mats.data(), nullptr, &x);
         };
@@ -168,7 +168,7 @@ int main() {
         const rt_mesh_desc pair[3] = {{two.data(), 2, 0}, {two.data(), 2, 0}, {two.data(), 2, 0}};
         auto decide2 = [&](const std::vector<rt_shape_desc>& shapes, const std::vector<rt_instance_desc>& in,
                            const std::vector<rt_smooth_desc>& l) {
-            const inst::SmoothIndex x = inst::smooth_index((uint32_t)shapes.size(), pair, 3, l.data(), (uint32_t)l.size());
+            const inst::SideIndex x = inst::side_index<inst::SmoothSide>((uint32_t)shapes.size(), pair, 3, l.data(), (uint32_t)l.size());
             return inst::decide_expanded(shapes.data(), (uint32_t)shapes.size(), pair, 3, in.data(), (uint32_t)in.size(),
                                          mats.data(), nullptr, &x);
         };
@@ -200,10 +200,10 @@ int main() {
         const std::vector<uint32_t> bases = inst::world_bases(0, pair, in.data(), (uint32_t)in.size());
         std::vector<rt_shape_desc> flat(bases.back());
         inst::expand(nullptr, 0, pair, in.data(), (uint32_t)in.size(), flat.data());
-        const uint32_t n = inst::expand_smooth(0, pair, 3, in.data(), (uint32_t)in.size(), l2.data(), (uint32_t)l2.size(), nullptr);
+        const uint32_t n = inst::expand_side<inst::SmoothSide>(0, pair, 3, in.data(), (uint32_t)in.size(), l2.data(), (uint32_t)l2.size(), nullptr);
         std::vector<rt_smooth_desc> fl(n);
-        inst::expand_smooth(0, pair, 3, in.data(), (uint32_t)in.size(), l2.data(), (uint32_t)l2.size(), fl.data());
-        const inst::SmoothIndex fx = inst::smooth_index((uint32_t)flat.size(), nullptr, 0, fl.data(), n);
+        inst::expand_side<inst::SmoothSide>(0, pair, 3, in.data(), (uint32_t)in.size(), l2.data(), (uint32_t)l2.size(), fl.data());
+        const inst::SideIndex fx = inst::side_index<inst::SmoothSide>((uint32_t)flat.size(), nullptr, 0, fl.data(), n);
         std::vector<uint32_t> cls;
         ident::shape_classes(flat.data(), (uint32_t)flat.size(), mats.data(), nullptr, cls, fx.of_plain());
         std::vector<char> want(in.size(), 0);

@@ -364,6 +364,71 @@ def test_status_says_the_area_build_ran(rtc):
     assert np.array_equal(img, want) and _counts(st) == _counts(wst)
 
 
+# ------------------------------------------------------------------ 9: one context, every build of the kernels
+WALK = ("plain", "instanced", "smooth", "textured", "area", "instanced", "area", "plain", "textured", "plain")
+# world -> (ran_smooth, ran_textured, ran_area) after a launch (an area world holds the texture tables)
+RAN = {"plain": (0, 0, 0), "instanced": (0, 0, 0), "smooth": (1, 0, 0), "textured": (0, 1, 0), "area": (0, 1, 1)}
+_walk_cache = {}
+
+
+def _walk_worlds(rtc):
+    """Small worlds, one per path of an upload, with their depths; frames of 80 x 60 and 64 x 32 (no per-scene
+    build starts below 64K pixels).  Each with the fresh context's frames, counters and ray batch, f32 and f64."""
+    if _walk_cache:
+        return _walk_cache["worlds"], _walk_cache["rays"], _walk_cache["fresh"]
+    import smooth_worlds as S
+    import texture_worlds as X
+    worlds = {"plain": (S.box_world(rtc, smooth=False), 4), "instanced": (S.box_instances(rtc, smooth=False), 4),
+              "smooth": (S.box_world(rtc), 4), "textured": (X.box_world(rtc, X.SIX, "bilinear"), 4),
+              "area": (AW.mirror(), 4)}
+    assert not worlds["plain"][0].instanced and worlds["instanced"][0].instanced and worlds["smooth"][0].smoothed
+    assert worlds["textured"][0].textured and worlds["area"][0].lit
+    rays = M.random_rays(256, 31)
+    fresh = {}
+    for name, (t, depth) in worlds.items():
+        with rtc.Context(0) as c:
+            c.upload(t)
+            fresh[name] = _walk_results(c, t, depth, rays)
+            assert _ran(c) == RAN[name], (name, _ran(c))
+    _walk_cache.update(worlds=worlds, rays=rays, fresh=fresh)
+    return worlds, rays, fresh
+
+
+def _ran(ctx):
+    return (ctx.smooth_info()["ran_smooth"], ctx.texture_info()["ran_textured"], ctx.light_info()["ran_area"])
+
+
+def _walk_results(ctx, tables, depth, rays):
+    out = []
+    for precision in ("f32", "f64"):
+        img, st = ctx.render(tables.camera, depth, precision=precision)
+        got, rst = ctx.trace_rays(rays, depth, precision=precision)
+        out.append((img.tobytes(), _counts(st), got.tobytes(), _counts(rst)))
+    return out
+
+
+@pytest.mark.parametrize("devices", [None, [0], [0, 1]], ids=["single", "group of one", "group of two"])
+def test_one_context_walks_every_build_and_back(rtc, devices):
+    """plain -> instanced -> smooth -> textured -> area -> instanced -> area -> plain -> textured -> plain on one
+    context: after every upload the frames, the counters and a batch of 256 rays are the fresh context's bit for
+    bit, in f32 and f64, and ran_smooth, ran_textured and ran_area say which kernels ran.  On a group of two the
+    other rank takes its kernels from the header."""
+    if devices and len(devices) > rtc.device_count():
+        pytest.skip("fewer than two devices are visible")
+    worlds, rays, fresh = _walk_worlds(rtc)
+    with (rtc.Context.multi(devices) if devices else rtc.Context(0)) as c:
+        for step, name in enumerate(WALK):
+            t, depth = worlds[name]
+            c.upload(t)
+            got = _walk_results(c, t, depth, rays)
+            for precision, g, w in zip(("f32", "f64"), got, fresh[name]):
+                assert g[0] == w[0], (step, name, precision, "frame")
+                assert g[1] == w[1], (step, name, precision, "frame counters")
+                assert g[2] == w[2], (step, name, precision, "rays")
+                assert g[3] == w[3], (step, name, precision, "ray counters")
+            assert _ran(c) == RAN[name], (step, name, _ran(c))
+
+
 # ------------------------------------------------------------------ the CLI
 def test_cli_area_light(rtc, tmp_path):
     import ctypes as C

@@ -443,6 +443,81 @@ def test_upload_refusals_have_their_own_messages_with_a_null_context(rtc):
     assert rtc._lib.rt_last_error().decode() == "uv entry 0: list index out of range"
 
 
+def test_of_two_defects_the_earlier_check_is_the_one_reported(rtc):
+    """The order of the refusals is part of the contract (rtc.h: "checked before the context is looked at").
+    Every entry point gets tables with two defects from different steps of its order, and a null context:
+      rt_scene_upload            the context, then the base tables;
+      _instanced, _smooth        base tables, mesh/instance lists, smooth list, then the context;
+      _textured                  texture list, base tables, mesh/instance lists, smooth list, uv list, context;
+      _lit                       area list, then as _textured, then the light total, then the context;
+    an empty newest list is the previous entry point."""
+    base, _ = _base_world(rtc)
+    lib = rtc._lib
+    SHAPE, INSTANCE = "shape 0: unknown kind", "instance 0: mesh index out of range"
+    SMOOTH, UV = "smooth entry 0: list index out of range", "uv entry 0: list index out of range"
+    TEXTURE, AREA = "texture 0: zero width or height", "area light 0: a step count of 0"
+
+    def call(entry, *defects, images=True):
+        t = base.tables()
+        if not images:  # the older entry points do not know pattern kind 6
+            for p in t.patterns:
+                p.kind = 0
+        a = list(t.textured_args()) + [(rtc.AreaLightDesc * 1)(), 1]
+        a[18][0].usteps = a[18][0].vsteps = 1  # one valid light of one sample (rt_scene_upload_lit only)
+        for d in defects:
+            if d == "shape":
+                t.shapes[0].kind = 99
+            elif d == "instance":
+                t.instances[0].mesh = 5
+            elif d == "smooth":
+                a[6], a[7] = (rtc.SmoothDesc * 1)(), 1
+                a[6][0].list = 9
+            elif d == "uv":
+                t.uvs[0].list = 9
+            elif d == "texture":
+                a[10][0].width = 0
+            elif d == "area":
+                a[18][0].usteps = 0
+            elif d == "total":  # 2^31 - 1 point lights and one sample (the checks never read the lights)
+                a[17] = 0x7FFFFFFF
+            elif d == "no area":
+                a[19] = 0
+            elif d == "no smooth":
+                a[6], a[7] = None, 0
+        args = {"upload": a[0:2] + a[12:18], "instanced": a[0:6] + a[12:18], "smooth": a[0:8] + a[12:18],
+                "textured": a[0:18], "lit": a[0:18] + a[18:20]}[entry]
+        assert getattr(lib, "rt_scene_upload" + ("" if entry == "upload" else "_" + entry))(None, *args) == rtc.RT_ERR_INVALID
+        return lib.rt_last_error().decode()
+
+    assert call("upload", "shape", images=False) == "null context"
+    assert call("upload", "shape") == "null context"
+    for entry in ("instanced", "smooth"):
+        assert call(entry, "shape", "instance", images=False) == SHAPE
+        assert call(entry, "instance", images=False) == INSTANCE  # (... and the null context)
+        assert call(entry, images=False) == "null context"
+        assert call(entry, "instance") == "pattern 0: unknown kind"
+    assert call("smooth", "instance", "smooth", images=False) == INSTANCE
+    assert call("smooth", "smooth", images=False) == SMOOTH
+    assert call("smooth", "no smooth", "instance", images=False) == INSTANCE  # rt_scene_upload_instanced itself
+    assert call("textured", "texture", "shape") == TEXTURE
+    assert call("textured", "shape", "instance") == SHAPE
+    assert call("textured", "instance", "smooth") == INSTANCE
+    assert call("textured", "smooth", "uv") == SMOOTH
+    assert call("textured", "uv") == UV
+    assert call("textured") == "null context"
+    assert call("lit", "area", "texture") == AREA
+    assert call("lit", "area", "uv") == AREA
+    assert call("lit", "texture", "shape") == TEXTURE
+    assert call("lit", "shape", "instance") == SHAPE
+    assert call("lit", "smooth", "uv") == SMOOTH
+    assert call("lit", "uv", "total") == UV
+    assert call("lit", "total") == "table too large"
+    assert call("lit") == "null context"
+    assert call("lit", "no area", "texture", "shape") == TEXTURE  # rt_scene_upload_textured itself
+    assert call("lit", "no area", "uv") == UV
+    assert call("lit", "no area") == "null context"
+
+
 def test_the_older_entry_points_do_not_know_pattern_kind_6(rtc):
     base, _ = _base_world(rtc)
     t = base.tables()

@@ -1,5 +1,5 @@
 // CPU checks of the host side of image textures (csrc/instances.hpp
-// validate_textures / validate_uvs / uv_index / expand_uvs / texture_eq /
+// validate_textures, validate_side / side_index / expand_side over UVSide, texture_eq /
 // decide_expanded and csrc/shape_identity.hpp with texture coordinates and
 // image patterns), compiled stand-alone by tests/test_texture_cpu.py, with the
 // address and undefined-behaviour sanitizers where the compiler has them.
@@ -84,10 +84,10 @@ int main() {
         const std::vector<rt_shape_desc> mixed = {shapes[0], sphere};
         const rt_mesh_desc meshes[1] = {{a.data(), (uint32_t)a.size(), 0}};
         auto why = [&](const std::vector<rt_shape_desc>& s, std::vector<rt_uv_desc> list) {
-            return inst::validate_uvs(s.data(), (uint32_t)s.size(), meshes, 1, list.data(), (uint32_t)list.size());
+            return inst::validate_side<inst::UVSide>(s.data(), (uint32_t)s.size(), meshes, 1, list.data(), (uint32_t)list.size());
         };
         CHECK(why(shapes, {uv(RT_SMOOTH_SHAPES, 2), uv(0, 3)}).empty(), "a well-formed list passes");
-        CHECK(inst::validate_uvs(shapes.data(), 3, meshes, 1, nullptr, 2).find("null uv list") != std::string::npos, "null list");
+        CHECK(inst::validate_side<inst::UVSide>(shapes.data(), 3, meshes, 1, nullptr, 2).find("null uv list") != std::string::npos, "null list");
         CHECK(why(shapes, {uv(1, 0)}).find("list index out of range") != std::string::npos, "list index");
         CHECK(why(shapes, {uv(RT_SMOOTH_SHAPES, 3)}).find("triangle index out of range") != std::string::npos, "index");
         CHECK(why(shapes, {uv(0, 4)}).find("triangle index out of range") != std::string::npos, "mesh index");
@@ -121,9 +121,9 @@ int main() {
         const rt_mesh_desc meshes[2] = {{a.data(), 4, 0}, {b.data(), 2, 0}};
         const std::vector<rt_instance_desc> in = {place(0, 0, 1.0), place(1, 0, 2.0), place(0, 1, 3.0)};
         const std::vector<rt_uv_desc> list = {uv(0, 3), uv(RT_SMOOTH_SHAPES, 1), uv(0, 0), uv(1, 1)};
-        const uint32_t n = inst::expand_uvs(3, meshes, 2, in.data(), 3, list.data(), 4, nullptr);
+        const uint32_t n = inst::expand_side<inst::UVSide>(3, meshes, 2, in.data(), 3, list.data(), 4, nullptr);
         std::vector<rt_uv_desc> out(n);
-        inst::expand_uvs(3, meshes, 2, in.data(), 3, list.data(), 4, out.data());
+        inst::expand_side<inst::UVSide>(3, meshes, 2, in.data(), 3, list.data(), 4, out.data());
         const uint32_t want_index[6] = {1, 3 + 0, 3 + 3, 7 + 1, 9 + 0, 9 + 3};
         const int from[6] = {1, 2, 0, 3, 2, 0};
         CHECK(n == 6, "1 plain + 2 + 1 + 2 entries, got %u", n);
@@ -225,9 +225,9 @@ int main() {
         std::vector<rt_shape_desc> flat(1 + 3 * 2);
         flat[0] = shapes[0];
         for (int k = 0; k < 3; ++k) inst::expand_instance(meshes[0], in[k], flat.data() + 1 + 2 * k);
-        const uint32_t n = inst::expand_uvs(1, meshes, 1, in.data(), 3, list.data(), 3, nullptr);
+        const uint32_t n = inst::expand_side<inst::UVSide>(1, meshes, 1, in.data(), 3, list.data(), 3, nullptr);
         std::vector<rt_uv_desc> out(n);
-        inst::expand_uvs(1, meshes, 1, in.data(), 3, list.data(), 3, out.data());
+        inst::expand_side<inst::UVSide>(1, meshes, 1, in.data(), 3, list.data(), 3, out.data());
         std::vector<const double*> table(flat.size(), nullptr);
         for (const rt_uv_desc& d : out) table[d.index] = d.uv_1;
         std::vector<uint32_t> cls;
