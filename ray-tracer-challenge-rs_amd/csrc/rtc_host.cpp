@@ -24,6 +24,7 @@
 #include "flop_model.hpp"
 #include "host_math.hpp"
 #include "debug_knobs.hpp"
+#include "launch_terms.hpp"
 #include "primary_rect.hpp"
 #include "rtc_context.hpp"
 #include "rtc_internal.hpp"
@@ -1061,8 +1062,13 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
         // (light, plane, caster), well under a microsecond for a small world.
         const size_t ns = ctx->jit.shapes.size();
         // (a supersampled launch takes no primary cull: the tables stay zero)
-        if (jf && !ls.pool && cam && !ss && ns <= (size_t)kPrimaryRectSlots && (int)ns == w.scene.kind_begin[kNumKinds] &&
-            P.width <= kCullCols * kCullCellW && P.height <= kCullRows * kCullCellH) {
+        const bool small_direct = jf && !ls.pool && cam && !ss && ns <= (size_t)kPrimaryRectSlots &&
+                                  (int)ns == w.scene.kind_begin[kNumKinds];
+        // The same kernel's launch terms (launch_terms.hpp): what its shape
+        // tests form from the origin alone, from the same f32 records, for
+        // any canvas.  A few dozen f32 operations per slot.
+        if (small_direct) launch_terms(ctx->jit.shapes.data(), w.scene.kind_begin, (int)ns, P.cam.origin, P.terms);
+        if (small_direct && P.width <= kCullCols * kCullCellW && P.height <= kCullRows * kCullCellH) {
             const uint32_t nc = (P.width + kCullCellW - 1) / kCullCellW, nr = (P.height + kCullCellH - 1) / kCullCellH;
             // Each bit changes at a few edges only, so the tables are built
             // from toggles: flip_*[i] holds the bits that change value between

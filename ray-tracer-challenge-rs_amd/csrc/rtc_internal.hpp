@@ -40,9 +40,13 @@ RTC_HD inline uint32_t shard_tile_rows(uint32_t height, uint32_t shards, uint32_
     const uint32_t trows = (height + RT_TILE_H - 1) / RT_TILE_H;
     return trows > shard ? (trows - shard + shards - 1) / shards : 0;
 }
+// first image row of tile row `tile_row` of shard `shard`'s strip
+RTC_HD inline uint32_t shard_tile_image_row(uint32_t tile_row, uint32_t shards, uint32_t shard) {
+    return (tile_row * shards + shard) * RT_TILE_H;
+}
 // image row of row `strip_row` of shard `shard`'s strip
 RTC_HD inline uint32_t shard_image_row(uint32_t strip_row, uint32_t shards, uint32_t shard) {
-    return ((strip_row / RT_TILE_H) * shards + shard) * RT_TILE_H + strip_row % RT_TILE_H;
+    return shard_tile_image_row(strip_row / RT_TILE_H, shards, shard) + strip_row % RT_TILE_H;
 }
 // shard and strip row of image row y (the inverse)
 RTC_HD inline void shard_of_image_row(uint32_t y, uint32_t shards, uint32_t* shard, uint32_t* strip_row) {
@@ -513,6 +517,22 @@ struct ShadowLayout {
     }
 };
 
+// Launch terms of the same kernel (launch_terms.hpp, rtc_kernels.hip
+// closest_hit and prepare_hit_const): every primary ray of a frame starts at
+// the camera's origin, so what a test forms from the origin alone is one
+// value per launch.  The host works the values out in the kernel's own f32
+// operations (sub, mul, fma, max: the device's bits) and a wave reads them
+// with its block's cull words, one scalar load per tile:
+//   [0]     max(|o.x|, |o.y|, |o.z|), the origin's part of the flat kinds' offset scale
+//   [1 + p] plane p of the plane run: lo.y of xform_point(inv, origin), all its test reads
+// (planes are never culled, so every tile wants them all; the terms of the
+// other kinds' tests were measured too and left out).
+// Filled for the launches the kernel reads them in (camera frames of the
+// per-scene f32 direct kernel, worlds of at most kPrimaryRectSlots slots).
+struct alignas(16) LaunchTerms {
+    float head[kPrimaryRectSlots + 4];
+};
+
 // One launch of the tracer.
 template <typename R>
 struct LaunchParams {
@@ -599,6 +619,11 @@ struct LaunchParams {
     uint32_t n_area;
     uint32_t area_samples;
     uint32_t area_cull;  // 1: the light-level caster cull runs (rtc_kernels.hip area_pass_mask); RTC_DEBUG=area_cull=0 clears it
+    // The per-scene f32 direct kernel's launch terms (above); zero for every
+    // other launch.  Appended, like the fields before it.
+    LaunchTerms terms;
 };
+// (the kernels take LaunchParams by value with four table pointers behind it: one 4 KB kernarg segment)
+static_assert(sizeof(LaunchParams<float>) + 4 * sizeof(void*) <= 4096 && sizeof(LaunchParams<double>) + 4 * sizeof(void*) <= 4096);
 
 }  // namespace rtc

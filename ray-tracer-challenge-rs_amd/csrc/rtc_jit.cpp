@@ -66,6 +66,9 @@ extern char** environ;
 
 namespace rtc {
 
+// rtc_kernels.hip (the f32 build): out[i] = normalized(in[i]), n <= 64 vectors
+hipError_t launch_unit_vectors(const float* in, float* out, uint32_t n, hipStream_t stream);
+
 // One per-scene kernel build: the code object of (world table, variant),
 // compiled by a child process and shared by every context of the process
 // that uploads the same world.
@@ -267,9 +270,12 @@ Clusters make_clusters(const std::vector<ShapeRec<float>>& sh) {
 
 // rtc_jit_scene.hpp: the world's f32 shape table, its lights and whether any
 // material has a pattern, as constexpr data.
+// `unit`: three floats per slot, a plane slot's unit world normal as the
+// device forms it (unit_normals below), or empty: a header without the table
+// (RTC_JIT_UNIT_NORMALS undefined: the kernels normalise per hit).
 std::string scene_header(const std::vector<ShapeRec<float>>& sh, const int32_t begin[kNumKinds + 1],
                          const std::vector<LightRec<float>>& lights, const std::vector<MaterialRec<float>>& mats,
-                         bool patterns, uint32_t pattern_kinds, bool transparent) {
+                         bool patterns, uint32_t pattern_kinds, bool transparent, const std::vector<float>& unit) {
     std::string s = "#pragma once\n#include \"rtc_internal.hpp\"\nnamespace rtc {\nnamespace jit {\n";
     s += "constexpr int kBegin[" + std::to_string(kNumKinds + 1) + "] = {";
     for (int k = 0; k <= kNumKinds; ++k) s += (k ? ", " : "") + std::to_string(begin[k]);
@@ -310,8 +316,50 @@ std::string scene_header(const std::vector<ShapeRec<float>>& sh, const int32_t b
     s += std::string("constexpr bool kPatterns = ") + (patterns ? "true" : "false") + ";\n";
     s += "constexpr uint32_t kPatternKinds = " + std::to_string(pattern_kinds) + "u;\n";
     s += std::string("constexpr bool kTransparent = ") + (transparent ? "true" : "false") + ";\n";
+    if (unit.size() == 3 * sh.size() && !sh.empty()) {
+        s += "#define RTC_JIT_UNIT_NORMALS 1\nconstexpr float kUnitNormal[" + std::to_string(sh.size() + 1) + "][3] = {\n";
+        for (size_t i = 0; i < sh.size(); ++i)
+            s += "    {" + hexf(unit[3 * i]) + ", " + hexf(unit[3 * i + 1]) + ", " + hexf(unit[3 * i + 2]) + "},\n";
+        s += "    {}};\n";
+    }
     s += "}  // namespace jit\n}  // namespace rtc\n";
     return s;
+}
+
+// The unit world normals of the world's planes for a per-scene direct build
+// (rtc_kernels.hip prepare_hit_const): three floats per slot, zero for the
+// other kinds.  A plane's unnormalised normal xform_normal(inv, (0, 1, 0)) is
+// a constant the compiler folds (IEEE f32, the zero entries' terms dropped:
+// kfma), restated here; what normalized() makes of it takes the hardware's
+// reciprocal square root, so one tiny launch on the context's device does
+// that part (launch_unit_vectors) and the host waits for it.  Empty when the
+// world has no plane or a call fails: the build then normalises per hit.
+std::vector<float> unit_normals(rt_context* ctx) {
+    const std::vector<ShapeRec<float>>& sh = ctx->jit.shapes;
+    const int p0 = ctx->jit.begin[RT_SHAPE_PLANE], p1 = ctx->jit.begin[RT_SHAPE_PLANE + 1];
+    if (p1 <= p0 || sh.size() > 64) return {};
+    auto kmul = [](float m, float x) { return m == 0.0f ? 0.0f : m * x; };
+    auto kfma = [](float m, float x, float acc) { return m == 0.0f ? acc : std::fmaf(m, x, acc); };
+    std::vector<float> w(3 * sh.size(), 0.0f), out(3 * sh.size(), 0.0f);
+    for (int s = p0; s < p1; ++s)
+        for (int c = 0; c < 3; ++c)  // xform_normal(inv, {0, 1, 0})
+            w[3 * s + c] = kfma(sh[s].inv[8 + c], 0.0f, kfma(sh[s].inv[4 + c], 1.0f, kmul(sh[s].inv[c], 0.0f)));
+    const size_t bytes = w.size() * sizeof(float);
+    float* d = nullptr;
+    bool ok = hipSetDevice(ctx->device) == hipSuccess && hipMalloc(&d, 2 * bytes) == hipSuccess;
+    if (ok) {
+        ok = hipMemcpy(d, w.data(), bytes, hipMemcpyHostToDevice) == hipSuccess &&
+             launch_unit_vectors(d, d + w.size(), (uint32_t)sh.size(), nullptr) == hipSuccess &&
+             hipMemcpy(out.data(), d + w.size(), bytes, hipMemcpyDeviceToHost) == hipSuccess;
+        (void)hipFree(d);
+    }
+    if (!ok) {
+        (void)hipGetLastError();
+        return {};
+    }
+    for (int s = 0; s < (int)sh.size(); ++s)
+        if (s < p0 || s >= p1) out[3 * s] = out[3 * s + 1] = out[3 * s + 2] = 0.0f;  // (normalized(0) is no number)
+    return out;
 }
 
 const char* kernel_name(bool pool, bool lds, bool ss) {
@@ -635,10 +683,12 @@ int jit_variant(rt_context* ctx, int variant, bool pool, bool lds, size_t dyn_ld
         if (start) {
             ctx->jit.owner[variant] = true;
             uint64_t key = 0;
+            // (the frame kernel's direct builds alone read the unit normals)
+            const std::vector<float> unit = !pool && !ss ? unit_normals(ctx) : std::vector<float>();
             const jitfile::Request rq =
                 make_request(scene_header(ctx->jit.shapes, ctx->jit.begin, ctx->jit.lights, ctx->jit.materials,
                                           ctx->jit.patterns,
-                                          ctx->jit.pattern_kinds, ctx->jit.transparent),
+                                          ctx->jit.pattern_kinds, ctx->jit.transparent, unit),
                              kernel_name(pool, lds, ss), device_arch(ctx), &key, no_skips, pool_waves);
             start_build(b, rq, key, sync && !start_only);
         }

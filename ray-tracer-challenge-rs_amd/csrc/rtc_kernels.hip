@@ -937,6 +937,16 @@ __device__ inline void jit_fence(V3<R>& o, V3<R>& d, int slot = 0) {
             asm volatile("" : "+v"(o.x), "+v"(o.y), "+v"(o.z), "+v"(d.x), "+v"(d.y), "+v"(d.z));
 #endif
 }
+// The fence for a frame's primary rays under launch terms: the origin is one
+// value for the wave and stays in SGPRs (a "+v" would copy it into three VGPRs
+// at every fence); only the direction passes the asm.
+template <typename R>
+__device__ inline void jit_fence_dir(V3<R>& d, int slot = 0) {
+#if defined(RTC_JIT) && !defined(RTC_JIT_NO_FENCE)
+    if constexpr (sizeof(R) == 4 && jit::kBegin[kNumKinds] >= RTC_JIT_FENCE_MIN_SHAPES)
+        if (slot % RTC_JIT_FENCE_EVERY == 0) asm volatile("" : "+v"(d.x), "+v"(d.y), "+v"(d.z));
+#endif
+}
 
 // Every shape, as for_all_kinds, but per-scene builds of worlds with shape
 // clusters (rtc_jit.cpp make_clusters) visit them cluster by cluster: a
@@ -1154,11 +1164,34 @@ __device__ inline bool skips_on(const DevScene<R>& sc) {
 struct NoBlock {
     static constexpr bool kOn = false;
     __device__ bool misses(int) const { return false; }
+    __device__ float plane_height(int) const { return 0.0f; }
+    __device__ float origin_max() const { return 0.0f; }
 };
+// Launch terms (rtc_internal.hpp LaunchTerms): what the tests form from the
+// origin alone, one value for every primary ray of the launch, come from the
+// launch: a plane's object-space height lo.y and the origin's part of the
+// offset scale.  A wave reads them with the block's cull words at the tile
+// head (planes are never culled: every tile tests them all; a load in front
+// of each plane's test was a round trip on the wave's critical path and lost
+// more than the terms saved).  A/B builds: 0 forms them per lane.
+#ifndef RTC_LAUNCH_TERMS
+#define RTC_LAUNCH_TERMS 1
+#endif
+#ifdef RTC_JIT
+constexpr int kJitPlane0 = jit::kBegin[RT_SHAPE_PLANE];  // the first plane's slot
+constexpr int kJitPlanes = jit::kBegin[RT_SHAPE_PLANE + 1] - kJitPlane0;
+#else
+constexpr int kJitPlane0 = 0, kJitPlanes = 0;
+#endif
 struct PixelBlock {
     static constexpr bool kOn = true;
     uint32_t miss;
     __device__ inline bool misses(int slot) const { return (miss >> slot) & 1u; }
+    // LaunchTerms::head, in whole dwordx4 loads: [0] the origin's offset scale, [1 + p] plane p's height
+    static constexpr int kHead = kJitPlanes <= kPrimaryRectSlots ? (1 + kJitPlanes + 3) / 4 * 4 : 4;
+    float head[kHead];
+    __device__ inline float plane_height(int plane) const { return head[1 + plane]; }
+    __device__ inline float origin_max() const { return head[0]; }
 };
 
 template <typename R, typename B = NoBlock>
@@ -1173,6 +1206,14 @@ __device__ inline Hit<R> closest_hit(const DevScene<R>& sc, V3<R> o, V3<R> d, B 
 #else
     constexpr bool kRects = false, kLazy = false;
 #endif
+    // Launch terms (PixelBlock::head): a plane's height comes ready-made from
+    // the launch, and the origin itself stays the wave-uniform value it is
+    // (SGPR operands of the other kinds' tests, no fence).
+#if defined(RTC_JIT) && RTC_LAUNCH_TERMS
+    constexpr bool kTerms = B::kOn && sizeof(R) == 4 && jit::kBegin[kNumKinds] <= kPrimaryRectSlots;
+#else
+    constexpr bool kTerms = false;
+#endif
     R dd0 = (R)0, rdd0 = (R)0;
     V3<R> rd0 = {(R)0, (R)0, (R)0};
     if constexpr (!kLazy) {
@@ -1181,7 +1222,8 @@ __device__ inline Hit<R> closest_hit(const DevScene<R>& sc, V3<R> o, V3<R> d, B 
         rd0 = recip3(d);
     }
     for_all_culled<R, true>(sc, o, d, dd0, [&]<int K>(const ShapeRec<R>& s, int slot) {
-        jit_fence(o, d, slot);
+        if constexpr (kTerms) jit_fence_dir(d, slot);
+        else jit_fence(o, d, slot);
         if constexpr (kRects && K != RT_SHAPE_PLANE)
             if (blk.misses(slot)) return;  // wave-uniform, SALU
         const R dd = kLazy ? dot(d, d) : dd0;
@@ -1199,7 +1241,9 @@ __device__ inline Hit<R> closest_hit(const DevScene<R>& sc, V3<R> o, V3<R> d, B 
             cube_world<R, true>(s, o, d, rd, [&](R t, bool v) { best.offer(t, v, w); });
             return;
         }
-        const V3<R> lo = xform_point(s.inv, o);
+        V3<R> lo = {(R)0, (R)0, (R)0};
+        if constexpr (kTerms && K == RT_SHAPE_PLANE) lo.y = blk.plane_height(slot - kJitPlane0);  // (its test reads lo.y alone)
+        else lo = xform_point(s.inv, o);
         const V3<R> ld = xform_vector(s.inv, d);
         if (K == RT_SHAPE_PLANE && skips_on(sc)) {
             // A plane's one entry is at t = -o_y / d_y (object space): with
@@ -1962,21 +2006,48 @@ __device__ inline R hit_offset(const Hit<R>& h, V3<R> p, V3<R> o) {
 // the material as constants of the slot's branch (kJitConstMaterials).
 // slot: h.slot per lane (LaneSlot), or the one slot of a wave-uniform hit as
 // a constant (ConstSlot: the record, its kind and the material fold).
-template <typename S>
+#ifndef RTC_UNIT_NORMALS
+#define RTC_UNIT_NORMALS 1  // (A/B builds: 0 normalises a plane's constant normal at every hit)
+#endif
+// kDirect: (o, d) is a frame's primary ray (shade_ray's pixel block): the
+// origin's part of the offset scale comes with the launch (LaunchTerms).
+template <bool kDirect, typename S>
 __device__ inline void prepare_hit_const(const DevScene<float>& sc, V3<float> o, V3<float> d, const Hit<float>& h,
-                                         S slot, Prepared<float>& q, bool& patterned, MaterialRec<float>& m) {
+                                         S slot, Prepared<float>& q, bool& patterned, MaterialRec<float>& m,
+                                         float origin_max = 0.0f) {
     q.p = along(o, d, h.t);
     V3<float> w = {0.0f, 0.0f, 0.0f};
     jit_record_material(slot, q.p, w, m);
-    asm volatile("" : "+v"(w.x), "+v"(w.y), "+v"(w.z));  // the hardware rsq, as hit_normal (bit for bit)
-    q.n = normalized(w);
+#if defined(RTC_JIT_UNIT_NORMALS) && RTC_UNIT_NORMALS
+    // A plane's unnormalised normal is a constant of the build, and so is
+    // what normalized() makes of it: the build brings the device's own result
+    // (jit::kUnitNormal, rtc_jit.cpp unit_normals), immediates here.
+    constexpr int kPlaneSlot = [] {
+        if constexpr (S::kConst) return jit_kind_of<S::v>() == RT_SHAPE_PLANE ? S::v : -1;
+        else return -1;
+    }();
+    if constexpr (kPlaneSlot >= 0) {
+        q.n = {jit::kUnitNormal[kPlaneSlot][0], jit::kUnitNormal[kPlaneSlot][1], jit::kUnitNormal[kPlaneSlot][2]};
+    } else
+#endif
+    {
+        asm volatile("" : "+v"(w.x), "+v"(w.y), "+v"(w.z));  // the hardware rsq, as hit_normal (bit for bit)
+        q.n = normalized(w);
+    }
     q.eye = vneg(d);
     if (dot(q.n, q.eye) < 0.0f) q.n = vneg(q.n);
     q.mat = -1;  // (the direct kernel walks no refractive indices)
     int cls;
     if constexpr (S::kConst) cls = offset_class_of_kind(jit_kind_of<S::v>());
     else cls = offset_class(h);
-    q.off = Real<float>::surface_offset(q.p.x, q.p.y, q.p.z, o.x, o.y, o.z, cls);  // (hit_offset)
+#if RTC_LAUNCH_TERMS
+    if constexpr (kDirect && jit::kBegin[kNumKinds] <= kPrimaryRectSlots) {
+        // max is exact and takes its operands in any order: surface_offset's
+        // scale with max(|o.x|, |o.y|, |o.z|) as one operand, the same bits
+        q.off = Real<float>::surface_offset(q.p.x, q.p.y, q.p.z, origin_max, origin_max, origin_max, cls);
+    } else
+#endif
+        q.off = Real<float>::surface_offset(q.p.x, q.p.y, q.p.z, o.x, o.y, o.z, cls);  // (hit_offset)
     q.over = along(q.p, q.n, q.off);
     q.base = {m.color[0], m.color[1], m.color[2]};
     patterned = m.pattern >= 0;
@@ -2324,10 +2395,10 @@ __device__ inline void jit_light_each_bits(uint32_t w, F&& f) {
 template <bool kDirect, typename S>
 __device__ __attribute__((always_inline)) inline void shade_hit_const(const DevScene<float>& sc, V3<float> o, V3<float> d,
                                                                       const Hit<float>& h, S slot, Shaded<float>& out,
-                                                                      uint32_t miss = 0u) {
+                                                                      uint32_t miss = 0u, float origin_max = 0.0f) {
     Prepared<float> q;
     MaterialRec<float> m;
-    prepare_hit_const(sc, o, d, h, slot, q, out.patterned, m);
+    prepare_hit_const<kDirect>(sc, o, d, h, slot, q, out.patterned, m, origin_max);
     V3<float> surface = {0.0f, 0.0f, 0.0f};
     auto light = [&](const LightRec<float>& L, auto sb) {
         const LightSide<float> s = light_side<float, kDirect>(sc, L, q.over, q.n, sb);
@@ -2373,12 +2444,12 @@ __device__ inline bool shade_ray(const DevScene<R>& sc, V3<R> o, V3<R> d, uint32
             const int first = __builtin_amdgcn_readfirstlane(h.slot);
             if (!wave_any(h.slot != first)) {
                 jit_slot_ladder<0, jit::kBegin[kNumKinds]>(
-                    first, [&](auto slot) { shade_hit_const<B::kOn>(sc, o, d, h, slot, out, blk.miss); });
+                    first, [&](auto slot) { shade_hit_const<B::kOn>(sc, o, d, h, slot, out, blk.miss, blk.origin_max()); });
                 return true;
             }
         }
 #endif
-        shade_hit_const<B::kOn>(sc, o, d, h, LaneSlot{h.slot}, out);
+        shade_hit_const<B::kOn>(sc, o, d, h, LaneSlot{h.slot}, out, 0u, blk.origin_max());
         return true;
     }
 #endif
@@ -2510,10 +2581,21 @@ __device__ inline void store_pixel(const LaunchParams<R>& P, uint64_t idx, V3<R>
 #define RTC_WAVE_W 16  // a wave's pixel block: 16 x 4 (64: one 64-pixel row)
 #endif
 static_assert(RT_TILE_W % RTC_WAVE_W == 0 && RT_TILE_H % (64 / RTC_WAVE_W) == 0, "the 4 waves tile the tile");
+// Tile t of a frame, decoded: its row in the shard's strip and its column
+// (wave-uniform: SALU), the one place the tile index is divided.
+struct TileAt {
+    uint32_t lrow, tcol;
+};
+template <typename R>
+__device__ inline TileAt tile_at(const LaunchParams<R>& P, uint32_t t) {
+    const uint32_t lrow = div_by(t, P.tiles_x, P.tiles_x_magic);
+    return {lrow, t - lrow * P.tiles_x};
+}
 template <typename R>
 __device__ inline bool tile_pixel(const LaunchParams<R>& P, uint32_t t, uint32_t tid, uint32_t& x, uint32_t& y,
                                   uint64_t& out_idx) {
-    const uint32_t lrow = div_by(t, P.tiles_x, P.tiles_x_magic), tcol = t - lrow * P.tiles_x;
+    const TileAt at = tile_at(P, t);
+    const uint32_t lrow = at.lrow, tcol = at.tcol;
     // wave w of the tile covers one RTC_WAVE_W x (64 / RTC_WAVE_W) pixel block
     constexpr uint32_t kPerRow = RT_TILE_W / RTC_WAVE_W, kWaveH = 64 / RTC_WAVE_W;
     const uint32_t wave = tid / 64, lane = tid % 64;
@@ -2524,27 +2606,58 @@ __device__ inline bool tile_pixel(const LaunchParams<R>& P, uint32_t t, uint32_t
     return x < P.width && y < P.height;
 }
 
-// The slots this thread's wave passes by in tile t: the launch's miss bits of
-// the wave's block column and block row (LaunchParams::cull_cols/cull_rows),
-// indexed from the uniform terms of tile_pixel alone (tile row and column,
-// the wave's index, the shard's row map), so the loads are scalar and the
+// The per-scene direct kernel decodes tile t once per wave (wave_tile): the
+// first pixel of the wave's block, in the strip and in the image, all
+// wave-uniform, from which come both the lane's pixel (wave_tile_pixel:
+// tile_pixel's x, y and output index for the wave's lanes) and the slots the
+// wave passes by (wave_pixel_block): the launch's miss bits of the block's
+// column and row (LaunchParams::cull_cols/cull_rows), scalar loads, so the
 // test of a slot is one scalar bit test.  The tables are cut for the default
 // 16 x 4 block; other block shapes (RTC_WAVE_W builds) take no primary cull.
 #ifdef RTC_JIT
+struct WaveTile {
+    uint32_t x0;    // the block's first column
+    uint32_t row0;  // its first row in the shard's strip ...
+    uint32_t y0;    // ... and in the image (shard_image_row(row0): a block lies within one tile row)
+};
 template <typename R>
-__device__ inline PixelBlock wave_pixel_block(const LaunchParams<R>& P, uint32_t t) {
+__device__ inline WaveTile wave_tile(const LaunchParams<R>& P, uint32_t t) {
     constexpr uint32_t kPerRow = RT_TILE_W / RTC_WAVE_W, kWaveH = 64 / RTC_WAVE_W;
-    if constexpr (RTC_WAVE_W != kCullCellW || kWaveH != kCullCellH || RT_TILE_H % kCullCellH != 0) return {0u};
-    const uint32_t lrow = div_by(t, P.tiles_x, P.tiles_x_magic), tcol = t - lrow * P.tiles_x;
+    const TileAt at = tile_at(P, t);
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x / 64);
-    const uint32_t row0 = lrow * RT_TILE_H + (wave / kPerRow) * kWaveH;  // the block's first row in the strip
-    const uint32_t cx = tcol * (RT_TILE_W / kCullCellW) + wave % kPerRow;
-    const uint32_t cy = shard_image_row(row0, P.shard_count, P.shard_index) / kCullCellH;
+    const uint32_t wrow = (wave / kPerRow) * kWaveH;
+    return {at.tcol * RT_TILE_W + (wave % kPerRow) * RTC_WAVE_W, at.lrow * RT_TILE_H + wrow,
+            shard_tile_image_row(at.lrow, P.shard_count, P.shard_index) + wrow};
+}
+template <typename R>
+__device__ inline bool wave_tile_pixel(const LaunchParams<R>& P, const WaveTile& w, uint32_t lane, uint32_t& x,
+                                       uint32_t& y, uint64_t& out_idx) {
+    const uint32_t ly = lane / RTC_WAVE_W;
+    x = w.x0 + lane % RTC_WAVE_W;
+    y = w.y0 + ly;
+    out_idx = (uint64_t)((P.image_rows ? w.y0 : w.row0) + ly) * P.width + x;
+    return x < P.width && y < P.height;
+}
+template <typename R>
+__device__ inline PixelBlock wave_pixel_block(const LaunchParams<R>& P, const WaveTile& w) {
+    constexpr uint32_t kWaveH = 64 / RTC_WAVE_W;
+    PixelBlock block = {0u, {}};
+    // the head of this launch's terms, beside the cull words: one wait for both
+    constexpr bool kHeights = RTC_LAUNCH_TERMS && sizeof(R) == 4 && jit::kBegin[kNumKinds] <= kPrimaryRectSlots;
+    if constexpr (kHeights)
+        for (int i = 0; i < PixelBlock::kHead; ++i) block.head[i] = P.terms.head[i];
+    if constexpr (RTC_WAVE_W != kCullCellW || kWaveH != kCullCellH || RT_TILE_H % kCullCellH != 0) return block;
+    const uint32_t cx = w.x0 / kCullCellW, cy = w.y0 / kCullCellH;
     // (indices masked into the tables: a block with a pixel on a canvas the
     // tables cover is in range as it is; a canvas beyond them has them all
     // zero, and a ragged tile's blocks past the canvas have no pixels)
     static_assert((kCullCols & (kCullCols - 1)) == 0 && (kCullRows & (kCullRows - 1)) == 0);
-    return {P.cull_cols[cx & (kCullCols - 1)] | P.cull_rows[cy & (kCullRows - 1)]};
+    block.miss = P.cull_cols[cx & (kCullCols - 1)] | P.cull_rows[cy & (kCullRows - 1)];
+    // (held from here on: the compiler would sink each load to its plane's test)
+    asm volatile("" : "+s"(block.miss));
+    if constexpr (kHeights)
+        for (int i = 0; i < PixelBlock::kHead; ++i) asm volatile("" : "+s"(block.head[i]));
+    return block;
 }
 #endif
 
@@ -2744,6 +2857,9 @@ __device__ inline const LaunchParams<R>& kernarg_params() {
 #ifndef RTC_POOL_WAVES
 #define RTC_POOL_WAVES 6
 #endif
+#ifndef RTC_TILE_DECODE
+#define RTC_TILE_DECODE 1  // (A/B builds: 0 decodes the tile for the pixel and again for the block)
+#endif
 template <typename R, bool kLds>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(sizeof(R) == 4 ? RTC_DIRECT_WAVES : 1))) void trace_direct(
     LaunchParams<R> P, RTC_WORLD_PARAMS(R)) {
@@ -2771,7 +2887,19 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(sizeof(R
         V3<R> o, d;
         uint64_t out_idx;
 #ifdef RTC_JIT
+        // (camera frames only, rtc_host.cpp launch; RTC_TILE_DECODE=0: the two decodes of load_primary and the block)
+#if RTC_TILE_DECODE
+        const WaveTile wt = wave_tile(P, t);
+        {
+            uint32_t x, y;
+            valid = wave_tile_pixel(P, wt, tid % 64, x, y, out_idx);
+            if (valid) camera_ray(P.cam, x, y, o, d);
+            // (the origin is the launch's, whatever the lane: a wave-uniform value the compiler keeps in SGPRs)
+            o = {P.cam.origin[0], P.cam.origin[1], P.cam.origin[2]};
+        }
+#else
         load_primary<R, true>(P, t, tid, valid, o, d, out_idx);
+#endif
 #else
         load_primary(P, t, tid, valid, o, d, out_idx);
 #endif
@@ -2790,7 +2918,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(sizeof(R
                     c = {h.t * (R)0.01, (R)h.slot, (R)0};
                 }
 #ifdef RTC_JIT  // (camera frames only: load_primary above)
-            } else if (shade_ray<R, false>(sc, o, d, 0, sh, NoPush{}, wave_pixel_block(P, t))) {
+#if RTC_TILE_DECODE
+            } else if (shade_ray<R, false>(sc, o, d, 0, sh, NoPush{}, wave_pixel_block(P, wt))) {
+#else
+            } else if (shade_ray<R, false>(sc, o, d, 0, sh, NoPush{}, wave_pixel_block(P, wave_tile(P, t)))) {
+#endif
 #elif RTC_AREA_LIGHTS  // (the jitter hashes the ray's `remaining`: the primary ray's, though no child is made here)
             } else if (shade_ray<R, false>(sc, o, d, P.max_depth, sh)) {
 #else
@@ -3905,6 +4037,25 @@ template hipError_t launch_debug_shape<double>(const ShapeRec<double>*, int, int
 #endif  // !RTC_INSTANCES
 
 #if RTC_PRECISION != 2 && !RTC_INSTANCES
+// Unit vectors as the f32 tracer kernels form them: out[i] = normalized(in[i]),
+// n <= 64 vectors of three floats, one lane each.  normalized() runs the
+// hardware's reciprocal square root, which is not correctly rounded, so only
+// the device gives the device's bits: a per-scene direct build asks for its
+// planes' unit normals here, once, and holds them as constants where the
+// pixel loop normalised the same constant at every hit (rtc_jit.cpp).
+__global__ void unit_vectors(const float* __restrict__ in, float* __restrict__ out, uint32_t n) {
+    const uint32_t i = threadIdx.x;
+    if (i >= n) return;
+    const V3<float> v = normalized(V3<float>{in[3 * i], in[3 * i + 1], in[3 * i + 2]});
+    out[3 * i] = v.x;
+    out[3 * i + 1] = v.y;
+    out[3 * i + 2] = v.z;
+}
+hipError_t launch_unit_vectors(const float* in, float* out, uint32_t n, hipStream_t stream) {
+    (void)hipGetLastError();  // see launch_trace
+    hipLaunchKernelGGL(unit_vectors, dim3(1), dim3(64), 0, stream, in, out, n);
+    return hipGetLastError();
+}
 hipError_t launch_canvas_signal(unsigned long long* flag, unsigned long long seq, hipStream_t stream) {
     (void)hipGetLastError();  // see launch_trace
     hipLaunchKernelGGL(canvas_signal, dim3(1), dim3(64), 0, stream, flag, seq);
