@@ -796,6 +796,70 @@ typedef struct rt_light_info {
 } rt_light_info;
 int rt_scene_light_info(rt_context* ctx, rt_light_info* out);
 
+/* Thin-lens camera: depth of field.  The reference has no
+ * lens, so this text is the contract.
+ *
+ * rt_render_lens* is rt_render_supersampled* with one change: sample (i, j) of
+ * pixel (x, y) is a LENS RAY.  Everything else is that call's: `camera` is the
+ * output camera C (W x H), Cn = rt_camera_resize(C, grid W, grid H) the sample
+ * camera, grid in 1..RT_MAX_SAMPLE_GRID, the same flags, brightness rule,
+ * shards and refusal of groups of more than one rank; rt_stats counts the
+ * grid W x grid H ray set (primary = grid^2 W H); every sample weighs
+ * 1 / grid^2, summed j outer, i inner (plain sums in the direct kernel, the
+ * fixed-point sums in the pool kernel); u8 is quantized once, after the mean.
+ *
+ * The lens ray.  All arithmetic in the kernel's real type R, plain multiplies
+ * and adds, no FMA, in the order written.  With n = grid and Cn's fields:
+ *     px = n x + i,  py = n y + j
+ *     wx = half_width  - (px + 0.5) * pixel_size
+ *     wy = half_height - (py + 0.5) * pixel_size        (camera.rs:52-68)
+ * Lens cell (ci, cj) and position (ju, jv) in it:
+ *     RT_JITTER_NONE:    ci = i, cj = j, ju = jv = 0.5
+ *     RT_JITTER_HASHED, with mix of "Hashed jitter" above and uint32_t wraparound:
+ *         lk  = mix(seed ^ 0x4C454E53)
+ *         key = mix(lk ^ ray_id),  ray_id = (n y + j)(n W) + n x + i
+ *         ju  = (key >> 8) * 2^-24,  jv = (mix(key ^ 0x9E3779B9) >> 8) * 2^-24
+ *         r   = mix(lk ^ mix(y W + x)) mod n^2          (the cells rotate per pixel)
+ *         k'  = (j n + i + r) mod n^2,  ci = k' mod n,  cj = k' div n
+ *     y is the WHOLE-image row (shards hash what the whole frame hashes), ray_id
+ *     the value supersampled frames give the area lights' hash.
+ * Square to disc (no trigonometry: the device and a host restatement agree to
+ * the bit), inv_n = R(1) / R(n):
+ *     a  = 2 * ((ci + ju) * inv_n) - 1,   b = 2 * ((cj + jv) * inv_n) - 1
+ *     ex = a * sqrt(1 - (b * b) * 0.5),   ey = b * sqrt(1 - (a * a) * 0.5)
+ * Lens point and focal point in camera space, f = focal_distance:
+ *     L = (aperture * ex, aperture * ey, 0),   F = (wx * f, wy * f, -f)
+ * The ray: origin = inverse * L and target = inverse * F as points, each row
+ * the left fold (((0 + m0 x) + m1 y) + m2 z) + m3 (matrix.rs:332-346);
+ * direction = normalized(target - origin) (vector.rs:84-91).  That is the f64
+ * kernels' arithmetic to the bit.  The f32 kernels form the direction as
+ * M3 * (F - L) with their own fused transforms; their bar is statistical.
+ *
+ * aperture == 0 IS rt_render_supersampled* (after the checks): the same bytes
+ * and counters, as grid = 1 there is rt_render*.  grid = 1 with a positive
+ * aperture is one lens point per pixel: accumulate frames over seeds.
+ * RT_ERR_INVALID, each with its own rt_last_error text and checked before the
+ * context is looked at: a null lens, an aperture below 0 or not finite, a
+ * focal distance not above 0 or not finite, a jitter other than 0 or 1; then
+ * whatever rt_render_supersampled* refuses, with its text.
+ * rt_lens_ray (host only) writes the f64 ray {origin, direction} of sample
+ * (i, j) of pixel (x, y), `camera` being the OUTPUT camera, for either jitter
+ * mode. */
+typedef struct rt_lens_desc {      /* 24 bytes */
+    double aperture;               /* lens radius in camera space, >= 0, finite */
+    double focal_distance;         /* distance of the focal plane along the view axis, > 0, finite */
+    uint32_t jitter;               /* RT_JITTER_NONE | RT_JITTER_HASHED */
+    uint32_t seed;
+} rt_lens_desc;
+int rt_render_lens(rt_context* ctx, const rt_camera_desc* camera,
+                   const rt_render_options* options, uint32_t grid,
+                   const rt_lens_desc* lens, void* out_host, rt_stats* stats);
+int rt_render_lens_device(rt_context* ctx, const rt_camera_desc* camera,
+                          const rt_render_options* options, uint32_t grid,
+                          const rt_lens_desc* lens, void* out_device, void* hip_stream);
+int rt_lens_ray(const rt_camera_desc* camera, uint32_t grid, const rt_lens_desc* lens,
+                uint32_t x, uint32_t y, uint32_t i, uint32_t j, double ray[6]);
+
 /* Peer canvas: a frame assembled in place instead of gathered (SURVEY.md
  * §8e; the north star's "gather of framebuffer strips over xGMI" done as the
  * shards' own stores into rank 0's image).  The owner creates a device canvas

@@ -25,8 +25,11 @@
 // gets an image pattern and their vt lines are read: rt_scene_upload_textured,
 // DESIGN.md §3.12), --area-light cx,cy,cz:ux,uy,uz:vx,vy,vz:USTEPSxVSTEPS
 // [:r,g,b][:jitter[=SEED]] (repeatable: an area light added to the scene's
-// lights, rt_scene_upload_lit).  Pixels are quantized on the
-// device as canvas.rs:117-123 does.
+// lights, rt_scene_upload_lit), --aperture R --focus D
+// [--lens-jitter[=SEED]] (a thin lens of radius R focused at distance D, both
+// in camera space: rt_render_lens; works with --samples, whose
+// N x N samples leave the cells of an N x N grid on the lens disc).  Pixels are
+// quantized on the device as canvas.rs:117-123 does.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -45,6 +48,7 @@ static int usage() {
                  "           [--samples N] [--obj MESH.obj]... [--instance MESH.obj:tx,ty,tz[:s]]... [--smooth]\n"
                  "           [--texture IMAGE.ppm|png] [--texture-filter nearest|bilinear]\n"
                  "           [--area-light cx,cy,cz:ux,uy,uz:vx,vy,vz:USTEPSxVSTEPS[:r,g,b][:jitter[=SEED]]]...\n"
+                 "           [--aperture R --focus D [--lens-jitter[=SEED]]]\n"
                  "  --obj MESH.obj appends the mesh's triangles (v and f lines; faces fan-triangulated) to the\n"
                  "  scene's shapes, with the default material and no transformation; repeatable.\n"
                  "  --instance MESH.obj:tx,ty,tz[:s] places a copy of the mesh, scaled by s (default 1) and moved by\n"
@@ -59,6 +63,9 @@ static int usage() {
                  "  at the cell centres or, with jitter, at hashed positions per ray (seed SEED, default 0); repeatable.\n"
                  "  --samples N renders N x N samples per pixel (1..%d, default 1 = one ray per pixel centre) and\n"
                  "  averages them on the GPU.\n"
+                 "  --aperture R --focus D renders through a thin lens of radius R focused at distance D along the\n"
+                 "  view axis (depth of field); each of the N x N samples leaves its own point of the lens, the cell\n"
+                 "  centres of a grid on the disc or, with --lens-jitter[=SEED], hashed positions per sample.\n"
                  "  -r serial|parallel are accepted for the reference's command lines but render on the GPU like\n"
                  "  -r gpu: this build ships no CPU renderer (Camera::render / render_parallel are not in it).\n",
                  RT_LIGHT_MAX_STEPS, RT_MAX_SAMPLE_GRID);
@@ -144,6 +151,8 @@ int main(int argc, char** argv) {
     uint32_t width = 0, height = 0, depth = RT_DEFAULT_MAX_DEPTH, precision = RT_PRECISION_F32;
     int device = 0, gpus = 1;
     uint32_t samples = 1;
+    rt_lens_desc lens = {0.0, 0.0, RT_JITTER_NONE, 0};
+    bool have_aperture = false, have_focus = false, have_lens_jitter = false;
     bool smooth = false;
     const char* texture_path = nullptr;
     int texture_filter = RT_FILTER_BILINEAR;
@@ -181,6 +190,33 @@ int main(int argc, char** argv) {
             }
             samples = (uint32_t)n;
         }
+        else if (a == "--aperture" || a == "--focus") {
+            const char* v = next();
+            char* end = nullptr;
+            const double d = v ? std::strtod(v, &end) : 0.0;
+            const bool aperture = a == "--aperture";
+            if (!v || end == v || *end || !(d - d == 0.0) || (aperture ? d < 0.0 : !(d > 0.0))) {
+                std::fprintf(stderr, aperture ? "error: --aperture takes a lens radius, a number >= 0\n"
+                                              : "error: --focus takes a focal distance, a number > 0\n");
+                return usage();
+            }
+            (aperture ? lens.aperture : lens.focal_distance) = d;
+            (aperture ? have_aperture : have_focus) = true;
+        }
+        else if (a == "--lens-jitter" || a.rfind("--lens-jitter=", 0) == 0) {
+            if (a.size() > 13) {
+                const char* v = a.c_str() + 14;
+                char* end = nullptr;
+                const unsigned long seed = std::strtoul(v, &end, 0);
+                if (end == v || *end || *v == '-' || seed > 0xFFFFFFFFul) {
+                    std::fprintf(stderr, "error: --lens-jitter takes an optional =SEED, a whole number below 2^32\n");
+                    return usage();
+                }
+                lens.seed = (uint32_t)seed;
+            }
+            lens.jitter = RT_JITTER_HASHED;
+            have_lens_jitter = true;
+        }
         else if (a == "--obj") { const char* v = next(); if (!v) return usage(); obj_paths.push_back(v); }
         else if (a == "--instance") {
             const char* v = next();
@@ -206,6 +242,14 @@ int main(int argc, char** argv) {
             if (!v) return usage();
             precision = std::strcmp(v, "f64") == 0 ? RT_PRECISION_F64 : RT_PRECISION_F32;
         } else return usage();
+    }
+    if (have_aperture && !have_focus) {
+        std::fprintf(stderr, "error: --aperture needs --focus D, the distance of the plane in focus\n");
+        return usage();
+    }
+    if ((have_focus || have_lens_jitter) && !have_aperture) {
+        std::fprintf(stderr, "error: --focus and --lens-jitter describe a lens: give --aperture R\n");
+        return usage();
     }
     if (!quiet) std::printf("Rendering image using scene at %s\n", scene_path);
     using clk = std::chrono::steady_clock;
@@ -373,8 +417,9 @@ int main(int argc, char** argv) {
     std::vector<uint8_t> img((size_t)cam.width * cam.height * 3);
     rt_stats st;
     auto t0 = std::chrono::steady_clock::now();
-    if ((samples > 1 ? rt_render_supersampled(ctx, &cam, &o, samples, img.data(), &st)
-                     : rt_render(ctx, &cam, &o, img.data(), &st)) != RT_OK) {
+    if ((have_aperture ? rt_render_lens(ctx, &cam, &o, samples, &lens, img.data(), &st)
+         : samples > 1 ? rt_render_supersampled(ctx, &cam, &o, samples, img.data(), &st)
+                       : rt_render(ctx, &cam, &o, img.data(), &st)) != RT_OK) {
         std::fprintf(stderr, "error: %s\n", rt_last_error());
         return 1;
     }

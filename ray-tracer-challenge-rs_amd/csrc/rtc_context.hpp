@@ -259,8 +259,9 @@ struct rt_context {
         uint32_t pattern_kinds = ~0u;              // pattern kinds in the world's table (bit per RT_PATTERN_*)
         bool transparent = true;                   // some material is transparent (else no refraction code)
         int32_t begin[rtc::kNumKinds + 1] = {};
-        // variants: pool x LDS world x RT_FLAG_NO_SKIPS x (pool) 7 waves/SIMD x supersampled (rtc_jit.cpp jit_function)
-        static constexpr int kVariants = 32;
+        // variants: pool x LDS world x RT_FLAG_NO_SKIPS x (pool) 7 waves/SIMD x supersampled x lens
+        // (rtc_jit.cpp jit_function)
+        static constexpr int kVariants = 64;
         hipFunction_t fn[kVariants] = {};
         std::shared_ptr<rtc::CodeBuild> build[kVariants];  // the build each variant waits for (host thread)
         bool rejected[kVariants] = {};   // built, but refused for occupancy or scratch (that variant only)
@@ -314,9 +315,9 @@ struct rt_context {
     int cu_count = 0;
     size_t lds_per_block = 64 * 1024;
     rtc::KernelBuild kernel_build = rtc::KernelBuild::plain;  // the uploaded world's (set_kernel_build)
-    size_t occ_lds[20] = {};    // occupancy cache of kernel_build's kernels: {direct,pool} x {f32,f64} x
-    int occ_blocks[20] = {};    // {global,LDS world}, then the ray-batch kernel's {f32,f64} x {global,LDS world},
-                                // then the supersampled kernels' (as the first eight)
+    size_t occ_lds[28] = {};    // occupancy cache of kernel_build's kernels: {direct,pool} x {f32,f64} x
+    int occ_blocks[28] = {};    // {global,LDS world}, then the ray-batch kernel's {f32,f64} x {global,LDS world},
+                                // then the supersampled kernels' and the lens kernels' (each as the first eight)
     Knobs knobs;
     rtc::Stream stream;
     rtc::Event ev_start, ev_stop;
@@ -359,6 +360,7 @@ struct rt_context {
     rtc::DeviceBuffer<unsigned char> d_spill;
     TileOrder order;
     TileOrder order_ss;  // ... of the supersampled launches (rt_render_supersampled*): costs of n^2 samples per tile
+    TileOrder order_lens;  // ... of the lens launches (rt_render_lens*): the lens in the signature
     Jit jit;
     rtc::DeviceBuffer<unsigned char> d_scratch;  // host-buffer renders / color_at staging
     rtc::DeviceBuffer<unsigned long long> d_stamps;  // RT_FLAG_STAMPS diagnostics: two per workgroup
@@ -471,8 +473,9 @@ constexpr uint32_t kJitMinTiles = 256;  // 64K pixels
 // ss: the supersampled kernel (trace_direct_ss / trace_pool_ss), a build of
 // its own that only worlds rendered supersampled ask for; its pool build is
 // made at the static occupancy alone.
+// lens (with ss): the lens kernel (trace_direct_lens / trace_pool_lens), under ss's rules.
 int jit_function(rt_context* ctx, bool pool, bool lds, size_t dyn_lds, int static_blocks, hipFunction_t* fn,
-                 bool no_skips = false, int* pool_waves = nullptr, bool ss = false);
+                 bool no_skips = false, int* pool_waves = nullptr, bool ss = false, bool lens = false);
 int jit_wait(rt_context* ctx, double timeout_ms, int* pending);
 const std::string& device_arch(rt_context* ctx);  // rtc_jit.cpp: the device's gfx target, read once
 

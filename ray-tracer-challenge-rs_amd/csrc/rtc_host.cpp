@@ -36,7 +36,8 @@ namespace rtc {
 
 // The six launchers every build of the tracer kernels (rtc_kernels.hip, RTC_VARIANT) defines in its own
 // namespace: the frame kernels, the ray-batch kernel and the supersampled frame kernels (trace_direct_ss,
-// trace_pool_ss), each with its occupancy query.
+// trace_pool_ss; with `lens` the lens frame kernels, trace_direct_lens and trace_pool_lens), each with its
+// occupancy query.
 #define RTC_KERNEL_LAUNCHERS                                                                                          \
     template <typename R>                                                                                             \
     hipError_t launch_trace(const LaunchParams<R>& P, bool pool, bool dup, uint32_t grid, size_t dyn_lds,             \
@@ -49,10 +50,10 @@ namespace rtc {
     template <typename R>                                                                                             \
     hipError_t occupancy_rays(bool lds, size_t dyn_lds, int* blocks_per_cu);                                          \
     template <typename R>                                                                                             \
-    hipError_t launch_trace_ss(const LaunchParams<R>& P, bool pool, bool dup, uint32_t grid, size_t dyn_lds,          \
-                               hipStream_t stream);                                                                   \
+    hipError_t launch_trace_ss(const LaunchParams<R>& P, bool pool, bool dup, const LensParams<R>* lens,              \
+                               uint32_t grid, size_t dyn_lds, hipStream_t stream);                                    \
     template <typename R>                                                                                             \
-    hipError_t occupancy_ss(bool pool, bool lds, size_t dyn_lds, int* blocks_per_cu);
+    hipError_t occupancy_ss(bool pool, bool lds, bool lens, size_t dyn_lds, int* blocks_per_cu);
 RTC_KERNEL_LAUNCHERS                          // rtc_kernels*.o: the plain build
 namespace instanced { RTC_KERNEL_LAUNCHERS }  // rtc_kernels_inst*.o: with the instance level, for worlds with mesh instances
 namespace textured { RTC_KERNEL_LAUNCHERS }   // rtc_kernels_tex*.o: the instance build plus the texture code
@@ -630,17 +631,19 @@ int cap_by_lds(int api, size_t lds) {
 // Cached occupancy (workgroups per CU) of one kernel instantiation of the
 // world's build at a given dynamic LDS size (cap_by_lds); an upload that
 // changes the build clears the cache (set_kernel_build).  ss: the
-// supersampled kernels (keys 12..19 of the same table).
+// supersampled kernels (keys 12..19 of the same table); with lens, the lens
+// kernels (keys 20..27).
 template <typename R>
-int blocks_per_cu(rt_context* ctx, bool pool, bool lds_world, size_t lds, int* per_cu, bool ss = false) {
-    const int key = (pool ? 1 : 0) + (sizeof(R) == 8 ? 2 : 0) + (lds_world ? 4 : 0) + (ss ? 12 : 0);
+int blocks_per_cu(rt_context* ctx, bool pool, bool lds_world, size_t lds, int* per_cu, bool ss = false,
+                  bool lens = false) {
+    const int key = (pool ? 1 : 0) + (sizeof(R) == 8 ? 2 : 0) + (lds_world ? 4 : 0) + (lens ? 20 : ss ? 12 : 0);
     if (ctx->occ_lds[key] == lds && ctx->occ_blocks[key] > 0) {
         *per_cu = ctx->occ_blocks[key];
         return RT_OK;
     }
     int api = 0;
     const Launchers<R>& k = launchers<R>(ctx);
-    RT_HIP(ss ? k.occupancy_ss(pool, lds_world, lds, &api) : k.occupancy(pool, lds_world, lds, &api));
+    RT_HIP(ss ? k.occupancy_ss(pool, lds_world, lens, lds, &api) : k.occupancy(pool, lds_world, lds, &api));
     *per_cu = cap_by_lds(api, lds);
     ctx->occ_lds[key] = lds;
     ctx->occ_blocks[key] = *per_cu;
@@ -679,14 +682,16 @@ int pool_lds_plan(rt_context* ctx, uint32_t world_lds, uint32_t cap, Occ&& occ, 
 // ... for the static pool kernel (6 workgroups/CU for f32 at <= 80 VGPRs).
 // RTC_DEBUG=pool_lds_rays=N overrides (A/B).
 template <typename R>
-int pool_lds_rays(rt_context* ctx, uint32_t world_lds, uint32_t cap, uint32_t* lcap, bool ss = false) {
+int pool_lds_rays(rt_context* ctx, uint32_t world_lds, uint32_t cap, uint32_t* lcap, bool ss = false,
+                  bool lens = false) {
     if (ctx->knobs.pool_lds_rays > 0) {
         *lcap = std::min<uint32_t>(cap, std::max<uint32_t>(kBlock, ctx->knobs.pool_lds_rays & ~7u));
         return RT_OK;
     }
     const bool lw = world_lds != 0;
     return pool_lds_plan<R>(ctx, world_lds, cap,
-                            [&](size_t lds, int* b) { return blocks_per_cu<R>(ctx, true, lw, lds, b, ss); }, lcap, nullptr);
+                            [&](size_t lds, int* b) { return blocks_per_cu<R>(ctx, true, lw, lds, b, ss, lens); }, lcap,
+                            nullptr);
 }
 
 // LDS world of a per-scene kernel that takes the shape records from its
@@ -728,10 +733,11 @@ int plan_pool_for(rt_context* ctx, hipFunction_t fn, LaunchShape& ls) {
 }
 
 // samples: the grid of a supersampled launch (its kernels, their occupancy
-// and their pool bound), 0 = a plain one.
+// and their pool bound), 0 = a plain one; lens: a lens launch (its kernels,
+// planned as the supersampled ones are).
 template <typename R>
 int plan_launch(rt_context* ctx, const DevScene<R>& sc, uint32_t depth, uint32_t n_tiles, LaunchShape& ls,
-                bool jit_records = false, uint32_t samples = 0) {
+                bool jit_records = false, uint32_t samples = 0, bool lens = false) {
     const bool ss = samples != 0;
     ls.pool = sc.any_secondary && depth > 0;
     const size_t wb = jit_records ? std::max<size_t>(16, jit_world_lds_bytes(sc))
@@ -747,11 +753,11 @@ int plan_launch(rt_context* ctx, const DevScene<R>& sc, uint32_t depth, uint32_t
         // (the pool kernel takes its items from the per-XCD queues only)
         ls.batch = kPoolBatch;
         ls.cap = ss ? pool_capacity_ss(depth, ls.batch, samples) : pool_capacity(depth, ls.batch);
-        if ((rc = pool_lds_rays<R>(ctx, ls.world_lds, ls.cap, &ls.lcap, ss))) return rc;
+        if ((rc = pool_lds_rays<R>(ctx, ls.world_lds, ls.cap, &ls.lcap, ss, lens))) return rc;
         ls.lds += pool_lds_bytes<R>(ls.lcap);
     }
     int per_cu = 0;
-    if ((rc = blocks_per_cu<R>(ctx, ls.pool, ls.world_lds != 0, ls.lds, &per_cu, ss))) return rc;
+    if ((rc = blocks_per_cu<R>(ctx, ls.pool, ls.world_lds != 0, ls.lds, &per_cu, ss, lens))) return rc;
     if (per_cu < 1) per_cu = 1;
     ls.per_cu = per_cu;
     const uint64_t resident = (uint64_t)per_cu * (uint64_t)ctx->cu_count;
@@ -787,10 +793,11 @@ int plan_launch(rt_context* ctx, const DevScene<R>& sc, uint32_t depth, uint32_t
 // A supersampled launch keeps an order and costs of its own (`to` =
 // ctx->order_ss, the sample grid in the signature): its tiles cost n^2
 // samples each, and it neither reuses nor overwrites what the plain launches
-// of the same camera recorded.
+// of the same camera recorded.  So does a lens launch (ctx->order_lens, the
+// lens in the signature beside the camera).
 template <typename R>
 int plan_tile_order(rt_context* ctx, rt_context::TileOrder& to, LaunchParams<R>& P, const rt_camera_desc* cam,
-                    uint32_t depth, uint32_t grid, hipStream_t stream) {
+                    uint32_t depth, uint32_t grid, hipStream_t stream, const rt_lens_desc* lens = nullptr) {
     if (P.n_tiles > kItemTileMask + 1) return RT_OK;  // items carry 20 tile bits: raster order
     uint64_t h = 1469598103934665603ull;  // FNV-1a
     auto mix = [&h](const void* p, size_t n) {
@@ -802,6 +809,7 @@ int plan_tile_order(rt_context* ctx, rt_context::TileOrder& to, LaunchParams<R>&
     mix(fields, sizeof(fields));
     const uint64_t geometry = h;
     if (cam) mix(cam, sizeof(*cam));
+    if (lens) mix(lens, sizeof(*lens));
     bool grew_cost = false, grew_order = false;
     int rc = to.d_cost.reserve(P.n_tiles, &grew_cost);
     // up to 2^kMaxSplitLog2 items per tile, then the item count
@@ -885,7 +893,47 @@ struct LaunchRequest {
     bool image_rows = false;
     uint32_t samples = 0;  // a supersampled frame's grid (cam = the sample camera, out_w x out_h the output), 0 = plain
     uint32_t out_w = 0, out_h = 0;
+    const rt_lens_desc* lens = nullptr;  // with samples (a grid of 1 too): a lens frame (rt_render_lens*), aperture > 0
 };
+
+// Host restatement of the kernels' transforms (rtc_kernels.hip xform_point): the f64 left fold, the f32 fused chain.
+inline void lens_xform_point(const double* m, const double p[3], double out[3]) {
+    for (int r = 0; r < 3; ++r)
+        out[r] = (((0.0 + m[4 * r] * p[0]) + m[4 * r + 1] * p[1]) + m[4 * r + 2] * p[2]) + m[4 * r + 3];
+}
+inline void lens_xform_point(const float* m, const float p[3], float out[3]) {
+    for (int r = 0; r < 3; ++r)
+        out[r] = std::fmaf(m[4 * r + 2], p[2], std::fmaf(m[4 * r + 1], p[1], std::fmaf(m[4 * r], p[0], m[4 * r + 3])));
+}
+
+// The lens point of cell position (fu, fv) = (ci + ju, cj + jv) (rtc.h "Thin-lens
+// camera": square to disc, camera-space L, origin = inverse * L), in the
+// kernels' own operations (rtc_kernels.hip lens_ray's hashed branch; this file
+// is compiled with -ffp-contract=off).
+template <typename R>
+void lens_point(const R* inv, R aperture, R inv_n, R fu, R fv, LensPoint<R>& out) {
+    const R a = (R)2 * (fu * inv_n) - (R)1, b = (R)2 * (fv * inv_n) - (R)1;
+    const R ex = a * std::sqrt((R)1 - (b * b) * (R)0.5), ey = b * std::sqrt((R)1 - (a * a) * (R)0.5);
+    out.lx = aperture * ex;
+    out.ly = aperture * ey;
+    const R l[3] = {out.lx, out.ly, (R)0};
+    lens_xform_point(inv, l, out.origin);
+}
+
+// The launch's lens: under RT_JITTER_NONE the n^2 lens points, one per sample
+// (cell centres), which the kernels read instead of working them out per lane.
+template <typename R>
+void set_lens_params(const LaunchParams<R>& P, const rt_lens_desc& lens, uint32_t n, LensParams<R>& o) {
+    o.aperture = (R)lens.aperture;
+    o.focal = (R)lens.focal_distance;
+    o.inv_n = (R)1 / (R)n;
+    o.jitter = lens.jitter;
+    o.lk = hash_mix(lens.seed ^ kLensKey);
+    if (lens.jitter != RT_JITTER_NONE) return;
+    for (uint32_t j = 0; j < n; ++j)
+        for (uint32_t i = 0; i < n; ++i)
+            lens_point<R>(P.cam.inv, o.aperture, o.inv_n, (R)i + (R)0.5, (R)j + (R)0.5, o.points[j * n + i]);
+}
 
 // The launch's view of the world's mesh instances (none: no world index reaches inst_world_begin).
 template <typename R>
@@ -916,6 +964,7 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
     hipStream_t stream = q.stream;
     int rc;
     LaunchParams<R> P{};
+    LensParams<R> lens_params{};  // a lens launch's last kernel argument
     P.image_rows = q.image_rows ? 1u : 0u;
     P.scene = w.scene;
     P.tri_nodes = w.n_tri_nodes ? w.tri_nodes.get() : nullptr;
@@ -931,6 +980,7 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
         P.cam.pixel_size = (R)cam->pixel_size;
         // (a supersampled frame: the canvas and its tiles are the output's)
         P.ss_grid = q.samples;
+        if (q.lens) set_lens_params(P, *q.lens, q.samples, lens_params);
         P.width = q.samples ? q.out_w : cam->width;
         P.height = q.samples ? q.out_h : cam->height;
         P.tiles_x = (P.width + RT_TILE_W - 1) / RT_TILE_W;
@@ -954,8 +1004,8 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
     if (P.n_tiles == 0) return RT_OK;
     if ((rc = order_after_last(ctx, stream))) return rc;
     LaunchShape ls;
-    const bool ss = q.samples != 0;
-    rc = plan_launch<R>(ctx, w.scene, depth, P.n_tiles, ls, false, q.samples);
+    const bool ss = q.samples != 0, lens = q.lens != nullptr;
+    rc = plan_launch<R>(ctx, w.scene, depth, P.n_tiles, ls, false, q.samples, lens);
     if (rc) return rc;
     // value-equal shapes (rt_scene_upload's identity classes) take the pool
     // kernel whose containers walk aggregates per class
@@ -986,11 +1036,11 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
             ++ctx->jit.frames;
             LaunchShape lj = ls;
             if (ctx->knobs.lds_world && !ls.pool && w.scene.kind_begin[kNumKinds] <= kJitRecordsMaxShapes &&
-                (rc = plan_launch<R>(ctx, w.scene, depth, P.n_tiles, lj, true, q.samples)))
+                (rc = plan_launch<R>(ctx, w.scene, depth, P.n_tiles, lj, true, q.samples, lens)))
                 return rc;
             int waves = 0;
             if ((rc = jit_function(ctx, lj.pool, lj.world_lds != 0, lj.lds, lj.per_cu, &jf,
-                                   (flags & RT_FLAG_NO_SKIPS) != 0, &waves, ss)))
+                                   (flags & RT_FLAG_NO_SKIPS) != 0, &waves, ss, lens)))
                 return rc;
             if (jf && waves > 0 && (rc = plan_pool_for<R>(ctx, jf, lj))) return rc;
             if (jf) ls = lj;
@@ -1024,7 +1074,8 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
         P.tile_counter = ctx->d_tile_counter.get() + (ctx->head_set ? set : 0);
         P.next_tile_counter = ctx->d_tile_counter.get() + (ctx->head_set ? 0 : set);
         if (ls.pool && ctx->knobs.tile_order && cam) {  // frames only: a ray batch's content is not in the signature
-            if ((rc = plan_tile_order<R>(ctx, ss ? ctx->order_ss : ctx->order, P, cam, depth, ls.grid, stream)))
+            if ((rc = plan_tile_order<R>(ctx, lens ? ctx->order_lens : ss ? ctx->order_ss : ctx->order, P, cam, depth,
+                                         ls.grid, stream, q.lens)))
                 return rc;
         }
     }
@@ -1142,14 +1193,15 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
         const MaterialRec<R>* mt = P.scene.materials;
         const PatternRec<R>* pt = P.scene.patterns;
         const LightRec<R>* lt = P.scene.lights;
-        void* args[] = {&P, &sh, &mt, &pt, &lt};
+        void* args[] = {&P, &sh, &mt, &pt, &lt, &lens_params};  // (the last: read by the lens kernels only)
         (void)hipGetLastError();
         RT_HIP(hipModuleLaunchKernel(jf, ls.grid, 1, 1, kBlock, 1, 1, (unsigned)ls.lds, stream, args, nullptr));
-    } else if (hipError_t e = ss   ? launchers<R>(ctx).launch_trace_ss(P, ls.pool, dup, ls.grid, ls.lds, stream)
+    } else if (hipError_t e = ss   ? launchers<R>(ctx).launch_trace_ss(P, ls.pool, dup, lens ? &lens_params : nullptr, ls.grid,
+                                                                  ls.lds, stream)
                               : sp ? sp::launch_trace<R>(P, ls.pool, dup, ls.grid, ls.lds, stream)
                                    : launchers<R>(ctx).launch_trace(P, ls.pool, dup, ls.grid, ls.lds, stream);
                e != hipSuccess)
-        return set_error(RT_ERR_HIP, std::string("launch of the ") + (ss ? "supersampled " : "") +
+        return set_error(RT_ERR_HIP, std::string("launch of the ") + (lens ? "lens " : ss ? "supersampled " : "") +
                                          (ls.pool ? "pool" : "direct") + " kernel (grid " +
                                          std::to_string(ls.grid) + ", dynamic LDS " + std::to_string(ls.lds) +
                                          " B, pool " + std::to_string(ls.lcap) + "/" + std::to_string(ls.cap) +
@@ -2466,6 +2518,18 @@ int rt_render_device(rt_context* ctx, const rt_camera_desc* cam, const rt_render
 
 namespace {
 
+// rt_camera_resize(cam, w, h), rtc_scene.h
+rt_camera_desc camera_resized(const rt_camera_desc& c, uint32_t w, uint32_t h) {
+    rt_camera_desc r = c;
+    const hm::CameraSize z = hm::camera_size(w, h, c.field_of_view);
+    r.width = w;
+    r.height = h;
+    r.half_width = z.half_width;
+    r.half_height = z.half_height;
+    r.pixel_size = z.pixel_size;
+    return r;
+}
+
 // What a supersampled call may ask for (rtc.h), checked before any work; the
 // sample camera Cn of `cam` into *cn.
 int check_supersampled(rt_context* ctx, const rt_camera_desc* cam, const rt_render_options* o, uint32_t samples,
@@ -2488,46 +2552,50 @@ int check_supersampled(rt_context* ctx, const rt_camera_desc* cam, const rt_rend
         return set_error(RT_ERR_INVALID, "supersampled frames are not split across a group of " +
                                              std::to_string(ctx->group.n_ranks) +
                                              " ranks: render shards per context (shard_index, shard_count)");
-    // rt_camera_resize(cam, n W, n H), rtc_scene.h
-    auto resized = [](const rt_camera_desc& c, uint32_t w, uint32_t h) {
-        rt_camera_desc r = c;
-        const hm::CameraSize z = hm::camera_size(w, h, c.field_of_view);
-        r.width = w;
-        r.height = h;
-        r.half_width = z.half_width;
-        r.half_height = z.half_height;
-        r.pixel_size = z.pixel_size;
-        return r;
-    };
-    *cn = resized(*cam, samples * cam->width, samples * cam->height);
+    *cn = camera_resized(*cam, samples * cam->width, samples * cam->height);
     // The sample camera keeps the output camera's half extents bit for bit
     // (n W / n H and W / H round to the same f64; tests/test_supersample_cpu.py):
     // the premise of "a pixel is the mean of Cn's pixels".  A size where it
     // failed would be refused here.
-    const rt_camera_desc c1 = resized(*cam, cam->width, cam->height);
+    const rt_camera_desc c1 = camera_resized(*cam, cam->width, cam->height);
     if (cam->width && cam->height && (c1.half_width != cn->half_width || c1.half_height != cn->half_height))
         return set_error(RT_ERR_INVALID, "sample grid " + std::to_string(samples) +
                                              ": the sample camera's half extents differ from the output camera's");
     return RT_OK;
 }
 
+// What a lens is (rtc.h "Thin-lens camera"), checked before the context is looked at.
+int check_lens(const rt_lens_desc* lens) {
+    if (!lens) return set_error(RT_ERR_INVALID, "null lens");
+    if (!(lens->aperture >= 0.0) || !std::isfinite(lens->aperture))
+        return set_error(RT_ERR_INVALID, "lens aperture below 0 or not finite");
+    if (!(lens->focal_distance > 0.0) || !std::isfinite(lens->focal_distance))
+        return set_error(RT_ERR_INVALID, "lens focal distance not above 0 or not finite");
+    if (lens->jitter != RT_JITTER_NONE && lens->jitter != RT_JITTER_HASHED)
+        return set_error(RT_ERR_INVALID, "lens jitter " + std::to_string(lens->jitter) +
+                                             " is neither RT_JITTER_NONE nor RT_JITTER_HASHED");
+    return RT_OK;
+}
+
 // One supersampled frame (or shard strip) of output camera `cam`, sample
 // camera `cn`, into `out_device` on `s`.  A grid of 1 is the plain frame.
+// lens: the same frame through a lens of positive aperture (null: none); a
+// grid of 1 is then one lens ray per pixel.
 int launch_frame_ss(rt_context* ctx, const rt_camera_desc* cam, const rt_camera_desc* cn, const rt_render_options* o,
-                    uint32_t samples, void* out_device, hipStream_t s) {
-    if (samples == 1) return launch_frame(ctx, cam, o, o->shard_index, o->shard_count, out_device, s);
+                    uint32_t samples, void* out_device, hipStream_t s, const rt_lens_desc* lens = nullptr) {
+    if (samples == 1 && !lens) return launch_frame(ctx, cam, o, o->shard_index, o->shard_count, out_device, s);
     RT_HIP(hipSetDevice(ctx->device));
     return launch_precision(ctx, o->precision,
                             {.cam = cn, .depth = o->max_depth, .out_format = o->out_format,
                              .shard_index = o->shard_index, .shard_count = o->shard_count, .out_device = out_device,
                              .stream = s, .flags = o->flags, .samples = samples, .out_w = cam->width,
-                             .out_h = cam->height});
+                             .out_h = cam->height, .lens = lens});
 }
 
 // rt_render's frame into a host buffer; samples != 0: rt_render_supersampled's
-// (cn = the sample camera).
+// (cn = the sample camera), with a lens rt_render_lens's.
 int render_to_host(rt_context* ctx, const rt_camera_desc* cam, const rt_render_options* o, void* out_host,
-                   rt_stats* stats, uint32_t samples, const rt_camera_desc* cn) {
+                   rt_stats* stats, uint32_t samples, const rt_camera_desc* cn, const rt_lens_desc* lens = nullptr) {
     int rc;
     if (!out_host) return set_error(RT_ERR_INVALID, "null output");
     RT_HIP(hipSetDevice(ctx->device));
@@ -2557,7 +2625,7 @@ int render_to_host(rt_context* ctx, const rt_camera_desc* cam, const rt_render_o
     if (o->shard_count > 1) RT_HIP(hipMemsetAsync(ctx->d_scratch.get(), 0, bytes, s));  // strip rows past the canvas
     RT_HIP(hipEventRecord(ctx->ev_start, s));
     tr.step("enqueue before launch");
-    if ((rc = samples ? launch_frame_ss(ctx, cam, cn, o, samples, ctx->d_scratch.get(), s)
+    if ((rc = samples ? launch_frame_ss(ctx, cam, cn, o, samples, ctx->d_scratch.get(), s, lens)
                       : launch_frame(ctx, cam, o, o->shard_index, o->shard_count, ctx->d_scratch.get(), s)))
         return rc;
     tr.step("launch");
@@ -2612,6 +2680,60 @@ int rt_render_supersampled_device(rt_context* ctx, const rt_camera_desc* cam, co
     if (!out_device) return set_error(RT_ERR_INVALID, "null camera or output");
     if (cam->width == 0 || cam->height == 0) return RT_OK;  // empty canvas, as rt_render_device
     return launch_frame_ss(ctx, cam, &cn, o, samples, out_device, static_cast<hipStream_t>(hip_stream));
+}
+
+int rt_render_lens(rt_context* ctx, const rt_camera_desc* cam, const rt_render_options* o, uint32_t samples,
+                   const rt_lens_desc* lens, void* out_host, rt_stats* stats) {
+    if (int rc = check_lens(lens)) return rc;
+    rt_camera_desc cn;
+    if (int rc = check_supersampled(ctx, cam, o, samples, &cn)) return rc;
+    // (aperture 0: every lens point is the pinhole, and the frame is the supersampled one)
+    return render_to_host(ctx, cam, o, out_host, stats, samples, &cn, lens->aperture == 0.0 ? nullptr : lens);
+}
+
+int rt_render_lens_device(rt_context* ctx, const rt_camera_desc* cam, const rt_render_options* o, uint32_t samples,
+                          const rt_lens_desc* lens, void* out_device, void* hip_stream) {
+    if (int rc = check_lens(lens)) return rc;
+    rt_camera_desc cn;
+    if (int rc = check_supersampled(ctx, cam, o, samples, &cn)) return rc;
+    if (!out_device) return set_error(RT_ERR_INVALID, "null camera or output");
+    if (cam->width == 0 || cam->height == 0) return RT_OK;  // empty canvas, as rt_render_device
+    return launch_frame_ss(ctx, cam, &cn, o, samples, out_device, static_cast<hipStream_t>(hip_stream),
+                           lens->aperture == 0.0 ? nullptr : lens);
+}
+
+int rt_lens_ray(const rt_camera_desc* cam, uint32_t n, const rt_lens_desc* lens, uint32_t x, uint32_t y, uint32_t i,
+                uint32_t j, double ray[6]) {
+    if (int rc = check_lens(lens)) return rc;
+    if (!cam || !ray) return set_error(RT_ERR_INVALID, "null argument");
+    if (n < 1 || n > RT_MAX_SAMPLE_GRID || (uint64_t)n * cam->width > 0xFFFFFFFFull ||
+        (uint64_t)n * cam->height > 0xFFFFFFFFull)
+        return set_error(RT_ERR_INVALID, "sample grid " + std::to_string(n) + " outside 1.." +
+                                             std::to_string(RT_MAX_SAMPLE_GRID));
+    if (x >= cam->width || y >= cam->height || i >= n || j >= n)
+        return set_error(RT_ERR_INVALID, "rt_lens_ray: pixel or sample out of range");
+    // The kernels' arithmetic in R = double (rtc_kernels.hip lens_ray).
+    const rt_camera_desc cn = camera_resized(*cam, n * cam->width, n * cam->height);
+    const uint32_t px = n * x + i, py = n * y + j;
+    const double ox = ((double)px + 0.5) * cn.pixel_size, oy = ((double)py + 0.5) * cn.pixel_size;
+    const double wx = cn.half_width - ox, wy = cn.half_height - oy;
+    const double f = lens->focal_distance;
+    double fu = (double)i + 0.5, fv = (double)j + 0.5;
+    if (lens->jitter == RT_JITTER_HASHED)
+        lens_hashed_cell<double>(hash_mix(lens->seed ^ kLensKey), py * (n * cam->width) + px, y * cam->width + x, n, i,
+                                 j, fu, fv);
+    LensPoint<double> lp;
+    lens_point<double>(cn.inverse, lens->aperture, 1.0 / (double)n, fu, fv, lp);
+    const double focal[3] = {wx * f, wy * f, -f};
+    double target[3];
+    lens_xform_point(cn.inverse, focal, target);
+    const double d[3] = {target[0] - lp.origin[0], target[1] - lp.origin[1], target[2] - lp.origin[2]};
+    const double m = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+    for (int q = 0; q < 3; ++q) {
+        ray[q] = lp.origin[q];
+        ray[3 + q] = d[q] / m;
+    }
+    return RT_OK;
 }
 
 int rt_color_at(rt_context* ctx, const double* rays, uint64_t n, uint32_t depth, uint32_t precision, double* out,
@@ -2806,7 +2928,7 @@ int rt_context_set_frames_in_flight(rt_context* ctx, uint32_t frames) {
         const double split = frames > 1 ? 1.5 : 1.0;
         if (!split_knob && m->knobs.split_factor != split) {
             m->knobs.split_factor = split;
-            m->order.valid = m->order_ss.valid = false;  // the next launches rebuild the tile order with it
+            m->order.valid = m->order_ss.valid = m->order_lens.valid = false;  // the next launches rebuild the tile order with it
         }
     }
     return RT_OK;

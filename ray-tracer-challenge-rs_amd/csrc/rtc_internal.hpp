@@ -533,6 +533,57 @@ struct alignas(16) LaunchTerms {
     float head[kPrimaryRectSlots + 4];
 };
 
+// The thin lens of a lens frame (rtc.h "Thin-lens camera"),
+// in the kernel's real type.  `lk` = mix(seed ^ 0x4C454E53), hashed once on
+// the host.  Under RT_JITTER_NONE the lens point of sample (i, j) is the same
+// for every pixel, so the host works all n^2 of them out in the kernel's own
+// operations (lens_points) and the kernels read entry j * n + i with scalar
+// loads: a sample trip is a pinhole frame from a shifted origin.  Under
+// RT_JITTER_HASHED the table is unread and each lane works out its own.
+// The lens kernels (trace_direct_lens, trace_pool_lens) take it as one more
+// argument behind the four table pointers: LaunchParams, which every shipped
+// kernel takes, stays as it is, to the byte.
+constexpr uint32_t kLensKey = 0x4C454E53u;
+template <typename R>
+struct LensPoint {
+    R origin[3];  // inverse * (lx, ly, 0): the ray's origin in world space
+    R lx, ly;     // the lens point in camera space
+};
+template <typename R>
+struct LensParams {
+    R aperture, focal, inv_n;
+    uint32_t jitter, lk;
+    LensPoint<R> points[RT_MAX_SAMPLE_GRID * RT_MAX_SAMPLE_GRID];
+};
+
+// The jitter hash of rtc.h ("Hashed jitter"), uint32_t wraparound.
+RTC_HD inline uint32_t hash_mix(uint32_t x) {
+    x ^= x >> 16;
+    x *= 0x7feb352du;
+    x ^= x >> 15;
+    x *= 0x846ca68bu;
+    x ^= x >> 16;
+    return x;
+}
+
+// Lens cell (ci, cj) and position (ju, jv) in it of sample (i, j) of pixel
+// (x, y) under RT_JITTER_HASHED: `ray_id` the sample's pixel index in the
+// sample camera, `pixel_id` = y * W + x in whole-image coordinates.  One
+// definition for the kernels and rt_lens_ray.
+template <typename R>
+RTC_HD inline void lens_hashed_cell(uint32_t lk, uint32_t ray_id, uint32_t pixel_id, uint32_t n, uint32_t i, uint32_t j,
+                                    R& fu, R& fv) {
+    const uint32_t key = hash_mix(lk ^ ray_id);
+    const R ju = (R)(key >> 8) * (R)0x1p-24;
+    const R jv = (R)(hash_mix(key ^ 0x9E3779B9u) >> 8) * (R)0x1p-24;
+    const uint32_t n2 = n * n;
+    const uint32_t r = hash_mix(lk ^ hash_mix(pixel_id)) % n2;
+    const uint32_t k = (j * n + i + r) % n2;
+    const uint32_t cj = k / n, ci = k - cj * n;
+    fu = (R)ci + ju;
+    fv = (R)cj + jv;
+}
+
 // One launch of the tracer.
 template <typename R>
 struct LaunchParams {
@@ -625,5 +676,10 @@ struct LaunchParams {
 };
 // (the kernels take LaunchParams by value with four table pointers behind it: one 4 KB kernarg segment)
 static_assert(sizeof(LaunchParams<float>) + 4 * sizeof(void*) <= 4096 && sizeof(LaunchParams<double>) + 4 * sizeof(void*) <= 4096);
+// (the lens kernels: LensParams behind the pointers, at this offset of the same segment)
+template <typename R>
+constexpr size_t kLensArgOffset = sizeof(LaunchParams<R>) + 4 * sizeof(void*);
+static_assert(kLensArgOffset<float> % alignof(LensParams<float>) == 0 && kLensArgOffset<double> % alignof(LensParams<double>) == 0);
+static_assert(kLensArgOffset<float> + sizeof(LensParams<float>) <= 4096 && kLensArgOffset<double> + sizeof(LensParams<double>) <= 4096);
 
 }  // namespace rtc

@@ -60,7 +60,7 @@
 #include "jit_options.hpp"
 #include "rtc_context.hpp"
 #include "rtc_jit_cache.hpp"
-#include "rtc_jit_sources.inc"  // kSrcKernels, kSrcInternal, kSrcRtcH, kBuildExtra (tools/embed_sources.py)
+#include "rtc_jit_sources.inc"  // kSrcKernels, kSrcInternal, kSrcRtcH, kSrcSsFrames, kBuildExtra (tools/embed_sources.py)
 
 extern char** environ;
 
@@ -362,7 +362,11 @@ std::vector<float> unit_normals(rt_context* ctx) {
     return out;
 }
 
-const char* kernel_name(bool pool, bool lds, bool ss) {
+const char* kernel_name(bool pool, bool lds, bool ss, bool lens) {
+    if (lens) {  // the lens frame kernels: builds of their own again
+        if (pool) return lds ? "rtc::trace_pool_lens<float, true, false>" : "rtc::trace_pool_lens<float, false, false>";
+        return lds ? "rtc::trace_direct_lens<float, true>" : "rtc::trace_direct_lens<float, false>";
+    }
     if (ss) {  // the supersampled frame kernels: builds of their own, named apart (the disk cache key holds the name)
         if (pool) return lds ? "rtc::trace_pool_ss<float, true, false>" : "rtc::trace_pool_ss<float, false, false>";
         return lds ? "rtc::trace_direct_ss<float, true>" : "rtc::trace_direct_ss<float, false>";
@@ -441,7 +445,8 @@ jitfile::Request make_request(const std::string& scene, const char* name, const 
     jitfile::Request rq;
     rq.name = name;
     rq.main_src = std::string("#define RTC_JIT 1\n#include \"rtc_jit_scene.hpp\"\n") + kSrcKernels;
-    rq.headers = {{"rtc_jit_scene.hpp", scene}, {"rtc_internal.hpp", kSrcInternal}, {"../../include/rtc.h", kSrcRtcH}};
+    rq.headers = {{"rtc_jit_scene.hpp", scene}, {"rtc_internal.hpp", kSrcInternal}, {"../../include/rtc.h", kSrcRtcH},
+                  {"rtc_ss_frames.inc", kSrcSsFrames}};
     // The flags of the static build (Makefile): no contraction beyond the
     // source's explicit fmas, no SLP packing.  Plus no machine-level LICM:
     // with the records as constants it hoists their materialisations (and
@@ -646,7 +651,7 @@ namespace {
 // scratch_max: the B/lane of scratch a pool build may use (direct: none).
 int jit_variant(rt_context* ctx, int variant, bool pool, bool lds, size_t dyn_lds, int static_blocks,
                 hipFunction_t* fn, bool no_skips, int pool_waves, int scratch_max, bool start_only = false,
-                bool ss = false) {
+                bool ss = false, bool lens = false) {
     *fn = nullptr;
     if (ctx->jit.fn[variant]) {
         *fn = ctx->jit.fn[variant];
@@ -689,7 +694,7 @@ int jit_variant(rt_context* ctx, int variant, bool pool, bool lds, size_t dyn_ld
                 make_request(scene_header(ctx->jit.shapes, ctx->jit.begin, ctx->jit.lights, ctx->jit.materials,
                                           ctx->jit.patterns,
                                           ctx->jit.pattern_kinds, ctx->jit.transparent, unit),
-                             kernel_name(pool, lds, ss), device_arch(ctx), &key, no_skips, pool_waves);
+                             kernel_name(pool, lds, ss, lens), device_arch(ctx), &key, no_skips, pool_waves);
             start_build(b, rq, key, sync && !start_only);
         }
     }
@@ -711,8 +716,8 @@ int jit_variant(rt_context* ctx, int variant, bool pool, bool lds, size_t dyn_ld
     // for this world.
     // So does a failed supersampled build (bit 16): its launches fall back to
     // the generic supersampled kernel, and the world's plain frames keep
-    // their per-scene kernels.
-    const bool optional = (variant & (8 | 16)) != 0;
+    // their per-scene kernels.  A lens build (bit 32) likewise.
+    const bool optional = (variant & (8 | 16 | 32)) != 0;
     if (state == 2) {
         (optional ? ctx->jit.rejected[variant] : ctx->jit.failed) = true;
         ctx->jit.log = b->log;
@@ -764,7 +769,7 @@ int jit_variant(rt_context* ctx, int variant, bool pool, bool lds, size_t dyn_ld
     if (std::string v; ss && pool && debug_knob("jit_ss_scratch", &v)) scratch_max = std::atoi(v.c_str());
     if (blocks < static_blocks || scratch > (pool ? scratch_max : 0)) {
         ctx->jit.rejected[variant] = true;
-        ctx->jit.log = std::string("per-scene ") + (ss ? "supersampled " : "") + (pool ? "pool" : "direct") +
+        ctx->jit.log = std::string("per-scene ") + (lens ? "lens " : ss ? "supersampled " : "") + (pool ? "pool" : "direct") +
                        " kernel not used: " +
                        std::to_string(blocks) + " workgroups/CU (generic " + std::to_string(static_blocks) + "), " +
                        std::to_string(scratch) + " B/lane of scratch";
@@ -777,16 +782,16 @@ int jit_variant(rt_context* ctx, int variant, bool pool, bool lds, size_t dyn_ld
 }  // namespace
 
 int jit_function(rt_context* ctx, bool pool, bool lds, size_t dyn_lds, int static_blocks, hipFunction_t* fn,
-                 bool no_skips, int* pool_waves, bool ss) {
+                 bool no_skips, int* pool_waves, bool ss, bool lens) {
     *fn = nullptr;
     if (pool_waves) *pool_waves = 0;
     if (ctx->jit.failed || ctx->jit.shapes.empty()) return RT_OK;
-    const int variant = (ss ? 16 : 0) + (no_skips ? 4 : 0) + (pool ? 2 : 0) + (lds ? 1 : 0);
-    if (!pool) return jit_variant(ctx, variant, pool, lds, dyn_lds, static_blocks, fn, no_skips, 0, 0, false, ss);
-    // (the supersampled pool kernel: the static occupancy's build alone)
+    const int variant = (lens ? 32 : 0) + (ss ? 16 : 0) + (no_skips ? 4 : 0) + (pool ? 2 : 0) + (lds ? 1 : 0);
+    if (!pool) return jit_variant(ctx, variant, pool, lds, dyn_lds, static_blocks, fn, no_skips, 0, 0, false, ss, lens);
+    // (the supersampled and the lens pool kernels: the static occupancy's build alone)
     if (ss)
         return jit_variant(ctx, variant, pool, lds, dyn_lds, static_blocks, fn, no_skips, 0, kPoolSsScratchMax, false,
-                           ss);
+                           ss, lens);
     // The pool kernel at 7 waves/SIMD (jit_options.hpp) and, compiled beside
     // it, at the static build's occupancy: a 7-wave build that spills more
     // than kPool7ScratchMax is refused and the other is taken (also while the

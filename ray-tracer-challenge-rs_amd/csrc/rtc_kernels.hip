@@ -2554,6 +2554,47 @@ __device__ inline void camera_ray(const CameraRec<R>& c, uint32_t x, uint32_t y,
     }
 }
 
+// rtc.h "Thin-lens camera" (DESIGN.md §3.14): sample (i, j) of pixel (x, y) of
+// a lens frame of grid n (wave-uniform).  P.cam is the sample camera; y is the
+// whole-image row, L the launch's lens.  The ray leaves the lens point and passes through the
+// pinhole ray's point F on the focal plane.  RT_JITTER_NONE (a wave-uniform
+// branch): L and inverse * L are sample (i, j)'s entry of the launch's table,
+// scalar loads, and what is left per lane is camera_ray's work with one more
+// multiply per axis.  RT_JITTER_HASHED: the lane's own cell and lens point.
+template <typename R>
+__device__ inline void lens_ray(const LaunchParams<R>& P, const LensParams<R>& L, uint32_t n, uint32_t x, uint32_t y,
+                                uint32_t i, uint32_t j, V3<R>& o, V3<R>& d) {
+    const CameraRec<R>& c = P.cam;
+    const uint32_t px = n * x + i, py = n * y + j;
+    const R ox = ((R)px + (R)0.5) * c.pixel_size;
+    const R oy = ((R)py + (R)0.5) * c.pixel_size;
+    const R wx = c.half_width - ox;
+    const R wy = c.half_height - oy;
+    const R f = L.focal;
+    R lx, ly;
+    if (L.jitter == RT_JITTER_NONE) {
+        const LensPoint<R>& q = L.points[j * n + i];
+        o = {q.origin[0], q.origin[1], q.origin[2]};
+        lx = q.lx;
+        ly = q.ly;
+    } else {
+        R fu, fv;
+        lens_hashed_cell<R>(L.lk, py * (n * P.width) + px, y * P.width + x, n, i, j, fu, fv);
+        const R a = (R)2 * (fu * L.inv_n) - (R)1, b = (R)2 * (fv * L.inv_n) - (R)1;
+        const R ex = a * Real<R>::sqrt((R)1 - (b * b) * (R)0.5), ey = b * Real<R>::sqrt((R)1 - (a * a) * (R)0.5);
+        lx = L.aperture * ex;
+        ly = L.aperture * ey;
+        o = xform_point(c.inv, V3<R>{lx, ly, (R)0});
+    }
+    if constexpr (sizeof(R) == 4) {
+        // target - origin == M3 * (F - L): skip the cancelling translation
+        d = normalized(xform_vector(c.inv, V3<R>{wx * f - lx, wy * f - ly, -f}));
+    } else {
+        const V3<R> target = xform_point(c.inv, V3<R>{wx * f, wy * f, -f});
+        d = normalized(vsub(target, o));
+    }
+}
+
 template <typename R>
 __device__ inline void store_pixel(const LaunchParams<R>& P, uint64_t idx, V3<R> c) {
     if (P.out_format == RT_OUT_U8) {
@@ -2829,6 +2870,15 @@ __device__ inline const LaunchParams<R>& kernarg_params() {
     auto k = __builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(k));
     return *(const LaunchParams<R>*)k;  // address-space cast (constant -> generic)
+}
+
+// The lens of a lens kernel, re-read from the same segment in the same way
+// (its last argument, behind the four table pointers).
+template <typename R>
+__device__ inline const LensParams<R>& kernarg_lens() {
+    auto k = __builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(k));
+    return *(const LensParams<R>*)((const char*)k + kLensArgOffset<R>);
 }
 
 #define RTC_WORLD_PARAMS(R)                                                                                  \
@@ -3304,219 +3354,22 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(sizeof(R
 #ifndef RTC_DIRECT_SS_WAVES
 #define RTC_DIRECT_SS_WAVES 8
 #endif
-template <typename R, bool kLds>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(sizeof(R) == 4 ? RTC_DIRECT_SS_WAVES : 1))) void trace_direct_ss(
-    LaunchParams<R> P, RTC_WORLD_PARAMS(R)) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    (void)scene_view<R, kLds>(P, shapes, materials, patterns, lights, smem, true);
-    Counts k = {};
-    const uint32_t tid = threadIdx.x;
-    for (uint32_t t = blockIdx.x;; t += gridDim.x) {  // (tiles as in trace_direct)
-        const LaunchParams<R>& P = kernarg_params<R>();
-        const DevScene<R> sc = scene_view<R, kLds>(P, shapes, materials, patterns, lights, smem);
-        if (t >= P.n_tiles) break;
-        uint32_t x, y;
-        uint64_t out_idx;
-        const bool valid = tile_pixel(P, t, tid, x, y, out_idx);
-        const uint32_t n = __builtin_amdgcn_readfirstlane(P.ss_grid);
-        V3<R> c = {(R)0, (R)0, (R)0};
-        for (uint32_t j = 0; j < n; ++j) {
-            for (uint32_t i = 0; i < n; ++i) {
-                Shaded<R> sh;
-                bool hit = false;
-                if (valid) {
-                    V3<R> o, d;
-                    camera_ray(P.cam, n * x + i, n * y + j, o, d);
-#if RTC_AREA_LIGHTS
-                    sh.ray_id = (n * y + j) * (n * P.width) + n * x + i;
-                    if (shade_ray<R, false>(sc, o, d, P.max_depth, sh)) {
-#else
-                    if (shade_ray<R, false>(sc, o, d, 0, sh)) {
-#endif
-                        hit = true;
-                        c = {c.x + sh.surface.x, c.y + sh.surface.y, c.z + sh.surface.z};
-                    }
-                }
-                count_events(k, valid, hit, sh, sc.n_lights);
-            }
-        }
-        const R inv = (R)1 / (R)(n * n);
-        if (valid) store_pixel(P, out_idx, V3<R>{c.x * inv, c.y * inv, c.z * inv});
-    }
-    if (!(P.flags & RT_FLAG_NO_COUNTERS)) flush_counts(k, P.counters);
-}
-
-// trace_pool_ss: trace_pool with n^2 seedings per item.  The item loop, the
-// accumulators, generations, split parts, priorities and cost stamps are
-// trace_pool's; a sample is one more batch of the item's pixels, seeded at
-// weight R(1) / R(n^2) and remaining = max_depth into the same fixed-point
-// sums, which are order-independent, so the frame stays bit-deterministic.
-// The weights of a pixel's samples sum to 1: the brightness bound behind
-// acc_log2 and check_pixel_range is that of a plain frame.
-// Seeding rule: sample s + 1 is seeded when the pool has drained.  The pool
-// then never holds rays of two samples, and its bound is the plain frame's
-// (rtc_internal.hpp pool_capacity_ss, with the proof).  The price is the
-// thin generations at the end of each sample's tree instead of the item's.
-// A tile's recorded cost is its whole n^2-sample duration.
-template <typename R, bool kLds, bool kDup>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(sizeof(R) == 4 ? RTC_POOL_WAVES : 1))) void trace_pool_ss(
-    LaunchParams<R> P, RTC_WORLD_PARAMS(R)) {
-    extern __shared__ __align__(16) unsigned char smem_all[];
-    const DevScene<R> sc = scene_view<R, kLds>(P, shapes, materials, patterns, lights, smem_all, true);
-    unsigned char* smem = smem_all + (kLds ? P.world_lds : 0);
-    __shared__ unsigned int s_tile[2];
-    __shared__ int s_top[2];
-    const uint32_t cap = P.pool_capacity;
-    const uint32_t lcap = P.pool_lds_capacity, gcap = cap - lcap;
-    Pool<R> pl;
-    pl.acc = reinterpret_cast<PoolAcc<R>*>(smem);
-    pl.lds = reinterpret_cast<R*>(smem + 3 * kBlock * sizeof(PoolAcc<R>));
-    const float acc_scale = __builtin_ldexpf(1.0f, (int)P.acc_log2);
-    pl.lds_cap = (int)lcap;
-    pl.spill = reinterpret_cast<R*>(P.spill) + spill_word(blockIdx.x, gcap, lcap, lcap);
-    pl.spill_cap = (int)gcap;
-#ifdef RTC_BOUNDS_CHECK
-    pl.err = P.error_flag;
-    if (!in_bounds(gcap == 0 || blockIdx.x < P.spill_blocks, P.error_flag, kErrBoundsSpill)) pl.spill_cap = 0;
-#endif
-
-    Counts k = {};
-    const uint32_t tid = threadIdx.x;
-    // (the queue heads alternate between dynamic launches as in trace_pool)
-    if (P.persistent == kSchedDynamic && blockIdx.x == 0 && tid < (uint32_t)kTileQueues)
-        P.next_tile_counter[tid * kQueueStride] = 0ull;
-    uint32_t probe = 0;
-    const uint32_t n_items = P.item_count && tid == 0 ? *P.item_count : P.n_tiles;
-    const uint32_t n = __builtin_amdgcn_readfirstlane(P.ss_grid), n2 = n * n;
-    const R seed_w = (R)1 / (R)n2;
-    unsigned long long tile_start = 0;  // thread 0: s_memrealtime at the tile's start
-    for (uint32_t it = 0;; ++it) {
-        if (tid == 0) {
-            s_tile[it & 1] = next_tile(P, it, probe, n_items);
-            s_top[0] = 0;
-            tile_start = __builtin_amdgcn_s_memrealtime();
-        }
-        for (int c = 0; c < 3; ++c) pl.acc[c * kBlock + tid] = 0;
-        __syncthreads();
-        const uint32_t item = __builtin_amdgcn_readfirstlane(s_tile[it & 1]);
-        if (item == kNoItem) break;
-        const WorkItem wi = decode_item(item, P.tile_order != nullptr);
-        const uint32_t t = wi.tile, split = wi.split_log2;
-#ifdef RTC_BOUNDS_CHECK
-        if (!in_bounds(t < P.n_tiles, P.error_flag, kErrBoundsTile)) continue;  // (every thread: uniform)
-#endif
-        const uint32_t prio = wi.prio;
-        if (prio) set_wave_prio(prio);
-        // This thread's pixel, if it is on the canvas and in this item's part
-        // of the tile (all of it unless split).  Worked out from the thread
-        // index at each seeding and at the store: the opaque copy keeps the
-        // compiler from hoisting the pixel, its sample coordinates and their
-        // conversions above the generations, where they would be held in
-        // VGPRs through every tree (reflect_refract's per-scene build: 56
-        // B/lane of scratch held, 44 this way).
-        // The generic build is the other way round: worked out once per item
-        // and held it takes 36-56 B/lane, recomputed 92-112 (with or without
-        // the opaque copy), so it keeps trace_pool's way.
-#ifdef RTC_JIT
-        auto pixel = [&](uint32_t& x, uint32_t& y, uint64_t& out_idx) {
-            uint32_t lane = tid;
-            asm volatile("" : "+v"(lane));
-            return tile_pixel(P, t, lane, x, y, out_idx) && item_seeds(lane, wi);
-        };
-#else
-        uint32_t x, y;
-        uint64_t out_idx;
-        const bool valid = tile_pixel(P, t, tid, x, y, out_idx) && item_seeds(tid, wi);
-#endif
-        // One sample after the other, j outer and i inner: its seeds enter a
-        // drained pool (s_top[0] = 0: set with the item, and below once the
-        // sample before has run out), then its generations run as trace_pool's.
-        for (uint32_t sample = 0; sample < n2; ++sample) {
-            if (sample) {
-                // (the generations end on s_top[gen & 1] == 0; s_top[0] may hold
-                // an older size.  Every thread has read the top it left on.)
-                if (tid == 0) s_top[0] = 0;
-                __syncthreads();
-            }
-            {
-                const uint32_t j = sample / n, i = sample - j * n;
-#ifdef RTC_JIT
-                uint32_t x, y;
-                uint64_t out_idx;
-                const bool valid = pixel(x, y, out_idx);
-#endif
-                V3<R> o, d;
-                if (valid) camera_ray(P.cam, n * x + i, n * y + j, o, d);
-                k.c[0] += wave_count(valid);
-                const int slot = wave_reserve(valid, &s_top[0]);
-                if (valid) pool_put(pl, slot, o, d, seed_w, tid | (P.max_depth << 8));
-            }
-            __syncthreads();
-            for (uint32_t gen = 0;; ++gen) {
-                const int cur = gen & 1;
-                const int size = s_top[cur];
-                if (size == 0) break;
-                const int kpop = size < (int)P.pop_batch ? size : (int)P.pop_batch;
-                const int bottom = size - kpop;
-                const bool active = (int)tid < kpop;
-                V3<R> ro, rd;
-                R rw = (R)0;
-                uint32_t meta = 0;
-                if (active) pool_get(pl, bottom + (int)tid, ro, rd, rw, meta);
-                if (tid == 0) s_top[cur ^ 1] = bottom;
-                __syncthreads();  // every lane holds its ray; the next top is set
-                Shaded<R> sh;
-                bool hit = false;
-                const uint32_t pix = meta & 0xFFu;
-                const uint32_t child_meta = pix | (((meta >> 8) - 1u) << 8);
-                auto push = [&](V3<R> co, V3<R> cd, R cw) {
-                    const int slot = wave_reserve(true, &s_top[cur ^ 1]);
-                    if (slot < (int)cap) pool_put(pl, slot, co, cd, rw * cw, child_meta);
-                    else atomicOr(P.error_flag, kErrPoolOverflow);
-                };
-#if RTC_AREA_LIGHTS
-                // (one sample's rays at a time in the pool: the sample is the loop's, the pixel the entry's)
-                sh.ray_id = sample_ray_id(P, t, pix, n, sample - (sample / n) * n, sample / n);
-#endif
-                if (active) hit = shade_ray<R, true, kDup>(sc, ro, rd, meta >> 8, sh, push);
-                count_events(k, false, hit, sh, sc.n_lights);
-                if (hit) {
-                    acc_add(pl.acc, pix, sh.surface.x * rw, acc_scale);
-                    acc_add(pl.acc + kBlock, pix, sh.surface.y * rw, acc_scale);
-                    acc_add(pl.acc + 2 * kBlock, pix, sh.surface.z * rw, acc_scale);
-                }
-                __syncthreads();  // pushes complete before the next pop
-                if (s_top[cur ^ 1] > (int)cap) {  // overflowed: drop the pool (error already flagged)
-                    __syncthreads();
-                    if (tid == 0) s_top[cur ^ 1] = 0;
-                    __syncthreads();
-                }
-            }
-        }
-        const double inv = sizeof(PoolAcc<R>) == 4 ? __builtin_ldexp(1.0, -(int)P.acc_log2) : kAccInvScale;
-        const V3<R> c = {(R)((double)pl.acc[tid] * inv), (R)((double)pl.acc[kBlock + tid] * inv),
-                         (R)((double)pl.acc[2 * kBlock + tid] * inv)};
-#ifdef RTC_JIT
-        uint32_t x, y;
-        uint64_t out_idx;
-        const bool valid = pixel(x, y, out_idx);
-#endif
-        bool store = valid;
-#ifdef RTC_BOUNDS_CHECK
-        store &= in_bounds(!valid || out_idx < (uint64_t)(P.image_rows ? P.height : P.tile_rows * RT_TILE_H) * P.width,
-                           P.error_flag, kErrBoundsOut);
-#endif
-        if (store) store_pixel(P, out_idx, c);
-        if (prio) __builtin_amdgcn_s_setprio(0);
-        __syncthreads();  // accumulators are re-zeroed for the next tile
-        if (tid == 0 && P.tile_cost) {  // (as trace_pool: a split tile's slowest part times the parts)
-            const uint32_t c = (uint32_t)min(__builtin_amdgcn_s_memrealtime() - tile_start, 0x0FFFFFFFull);
-            if (split) atomicMax(&P.tile_cost[t], c << split);
-            else P.tile_cost[t] = c;
-        }
-    }
-    if (!(P.flags & RT_FLAG_NO_COUNTERS)) flush_counts(k, P.counters);
-}
+// The bodies are rtc_ss_frames.inc, compiled twice: as they were, and with
+// lens_ray in camera_ray's place (rt_render_lens*).
+#define RTC_SS_DIRECT trace_direct_ss
+#define RTC_SS_POOL trace_pool_ss
+#define RTC_SS_LENS 0
+#include "rtc_ss_frames.inc"
+#undef RTC_SS_DIRECT
+#undef RTC_SS_POOL
+#undef RTC_SS_LENS
+#define RTC_SS_DIRECT trace_direct_lens
+#define RTC_SS_POOL trace_pool_lens
+#define RTC_SS_LENS 1
+#include "rtc_ss_frames.inc"
+#undef RTC_SS_DIRECT
+#undef RTC_SS_POOL
+#undef RTC_SS_LENS
 
 #ifndef RTC_JIT  // ray batches run the generic build only: per-scene sources stop here
 // Waves per SIMD the f32 ray-batch kernel is register-limited to.  Left to
@@ -3959,50 +3812,65 @@ template hipError_t launch_trace_rays<double>(const LaunchParams<double>&, bool,
 template hipError_t occupancy_rays<double>(bool, size_t, int*);
 #endif
 
-// The supersampled frame kernels (trace_direct_ss, trace_pool_ss): the
+// The supersampled frame kernels (trace_direct_ss, trace_pool_ss) and, with
+// `lens`, the lens frame kernels (trace_direct_lens, trace_pool_lens): the
 // all-kinds builds only.
 template <typename R>
-hipError_t launch_trace_ss(const LaunchParams<R>& P, bool pool, bool dup, uint32_t grid, size_t dyn_lds,
-                           hipStream_t stream) {
+hipError_t launch_trace_ss(const LaunchParams<R>& P, bool pool, bool dup, const LensParams<R>* lens, uint32_t grid,
+                           size_t dyn_lds, hipStream_t stream) {
     (void)hipGetLastError();  // see launch_trace
     const bool lds = P.world_lds != 0;
-#define RTC_LAUNCH(K, ...)                                                                                \
-    hipLaunchKernelGGL((K<R, __VA_ARGS__>), dim3(grid), dim3(kBlock), dyn_lds, stream, P, P.scene.shapes,         \
-                       P.scene.materials, P.scene.patterns, P.scene.lights)
-    if (pool) {
-        if (lds) {
-            if (dup) RTC_LAUNCH(trace_pool_ss, true, true);
-            else RTC_LAUNCH(trace_pool_ss, true, false);
-        } else {
-            if (dup) RTC_LAUNCH(trace_pool_ss, false, true);
-            else RTC_LAUNCH(trace_pool_ss, false, false);
-        }
-    } else {
-        if (lds) RTC_LAUNCH(trace_direct_ss, true);
-        else RTC_LAUNCH(trace_direct_ss, false);
+#define RTC_LAUNCH_FRAME(DIRECT, POOL, ...)                      \
+    if (pool) {                                                 \
+        if (lds) {                                              \
+            if (dup) RTC_LAUNCH((POOL<R, true, true>), __VA_ARGS__);  \
+            else RTC_LAUNCH((POOL<R, true, false>), __VA_ARGS__);     \
+        } else {                                                \
+            if (dup) RTC_LAUNCH((POOL<R, false, true>), __VA_ARGS__); \
+            else RTC_LAUNCH((POOL<R, false, false>), __VA_ARGS__);    \
+        }                                                       \
+    } else {                                                    \
+        if (lds) RTC_LAUNCH((DIRECT<R, true>), __VA_ARGS__);    \
+        else RTC_LAUNCH((DIRECT<R, false>), __VA_ARGS__);       \
     }
+    if (lens) {
+#define RTC_LAUNCH(K, ...)                                                                              \
+    hipLaunchKernelGGL(K, dim3(grid), dim3(kBlock), dyn_lds, stream, P, P.scene.shapes, P.scene.materials, \
+                       P.scene.patterns, P.scene.lights, __VA_ARGS__)
+        RTC_LAUNCH_FRAME(trace_direct_lens, trace_pool_lens, *lens)
 #undef RTC_LAUNCH
+    } else {
+#define RTC_LAUNCH(K, ...)                                                                              \
+    hipLaunchKernelGGL(K, dim3(grid), dim3(kBlock), dyn_lds, stream, P, P.scene.shapes, P.scene.materials, \
+                       P.scene.patterns, P.scene.lights)
+        RTC_LAUNCH_FRAME(trace_direct_ss, trace_pool_ss, 0)
+#undef RTC_LAUNCH
+    }
+#undef RTC_LAUNCH_FRAME
     return hipGetLastError();
 }
 
 template <typename R>
-hipError_t occupancy_ss(bool pool, bool lds, size_t dyn_lds, int* blocks_per_cu) {
-    if (pool)
-        return lds ? hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, trace_pool_ss<R, true, false>, kBlock,
-                                                                  dyn_lds)
-                   : hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, trace_pool_ss<R, false, false>,
-                                                                  kBlock, dyn_lds);
-    return lds ? hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, trace_direct_ss<R, true>, kBlock, dyn_lds)
-               : hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, trace_direct_ss<R, false>, kBlock,
-                                                              dyn_lds);
+hipError_t occupancy_ss(bool pool, bool lds, bool lens, size_t dyn_lds, int* blocks_per_cu) {
+#define RTC_OCCUPANCY(K) hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, K, kBlock, dyn_lds)
+    if (lens) {
+        if (pool)
+            return lds ? RTC_OCCUPANCY((trace_pool_lens<R, true, false>)) : RTC_OCCUPANCY((trace_pool_lens<R, false, false>));
+        return lds ? RTC_OCCUPANCY((trace_direct_lens<R, true>)) : RTC_OCCUPANCY((trace_direct_lens<R, false>));
+    }
+    if (pool) return lds ? RTC_OCCUPANCY((trace_pool_ss<R, true, false>)) : RTC_OCCUPANCY((trace_pool_ss<R, false, false>));
+    return lds ? RTC_OCCUPANCY((trace_direct_ss<R, true>)) : RTC_OCCUPANCY((trace_direct_ss<R, false>));
+#undef RTC_OCCUPANCY
 }
 #if RTC_PRECISION != 2
-template hipError_t launch_trace_ss<float>(const LaunchParams<float>&, bool, bool, uint32_t, size_t, hipStream_t);
-template hipError_t occupancy_ss<float>(bool, bool, size_t, int*);
+template hipError_t launch_trace_ss<float>(const LaunchParams<float>&, bool, bool, const LensParams<float>*, uint32_t, size_t,
+                                           hipStream_t);
+template hipError_t occupancy_ss<float>(bool, bool, bool, size_t, int*);
 #endif
 #if RTC_PRECISION != 1
-template hipError_t launch_trace_ss<double>(const LaunchParams<double>&, bool, bool, uint32_t, size_t, hipStream_t);
-template hipError_t occupancy_ss<double>(bool, bool, size_t, int*);
+template hipError_t launch_trace_ss<double>(const LaunchParams<double>&, bool, bool, const LensParams<double>*, uint32_t,
+                                            size_t, hipStream_t);
+template hipError_t occupancy_ss<double>(bool, bool, bool, size_t, int*);
 #endif
 
 #if RTC_PRECISION != 2 && !RTC_INSTANCES

@@ -29,6 +29,7 @@ __all__ = [
     "camera_resize", "camera_set_transform", "camera_bound_rect", "load_scene", "load_scene_text", "SceneTables", "Context", "shard_rows",
     "load_obj", "Mesh", "SmoothDesc", "RT_SMOOTH_SHAPES", "RT_OBJ_NORMALS", "RT_NO_NORMAL",
     "AreaLightDesc", "RT_LIGHT_MAX_STEPS", "RT_JITTER_NONE", "RT_JITTER_HASHED", "area_light_sample",
+    "LensDesc", "Lens", "lens_ray",
     "UVDesc", "TextureDesc", "RT_OBJ_TEXCOORDS", "RT_NO_TEXCOORD", "TEXTURE_FILTERS", "read_image",
     "RT_DEFAULT_MAX_DEPTH", "RT_TILE_H", "RT_TILE_W",
 ]
@@ -204,6 +205,10 @@ class AreaLightDesc(C.Structure):
                 ("jitter", C.c_uint32), ("seed", C.c_uint32)]
 
 
+class LensDesc(C.Structure):
+    _fields_ = [("aperture", C.c_double), ("focal_distance", C.c_double), ("jitter", C.c_uint32), ("seed", C.c_uint32)]
+
+
 class LightInfo(C.Structure):
     _fields_ = [("area_lights", C.c_uint32), ("samples", C.c_uint32), ("ran_area", C.c_uint32),
                 ("reserved", C.c_uint32), ("area_bytes", C.c_uint64)]
@@ -321,6 +326,12 @@ def _load() -> C.CDLL:
                                           C.c_uint32]),
         "rt_lights_expand": (C.c_int, [P(LightDesc), C.c_uint32, P(AreaLightDesc), C.c_uint32, P(LightDesc),
                                        P(C.c_uint32)]),
+        "rt_render_lens": (C.c_int, [C.c_void_p, P(CameraDesc), P(RenderOptions), C.c_uint32, P(LensDesc), C.c_void_p,
+                                     P(Stats)]),
+        "rt_render_lens_device": (C.c_int, [C.c_void_p, P(CameraDesc), P(RenderOptions), C.c_uint32, P(LensDesc),
+                                            C.c_void_p, C.c_void_p]),
+        "rt_lens_ray": (C.c_int, [P(CameraDesc), C.c_uint32, P(LensDesc), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                  P(C.c_double)]),
         "rt_area_light_sample": (C.c_int, [P(AreaLightDesc), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                            P(C.c_double)]),
         "rt_scene_light_info": (C.c_int, [C.c_void_p, P(LightInfo)]),
@@ -395,6 +406,7 @@ EXPORTED_SYMBOLS = (
     "rt_scene_upload_textured", "rt_uv_expand", "rt_scene_texture_info", "rt_mesh_texcoords_get", "rt_mesh_uvs",
     "rt_image_read", "rt_image_free",
     "rt_scene_upload_lit", "rt_lights_expand", "rt_area_light_sample", "rt_scene_light_info",
+    "rt_render_lens", "rt_render_lens_device", "rt_lens_ray",
 )
 
 
@@ -497,6 +509,21 @@ def read_image(path) -> np.ndarray:
         return np.ctypeslib.as_array(rgb, (h.value, w.value, 3)).copy()
     finally:
         _lib.rt_image_free(rgb)
+
+
+def Lens(aperture: float, focal_distance: float, jitter: bool = False, seed: int = 0) -> "LensDesc":
+    """A thin lens (rtc.h rt_lens_desc): its radius and the focal plane's distance along the view axis, both in
+    camera space; jitter False = cell centres (RT_JITTER_NONE), True = hashed per sample with `seed`."""
+    return LensDesc(float(aperture), float(focal_distance), RT_JITTER_HASHED if jitter else RT_JITTER_NONE,
+                    int(seed) & 0xFFFFFFFF)
+
+
+def lens_ray(camera: "CameraDesc", grid: int, lens: "LensDesc", x: int, y: int, i: int, j: int) -> np.ndarray:
+    """rt_lens_ray: the f64 ray (origin, direction) of sample (i, j) of pixel (x, y) of a lens frame of the
+    output camera `camera`, for either jitter mode."""
+    ray = (C.c_double * 6)()
+    _check(_lib.rt_lens_ray(C.byref(camera), grid, C.byref(lens), x, y, i, j, ray))
+    return np.array(ray[:], dtype=np.float64)
 
 
 def area_light_sample(desc: "AreaLightDesc", area_index: int, ray_id: int, remaining: int, k: int) -> np.ndarray:
@@ -1031,6 +1058,37 @@ class Context:
         opts = self.options(depth, precision, out_format, shard, flags)
         _check(_lib.rt_render_supersampled_device(self._h, C.byref(camera), C.byref(opts), grid,
                                                   C.c_void_p(out_ptr or 0), C.c_void_p(stream_ptr or 0)))
+
+    def render_lens(self, camera: CameraDesc, grid: int, lens: "LensDesc", depth: int = RT_DEFAULT_MAX_DEPTH,
+                    precision: str = "f32", out_format: str = "real", shard=(0, 1),
+                    out: np.ndarray | None = None, flags: int = 0):
+        """render_supersampled() through a thin lens (rtc.h rt_render_lens): sample (i, j) of a pixel leaves its
+        point of the lens disc and passes through the pinhole ray's point on the focal plane.  An aperture of 0
+        is render_supersampled(); grid 1 is one lens point per pixel (accumulate frames over seeds)."""
+        opts = self.options(depth, precision, out_format, shard, flags)
+        rows = camera.height if shard[1] == 1 else shard_rows(camera.height, shard[1])
+        dtype = np.uint8 if out_format == "u8" else (np.float32 if precision == "f32" else np.float64)
+        if out is not None:
+            if out.shape != (rows, camera.width, 3) or out.dtype != dtype or not out.flags.c_contiguous:
+                raise ValueError(f"out must be a C-contiguous {dtype.__name__} array of shape {(rows, camera.width, 3)}")
+            img = out
+        else:
+            img = np.zeros((rows, camera.width, 3), dtype=dtype)
+        st = Stats()
+        _check(_lib.rt_render_lens(self._h, C.byref(camera), C.byref(opts), grid,
+                                   None if lens is None else C.byref(lens), img.ctypes.data_as(C.c_void_p),
+                                   C.byref(st)))
+        return img, st.as_dict()
+
+    def render_lens_device(self, camera: CameraDesc, grid: int, lens: "LensDesc", out_ptr: int,
+                           stream_ptr: int | None = None, depth: int = RT_DEFAULT_MAX_DEPTH, precision: str = "f32",
+                           out_format: str = "real", shard=(0, 1), flags: int = 0) -> None:
+        """render_supersampled_device() through a thin lens (rtc.h rt_render_lens_device): the W x H x 3 buffer
+        of the output camera, asynchronous on the stream."""
+        opts = self.options(depth, precision, out_format, shard, flags)
+        _check(_lib.rt_render_lens_device(self._h, C.byref(camera), C.byref(opts), grid,
+                                          None if lens is None else C.byref(lens), C.c_void_p(out_ptr or 0),
+                                          C.c_void_p(stream_ptr or 0)))
 
     def color_at(self, rays, depth: int = RT_DEFAULT_MAX_DEPTH, precision: str = "f32"):
         """Batched World::color_at: rays (n, 6) = origin, direction -> colours (n, 3) f64.  In a world with

@@ -13,14 +13,15 @@ T=$(mktemp -d)
 trap 'rm -rf "$T"' EXIT
 mkdir -p "$T/a/b" "$T/include"
 cp "$HPP" "$T/a/b/rtc_jit_scene.hpp"
-cp "$ROOT/ray-tracer-challenge-rs_amd/csrc/rtc_internal.hpp" "$T/a/b/"
+cp "$ROOT/ray-tracer-challenge-rs_amd/csrc/rtc_internal.hpp" "$ROOT/ray-tracer-challenge-rs_amd/csrc/rtc_ss_frames.inc" "$T/a/b/"
 cp "$ROOT/include/rtc.h" "$T/include/"
 EXTRA_DEF=
 KERNEL=${JIT_KERNEL:-"trace_pool<float, true, false>"}
 case "$HPP" in *_direct.hpp) EXTRA_DEF=-DRTC_JIT_FENCE_EVERY=3; KERNEL=${JIT_KERNEL:-"trace_direct<float, false>"} ;; esac
+LENS_ARG=; case "$KERNEL" in *_lens*) LENS_ARG=", LensParams<float>" ;; esac  # (the lens kernels' last argument)
 # hipRTC instantiates the kernel from its name expression; here explicitly
 { printf '#define RTC_JIT 1\n#include "rtc_jit_scene.hpp"\n'; cat "$ROOT/ray-tracer-challenge-rs_amd/csrc/rtc_kernels.hip"
-  printf '\nnamespace rtc {\ntemplate __global__ void %s(LaunchParams<float>, RTC_WORLD_PARAMS(float));\n}\n' "$KERNEL"; } > "$T/a/b/k.hip"
+  printf '\nnamespace rtc {\ntemplate __global__ void %s(LaunchParams<float>, RTC_WORLD_PARAMS(float)%s);\n}\n' "$KERNEL" "$LENS_ARG"; } > "$T/a/b/k.hip"
 /opt/rocm/bin/hipcc -O3 -std=c++20 --offload-arch=gfx950 -ffp-contract=off -fno-slp-vectorize \
     -mllvm -disable-machine-licm $EXTRA_DEF "$@" --cuda-device-only -S -o "$OUT" "$T/a/b/k.hip"
 python3 - "$OUT" <<'PY'
