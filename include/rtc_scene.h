@@ -203,6 +203,18 @@ int rt_camera_shadow_rect(const rt_camera_desc* camera, const float plane[4], co
  * lies in those columns or in those rows.  Host only. */
 int rt_camera_shadow_near(const rt_camera_desc* camera, const float plane[4], const float light[3], uint32_t span[4]);
 
+/* The primary cull of the same kernel for planes: `planes` holds row 1 of
+ * each plane record's f32 inverse, four floats a plane ({n, d}: object
+ * y = n . x + d), `n_planes` of them (1 to 8).  The inclusive rectangle
+ * {x0, y0, x1, y1} holds every pixel at which plane `q`'s entry can be the
+ * nearest of those planes' entries in front of the eye, as the f32 kernel
+ * evaluates them; outside it the entry lies behind the eye or another
+ * plane's is nearer by a margin no rounding of the kernel's crosses.  The
+ * whole canvas where no cull applies; x0 > x1 where the plane is never the
+ * nearest.  What a frame's launch works out per plane slot.  Host only. */
+int rt_camera_plane_rect(const rt_camera_desc* camera, const float* planes, uint32_t n_planes, uint32_t q,
+                         uint32_t rect[4]);
+
 /* Matrix<4>::inverse, row-major 16 doubles. */
 int rt_matrix_inverse(const double m[16], double out[16]);
 

@@ -392,4 +392,207 @@ inline bool shadow_self_clear(const CameraRec<float>& cam, const float n[3], flo
     const double over_max = 3e-6 * (1.0 + omax + std::fabs(ye) * nn / 8e-8);  // (t in object units of y)
     return over_max <= 1e3 * std::fabs(yl);
 }
+
+// The primary cull of a plane (rtc_kernels.hip closest_hit, RTC_PLANE_RECTS):
+// the rectangle outside which plane q cannot be the nearest entry of a primary
+// ray, because its own entry lies behind the origin or because another
+// plane's entry in front is nearer.  Both questions are linear in the pixel.
+//
+// Pixel (x, y) looks along D = M v, v = (wx, wy, -1) as above, affine in
+// (x, y).  The kernel tests plane i (row 1 of its record's inverse: n_i, and
+// the launch term h_i = n_i . o + inv[7], the origin's object-space height)
+// with
+//     ld = n_i . d,  d = D / |D|;   valid: |ld| >= 8e-8;   t_i = rcp(ld) (-h_i),
+// an entry in front iff it is valid and t_i >= 0.  With s_i = -h_i,
+// g_i = |n_i| / |s_i| and
+//     u_i(x, y) = (n_i . D) / s_i        (affine in the pixel),
+// 1 / t_i = u_i / |D| =: w_i, so the entry is in front iff u_i > 0 and, where
+// both are, t_p < t_q iff u_p > u_q: half-planes of the canvas.
+//
+// What the kernel evaluates, in f32 (eta = 2^-24 a rounding):
+//   - wx = half_width - (x + 0.5) pixel_size: two roundings of values up to
+//     2 half_width, |dwx| <= 3 eta half_width; likewise wy;
+//   - D_k, three fused terms: three roundings of partial sums bounded by
+//     S_k = |M_k0| half_width + |M_k1| half_height + |M_k2|, plus dwx and dwy
+//     carried through: |dD_k| <= 6 eta S_k, |dD| <= 6 eta |S|;
+//   - d = D rsq(|D|^2): the sum of squares to 3 eta, v_rsq_f32 to an ulp
+//     (2 eta) and half the sum's error, the product one more: the direction
+//     turns by at most 2 |dD| / |D| and its length is off by 5 eta;
+//   - ld, three fused terms: 3 eta |n_i| |d|;
+// so the cosine c_i = n_i . D / (|n_i| |D|) reaches the kernel as ld / |n_i|
+// within
+//     eps = 2 eta (6 |S| / Dmin + 5),   Dmin = 1 / |M^-1|_F <= |D|  (|v| >= 1),
+// and t_i = rcp(ld) s_i adds v_rcp_f32's ulp and the product's rounding,
+// 4 eta of t_i: |1 / t_i - w_i| <= 4 eta |w_i| + 1.001 eps g_i.  Every margin
+// below is 100 times that bound:
+//   - plane i counts as behind the origin only where c_i sign(s_i) < -tau_i,
+//     and as in front and valid only where it is > tau_i,
+//     tau_i = 100 eps + 1e-6 / |n_i| (the second for the validity test);
+//   - p counts as nearer than q only where
+//         w_p (1 - kappa) - w_q (1 + kappa) > 100.1 eps (g_p + g_q) + 1.001 tau_q g_q,
+//     kappa = 400 eta.  The last term covers a q whose true entry lies just
+//     behind the origin (w_q in [-tau_q g_q, 0)) and which the kernel may see
+//     just in front of it: there w_p (1 - kappa) alone exceeds 100 times the
+//     bound.  Elsewhere the two entries differ by 99 times the bound, some 400
+//     ulp of t, so neither the reciprocal's nor the root's last bit reorders
+//     them.
+// The inequalities are taken in u = w |D| with the right sides times
+// Dmax >= |D| (|D| is convex in the pixel: the largest of the corners).
+//
+// Against one p, the pixels where q may still be the nearest plane are
+//     A_q and (p possibly not in front)  or  A_q and (p not clearly nearer),
+// A_q = the canvas where q is possibly in front: two convex polygons, the
+// canvas cut by two half-planes each.  The rectangle is the bounding box of
+// their union, intersected over p (plane_rect below intersects the polygons
+// themselves where it can), rounded outward and widened by a pixel.
+// Coincident and nearly coincident planes, ties that the world index would
+// break and an eye on or next to a plane never separate by the margin: no
+// cull for that pair.  A plane whose numbers leave the range where f32 keeps
+// t normal (|n|, |h| / |n| outside 1e-15 .. 1e15, anything not finite) is not
+// culled and culls nothing; a singular or non-finite camera culls nothing.
+struct PlaneView {
+    bool ok = false;
+    double m[3][3];      // camera -> world
+    double hw, hh, ps;   // as the kernel reads them
+    double eps, dmax;
+    uint32_t width, height;
+};
+inline void plane_view(const CameraRec<float>& cam, uint32_t width, uint32_t height, PlaneView& v) {
+    v.ok = false;
+    v.width = width, v.height = height;
+    v.hw = cam.half_width, v.hh = cam.half_height, v.ps = cam.pixel_size;
+    auto& m = v.m;
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) m[i][j] = cam.inv[4 * i + j];
+    if (!(v.ps > 0.0) || !std::isfinite(v.hw) || !std::isfinite(v.hh) || !std::isfinite(v.ps)) return;
+    const double det = m[0][0] * (m[1][1] * m[2][2] - m[1][2] * m[2][1]) - m[0][1] * (m[1][0] * m[2][2] - m[1][2] * m[2][0]) +
+                       m[0][2] * (m[1][0] * m[2][1] - m[1][1] * m[2][0]);
+    double adj2 = 0.0, s2 = 0.0;  // |adj(M)|_F^2, |S|^2
+    for (int i = 0; i < 3; ++i) {
+        const int i1 = (i + 1) % 3, i2 = (i + 2) % 3;
+        for (int j = 0; j < 3; ++j) {
+            const int j1 = (j + 1) % 3, j2 = (j + 2) % 3;
+            const double c = m[i1][j1] * m[i2][j2] - m[i1][j2] * m[i2][j1];
+            adj2 += c * c;
+        }
+        const double s = std::fabs(m[i][0]) * (std::fabs(v.hw) + v.ps) + std::fabs(m[i][1]) * (std::fabs(v.hh) + v.ps) +
+                         std::fabs(m[i][2]);
+        s2 += s * s;
+    }
+    if (!std::isfinite(det) || !std::isfinite(adj2) || !std::isfinite(s2) || !(std::fabs(det) > 1e-12 * std::sqrt(adj2) * std::sqrt(s2)))
+        return;
+    const double dmin = std::fabs(det) / std::sqrt(adj2);
+    v.dmax = 0.0;
+    for (int c = 0; c < 4; ++c) {  // the corners, a pixel outside the canvas
+        const double wx = v.hw - ((c & 1 ? (double)width : -1.0) + 0.5) * v.ps, wy = v.hh - ((c & 2 ? (double)height : -1.0) + 0.5) * v.ps;
+        double dd = 0.0;
+        for (int i = 0; i < 3; ++i) {
+            const double d = m[i][0] * wx + m[i][1] * wy - m[i][2];
+            dd += d * d;
+        }
+        v.dmax = std::fmax(v.dmax, std::sqrt(dd));
+    }
+    constexpr double eta = 1.0 / 16777216.0;
+    v.eps = 2.0 * eta * (6.0 * std::sqrt(s2) / dmin + 5.0);
+    v.ok = std::isfinite(v.eps) && std::isfinite(v.dmax) && v.eps < 1e-3 && v.dmax > 0.0;
+}
+// u_i = a x + b y + c over the pixels, and its margins (already times Dmax)
+struct PlaneLine {
+    bool ok = false;
+    double a, b, c;
+    double side;  // tau_i g_i Dmax
+    double gap;   // 100.1 eps g_i Dmax
+};
+// row = {n, inv[7]}: row 1 of the record's inverse; h = the launch term (launch_terms.hpp)
+inline void plane_line(const PlaneView& v, const float row[4], float h, PlaneLine& l) {
+    l.ok = false;
+    if (!v.ok) return;
+    const double n[3] = {row[0], row[1], row[2]}, s = -(double)h;
+    const double nn = std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]), sa = std::fabs(s);
+    if (!std::isfinite(nn) || !std::isfinite(sa) || !(nn > 1e-15) || !(nn < 1e15) || !(sa > 1e-15 * nn) || !(sa < 1e15 * nn)) return;
+    double nm[3];
+    for (int j = 0; j < 3; ++j) nm[j] = (n[0] * v.m[0][j] + n[1] * v.m[1][j] + n[2] * v.m[2][j]) / s;
+    l.a = -nm[0] * v.ps;
+    l.b = -nm[1] * v.ps;
+    l.c = nm[0] * (v.hw - 0.5 * v.ps) + nm[1] * (v.hh - 0.5 * v.ps) - nm[2];
+    const double g = nn / sa;
+    l.side = (100.0 * v.eps + 1e-6 / nn) * g * v.dmax;
+    l.gap = 100.1 * v.eps * g * v.dmax;
+    // (finite, and far from where the clipping's products could overflow)
+    l.ok = std::fabs(l.a) < 1e100 && std::fabs(l.b) < 1e100 && std::fabs(l.c) < 1e100 && l.side < 1e100 && l.gap < 1e100;
+}
+struct PlanePoly {
+    static constexpr int kMax = 16;  // the canvas's four corners and one more per cut (at most 1 + 7 cuts)
+    int n = 0;
+    double x[kMax], y[kMax];
+    // keep a x + b y + c >= 0 (a convex polygon gains at most one corner)
+    void clip(double a, double b, double c) {
+        double ox[kMax], oy[kMax], f[kMax];
+        for (int i = 0; i < n; ++i) f[i] = a * x[i] + b * y[i] + c;
+        int k = 0;
+        for (int i = 0; i < n && k + 2 <= kMax; ++i) {
+            const int j = i + 1 == n ? 0 : i + 1;
+            if (f[i] >= 0.0) ox[k] = x[i], oy[k] = y[i], ++k;
+            if ((f[i] >= 0.0) != (f[j] >= 0.0)) {
+                const double t = f[i] / (f[i] - f[j]);
+                ox[k] = x[i] + t * (x[j] - x[i]), oy[k] = y[i] + t * (y[j] - y[i]), ++k;
+            }
+        }
+        n = k;
+        for (int i = 0; i < k; ++i) x[i] = ox[i], y[i] = oy[i];
+    }
+    void extend(double box[4]) const {  // {x0, y0, x1, y1}
+        for (int i = 0; i < n; ++i) {
+            box[0] = std::fmin(box[0], x[i]), box[1] = std::fmin(box[1], y[i]);
+            box[2] = std::fmax(box[2], x[i]), box[3] = std::fmax(box[3], y[i]);
+        }
+    }
+};
+// The rectangle of plane q among `n` planes (lines[i] of plane i, n <= kPrimaryRectSlots); as primary_rect's.
+// Where p is in front on all of what is left of A_q (the usual case: a room's
+// walls and floor), the pixels where q may win form one convex polygon, and
+// the cuts of the planes p accumulate in it; a p that may lie behind the eye
+// somewhere in it bounds the rectangle by the box of its two polygons instead.
+inline void plane_rect(const PlaneView& v, const PlaneLine* lines, int n, int q, uint32_t rect[4]) {
+    rect_full(v.width, v.height, rect);
+    if (!v.ok || q < 0 || q >= n || n > kPrimaryRectSlots || !lines[q].ok) return;
+    const PlaneLine& lq = lines[q];
+    constexpr double kappa = 400.0 / 16777216.0;
+    PlanePoly aq;  // the canvas (a pixel outside it) where q is possibly in front
+    aq.n = 4;
+    aq.x[0] = aq.x[3] = -1.0, aq.x[1] = aq.x[2] = (double)v.width;
+    aq.y[0] = aq.y[1] = -1.0, aq.y[2] = aq.y[3] = (double)v.height;
+    aq.clip(lq.a, lq.b, lq.c + lq.side);
+    double box[4] = {-HUGE_VAL, -HUGE_VAL, HUGE_VAL, HUGE_VAL};
+    for (int p = 0; p < n && aq.n; ++p) {
+        if (p == q || !lines[p].ok) continue;
+        const PlaneLine& lp = lines[p];
+        PlanePoly behind = aq;
+        behind.clip(-lp.a, -lp.b, lp.side - lp.c);  // p possibly not in front
+        const double rhs = lp.gap + lq.gap + 1.001 * lq.side;
+        const double la = lq.a * (1.0 + kappa) - lp.a * (1.0 - kappa), lb = lq.b * (1.0 + kappa) - lp.b * (1.0 - kappa),
+                     lc = rhs + lq.c * (1.0 + kappa) - lp.c * (1.0 - kappa);  // >= 0: p not clearly nearer
+        if (behind.n == 0) {
+            aq.clip(la, lb, lc);
+            continue;
+        }
+        PlanePoly level = aq;
+        level.clip(la, lb, lc);
+        double bp[4] = {HUGE_VAL, HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
+        behind.extend(bp);
+        level.extend(bp);
+        box[0] = std::fmax(box[0], bp[0]), box[1] = std::fmax(box[1], bp[1]);
+        box[2] = std::fmin(box[2], bp[2]), box[3] = std::fmin(box[3], bp[3]);
+    }
+    double bq[4] = {HUGE_VAL, HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
+    aq.extend(bq);
+    box[0] = std::fmax(box[0], bq[0]), box[1] = std::fmax(box[1], bq[1]);
+    box[2] = std::fmin(box[2], bq[2]), box[3] = std::fmin(box[3], bq[3]);
+    if (!(box[0] == box[0]) || !(box[1] == box[1]) || !(box[2] == box[2]) || !(box[3] == box[3])) return;  // NaN: no cull
+    const double x0 = std::floor(box[0]) - 1.0, y0 = std::floor(box[1]) - 1.0, x1 = std::ceil(box[2]) + 1.0, y1 = std::ceil(box[3]) + 1.0;
+    const double xm = (double)(v.width - 1), ym = (double)(v.height - 1);
+    if (!(x0 <= x1) || !(y0 <= y1) || x1 < 0.0 || y1 < 0.0 || x0 > xm || y0 > ym) return rect_empty(rect);
+    rect[0] = (uint32_t)(x0 < 0.0 ? 0.0 : x0), rect[1] = (uint32_t)(y0 < 0.0 ? 0.0 : y0);
+    rect[2] = (uint32_t)(x1 > xm ? xm : x1), rect[3] = (uint32_t)(y1 > ym ? ym : y1);
+}
 }  // namespace rtc

@@ -1138,6 +1138,21 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
                 primary_rect(P.cam, P.width, P.height, ctx->jit.shapes[s].bound, r);
                 outside(r, 1u << s);
             }
+            // A plane's bit: the blocks where its entry lies behind the eye or
+            // another plane's is nearer (plane_rect), from the records' rows
+            // and the heights the kernel reads (P.terms above).
+            const int p0 = w.scene.kind_begin[RT_SHAPE_PLANE], np = w.scene.kind_begin[RT_SHAPE_PLANE + 1] - p0;
+            if (np > 0) {
+                PlaneView pv;
+                PlaneLine pl[kPrimaryRectSlots];
+                plane_view(P.cam, P.width, P.height, pv);
+                for (int p = 0; p < np; ++p) plane_line(pv, ctx->jit.shapes[p0 + p].inv + 4, P.terms.head[1 + p], pl[p]);
+                for (int p = 0; p < np; ++p) {
+                    uint32_t r[4];
+                    plane_rect(pv, pl, np, p, r);
+                    outside(r, 1u << (p0 + p));
+                }
+            }
             // The shadow cull's bits (rtc_internal.hpp ShadowLayout), from the
             // f32 records and lights the per-scene kernel holds as constants.
             const ShadowLayout lay(w.scene.kind_begin, (int)ctx->jit.lights.size());

@@ -476,7 +476,11 @@ struct DevScene {
 // when either bit of its block is set: two scalar loads and an OR per wave
 // and tile, whatever the number of slots (a compare of the block against each
 // rectangle cost ~14 SALU per slot and ate the gain: the scalar unit is as
-// busy as the vector units in this kernel).  All zero (no
+// busy as the vector units in this kernel).  A plane's slot
+// has a bit too: its rectangle (primary_rect.hpp plane_rect) holds every pixel
+// where the plane's entry can be the nearest of the planes' entries in front
+// of the eye; outside it the entry lies behind the eye or another plane's is
+// nearer, and the wave passes the plane's test by.  All zero (no
 // cull) for every other launch, for worlds of more than kPrimaryRectSlots
 // slots (the same small-world limit as RTC_JIT_NORMAL_MAX) and for canvases
 // beyond the tables.
@@ -525,8 +529,8 @@ struct ShadowLayout {
 // with its block's cull words, one scalar load per tile:
 //   [0]     max(|o.x|, |o.y|, |o.z|), the origin's part of the flat kinds' offset scale
 //   [1 + p] plane p of the plane run: lo.y of xform_point(inv, origin), all its test reads
-// (planes are never culled, so every tile wants them all; the terms of the
-// other kinds' tests were measured too and left out).
+// (nearly every tile tests some plane, so every tile loads them all; the terms
+// of the other kinds' tests were measured too and left out).
 // Filled for the launches the kernel reads them in (camera frames of the
 // per-scene f32 direct kernel, worlds of at most kPrimaryRectSlots slots).
 struct alignas(16) LaunchTerms {

@@ -1161,6 +1161,15 @@ __device__ inline bool skips_on(const DevScene<R>& sc) {
 #ifndef RTC_PRIMARY_RECTS
 #define RTC_PRIMARY_RECTS 1  // (A/B builds: 0 keeps the per-lane test alone)
 #endif
+// A plane has no ball, but among a world's planes most cannot be hit first in
+// most of the frame: the floor hides the walls below their common edge, a wall
+// hides the floor above it.  The launch sets a plane slot's miss bit where its
+// entry lies behind the eye or another plane's entry in front is nearer, both
+// by a margin of 100 times the kernel's rounding (primary_rect.hpp
+// plane_rect), so the nearest entry and its key are what they were.
+#ifndef RTC_PLANE_RECTS
+#define RTC_PLANE_RECTS 1  // (A/B builds: 0 tests every plane in every block)
+#endif
 struct NoBlock {
     static constexpr bool kOn = false;
     __device__ bool misses(int) const { return false; }
@@ -1171,9 +1180,9 @@ struct NoBlock {
 // origin alone, one value for every primary ray of the launch, come from the
 // launch: a plane's object-space height lo.y and the origin's part of the
 // offset scale.  A wave reads them with the block's cull words at the tile
-// head (planes are never culled: every tile tests them all; a load in front
-// of each plane's test was a round trip on the wave's critical path and lost
-// more than the terms saved).  A/B builds: 0 forms them per lane.
+// head (nearly every tile tests some plane, so all the heights come in one
+// load: a load in front of each plane's test was a round trip on the wave's
+// critical path and lost more than the terms saved).  A/B builds: 0 forms them per lane.
 #ifndef RTC_LAUNCH_TERMS
 #define RTC_LAUNCH_TERMS 1
 #endif
@@ -1224,7 +1233,7 @@ __device__ inline Hit<R> closest_hit(const DevScene<R>& sc, V3<R> o, V3<R> d, B 
     for_all_culled<R, true>(sc, o, d, dd0, [&]<int K>(const ShapeRec<R>& s, int slot) {
         if constexpr (kTerms) jit_fence_dir(d, slot);
         else jit_fence(o, d, slot);
-        if constexpr (kRects && K != RT_SHAPE_PLANE)
+        if constexpr (kRects && (K != RT_SHAPE_PLANE || RTC_PLANE_RECTS))
             if (blk.misses(slot)) return;  // wave-uniform, SALU
         const R dd = kLazy ? dot(d, d) : dd0;
         if (!wave_may_hit<R, K>(s, o, d, dd)) return;

@@ -29,6 +29,7 @@
 
 #include "../../include/rtc_scene.h"
 #include "host_math.hpp"
+#include "launch_terms.hpp"
 #include "primary_rect.hpp"
 #include "rtc_internal.hpp"
 #include "shape_identity.hpp"
@@ -852,6 +853,25 @@ int rt_camera_shadow_near(const rt_camera_desc* cam, const float plane[4], const
     if (!cam || !plane || !light || !span) return rtc::set_error(RT_ERR_INVALID, "rt_camera_shadow_near: null argument");
     if (cam->width == 0 || cam->height == 0) return rtc::set_error(RT_ERR_INVALID, "rt_camera_shadow_near: empty canvas");
     rtc::shadow_near(launch_camera(cam), cam->width, cam->height, plane, plane[3], light, span);
+    return RT_OK;
+}
+
+int rt_camera_plane_rect(const rt_camera_desc* cam, const float* planes, uint32_t n_planes, uint32_t q, uint32_t rect[4]) {
+    if (!cam || !planes || !rect) return rtc::set_error(RT_ERR_INVALID, "rt_camera_plane_rect: null argument");
+    if (cam->width == 0 || cam->height == 0) return rtc::set_error(RT_ERR_INVALID, "rt_camera_plane_rect: empty canvas");
+    if (n_planes == 0 || n_planes > (uint32_t)rtc::kPrimaryRectSlots || q >= n_planes)
+        return rtc::set_error(RT_ERR_INVALID, "rt_camera_plane_rect: 1 to 8 planes, q one of them");
+    const rtc::CameraRec<float> c = launch_camera(cam);
+    rtc::PlaneView view;
+    rtc::PlaneLine lines[rtc::kPrimaryRectSlots];
+    rtc::plane_view(c, cam->width, cam->height, view);
+    for (uint32_t p = 0; p < n_planes; ++p) {
+        // the launch term: lo.y of xform_point(inv, origin), in the kernel's operations (launch_terms.hpp)
+        const float* m = planes + 4 * p;
+        const float h = rtc::launch_kfma(m[2], c.origin[2], rtc::launch_kfma(m[1], c.origin[1], rtc::launch_kfma(m[0], c.origin[0], m[3])));
+        rtc::plane_line(view, m, h, lines[p]);
+    }
+    rtc::plane_rect(view, lines, (int)n_planes, (int)q, rect);
     return RT_OK;
 }
 

@@ -26,7 +26,7 @@ import numpy as np
 
 __all__ = [
     "RenderError", "lib_path", "abi_version", "device_count", "matrix_inverse", "camera_make",
-    "camera_resize", "camera_set_transform", "camera_bound_rect", "load_scene", "load_scene_text", "SceneTables", "Context", "shard_rows",
+    "camera_resize", "camera_set_transform", "camera_bound_rect", "camera_plane_rect", "load_scene", "load_scene_text", "SceneTables", "Context", "shard_rows",
     "load_obj", "Mesh", "SmoothDesc", "RT_SMOOTH_SHAPES", "RT_OBJ_NORMALS", "RT_NO_NORMAL",
     "AreaLightDesc", "RT_LIGHT_MAX_STEPS", "RT_JITTER_NONE", "RT_JITTER_HASHED", "area_light_sample",
     "LensDesc", "Lens", "lens_ray",
@@ -348,6 +348,7 @@ def _load() -> C.CDLL:
         "rt_camera_bound_rect": (C.c_int, [P(CameraDesc), P(C.c_float), P(C.c_uint32)]),
         "rt_camera_shadow_rect": (C.c_int, [P(CameraDesc), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_uint32)]),
         "rt_camera_shadow_near": (C.c_int, [P(CameraDesc), P(C.c_float), P(C.c_float), P(C.c_uint32)]),
+        "rt_camera_plane_rect": (C.c_int, [P(CameraDesc), P(C.c_float), C.c_uint32, C.c_uint32, P(C.c_uint32)]),
         "rt_matrix_inverse": (C.c_int, [P(C.c_double), P(C.c_double)]),
         "rt_camera_set_transform": (C.c_int, [P(CameraDesc), P(C.c_double)]),
         "rt_shard_row_map": (C.c_int, [C.c_uint32, C.c_uint32, P(C.c_uint32), P(C.c_uint32)]),
@@ -396,7 +397,7 @@ EXPORTED_SYMBOLS = (
     "rt_render_to_canvas", "rt_canvas_wait", "rt_canvas_release", "rt_canvas_read", "rt_context_set_gather",
     "rt_assemble_shards", "rt_scene_load_yaml", "rt_scene_load_yaml_text", "rt_scene_view_get", "rt_scene_free",
     "rt_camera_make", "rt_camera_resize", "rt_camera_bound_rect", "rt_camera_shadow_rect", "rt_camera_shadow_near",
-    "rt_matrix_inverse", "rt_image_write", "rt_image_write_format",
+    "rt_camera_plane_rect", "rt_matrix_inverse", "rt_image_write", "rt_image_write_format",
     "rt_canvas_quantize",
     "rt_mesh_load_obj", "rt_mesh_load_obj_text", "rt_mesh_view_get", "rt_mesh_free", "rt_mesh_triangles",
     "rt_scene_tree_info",
@@ -483,6 +484,15 @@ def camera_shadow_near(cam: CameraDesc, plane, light) -> tuple:
     reach of `light`; lo > hi = none (rt_camera_shadow_near)."""
     r = (C.c_uint32 * 4)()
     _check(_lib.rt_camera_shadow_near(C.byref(cam), _f32s(plane, 4), _f32s(light, 3), r))
+    return tuple(r[:])
+
+
+def camera_plane_rect(cam: CameraDesc, planes, q: int) -> tuple:
+    """(x0, y0, x1, y1), inclusive: the pixels of `cam` at which plane `q` of `planes` (row 1 of each record's f32
+    inverse, shape (n, 4)) can be the nearest plane in front of the eye; x0 > x1 = none (rt_camera_plane_rect)."""
+    rows = np.ascontiguousarray(planes, dtype=np.float32).reshape(-1, 4)
+    r = (C.c_uint32 * 4)()
+    _check(_lib.rt_camera_plane_rect(C.byref(cam), _f32s(rows, rows.size), rows.shape[0], int(q), r))
     return tuple(r[:])
 
 
