@@ -17,6 +17,7 @@
 #include "../../include/rtc.h"
 #include "device_memory.hpp"
 #include "flop_model.hpp"
+#include "kernel_id.hpp"
 #include "rtc_internal.hpp"
 
 namespace rtc {
@@ -61,7 +62,7 @@ struct SideTable {
 // build holds the code of the ones before it.  Stored in rt_context::kernel_build
 // by set_kernel_build and nowhere re-derived.
 enum class KernelBuild : uint32_t {
-    plain,      // rtc::launch_trace*: worlds of shapes alone
+    plain,      // rtc::launch_kernel: worlds of shapes alone
     instanced,  // rtc::instanced::*: the instance level and the smooth triangle's normal (rtc_kernels.hip prepare_hit)
     textured,   // rtc::textured::*: ... plus the texture code, for an image pattern or a coordinate entry
     area,       // rtc::area::*: ... plus the area lights' sample loop
@@ -259,9 +260,9 @@ struct rt_context {
         uint32_t pattern_kinds = ~0u;              // pattern kinds in the world's table (bit per RT_PATTERN_*)
         bool transparent = true;                   // some material is transparent (else no refraction code)
         int32_t begin[rtc::kNumKinds + 1] = {};
-        // variants: pool x LDS world x RT_FLAG_NO_SKIPS x (pool) 7 waves/SIMD x supersampled x lens
-        // (rtc_jit.cpp jit_function)
-        static constexpr int kVariants = 64;
+        // one entry per build of the world: KernelId::variant (kernel_id.hpp), the kernel's identity x
+        // RT_FLAG_NO_SKIPS x (pool) 7 waves/SIMD (rtc_jit.cpp jit_function)
+        static constexpr int kVariants = rtc::KernelId::kVariants;
         hipFunction_t fn[kVariants] = {};
         std::shared_ptr<rtc::CodeBuild> build[kVariants];  // the build each variant waits for (host thread)
         bool rejected[kVariants] = {};   // built, but refused for occupancy or scratch (that variant only)
@@ -315,9 +316,10 @@ struct rt_context {
     int cu_count = 0;
     size_t lds_per_block = 64 * 1024;
     rtc::KernelBuild kernel_build = rtc::KernelBuild::plain;  // the uploaded world's (set_kernel_build)
-    size_t occ_lds[28] = {};    // occupancy cache of kernel_build's kernels: {direct,pool} x {f32,f64} x
-    int occ_blocks[28] = {};    // {global,LDS world}, then the ray-batch kernel's {f32,f64} x {global,LDS world},
-                                // then the supersampled kernels' and the lens kernels' (each as the first eight)
+    // occupancy cache of kernel_build's kernels, by KernelId::occupancy_slot (kernel_id.hpp): the dynamic LDS
+    // size last asked about and the workgroups per CU at it (0: nothing cached)
+    size_t occ_lds[rtc::KernelId::kOccupancySlots] = {};
+    int occ_blocks[rtc::KernelId::kOccupancySlots] = {};
     Knobs knobs;
     rtc::Stream stream;
     rtc::Event ev_start, ev_stop;
@@ -469,13 +471,13 @@ unsigned long long timeout_ticks(double timeout_ms);
 // `static_blocks` workgroups per CU, or null (use the generic kernel)
 constexpr uint32_t kJitMinTiles = 256;  // 64K pixels
 // *pool_waves: the waves/SIMD the returned pool kernel was built for (7, or
-// 6 = the static build's), so the caller can plan its LDS for them.
-// ss: the supersampled kernel (trace_direct_ss / trace_pool_ss), a build of
-// its own that only worlds rendered supersampled ask for; its pool build is
-// made at the static occupancy alone.
-// lens (with ss): the lens kernel (trace_direct_lens / trace_pool_lens), under ss's rules.
-int jit_function(rt_context* ctx, bool pool, bool lds, size_t dyn_lds, int static_blocks, hipFunction_t* fn,
-                 bool no_skips = false, int* pool_waves = nullptr, bool ss = false, bool lens = false);
+// 0 = the static build's), so the caller can plan its LDS for them.
+// id: the kernel the launch was planned for.  A supersampled kernel
+// (trace_direct_ss / trace_pool_ss) is a build of its own that only worlds
+// rendered supersampled ask for; its pool build is made at the static
+// occupancy alone.  A lens kernel (trace_direct_lens / trace_pool_lens) likewise.
+int jit_function(rt_context* ctx, KernelId id, size_t dyn_lds, int static_blocks, hipFunction_t* fn, bool no_skips,
+                 int* pool_waves);
 int jit_wait(rt_context* ctx, double timeout_ms, int* pending);
 const std::string& device_arch(rt_context* ctx);  // rtc_jit.cpp: the device's gfx target, read once
 

@@ -25,6 +25,8 @@
 #include "host_math.hpp"
 #include "debug_knobs.hpp"
 #include "launch_terms.hpp"
+#include "cull_tables.hpp"
+#include "kernel_id.hpp"
 #include "primary_rect.hpp"
 #include "rtc_context.hpp"
 #include "rtc_internal.hpp"
@@ -34,55 +36,35 @@
 
 namespace rtc {
 
-// The six launchers every build of the tracer kernels (rtc_kernels.hip, RTC_VARIANT) defines in its own
-// namespace: the frame kernels, the ray-batch kernel and the supersampled frame kernels (trace_direct_ss,
-// trace_pool_ss; with `lens` the lens frame kernels, trace_direct_lens and trace_pool_lens), each with its
-// occupancy query.
-#define RTC_KERNEL_LAUNCHERS                                                                                          \
-    template <typename R>                                                                                             \
-    hipError_t launch_trace(const LaunchParams<R>& P, bool pool, bool dup, uint32_t grid, size_t dyn_lds,             \
-                            hipStream_t stream);                                                                      \
-    template <typename R>                                                                                             \
-    hipError_t occupancy(bool pool, bool lds, size_t dyn_lds, int* blocks_per_cu);                                    \
-    template <typename R>                                                                                             \
-    hipError_t launch_trace_rays(const LaunchParams<R>& P, bool dup, uint32_t grid, size_t dyn_lds, const void* rays, \
-                                 void* rgb, void* hits, hipStream_t stream);                                          \
-    template <typename R>                                                                                             \
-    hipError_t occupancy_rays(bool lds, size_t dyn_lds, int* blocks_per_cu);                                          \
-    template <typename R>                                                                                             \
-    hipError_t launch_trace_ss(const LaunchParams<R>& P, bool pool, bool dup, const LensParams<R>* lens,              \
-                               uint32_t grid, size_t dyn_lds, hipStream_t stream);                                    \
-    template <typename R>                                                                                             \
-    hipError_t occupancy_ss(bool pool, bool lds, bool lens, size_t dyn_lds, int* blocks_per_cu);
+// The two entry points every build of the tracer kernels (rtc_kernels.hip, RTC_VARIANT) defines in its own
+// namespace: the launch of the kernel a KernelId names (`extra`: a ray batch's RayBatchArg, a lens frame's
+// LensParams<R>, else unread) and its occupancy.  A build answers hipErrorInvalidValue for a kernel it does not hold.
+#define RTC_KERNEL_LAUNCHERS                                                                                  \
+    template <typename R>                                                                                     \
+    hipError_t launch_kernel(KernelId id, const LaunchParams<R>& P, const void* extra, uint32_t grid, size_t dyn_lds, \
+                             hipStream_t stream);                                                             \
+    template <typename R>                                                                                     \
+    hipError_t kernel_occupancy(KernelId id, size_t dyn_lds, int* blocks_per_cu);
 RTC_KERNEL_LAUNCHERS                          // rtc_kernels*.o: the plain build
 namespace instanced { RTC_KERNEL_LAUNCHERS }  // rtc_kernels_inst*.o: with the instance level, for worlds with mesh instances
 namespace textured { RTC_KERNEL_LAUNCHERS }   // rtc_kernels_tex*.o: the instance build plus the texture code
 namespace area { RTC_KERNEL_LAUNCHERS }       // rtc_kernels_area*.o: the texture build plus the area lights' sample loop
+namespace sp { RTC_KERNEL_LAUNCHERS }         // rtc_kernels_sp.o: the f32 frame pool kernel for worlds of spheres and planes only
 #undef RTC_KERNEL_LAUNCHERS
-namespace sp {  // rtc_kernels_sp.o: the f32 pool kernel for worlds of spheres and planes only
-template <typename R>
-hipError_t launch_trace(const LaunchParams<R>& P, bool pool, bool dup, uint32_t grid, size_t dyn_lds,
-                        hipStream_t stream);
-}  // namespace sp
 constexpr uint32_t kKindsSp = (1u << RT_SHAPE_SPHERE) | (1u << RT_SHAPE_PLANE);
 
 // The launchers of each build, by KernelBuild: the one place that maps a world's stored build
 // (rt_context::kernel_build) to kernels.
 template <typename R>
 struct Launchers {
-    decltype(&launch_trace<R>) launch_trace;
-    decltype(&occupancy<R>) occupancy;
-    decltype(&launch_trace_rays<R>) launch_trace_rays;
-    decltype(&occupancy_rays<R>) occupancy_rays;
-    decltype(&launch_trace_ss<R>) launch_trace_ss;
-    decltype(&occupancy_ss<R>) occupancy_ss;
+    decltype(&launch_kernel<R>) launch_kernel;
+    decltype(&kernel_occupancy<R>) kernel_occupancy;
 };
-#define RTC_BUILD(ns)                                                                                    \
-    {ns launch_trace<R>, ns occupancy<R>, ns launch_trace_rays<R>, ns occupancy_rays<R>, ns launch_trace_ss<R>, \
-     ns occupancy_ss<R>}
 template <typename R>
-constexpr Launchers<R> kLaunchers[] = {RTC_BUILD(rtc::), RTC_BUILD(instanced::), RTC_BUILD(textured::), RTC_BUILD(area::)};
-#undef RTC_BUILD
+constexpr Launchers<R> kLaunchers[] = {{launch_kernel<R>, kernel_occupancy<R>},
+                                       {instanced::launch_kernel<R>, instanced::kernel_occupancy<R>},
+                                       {textured::launch_kernel<R>, textured::kernel_occupancy<R>},
+                                       {area::launch_kernel<R>, area::kernel_occupancy<R>}};
 template <typename R>
 const Launchers<R>& launchers(const rt_context* ctx) {
     return kLaunchers<R>[(uint32_t)ctx->kernel_build];
@@ -611,7 +593,7 @@ constexpr size_t kStaticLds = 512;
 
 struct LaunchShape {
     int per_cu;  // workgroups per CU the launch is planned for
-    bool pool;
+    KernelId id;  // the kernel the launch is planned for
     uint32_t world_lds;  // world tables staged in LDS (bytes, 0 = none)
     uint32_t sched;
     uint32_t grid;
@@ -628,25 +610,21 @@ int cap_by_lds(int api, size_t lds) {
     return std::min(api, (int)(kLdsPerCu / per_block));
 }
 
-// Cached occupancy (workgroups per CU) of one kernel instantiation of the
-// world's build at a given dynamic LDS size (cap_by_lds); an upload that
-// changes the build clears the cache (set_kernel_build).  ss: the
-// supersampled kernels (keys 12..19 of the same table); with lens, the lens
-// kernels (keys 20..27).
+// Cached occupancy (workgroups per CU) of kernel `id` of the world's build at
+// a given dynamic LDS size (cap_by_lds); an upload that changes the build
+// clears the cache (set_kernel_build).
 template <typename R>
-int blocks_per_cu(rt_context* ctx, bool pool, bool lds_world, size_t lds, int* per_cu, bool ss = false,
-                  bool lens = false) {
-    const int key = (pool ? 1 : 0) + (sizeof(R) == 8 ? 2 : 0) + (lds_world ? 4 : 0) + (lens ? 20 : ss ? 12 : 0);
-    if (ctx->occ_lds[key] == lds && ctx->occ_blocks[key] > 0) {
-        *per_cu = ctx->occ_blocks[key];
+int blocks_per_cu(rt_context* ctx, KernelId id, size_t lds, int* per_cu) {
+    const int slot = id.occupancy_slot(sizeof(R) == 8);
+    if (ctx->occ_lds[slot] == lds && ctx->occ_blocks[slot] > 0) {
+        *per_cu = ctx->occ_blocks[slot];
         return RT_OK;
     }
     int api = 0;
-    const Launchers<R>& k = launchers<R>(ctx);
-    RT_HIP(ss ? k.occupancy_ss(pool, lds_world, lens, lds, &api) : k.occupancy(pool, lds_world, lds, &api));
+    RT_HIP(launchers<R>(ctx).kernel_occupancy(id, lds, &api));
     *per_cu = cap_by_lds(api, lds);
-    ctx->occ_lds[key] = lds;
-    ctx->occ_blocks[key] = *per_cu;
+    ctx->occ_lds[slot] = lds;
+    ctx->occ_blocks[slot] = *per_cu;
     return RT_OK;
 }
 
@@ -679,19 +657,16 @@ int pool_lds_plan(rt_context* ctx, uint32_t world_lds, uint32_t cap, Occ&& occ, 
     return RT_OK;
 }
 
-// ... for the static pool kernel (6 workgroups/CU for f32 at <= 80 VGPRs).
+// ... for the static pool kernel `id` (6 workgroups/CU for f32 at <= 80 VGPRs).
 // RTC_DEBUG=pool_lds_rays=N overrides (A/B).
 template <typename R>
-int pool_lds_rays(rt_context* ctx, uint32_t world_lds, uint32_t cap, uint32_t* lcap, bool ss = false,
-                  bool lens = false) {
+int pool_lds_rays(rt_context* ctx, KernelId id, uint32_t world_lds, uint32_t cap, uint32_t* lcap) {
     if (ctx->knobs.pool_lds_rays > 0) {
         *lcap = std::min<uint32_t>(cap, std::max<uint32_t>(kBlock, ctx->knobs.pool_lds_rays & ~7u));
         return RT_OK;
     }
-    const bool lw = world_lds != 0;
-    return pool_lds_plan<R>(ctx, world_lds, cap,
-                            [&](size_t lds, int* b) { return blocks_per_cu<R>(ctx, true, lw, lds, b, ss, lens); }, lcap,
-                            nullptr);
+    return pool_lds_plan<R>(ctx, world_lds, cap, [&](size_t lds, int* b) { return blocks_per_cu<R>(ctx, id, lds, b); },
+                            lcap, nullptr);
 }
 
 // LDS world of a per-scene kernel that takes the shape records from its
@@ -732,32 +707,34 @@ int plan_pool_for(rt_context* ctx, hipFunction_t fn, LaunchShape& ls) {
     return RT_OK;
 }
 
-// samples: the grid of a supersampled launch (its kernels, their occupancy
-// and their pool bound), 0 = a plain one; lens: a lens launch (its kernels,
-// planned as the supersampled ones are).
+// id: the launch's family and dup; pool and lds are decided here, and ls.id
+// is the kernel planned for.  samples: the grid of a supersampled or lens
+// launch (its pool bound), 0 for a plain one.  jit_records: the plan of a
+// per-scene kernel that holds the shape records as constants.
 template <typename R>
-int plan_launch(rt_context* ctx, const DevScene<R>& sc, uint32_t depth, uint32_t n_tiles, LaunchShape& ls,
-                bool jit_records = false, uint32_t samples = 0, bool lens = false) {
-    const bool ss = samples != 0;
-    ls.pool = sc.any_secondary && depth > 0;
+int plan_launch(rt_context* ctx, const DevScene<R>& sc, uint32_t depth, uint32_t n_tiles, KernelId id, uint32_t samples,
+                bool jit_records, LaunchShape& ls) {
+    const bool pool = id.pool = sc.any_secondary && depth > 0;
     const size_t wb = jit_records ? std::max<size_t>(16, jit_world_lds_bytes(sc))
                                   : world_lds_bytes<R>(sc.kind_begin[kNumKinds], sc.n_materials, sc.n_patterns);
     // (a per-scene direct kernel takes its materials from constants too and
     // stages no world at all: rtc_kernels.hip kJitConstMaterials)
-    ls.world_lds = (ctx->knobs.lds_world && wb <= kMaxWorldLds && !(jit_records && !ls.pool)) ? (uint32_t)wb : 0;
+    ls.world_lds = (ctx->knobs.lds_world && wb <= kMaxWorldLds && !(jit_records && !pool)) ? (uint32_t)wb : 0;
+    id.lds = ls.world_lds != 0;
+    ls.id = id;
     ls.lds = ls.world_lds;
     ls.cap = ls.lcap = ls.batch = 0;
-    ls.sched = ls.pool ? kSchedDynamic : ctx->knobs.sched_direct;
+    ls.sched = pool ? kSchedDynamic : ctx->knobs.sched_direct;
     int rc;
-    if (ls.pool) {
+    if (pool) {
         // (the pool kernel takes its items from the per-XCD queues only)
         ls.batch = kPoolBatch;
-        ls.cap = ss ? pool_capacity_ss(depth, ls.batch, samples) : pool_capacity(depth, ls.batch);
-        if ((rc = pool_lds_rays<R>(ctx, ls.world_lds, ls.cap, &ls.lcap, ss, lens))) return rc;
+        ls.cap = samples ? pool_capacity_ss(depth, ls.batch, samples) : pool_capacity(depth, ls.batch);
+        if ((rc = pool_lds_rays<R>(ctx, id, ls.world_lds, ls.cap, &ls.lcap))) return rc;
         ls.lds += pool_lds_bytes<R>(ls.lcap);
     }
     int per_cu = 0;
-    if ((rc = blocks_per_cu<R>(ctx, ls.pool, ls.world_lds != 0, ls.lds, &per_cu, ss, lens))) return rc;
+    if ((rc = blocks_per_cu<R>(ctx, id, ls.lds, &per_cu))) return rc;
     if (per_cu < 1) per_cu = 1;
     ls.per_cu = per_cu;
     const uint64_t resident = (uint64_t)per_cu * (uint64_t)ctx->cu_count;
@@ -768,7 +745,7 @@ int plan_launch(rt_context* ctx, const DevScene<R>& sc, uint32_t depth, uint32_t
     // 3072 32.6 / 40.1, 4096 33.1 / 40.3, 5120 32.3 / 38.8, 6144 32.9 / 38.8,
     // 8160 (one tile each) 34.1 / 39.8; three_sphere 4K 115.6 -> 107.0 us.
     // The f64 kernel (3 waves/SIMD) measured 3.7% slower that way.
-    const bool oversub = !ls.pool && ls.sched == kSchedStatic && sizeof(R) == 4;
+    const bool oversub = !pool && ls.sched == kSchedStatic && sizeof(R) == 4;
     const uint64_t grid_cap = oversub ? std::max<uint64_t>(1, resident * ctx->knobs.direct_oversub10 / 10) : resident;
     ls.grid = ls.sched != kSchedGrid ? (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_tiles, grid_cap)) : n_tiles;
     ls.grid_tiles = n_tiles;
@@ -935,9 +912,15 @@ void set_lens_params(const LaunchParams<R>& P, const rt_lens_desc& lens, uint32_
             lens_point<R>(P.cam.inv, o.aperture, o.inv_n, (R)i + (R)0.5, (R)j + (R)0.5, o.points[j * n + i]);
 }
 
-// The launch's view of the world's mesh instances (none: no world index reaches inst_world_begin).
+// Step 1 of a launch (frames and ray batches alike): the launch's view of the
+// world, its tables, triangle hierarchy, mesh instances (none: no world index
+// reaches inst_world_begin), side tables, textures and area lights.
 template <typename R>
-void set_instance_params(LaunchParams<R>& P, const DeviceWorld<R>& w) {
+void set_world_params(const rt_context* ctx, const DeviceWorld<R>& w, LaunchParams<R>& P) {
+    P.scene = w.scene;
+    P.tri_nodes = w.n_tri_nodes ? w.tri_nodes.get() : nullptr;
+    P.n_tri_nodes = w.n_tri_nodes;
+    P.tri_flat_begin = w.tri_flat_begin;
     const InstanceCounts& c = w.inst_counts;
     P.n_instances = c.instances;
     P.inst_world_begin = c.instances ? c.world_begin : std::numeric_limits<int32_t>::max();
@@ -954,27 +937,17 @@ void set_instance_params(LaunchParams<R>& P, const DeviceWorld<R>& w) {
     P.area = w.n_area ? w.area.get() : nullptr;
     P.n_area = w.n_area;
     P.area_samples = w.area_samples;
-    P.area_cull = 1u;  // (the callers clear it under RTC_DEBUG=area_cull=0)
+    P.area_cull = ctx->knobs.area_cull ? 1u : 0u;  // (RTC_DEBUG=area_cull=0 clears it)
 }
 
+// Step 2: what the launch renders, a camera's canvas (with the lens of a lens
+// frame) or a ray batch, and where its output and counters go.
 template <typename R>
-int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
-    const rt_camera_desc* cam = q.cam;
-    const uint32_t depth = q.depth, flags = q.flags, shard_index = q.shard_index, shard_count = q.shard_count;
-    hipStream_t stream = q.stream;
-    int rc;
-    LaunchParams<R> P{};
-    LensParams<R> lens_params{};  // a lens launch's last kernel argument
+void set_target_params(rt_context* ctx, const LaunchRequest& q, LaunchParams<R>& P, LensParams<R>& lens_params) {
     P.image_rows = q.image_rows ? 1u : 0u;
-    P.scene = w.scene;
-    P.tri_nodes = w.n_tri_nodes ? w.tri_nodes.get() : nullptr;
-    P.n_tri_nodes = w.n_tri_nodes;
-    P.tri_flat_begin = w.tri_flat_begin;
-    set_instance_params(P, w);
-    if (!ctx->knobs.area_cull) P.area_cull = 0u;
-    if (cam) {
-        for (int q = 0; q < 12; ++q) P.cam.inv[q] = (R)cam->inverse[q];
-        for (int q = 0; q < 3; ++q) P.cam.origin[q] = (R)cam->origin[q];
+    if (const rt_camera_desc* cam = q.cam) {
+        for (int i = 0; i < 12; ++i) P.cam.inv[i] = (R)cam->inverse[i];
+        for (int i = 0; i < 3; ++i) P.cam.origin[i] = (R)cam->origin[i];
         P.cam.half_width = (R)cam->half_width;
         P.cam.half_height = (R)cam->half_height;
         P.cam.pixel_size = (R)cam->pixel_size;
@@ -984,7 +957,7 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
         P.width = q.samples ? q.out_w : cam->width;
         P.height = q.samples ? q.out_h : cam->height;
         P.tiles_x = (P.width + RT_TILE_W - 1) / RT_TILE_W;
-        P.tile_rows = tile_rows_for(P.height, shard_count, shard_index);
+        P.tile_rows = tile_rows_for(P.height, q.shard_count, q.shard_index);
         P.n_tiles = P.tiles_x * P.tile_rows;
         P.tiles_x_magic = div_magic(P.tiles_x, P.n_tiles);
     } else {
@@ -994,32 +967,44 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
     }
     P.out = q.out_device;
     P.out_format = q.out_format;
-    P.shard_index = shard_index;
-    P.shard_count = shard_count;
-    P.max_depth = depth;
+    P.shard_index = q.shard_index;
+    P.shard_count = q.shard_count;
+    P.max_depth = q.depth;
     P.tile_counter = ctx->d_tile_counter.get();
     P.counters = ctx->d_counters.get();
     P.error_flag = ctx->d_error.get();
-    if (flags & RT_FLAG_GENERATIONS) P.gen_counts = ctx->d_gen_counts.get();
-    if (P.n_tiles == 0) return RT_OK;
-    if ((rc = order_after_last(ctx, stream))) return rc;
-    LaunchShape ls;
-    const bool ss = q.samples != 0, lens = q.lens != nullptr;
-    rc = plan_launch<R>(ctx, w.scene, depth, P.n_tiles, ls, false, q.samples, lens);
-    if (rc) return rc;
+    if (q.flags & RT_FLAG_GENERATIONS) P.gen_counts = ctx->d_gen_counts.get();
+}
+
+// The kernel a frame launch runs and its plan.
+struct KernelChoice {
+    LaunchShape ls;               // ls.id: the kernel's identity
+    hipFunction_t jit = nullptr;  // the per-scene build of ls.id, or null: the generic kernel of the world's build ...
+    bool sp = false;              // ... or of the spheres-and-planes build
+};
+
+// Step 3: the generic kernel's plan, then the per-scene build of the same
+// kernel where the launch may take one and it has landed, else the
+// spheres-and-planes build where the world allows it.
+template <typename R>
+int choose_kernel(rt_context* ctx, const DeviceWorld<R>& w, const LaunchRequest& q, uint32_t n_tiles, KernelChoice& k) {
+    int rc;
+    LaunchShape& ls = k.ls;
+    KernelId id;
+    id.family = q.lens ? KernelFamily::lens : q.samples ? KernelFamily::supersampled : KernelFamily::frame;
     // value-equal shapes (rt_scene_upload's identity classes) take the pool
     // kernel whose containers walk aggregates per class
-    const bool dup = ctx->duplicate_shapes > 0;
+    id.dup = ctx->duplicate_shapes > 0;
+    if ((rc = plan_launch<R>(ctx, w.scene, q.depth, n_tiles, id, q.samples, false, ls))) return rc;
     // large f32 frames run the per-scene build of the same kernel (rtc_jit.cpp);
     // a direct one takes the shape records and materials from its instruction
     // stream and is planned with no LDS world (pool builds keep the LDS world:
     // rtc_jit.cpp make_request)
-    hipFunction_t jf = nullptr;
     if constexpr (sizeof(R) == 4) {
         // (the per-scene pool kernel keeps the stamps and item log: a stamped
         // launch times the kernel a warm renderer runs; the direct one has none)
         const uint32_t generic_only =
-            RT_FLAG_NO_SHADE | RT_FLAG_NO_TRACE | RT_FLAG_GENERATIONS | (ls.pool ? 0u : RT_FLAG_STAMPS);
+            RT_FLAG_NO_SHADE | RT_FLAG_NO_TRACE | RT_FLAG_GENERATIONS | (ls.id.pool ? 0u : RT_FLAG_STAMPS);
         // (a world with a triangle hierarchy runs the generic kernels, which walk it)
         const bool instanced = walked_instances(w), smooth = has_smooth(w);
         const bool tree = w.n_tri_nodes > 0 || instanced || smooth || has_textures(w);
@@ -1030,64 +1015,19 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
                            : instanced
                                ? "no per-scene build: the world has mesh instances, which the generic kernels walk"
                                : "no per-scene build: the world has a triangle hierarchy, which the generic kernels walk";
-        const bool want = cam && !dup && !tree && !(flags & generic_only) &&
-                          (ctx->jit.mode == RT_JIT_SYNC || (ctx->jit.mode >= RT_JIT_AUTO && P.n_tiles >= kJitMinTiles));
+        const bool want = q.cam && !id.dup && !tree && !(q.flags & generic_only) &&
+                          (ctx->jit.mode == RT_JIT_SYNC || (ctx->jit.mode >= RT_JIT_AUTO && n_tiles >= kJitMinTiles));
         if (want) {
             ++ctx->jit.frames;
             LaunchShape lj = ls;
-            if (ctx->knobs.lds_world && !ls.pool && w.scene.kind_begin[kNumKinds] <= kJitRecordsMaxShapes &&
-                (rc = plan_launch<R>(ctx, w.scene, depth, P.n_tiles, lj, true, q.samples, lens)))
+            if (ctx->knobs.lds_world && !ls.id.pool && w.scene.kind_begin[kNumKinds] <= kJitRecordsMaxShapes &&
+                (rc = plan_launch<R>(ctx, w.scene, q.depth, n_tiles, id, q.samples, true, lj)))
                 return rc;
             int waves = 0;
-            if ((rc = jit_function(ctx, lj.pool, lj.world_lds != 0, lj.lds, lj.per_cu, &jf,
-                                   (flags & RT_FLAG_NO_SKIPS) != 0, &waves, ss, lens)))
+            if ((rc = jit_function(ctx, lj.id, lj.lds, lj.per_cu, &k.jit, (q.flags & RT_FLAG_NO_SKIPS) != 0, &waves)))
                 return rc;
-            if (jf && waves > 0 && (rc = plan_pool_for<R>(ctx, jf, lj))) return rc;
-            if (jf) ls = lj;
-        }
-    }
-    ctx->jit.used = jf != nullptr;
-    P.pool_capacity = ls.cap;
-    P.pool_lds_capacity = ls.lcap;
-    P.pop_batch = ls.batch;
-    if (ls.pool && (rc = check_pixel_range(ctx, depth, sizeof(R) == 4))) return rc;
-    P.acc_log2 = acc_shift_f32(ctx->bright_hit, ctx->bright_w, depth);
-    if (ls.cap > ls.lcap) {
-        const size_t per_block = (size_t)8 * (ls.cap - ls.lcap) * sizeof(R);
-        if ((rc = ctx->d_spill.reserve((size_t)ls.grid * per_block))) return rc;
-        P.spill = ctx->d_spill.get();
-        P.spill_blocks = (uint32_t)(ctx->d_spill.capacity() / per_block);  // (of a buffer an earlier launch may have sized)
-    }
-    P.persistent = ls.sched;
-    P.flags = flags;
-    P.world_lds = ls.world_lds;
-    // Dynamic launches start from zeroed queue heads with no memset in
-    // between: two sets alternate, both zeroed at context creation, and each
-    // launch zeroes the other set for the next one (trace_pool; the
-    // previous user of that set is complete by stream order).
-    // The set flips only once the launch is enqueued: a launch that fails
-    // before that leaves its set unused and still zero for the next one.
-    // (pool launches only: the direct kernel reads no queue heads)
-    const bool dynamic = ls.pool;
-    if (dynamic) {
-        const size_t set = (size_t)kTileQueues * kQueueStride;
-        P.tile_counter = ctx->d_tile_counter.get() + (ctx->head_set ? set : 0);
-        P.next_tile_counter = ctx->d_tile_counter.get() + (ctx->head_set ? 0 : set);
-        if (ls.pool && ctx->knobs.tile_order && cam) {  // frames only: a ray batch's content is not in the signature
-            if ((rc = plan_tile_order<R>(ctx, lens ? ctx->order_lens : ss ? ctx->order_ss : ctx->order, P, cam, depth,
-                                         ls.grid, stream, q.lens)))
-                return rc;
-        }
-    }
-    if (flags & RT_FLAG_STAMPS) {
-        if ((rc = ctx->d_stamps.reserve((size_t)2 * ls.grid))) return rc;
-        P.stamps = ctx->d_stamps.get();
-        ctx->stamp_count = ls.grid;
-        if (ls.pool) {  // every item of the launch: up to 2^kMaxSplitLog2 per tile
-            const size_t items = (size_t)P.n_tiles << kMaxSplitLog2;
-            if ((rc = ctx->d_item_log.reserve(1 + 3 * items))) return rc;
-            RT_HIP(hipMemsetAsync(ctx->d_item_log.get(), 0, sizeof(uint64_t), stream));
-            P.item_log = ctx->d_item_log.get();
+            if (k.jit && waves > 0 && (rc = plan_pool_for<R>(ctx, k.jit, lj))) return rc;
+            if (k.jit) ls = lj;
         }
     }
     // Worlds of spheres and planes only run the pool kernel built without the
@@ -1097,151 +1037,150 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
     // builds are capped at the same waves/SIMD and use the same LDS, so the
     // occupancy planned above holds.  RTC_DEBUG=kind_variants=0 disables.
     uint32_t kinds = 0;
-    for (int k = 0; k < kNumKinds; ++k)
-        if (w.scene.kind_begin[k + 1] > w.scene.kind_begin[k]) kinds |= 1u << k;
+    for (int kind = 0; kind < kNumKinds; ++kind)
+        if (w.scene.kind_begin[kind + 1] > w.scene.kind_begin[kind]) kinds |= 1u << kind;
     // (supersampled launches: the all-kinds build only)
-    const bool sp = sizeof(R) == 4 && ls.pool && ctx->knobs.kind_variants && (kinds & ~kKindsSp) == 0 && !dup && !ss &&
-                    ctx->kernel_build == KernelBuild::plain;  // (the other builds' worlds hold triangles)
-    if (flags & RT_FLAG_FAIL_LAUNCH) return set_error(RT_ERR_HIP, "launch refused (RT_FLAG_FAIL_LAUNCH)");
-    if constexpr (sizeof(R) == 4) {
-        // The per-scene direct kernel's primary cull: each slot's screen
-        // rectangle for this camera (primary_rect.hpp), from the f32 bounds
-        // the kernel's own ball test reads, as miss bits per block column and
-        // block row (rtc_internal.hpp), and above them the shadow cull's bits
-        // for waves that hit one plane (shadow_rect).  Recomputed every launch
-        // (the camera is the call's argument): a conic per slot and per
-        // (light, plane, caster), well under a microsecond for a small world.
-        const size_t ns = ctx->jit.shapes.size();
-        // (a supersampled launch takes no primary cull: the tables stay zero)
-        const bool small_direct = jf && !ls.pool && cam && !ss && ns <= (size_t)kPrimaryRectSlots &&
-                                  (int)ns == w.scene.kind_begin[kNumKinds];
-        // The same kernel's launch terms (launch_terms.hpp): what its shape
-        // tests form from the origin alone, from the same f32 records, for
-        // any canvas.  A few dozen f32 operations per slot.
-        if (small_direct) launch_terms(ctx->jit.shapes.data(), w.scene.kind_begin, (int)ns, P.cam.origin, P.terms);
-        if (small_direct && P.width <= kCullCols * kCullCellW && P.height <= kCullRows * kCullCellH) {
-            const uint32_t nc = (P.width + kCullCellW - 1) / kCullCellW, nr = (P.height + kCullCellH - 1) / kCullCellH;
-            // Each bit changes at a few edges only, so the tables are built
-            // from toggles: flip_*[i] holds the bits that change value between
-            // entry i - 1 and entry i, and one running XOR fills the entries.
-            uint32_t flip_cols[kCullCols + 1] = {}, flip_rows[kCullRows + 1] = {};
-            // bit `b` set outside the rectangle's block columns and block rows
-            auto outside = [&](const uint32_t r[4], uint32_t b) {
-                const bool none = r[0] > r[2] || r[1] > r[3];  // empty: every block misses
-                const uint32_t c0 = none ? nc : r[0] / kCullCellW, c1 = none ? nc : r[2] / kCullCellW + 1;
-                const uint32_t r0 = none ? nr : r[1] / kCullCellH, r1 = none ? nr : r[3] / kCullCellH + 1;
-                flip_cols[0] ^= b, flip_cols[c0] ^= b, flip_cols[c1] ^= b;
-                flip_rows[0] ^= b, flip_rows[r0] ^= b, flip_rows[r1] ^= b;
-            };
-            for (size_t s = 0; s < ns; ++s) {
-                uint32_t r[4];
-                primary_rect(P.cam, P.width, P.height, ctx->jit.shapes[s].bound, r);
-                outside(r, 1u << s);
-            }
-            // A plane's bit: the blocks where its entry lies behind the eye or
-            // another plane's is nearer (plane_rect), from the records' rows
-            // and the heights the kernel reads (P.terms above).
-            const int p0 = w.scene.kind_begin[RT_SHAPE_PLANE], np = w.scene.kind_begin[RT_SHAPE_PLANE + 1] - p0;
-            if (np > 0) {
-                PlaneView pv;
-                PlaneLine pl[kPrimaryRectSlots];
-                plane_view(P.cam, P.width, P.height, pv);
-                for (int p = 0; p < np; ++p) plane_line(pv, ctx->jit.shapes[p0 + p].inv + 4, P.terms.head[1 + p], pl[p]);
-                for (int p = 0; p < np; ++p) {
-                    uint32_t r[4];
-                    plane_rect(pv, pl, np, p, r);
-                    outside(r, 1u << (p0 + p));
-                }
-            }
-            // The shadow cull's bits (rtc_internal.hpp ShadowLayout), from the
-            // f32 records and lights the per-scene kernel holds as constants.
-            const ShadowLayout lay(w.scene.kind_begin, (int)ctx->jit.lights.size());
-            if (lay.fits() &&(int)ctx->jit.lights.size() == w.scene.n_lights) {
-                for (int p = lay.plane0; p < lay.plane0 + lay.planes; ++p) {
-                    const ShapeRec<float>& pl = ctx->jit.shapes[p];
-                    const float n[3] = {pl.inv[4], pl.inv[5], pl.inv[6]}, h = -pl.inv[7];  // object y = n . x - h
-                    uint32_t near[4] = {0, 0, P.width - 1, P.height - 1};  // the columns and rows within every light's reach
-                    for (int l = 0; l < lay.lights; ++l) {
-                        const float* lp = ctx->jit.lights[l].position;
-                        uint32_t sp[4];
-                        shadow_near(P.cam, P.width, P.height, n, h, lp, sp);
-                        for (int a = 0; a < 2; ++a) {
-                            near[a] = sp[a] > near[a] ? sp[a] : near[a];
-                            near[a + 2] = sp[a + 2] < near[a + 2] ? sp[a + 2] : near[a + 2];
-                        }
-                        for (size_t c = 0; c < ns; ++c) {
-                            const int bit = lay.pair_bit(l, p, (int)c);
-                            if (bit < 0) continue;
-                            if ((int)c == p) {  // the plane itself: every block or none
-                                if (shadow_self_clear(P.cam, n, h, lp)) flip_cols[0] ^= 1u << bit;
-                                continue;
-                            }
-                            uint32_t r[4];
-                            shadow_rect(P.cam, P.width, P.height, n, h, lp, ctx->jit.shapes[c].bound, r);
-                            outside(r, 1u << bit);
-                        }
-                    }
-                    // whole blocks inside the span (the canvas's last, ragged block ends with the canvas)
-                    auto blocks = [](uint32_t lo, uint32_t hi, uint32_t cell, uint32_t pixels, uint32_t& b0, uint32_t& b1) {
-                        b0 = b1 = 0;
-                        if (lo > hi) return;
-                        b0 = (lo + cell - 1) / cell;
-                        b1 = hi + 1 >= pixels ? (pixels + cell - 1) / cell : (hi + 1) / cell;
-                        if (b1 < b0) b1 = b0;
-                    };
-                    const uint32_t nb = 1u << lay.near_bit(p);
-                    uint32_t b0, b1;
-                    blocks(near[0], near[2], kCullCellW, P.width, b0, b1);
-                    flip_cols[b0] ^= nb, flip_cols[b1] ^= nb;
-                    blocks(near[1], near[3], kCullCellH, P.height, b0, b1);
-                    flip_rows[b0] ^= nb, flip_rows[b1] ^= nb;
-                }
-            }
-            uint32_t acc = 0;
-            for (uint32_t i = 0; i < nc; ++i) P.cull_cols[i] = acc ^= flip_cols[i];
-            acc = 0;
-            for (uint32_t j = 0; j < nr; ++j) P.cull_rows[j] = acc ^= flip_rows[j];
-        }
+    k.sp = sizeof(R) == 4 && !k.jit && ls.id.family == KernelFamily::frame && ls.id.pool && !id.dup &&
+           ctx->knobs.kind_variants && (kinds & ~kKindsSp) == 0 &&
+           ctx->kernel_build == KernelBuild::plain;  // (the other builds' worlds hold triangles)
+    return RT_OK;
+}
+
+// Step 4: the pool's spill regions, one per workgroup of the grid.
+template <typename R>
+int reserve_spill(rt_context* ctx, const LaunchShape& ls, LaunchParams<R>& P) {
+    if (ls.cap <= ls.lcap) return RT_OK;
+    const size_t per_block = (size_t)8 * (ls.cap - ls.lcap) * sizeof(R);
+    if (int rc = ctx->d_spill.reserve((size_t)ls.grid * per_block)) return rc;
+    P.spill = ctx->d_spill.get();
+    P.spill_blocks = (uint32_t)(ctx->d_spill.capacity() / per_block);  // (of a buffer an earlier launch may have sized)
+    return RT_OK;
+}
+
+// The tile order a family's launches keep (plan_tile_order).
+inline rt_context::TileOrder& tile_order_of(rt_context* ctx, KernelFamily family) {
+    return family == KernelFamily::lens ? ctx->order_lens : family == KernelFamily::supersampled ? ctx->order_ss : ctx->order;
+}
+
+// Step 5 (pool launches only: the direct kernel reads no queue heads): the
+// launch's set of queue heads and its tile order.
+// Dynamic launches start from zeroed queue heads with no memset in
+// between: two sets alternate, both zeroed at context creation, and each
+// launch zeroes the other set for the next one (trace_pool; the
+// previous user of that set is complete by stream order).
+// The set flips only once the launch is enqueued (launch): a launch that fails
+// before that leaves its set unused and still zero for the next one.
+template <typename R>
+int set_queue_heads(rt_context* ctx, const LaunchRequest& q, const LaunchShape& ls, LaunchParams<R>& P) {
+    const size_t set = (size_t)kTileQueues * kQueueStride;
+    P.tile_counter = ctx->d_tile_counter.get() + (ctx->head_set ? set : 0);
+    P.next_tile_counter = ctx->d_tile_counter.get() + (ctx->head_set ? 0 : set);
+    if (!ctx->knobs.tile_order || !q.cam) return RT_OK;  // frames only: a ray batch's content is not in the signature
+    return plan_tile_order<R>(ctx, tile_order_of(ctx, ls.id.family), P, q.cam, q.depth, ls.grid, q.stream, q.lens);
+}
+
+// Step 6 (RT_FLAG_STAMPS): the workgroups' stamps and a pool launch's item log, reserved behind the tile order.
+template <typename R>
+int reserve_stamps(rt_context* ctx, const LaunchShape& ls, hipStream_t stream, LaunchParams<R>& P) {
+    int rc;
+    if ((rc = ctx->d_stamps.reserve((size_t)2 * ls.grid))) return rc;
+    P.stamps = ctx->d_stamps.get();
+    ctx->stamp_count = ls.grid;
+    if (ls.id.pool) {  // every item of the launch: up to 2^kMaxSplitLog2 per tile
+        const size_t items = (size_t)P.n_tiles << kMaxSplitLog2;
+        if ((rc = ctx->d_item_log.reserve(1 + 3 * items))) return rc;
+        RT_HIP(hipMemsetAsync(ctx->d_item_log.get(), 0, sizeof(uint64_t), stream));
+        P.item_log = ctx->d_item_log.get();
     }
-    if (jf) {
+    return RT_OK;
+}
+
+// The launches that read the launch terms and the cull tables: camera frames
+// of the per-scene f32 direct kernel, not supersampled (those take no primary
+// cull: the tables stay zero), of a world of at most kPrimaryRectSlots slots
+// whose records the per-scene tables hold.
+inline bool reads_launch_tables(const rt_context* ctx, const DeviceWorld<float>& w, const LaunchRequest& q,
+                                const KernelChoice& k) {
+    const size_t ns = ctx->jit.shapes.size();
+    return k.jit && k.ls.id.family == KernelFamily::frame && !k.ls.id.pool && q.cam && ns <= (size_t)kPrimaryRectSlots &&
+           (int)ns == w.scene.kind_begin[kNumKinds];
+}
+
+// Step 7: the per-scene direct kernel's launch terms (launch_terms.hpp): what
+// its shape tests form from the origin alone, from the same f32 records, for
+// any canvas (a few dozen f32 operations per slot); and, for a canvas within
+// them, its cull tables (cull_tables.hpp).
+inline void fill_launch_tables(const rt_context* ctx, const DeviceWorld<float>& w, LaunchParams<float>& P) {
+    const std::vector<ShapeRec<float>>& shapes = ctx->jit.shapes;
+    launch_terms(shapes.data(), w.scene.kind_begin, (int)shapes.size(), P.cam.origin, P.terms);
+    if (!cull_tables_hold(P.width, P.height)) return;
+    // (the shadow bits speak of the lights the kernel holds as constants: none unless those are the world's)
+    const std::vector<LightRec<float>>& lights = ctx->jit.lights;
+    const int n_lights = (int)lights.size() == w.scene.n_lights ? (int)lights.size() : 0;
+    fill_cull_tables(P.cam, P.width, P.height, shapes.data(), shapes.size(), w.scene.kind_begin, lights.data(), n_lights,
+                     P.terms, P.cull_cols, P.cull_rows);
+}
+
+// Step 8: the launch itself, of the per-scene function or of the generic
+// kernel of the world's build (or of the spheres-and-planes build).
+template <typename R>
+int dispatch(rt_context* ctx, const KernelChoice& k, const LaunchParams<R>& P, const LensParams<R>& lens_params,
+             hipStream_t stream) {
+    const LaunchShape& ls = k.ls;
+    if (k.jit) {
         const ShapeRec<R>* sh = P.scene.shapes;
         const MaterialRec<R>* mt = P.scene.materials;
         const PatternRec<R>* pt = P.scene.patterns;
         const LightRec<R>* lt = P.scene.lights;
-        void* args[] = {&P, &sh, &mt, &pt, &lt, &lens_params};  // (the last: read by the lens kernels only)
+        void* args[] = {const_cast<LaunchParams<R>*>(&P), &sh, &mt, &pt, &lt,
+                        const_cast<LensParams<R>*>(&lens_params)};  // (the last: read by the lens kernels only)
         (void)hipGetLastError();
-        RT_HIP(hipModuleLaunchKernel(jf, ls.grid, 1, 1, kBlock, 1, 1, (unsigned)ls.lds, stream, args, nullptr));
-    } else if (hipError_t e = ss   ? launchers<R>(ctx).launch_trace_ss(P, ls.pool, dup, lens ? &lens_params : nullptr, ls.grid,
-                                                                  ls.lds, stream)
-                              : sp ? sp::launch_trace<R>(P, ls.pool, dup, ls.grid, ls.lds, stream)
-                                   : launchers<R>(ctx).launch_trace(P, ls.pool, dup, ls.grid, ls.lds, stream);
-               e != hipSuccess)
-        return set_error(RT_ERR_HIP, std::string("launch of the ") + (lens ? "lens " : ss ? "supersampled " : "") +
-                                         (ls.pool ? "pool" : "direct") + " kernel (grid " +
+        RT_HIP(hipModuleLaunchKernel(k.jit, ls.grid, 1, 1, kBlock, 1, 1, (unsigned)ls.lds, stream, args, nullptr));
+        return RT_OK;
+    }
+    auto launch_kernel = launchers<R>(ctx).launch_kernel;
+    if constexpr (sizeof(R) == 4)
+        if (k.sp) launch_kernel = sp::launch_kernel<R>;
+    if (hipError_t e = launch_kernel(ls.id, P, &lens_params, ls.grid, ls.lds, stream); e != hipSuccess)
+        return set_error(RT_ERR_HIP, std::string("launch of the ") + ls.id.describe() + " kernel (grid " +
                                          std::to_string(ls.grid) + ", dynamic LDS " + std::to_string(ls.lds) +
                                          " B, pool " + std::to_string(ls.lcap) + "/" + std::to_string(ls.cap) +
                                          " rays in LDS): " + hipGetErrorString(e));
-    if (dynamic) ctx->head_set ^= 1;
-    ctx->smooth_info.ran_smooth = !jf && has_smooth(w) ? 1u : 0u;
-    ctx->texture_info.ran_textured = !jf && has_textures(w) ? 1u : 0u;
-    ctx->light_info.ran_area = !jf && has_area(w) ? 1u : 0u;
     return RT_OK;
 }
 
-// Workgroups per CU of the ray-batch kernel (trace_rays) at `lds` dynamic
-// bytes, cached like blocks_per_cu's (keys 8..11 of the same table).
 template <typename R>
-int ray_blocks_per_cu(rt_context* ctx, bool lds_world, size_t lds, int* per_cu) {
-    const int key = 8 + (sizeof(R) == 8 ? 1 : 0) + (lds_world ? 2 : 0);
-    if (ctx->occ_lds[key] == lds && ctx->occ_blocks[key] > 0) {
-        *per_cu = ctx->occ_blocks[key];
-        return RT_OK;
-    }
-    int api = 0;
-    RT_HIP(launchers<R>(ctx).occupancy_rays(lds_world, lds, &api));
-    *per_cu = cap_by_lds(api, lds);
-    ctx->occ_lds[key] = lds;
-    ctx->occ_blocks[key] = *per_cu;
+int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
+    int rc;
+    LaunchParams<R> P{};
+    LensParams<R> lens_params{};  // a lens launch's last kernel argument
+    set_world_params(ctx, w, P);
+    set_target_params(ctx, q, P, lens_params);
+    if (P.n_tiles == 0) return RT_OK;
+    if ((rc = order_after_last(ctx, q.stream))) return rc;
+    KernelChoice k;
+    if ((rc = choose_kernel(ctx, w, q, P.n_tiles, k))) return rc;
+    const LaunchShape& ls = k.ls;
+    ctx->jit.used = k.jit != nullptr;
+    P.pool_capacity = ls.cap;
+    P.pool_lds_capacity = ls.lcap;
+    P.pop_batch = ls.batch;
+    if (ls.id.pool && (rc = check_pixel_range(ctx, q.depth, sizeof(R) == 4))) return rc;
+    P.acc_log2 = acc_shift_f32(ctx->bright_hit, ctx->bright_w, q.depth);
+    if ((rc = reserve_spill(ctx, ls, P))) return rc;
+    P.persistent = ls.sched;
+    P.flags = q.flags;
+    P.world_lds = ls.world_lds;
+    if (ls.id.pool && (rc = set_queue_heads(ctx, q, ls, P))) return rc;
+    if ((q.flags & RT_FLAG_STAMPS) && (rc = reserve_stamps(ctx, ls, q.stream, P))) return rc;
+    if (q.flags & RT_FLAG_FAIL_LAUNCH) return set_error(RT_ERR_HIP, "launch refused (RT_FLAG_FAIL_LAUNCH)");
+    if constexpr (sizeof(R) == 4)
+        if (reads_launch_tables(ctx, w, q, k)) fill_launch_tables(ctx, w, P);
+    if ((rc = dispatch(ctx, k, P, lens_params, q.stream))) return rc;
+    if (ls.id.pool) ctx->head_set ^= 1;  // (the queue heads' set: see set_queue_heads)
+    ctx->smooth_info.ran_smooth = !k.jit && has_smooth(w) ? 1u : 0u;
+    ctx->texture_info.ran_textured = !k.jit && has_textures(w) ? 1u : 0u;
+    ctx->light_info.ran_area = !k.jit && has_area(w) ? 1u : 0u;
     return RT_OK;
 }
 
@@ -1249,16 +1188,17 @@ int ray_blocks_per_cu(rt_context* ctx, bool lds_world, size_t lds, int* per_cu) 
 // (cap = the per-lane LIFO's entries, none of them in LDS), a resident grid
 // striding over the batch's chunks of kBlock rays.
 template <typename R>
-int plan_rays(rt_context* ctx, const DevScene<R>& sc, uint32_t depth, uint32_t n_chunks, LaunchShape& ls) {
-    ls.pool = false;
+int plan_rays(rt_context* ctx, const DevScene<R>& sc, uint32_t depth, uint32_t n_chunks, KernelId id, LaunchShape& ls) {
     const size_t wb = world_lds_bytes<R>(sc.kind_begin[kNumKinds], sc.n_materials, sc.n_patterns);
     ls.world_lds = (ctx->knobs.lds_world && wb <= kMaxWorldLds) ? (uint32_t)wb : 0;
+    id.lds = ls.world_lds != 0;
+    ls.id = id;
     ls.lds = ls.world_lds;
     ls.cap = ray_stack_entries(depth);
     ls.lcap = ls.batch = 0;
     ls.sched = kSchedStatic;
     int per_cu = 0, rc;
-    if ((rc = ray_blocks_per_cu<R>(ctx, ls.world_lds != 0, ls.lds, &per_cu))) return rc;
+    if ((rc = blocks_per_cu<R>(ctx, id, ls.lds, &per_cu))) return rc;
     ls.per_cu = std::max(per_cu, 1);
     const uint64_t resident = (uint64_t)ls.per_cu * (uint64_t)ctx->cu_count;
     ls.grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_chunks, resident));
@@ -1274,12 +1214,7 @@ int launch_rays(rt_context* ctx, DeviceWorld<R>& w, const void* d_rays, uint64_t
                 void* d_rgb, void* d_hits, hipStream_t stream) {
     int rc;
     LaunchParams<R> P{};
-    P.scene = w.scene;
-    P.tri_nodes = w.n_tri_nodes ? w.tri_nodes.get() : nullptr;
-    P.n_tri_nodes = w.n_tri_nodes;
-    P.tri_flat_begin = w.tri_flat_begin;
-    set_instance_params(P, w);
-    if (!ctx->knobs.area_cull) P.area_cull = 0u;
+    set_world_params(ctx, w, P);
     P.n_rays = n;
     P.n_tiles = (uint32_t)((n + kBlock - 1) / kBlock);
     P.max_depth = o->max_depth;
@@ -1289,7 +1224,10 @@ int launch_rays(rt_context* ctx, DeviceWorld<R>& w, const void* d_rays, uint64_t
     if (o->flags & RT_FLAG_GENERATIONS) P.gen_counts = ctx->d_gen_counts.get();
     if ((rc = order_after_last(ctx, stream))) return rc;
     LaunchShape ls;
-    if ((rc = plan_rays<R>(ctx, w.scene, o->max_depth, P.n_tiles, ls))) return rc;
+    KernelId id;
+    id.family = KernelFamily::rays;
+    id.dup = ctx->duplicate_shapes > 0;
+    if ((rc = plan_rays<R>(ctx, w.scene, o->max_depth, P.n_tiles, id, ls))) return rc;
     P.pool_capacity = ls.cap;
     P.persistent = ls.sched;
     P.world_lds = ls.world_lds;
@@ -1303,12 +1241,11 @@ int launch_rays(rt_context* ctx, DeviceWorld<R>& w, const void* d_rays, uint64_t
     }
     ctx->jit.used = false;
     if (o->flags & RT_FLAG_FAIL_LAUNCH) return set_error(RT_ERR_HIP, "launch refused (RT_FLAG_FAIL_LAUNCH)");
-    if (hipError_t e = launchers<R>(ctx).launch_trace_rays(P, ctx->duplicate_shapes > 0, ls.grid, ls.lds, d_rays, d_rgb,
-                                                           d_hits, stream);
-        e != hipSuccess)
-        return set_error(RT_ERR_HIP, "launch of the ray-batch kernel (grid " + std::to_string(ls.grid) +
-                                         ", dynamic LDS " + std::to_string(ls.lds) + " B, " + std::to_string(ls.cap) +
-                                         " stack entries per lane): " + hipGetErrorString(e));
+    const RayBatchArg batch{d_rays, d_rgb, d_hits};
+    if (hipError_t e = launchers<R>(ctx).launch_kernel(ls.id, P, &batch, ls.grid, ls.lds, stream); e != hipSuccess)
+        return set_error(RT_ERR_HIP, std::string("launch of the ") + ls.id.describe() + " kernel (grid " +
+                                         std::to_string(ls.grid) + ", dynamic LDS " + std::to_string(ls.lds) + " B, " +
+                                         std::to_string(ls.cap) + " stack entries per lane): " + hipGetErrorString(e));
     ctx->smooth_info.ran_smooth = has_smooth(w) ? 1u : 0u;
     ctx->texture_info.ran_textured = has_textures(w) ? 1u : 0u;
     ctx->light_info.ran_area = has_area(w) ? 1u : 0u;

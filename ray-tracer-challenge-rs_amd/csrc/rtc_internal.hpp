@@ -560,6 +560,15 @@ struct LensParams {
     LensPoint<R> points[RT_MAX_SAMPLE_GRID * RT_MAX_SAMPLE_GRID];
 };
 
+// A caller's ray batch (rt_trace_rays*) as the host hands it to a launch: the
+// ray-batch kernel's (trace_rays) argument behind the four table pointers,
+// laid out as the kernel's own RayBatch<R> (rtc_kernels.hip, which checks it).
+struct RayBatchArg {
+    const void* rays;  // n_rays x {o, d} of R
+    void* rgb;         // n_rays x 3 of R
+    void* hits;        // n_rays x rt_ray_hit_f32 / rt_ray_hit_f64, or null
+};
+
 // The jitter hash of rtc.h ("Hashed jitter"), uint32_t wraparound.
 RTC_HD inline uint32_t hash_mix(uint32_t x) {
     x ^= x >> 16;
@@ -661,7 +670,7 @@ struct LaunchParams {
     // PatternRec of kind RT_PATTERN_IMAGE holds its texture in sub_a and its
     // filter in sub_b.  `textures` is non-null exactly when the world has an
     // image pattern or a coordinate entry (such a world runs the texture build,
-    // rtc::textured::launch_trace*); read by that build's prepare_hit only.
+    // rtc::textured::launch_kernel); read by that build's prepare_hit only.
     const R* uv_plain;
     const R* uv_inst;
     const uint32_t* texels;
@@ -669,7 +678,7 @@ struct LaunchParams {
     // Area lights (rt_scene_upload_lit; null / 0 for every other world): the
     // records in list order and the sum of their sample counts (what the event
     // counters add to n_lights per shaded hit).  A world with one runs the area
-    // build (rtc::area::launch_trace*); read by that build's shade_ray only.
+    // build (rtc::area::launch_kernel); read by that build's shade_ray only.
     const AreaLightRec<R>* area;
     uint32_t n_area;
     uint32_t area_samples;

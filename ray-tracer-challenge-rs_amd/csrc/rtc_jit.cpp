@@ -362,19 +362,6 @@ std::vector<float> unit_normals(rt_context* ctx) {
     return out;
 }
 
-const char* kernel_name(bool pool, bool lds, bool ss, bool lens) {
-    if (lens) {  // the lens frame kernels: builds of their own again
-        if (pool) return lds ? "rtc::trace_pool_lens<float, true, false>" : "rtc::trace_pool_lens<float, false, false>";
-        return lds ? "rtc::trace_direct_lens<float, true>" : "rtc::trace_direct_lens<float, false>";
-    }
-    if (ss) {  // the supersampled frame kernels: builds of their own, named apart (the disk cache key holds the name)
-        if (pool) return lds ? "rtc::trace_pool_ss<float, true, false>" : "rtc::trace_pool_ss<float, false, false>";
-        return lds ? "rtc::trace_direct_ss<float, true>" : "rtc::trace_direct_ss<float, false>";
-    }
-    if (pool) return lds ? "rtc::trace_pool<float, true, false>" : "rtc::trace_pool<float, false, false>";
-    return lds ? "rtc::trace_direct<float, true>" : "rtc::trace_direct<float, false>";
-}
-
 // Identity of a file: path, size and modification time.
 uint64_t file_identity(const char* path, uint64_t h) {
     struct stat st;
@@ -644,14 +631,16 @@ constexpr int kPool7ScratchMax = 40;
 constexpr int kPoolSsScratchMax = 80;
 
 namespace {
-// One variant's build: *fn stays null while it compiles, if it failed or if
+// One variant's build (kernel `id` with no_skips, for pool_waves = 7 or the
+// static occupancy): *fn stays null while it compiles, if it failed or if
 // it was refused (jit.rejected[variant]).
 // start_only: make sure the build runs (in the background even in
 // RT_JIT_SYNC mode) and return without waiting for it or taking it.
 // scratch_max: the B/lane of scratch a pool build may use (direct: none).
-int jit_variant(rt_context* ctx, int variant, bool pool, bool lds, size_t dyn_lds, int static_blocks,
-                hipFunction_t* fn, bool no_skips, int pool_waves, int scratch_max, bool start_only = false,
-                bool ss = false, bool lens = false) {
+int jit_variant(rt_context* ctx, KernelId id, size_t dyn_lds, int static_blocks, hipFunction_t* fn, bool no_skips,
+                int pool_waves, int scratch_max, bool start_only) {
+    const int variant = id.variant(no_skips, pool_waves == 7);
+    const bool pool = id.pool;
     *fn = nullptr;
     if (ctx->jit.fn[variant]) {
         *fn = ctx->jit.fn[variant];
@@ -689,12 +678,12 @@ int jit_variant(rt_context* ctx, int variant, bool pool, bool lds, size_t dyn_ld
             ctx->jit.owner[variant] = true;
             uint64_t key = 0;
             // (the frame kernel's direct builds alone read the unit normals)
-            const std::vector<float> unit = !pool && !ss ? unit_normals(ctx) : std::vector<float>();
+            const std::vector<float> unit = !pool && !id.sampled() ? unit_normals(ctx) : std::vector<float>();
             const jitfile::Request rq =
                 make_request(scene_header(ctx->jit.shapes, ctx->jit.begin, ctx->jit.lights, ctx->jit.materials,
                                           ctx->jit.patterns,
                                           ctx->jit.pattern_kinds, ctx->jit.transparent, unit),
-                             kernel_name(pool, lds, ss, lens), device_arch(ctx), &key, no_skips, pool_waves);
+                             id.name(), device_arch(ctx), &key, no_skips, pool_waves);
             start_build(b, rq, key, sync && !start_only);
         }
     }
@@ -710,14 +699,14 @@ int jit_variant(rt_context* ctx, int variant, bool pool, bool lds, size_t dyn_ld
         if (b->from_disk) ++ctx->jit.cache_hits;
         ctx->jit.owner[variant] = false;
     }
-    // A failed build of the optional 7-wave variant (bit 8 of the index) refuses
+    // A failed build of the optional 7-wave variant refuses
     // that variant only: jit_function falls back to the static-occupancy
     // build compiled beside it.  A failed base build keeps the generic kernel
     // for this world.
-    // So does a failed supersampled build (bit 16): its launches fall back to
+    // So does a failed supersampled build: its launches fall back to
     // the generic supersampled kernel, and the world's plain frames keep
-    // their per-scene kernels.  A lens build (bit 32) likewise.
-    const bool optional = (variant & (8 | 16 | 32)) != 0;
+    // their per-scene kernels.  A lens build likewise.
+    const bool optional = KernelId::is_optional(variant);
     if (state == 2) {
         (optional ? ctx->jit.rejected[variant] : ctx->jit.failed) = true;
         ctx->jit.log = b->log;
@@ -766,11 +755,10 @@ int jit_variant(rt_context* ctx, int variant, bool pool, bool lds, size_t dyn_ld
     RT_HIP(hipFuncGetAttribute(&scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, mf.second));
     // (RTC_DEBUG=jit_ss_scratch=N: the allowance of a supersampled pool
     // build, for A/B; read here, where a build is judged, once per variant)
-    if (std::string v; ss && pool && debug_knob("jit_ss_scratch", &v)) scratch_max = std::atoi(v.c_str());
+    if (std::string v; id.sampled() && pool && debug_knob("jit_ss_scratch", &v)) scratch_max = std::atoi(v.c_str());
     if (blocks < static_blocks || scratch > (pool ? scratch_max : 0)) {
         ctx->jit.rejected[variant] = true;
-        ctx->jit.log = std::string("per-scene ") + (lens ? "lens " : ss ? "supersampled " : "") + (pool ? "pool" : "direct") +
-                       " kernel not used: " +
+        ctx->jit.log = std::string("per-scene ") + id.describe() + " kernel not used: " +
                        std::to_string(blocks) + " workgroups/CU (generic " + std::to_string(static_blocks) + "), " +
                        std::to_string(scratch) + " B/lane of scratch";
         return RT_OK;
@@ -781,17 +769,14 @@ int jit_variant(rt_context* ctx, int variant, bool pool, bool lds, size_t dyn_ld
 }
 }  // namespace
 
-int jit_function(rt_context* ctx, bool pool, bool lds, size_t dyn_lds, int static_blocks, hipFunction_t* fn,
-                 bool no_skips, int* pool_waves, bool ss, bool lens) {
+int jit_function(rt_context* ctx, KernelId id, size_t dyn_lds, int static_blocks, hipFunction_t* fn, bool no_skips,
+                 int* pool_waves) {
     *fn = nullptr;
     if (pool_waves) *pool_waves = 0;
     if (ctx->jit.failed || ctx->jit.shapes.empty()) return RT_OK;
-    const int variant = (lens ? 32 : 0) + (ss ? 16 : 0) + (no_skips ? 4 : 0) + (pool ? 2 : 0) + (lds ? 1 : 0);
-    if (!pool) return jit_variant(ctx, variant, pool, lds, dyn_lds, static_blocks, fn, no_skips, 0, 0, false, ss, lens);
+    if (!id.pool) return jit_variant(ctx, id, dyn_lds, static_blocks, fn, no_skips, 0, 0, false);
     // (the supersampled and the lens pool kernels: the static occupancy's build alone)
-    if (ss)
-        return jit_variant(ctx, variant, pool, lds, dyn_lds, static_blocks, fn, no_skips, 0, kPoolSsScratchMax, false,
-                           ss, lens);
+    if (id.sampled()) return jit_variant(ctx, id, dyn_lds, static_blocks, fn, no_skips, 0, kPoolSsScratchMax, false);
     // The pool kernel at 7 waves/SIMD (jit_options.hpp) and, compiled beside
     // it, at the static build's occupancy: a 7-wave build that spills more
     // than kPool7ScratchMax is refused and the other is taken (also while the
@@ -800,16 +785,16 @@ int jit_function(rt_context* ctx, bool pool, bool lds, size_t dyn_lds, int stati
     // build is checked against the static plan's LDS (it passes at 6
     // workgroups/CU) and the caller re-plans the pool's LDS for 7
     // (rtc_host.cpp plan_pool_for).
-    int rc = jit_variant(ctx, variant, pool, lds, dyn_lds, static_blocks, fn, no_skips, 0, 16, true);
+    int rc = jit_variant(ctx, id, dyn_lds, static_blocks, fn, no_skips, 0, 16, true);
     if (rc) return rc;
-    rc = jit_variant(ctx, variant + 8, pool, lds, dyn_lds, static_blocks, fn, no_skips, 7, kPool7ScratchMax);
+    rc = jit_variant(ctx, id, dyn_lds, static_blocks, fn, no_skips, 7, kPool7ScratchMax, false);
     if (rc || ctx->jit.failed) return rc;
     if (*fn) {
         if (pool_waves) *pool_waves = 7;
         return RT_OK;
     }
     // (0 waves: the static build's occupancy, as planned)
-    return jit_variant(ctx, variant, pool, lds, dyn_lds, static_blocks, fn, no_skips, 0, 16);
+    return jit_variant(ctx, id, dyn_lds, static_blocks, fn, no_skips, 0, 16, false);
 }
 
 // Block until this context's builds in flight have finished (rt_jit_wait).

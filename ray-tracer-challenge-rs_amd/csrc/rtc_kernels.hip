@@ -38,14 +38,14 @@
 //
 // Kind variants: built a second time with -DRTC_KINDS=<mask of shape kinds>
 // -DRTC_VARIANT=<namespace>, the TU compiles the f32 pool kernel with the
-// shape loops of those kinds only (rtc::<namespace>::launch_trace).  Same
+// shape loops of those kinds only (rtc::<namespace>::launch_kernel).  Same
 // code for the kinds it keeps, so the same pixels; the host uses it for
 // worlds whose kinds it covers (rtc_host.cpp, pool_variant).
 //
 // Instance variant: built with -DRTC_INSTANCES=1 -DRTC_VARIANT=instanced (one TU
 // per precision), the TU compiles every tracer kernel with the instance level
 // of the triangle step and the hit's instance lookup (for_instances,
-// Nearest::hit, prepare_hit) as rtc::instanced::launch_trace*, for worlds uploaded
+// Nearest::hit, prepare_hit) as rtc::instanced::launch_kernel, for worlds uploaded
 // with rt_scene_upload_instanced.  Every other build compiles none of it, so
 // worlds without instances run the kernels they ran before: as a runtime
 // branch the instance level cost the f32 pool kernel 72 B/lane of scratch
@@ -54,7 +54,7 @@
 // Texture variant: built with -DRTC_INSTANCES=1 -DRTC_TEXTURES=1
 // -DRTC_VARIANT=textured (one TU per precision), the instance variant plus the
 // texture code of prepare_hit (a textured triangle's coordinates, image_color)
-// as rtc::textured::launch_trace*, for worlds uploaded with an image pattern or
+// as rtc::textured::launch_kernel, for worlds uploaded with an image pattern or
 // a texture coordinate (rt_scene_upload_textured).  Inside the instance variant
 // the same code, never run there, cost untextured instanced and smooth worlds
 // about 1 % a frame, so that variant compiles none of it.
@@ -63,7 +63,7 @@
 // -DRTC_AREA_LIGHTS=1 -DRTC_VARIANT=area (one TU per precision), the texture
 // variant plus the area lights' sample loop of shade_ray and the ray identity
 // its hashed jitter needs (Shaded::ray_id, set by every tracer kernel) as
-// rtc::area::launch_trace*, for worlds uploaded with an area light
+// rtc::area::launch_kernel, for worlds uploaded with an area light
 // (rt_scene_upload_lit).  Every line of it sits behind RTC_AREA_LIGHTS, so the
 // other builds compile to what they compiled to before.
 #ifndef RTC_INSTANCES
@@ -85,6 +85,11 @@
 #endif
 
 #include "rtc_internal.hpp"
+#ifndef RTC_JIT  // (the launchers at the end of the file: no part of a per-scene build)
+#include <cstddef>
+
+#include "kernel_id.hpp"
+#endif
 
 namespace rtc {
 #ifdef RTC_VARIANT
@@ -3724,169 +3729,82 @@ __global__ void debug_shape(const ShapeRec<R>* __restrict__ shapes, int slot, in
 }
 
 // ------------------------------------------------------------ launchers
+// The kernel of an identity (kernel_id.hpp) in this build, null where the
+// build does not hold it: the one place in the host part of this file that
+// names the tracer kernels' instantiations.
 template <typename R>
-hipError_t launch_trace(const LaunchParams<R>& P, bool pool, bool dup, uint32_t grid, size_t dyn_lds,
-                        hipStream_t stream) {
-    // hipLaunchKernelGGL reports through hipGetLastError(): drop any stale
+const void* kernel_of(KernelId id) {
+#define RTC_FN(...) reinterpret_cast<const void*>(&__VA_ARGS__)
+#define RTC_DIRECT_OF(K) (id.lds ? RTC_FN(K<R, true>) : RTC_FN(K<R, false>))
+#define RTC_POOL_OF(K)                                                            \
+    (id.lds ? (id.dup ? RTC_FN(K<R, true, true>) : RTC_FN(K<R, true, false>)) \
+            : (id.dup ? RTC_FN(K<R, false, true>) : RTC_FN(K<R, false, false>)))
+#ifdef RTC_POOL_ONLY
+    // a kind variant: the frame pool kernel alone, and worlds with value-equal shapes use the all-kinds build.
+    // (The object has always held trace_direct<R, *> as well, which no launch can reach; they are named
+    // here, unused, only so that its kernel symbols stay what they were.  Dropping them changes the set.)
+    if (id.family != KernelFamily::frame || !id.pool || id.dup) return (void)RTC_DIRECT_OF(trace_direct), nullptr;
+    return id.lds ? RTC_FN(trace_pool<R, true, false>) : RTC_FN(trace_pool<R, false, false>);
+#else
+    switch (id.family) {
+        case KernelFamily::frame: return id.pool ? RTC_POOL_OF(trace_pool) : RTC_DIRECT_OF(trace_direct);
+        case KernelFamily::supersampled: return id.pool ? RTC_POOL_OF(trace_pool_ss) : RTC_DIRECT_OF(trace_direct_ss);
+        case KernelFamily::lens: return id.pool ? RTC_POOL_OF(trace_pool_lens) : RTC_DIRECT_OF(trace_direct_lens);
+        case KernelFamily::rays: return id.pool ? nullptr : RTC_POOL_OF(trace_rays);
+    }
+    return nullptr;
+#endif
+#undef RTC_POOL_OF
+#undef RTC_DIRECT_OF
+#undef RTC_FN
+}
+
+// One launch of kernel `id`.  `extra`: the kernel's argument behind the four
+// table pointers, the RayBatchArg of a ray batch (RayBatch<R>'s bytes) or the
+// LensParams<R> of a lens frame; the other kernels have none and read none.
+static_assert(sizeof(RayBatchArg) == sizeof(RayBatch<float>) && sizeof(RayBatchArg) == sizeof(RayBatch<double>) &&
+              offsetof(RayBatchArg, rgb) == offsetof(RayBatch<float>, rgb) && offsetof(RayBatchArg, hits) == offsetof(RayBatch<double>, hits));
+template <typename R>
+hipError_t launch_kernel(KernelId id, const LaunchParams<R>& P, const void* extra, uint32_t grid, size_t dyn_lds,
+                         hipStream_t stream) {
+    const void* kernel = kernel_of<R>(id);
+    if (!kernel) return hipErrorInvalidValue;
+    // The launch reports through hipGetLastError(): drop any stale
     // error first (every earlier call's own status is checked by the host).
     (void)hipGetLastError();
-    const bool lds = P.world_lds != 0;
-#define RTC_LAUNCH(K, ...)                                                                                \
-    hipLaunchKernelGGL((K<R, __VA_ARGS__>), dim3(grid), dim3(kBlock), dyn_lds, stream, P, P.scene.shapes,         \
-                       P.scene.materials, P.scene.patterns, P.scene.lights)
-    if (pool) {
-#ifdef RTC_POOL_ONLY
-        if (dup) return hipErrorInvalidValue;  // worlds with value-equal shapes use the all-kinds build
-        if (lds) RTC_LAUNCH(trace_pool, true, false);
-        else RTC_LAUNCH(trace_pool, false, false);
-#else
-        if (lds) {
-            if (dup) RTC_LAUNCH(trace_pool, true, true);
-            else RTC_LAUNCH(trace_pool, true, false);
-        } else {
-            if (dup) RTC_LAUNCH(trace_pool, false, true);
-            else RTC_LAUNCH(trace_pool, false, false);
-        }
-#endif
-    } else {
-#ifdef RTC_POOL_ONLY
-        return hipErrorInvalidValue;  // kind variants hold the pool kernel only
-#else
-        if (lds) RTC_LAUNCH(trace_direct, true);
-        else RTC_LAUNCH(trace_direct, false);
-#endif
-    }
-#undef RTC_LAUNCH
+    const ShapeRec<R>* shapes = P.scene.shapes;
+    const MaterialRec<R>* materials = P.scene.materials;
+    const PatternRec<R>* patterns = P.scene.patterns;
+    const LightRec<R>* lights = P.scene.lights;
+    void* args[] = {const_cast<LaunchParams<R>*>(&P), &shapes, &materials, &patterns, &lights, const_cast<void*>(extra)};
+    (void)hipLaunchKernel(kernel, dim3(grid), dim3(kBlock), args, dyn_lds, stream);
     return hipGetLastError();
 }
 
 template <typename R>
-hipError_t occupancy(bool pool, bool lds, size_t dyn_lds, int* blocks_per_cu) {
-    if (pool)
-        return lds ? hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, trace_pool<R, true, false>, kBlock,
-                                                                  dyn_lds)
-                   : hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, trace_pool<R, false, false>, kBlock,
-                                                                  dyn_lds);
-#ifdef RTC_POOL_ONLY
-    return hipErrorInvalidValue;
-#endif
-    return lds ? hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, trace_direct<R, true>, kBlock, dyn_lds)
-               : hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, trace_direct<R, false>, kBlock, dyn_lds);
+hipError_t kernel_occupancy(KernelId id, size_t dyn_lds, int* blocks_per_cu) {
+    // (always of the dup = false instantiation: launches of the dup = true one are planned with its answer)
+    id.dup = false;
+    const void* kernel = kernel_of<R>(id);
+    if (!kernel) return hipErrorInvalidValue;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, kernel, kBlock, dyn_lds);
 }
 
 #if RTC_PRECISION != 2
-template hipError_t launch_trace<float>(const LaunchParams<float>&, bool, bool, uint32_t, size_t, hipStream_t);
-template hipError_t occupancy<float>(bool, bool, size_t, int*);
+template hipError_t launch_kernel<float>(KernelId, const LaunchParams<float>&, const void*, uint32_t, size_t, hipStream_t);
+template hipError_t kernel_occupancy<float>(KernelId, size_t, int*);
 #endif
 #ifndef RTC_POOL_ONLY
 #if RTC_PRECISION != 1
-template hipError_t launch_trace<double>(const LaunchParams<double>&, bool, bool, uint32_t, size_t, hipStream_t);
-template hipError_t occupancy<double>(bool, bool, size_t, int*);
-#endif
-
-// The ray-batch kernel (trace_rays): `rays`, `rgb` and `hits` in R.
-template <typename R>
-hipError_t launch_trace_rays(const LaunchParams<R>& P, bool dup, uint32_t grid, size_t dyn_lds, const void* rays,
-                             void* rgb, void* hits, hipStream_t stream) {
-    (void)hipGetLastError();  // see launch_trace
-    const RayBatch<R> B{static_cast<const R*>(rays), static_cast<R*>(rgb), hits};
-#define RTC_LAUNCH(...)                                                                                      \
-    hipLaunchKernelGGL((trace_rays<R, __VA_ARGS__>), dim3(grid), dim3(kBlock), dyn_lds, stream, P, P.scene.shapes, \
-                       P.scene.materials, P.scene.patterns, P.scene.lights, B)
-    if (P.world_lds != 0) {
-        if (dup) RTC_LAUNCH(true, true);
-        else RTC_LAUNCH(true, false);
-    } else {
-        if (dup) RTC_LAUNCH(false, true);
-        else RTC_LAUNCH(false, false);
-    }
-#undef RTC_LAUNCH
-    return hipGetLastError();
-}
-
-template <typename R>
-hipError_t occupancy_rays(bool lds, size_t dyn_lds, int* blocks_per_cu) {
-    return lds ? hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, trace_rays<R, true, false>, kBlock, dyn_lds)
-               : hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, trace_rays<R, false, false>, kBlock,
-                                                              dyn_lds);
-}
-#if RTC_PRECISION != 2
-template hipError_t launch_trace_rays<float>(const LaunchParams<float>&, bool, uint32_t, size_t, const void*, void*,
-                                             void*, hipStream_t);
-template hipError_t occupancy_rays<float>(bool, size_t, int*);
-#endif
-#if RTC_PRECISION != 1
-template hipError_t launch_trace_rays<double>(const LaunchParams<double>&, bool, uint32_t, size_t, const void*, void*,
-                                              void*, hipStream_t);
-template hipError_t occupancy_rays<double>(bool, size_t, int*);
-#endif
-
-// The supersampled frame kernels (trace_direct_ss, trace_pool_ss) and, with
-// `lens`, the lens frame kernels (trace_direct_lens, trace_pool_lens): the
-// all-kinds builds only.
-template <typename R>
-hipError_t launch_trace_ss(const LaunchParams<R>& P, bool pool, bool dup, const LensParams<R>* lens, uint32_t grid,
-                           size_t dyn_lds, hipStream_t stream) {
-    (void)hipGetLastError();  // see launch_trace
-    const bool lds = P.world_lds != 0;
-#define RTC_LAUNCH_FRAME(DIRECT, POOL, ...)                      \
-    if (pool) {                                                 \
-        if (lds) {                                              \
-            if (dup) RTC_LAUNCH((POOL<R, true, true>), __VA_ARGS__);  \
-            else RTC_LAUNCH((POOL<R, true, false>), __VA_ARGS__);     \
-        } else {                                                \
-            if (dup) RTC_LAUNCH((POOL<R, false, true>), __VA_ARGS__); \
-            else RTC_LAUNCH((POOL<R, false, false>), __VA_ARGS__);    \
-        }                                                       \
-    } else {                                                    \
-        if (lds) RTC_LAUNCH((DIRECT<R, true>), __VA_ARGS__);    \
-        else RTC_LAUNCH((DIRECT<R, false>), __VA_ARGS__);       \
-    }
-    if (lens) {
-#define RTC_LAUNCH(K, ...)                                                                              \
-    hipLaunchKernelGGL(K, dim3(grid), dim3(kBlock), dyn_lds, stream, P, P.scene.shapes, P.scene.materials, \
-                       P.scene.patterns, P.scene.lights, __VA_ARGS__)
-        RTC_LAUNCH_FRAME(trace_direct_lens, trace_pool_lens, *lens)
-#undef RTC_LAUNCH
-    } else {
-#define RTC_LAUNCH(K, ...)                                                                              \
-    hipLaunchKernelGGL(K, dim3(grid), dim3(kBlock), dyn_lds, stream, P, P.scene.shapes, P.scene.materials, \
-                       P.scene.patterns, P.scene.lights)
-        RTC_LAUNCH_FRAME(trace_direct_ss, trace_pool_ss, 0)
-#undef RTC_LAUNCH
-    }
-#undef RTC_LAUNCH_FRAME
-    return hipGetLastError();
-}
-
-template <typename R>
-hipError_t occupancy_ss(bool pool, bool lds, bool lens, size_t dyn_lds, int* blocks_per_cu) {
-#define RTC_OCCUPANCY(K) hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, K, kBlock, dyn_lds)
-    if (lens) {
-        if (pool)
-            return lds ? RTC_OCCUPANCY((trace_pool_lens<R, true, false>)) : RTC_OCCUPANCY((trace_pool_lens<R, false, false>));
-        return lds ? RTC_OCCUPANCY((trace_direct_lens<R, true>)) : RTC_OCCUPANCY((trace_direct_lens<R, false>));
-    }
-    if (pool) return lds ? RTC_OCCUPANCY((trace_pool_ss<R, true, false>)) : RTC_OCCUPANCY((trace_pool_ss<R, false, false>));
-    return lds ? RTC_OCCUPANCY((trace_direct_ss<R, true>)) : RTC_OCCUPANCY((trace_direct_ss<R, false>));
-#undef RTC_OCCUPANCY
-}
-#if RTC_PRECISION != 2
-template hipError_t launch_trace_ss<float>(const LaunchParams<float>&, bool, bool, const LensParams<float>*, uint32_t, size_t,
-                                           hipStream_t);
-template hipError_t occupancy_ss<float>(bool, bool, bool, size_t, int*);
-#endif
-#if RTC_PRECISION != 1
-template hipError_t launch_trace_ss<double>(const LaunchParams<double>&, bool, bool, const LensParams<double>*, uint32_t,
-                                            size_t, hipStream_t);
-template hipError_t occupancy_ss<double>(bool, bool, bool, size_t, int*);
+template hipError_t launch_kernel<double>(KernelId, const LaunchParams<double>&, const void*, uint32_t, size_t, hipStream_t);
+template hipError_t kernel_occupancy<double>(KernelId, size_t, int*);
 #endif
 
 #if RTC_PRECISION != 2 && !RTC_INSTANCES
 hipError_t launch_order_tiles(uint32_t* cost, uint32_t* order, uint32_t n, uint32_t* n_items, float split_per_cost,
                               uint32_t max_split_log2, float urgent_per_cost, uint32_t graded, uint32_t min_split_log2,
                               hipStream_t stream) {
-    (void)hipGetLastError();  // see launch_trace
+    (void)hipGetLastError();  // see launch_kernel
     hipLaunchKernelGGL(order_tiles, dim3(1), dim3(kOrderThreads), 0, stream, cost, order, n, n_items, split_per_cost,
                        max_split_log2, urgent_per_cost, graded, min_split_log2);
     return hipGetLastError();
@@ -3897,7 +3815,7 @@ hipError_t launch_order_tiles(uint32_t* cost, uint32_t* order, uint32_t n, uint3
 template <typename R>
 hipError_t launch_debug_shape(const ShapeRec<R>* shapes, int slot, int kind, uint32_t mode, uint32_t world_space,
                               const double* in, uint32_t n, double* out, hipStream_t stream) {
-    (void)hipGetLastError();  // see launch_trace
+    (void)hipGetLastError();  // see launch_kernel
     hipLaunchKernelGGL(debug_shape<R>, dim3((n + 255) / 256), dim3(256), 0, stream, shapes, slot, kind, mode,
                        world_space, in, n, out);
     return hipGetLastError();
@@ -3929,18 +3847,18 @@ __global__ void unit_vectors(const float* __restrict__ in, float* __restrict__ o
     out[3 * i + 2] = v.z;
 }
 hipError_t launch_unit_vectors(const float* in, float* out, uint32_t n, hipStream_t stream) {
-    (void)hipGetLastError();  // see launch_trace
+    (void)hipGetLastError();  // see launch_kernel
     hipLaunchKernelGGL(unit_vectors, dim3(1), dim3(64), 0, stream, in, out, n);
     return hipGetLastError();
 }
 hipError_t launch_canvas_signal(unsigned long long* flag, unsigned long long seq, hipStream_t stream) {
-    (void)hipGetLastError();  // see launch_trace
+    (void)hipGetLastError();  // see launch_kernel
     hipLaunchKernelGGL(canvas_signal, dim3(1), dim3(64), 0, stream, flag, seq);
     return hipGetLastError();
 }
 hipError_t launch_canvas_wait(const unsigned long long* flags, uint32_t n, unsigned long long seq,
                               unsigned long long timeout_ticks, int32_t* err, hipStream_t stream) {
-    (void)hipGetLastError();  // see launch_trace
+    (void)hipGetLastError();  // see launch_kernel
     hipLaunchKernelGGL(canvas_wait, dim3(1), dim3(64), 0, stream, flags, n, seq, timeout_ticks, err);
     return hipGetLastError();
 }
@@ -3949,7 +3867,7 @@ hipError_t launch_canvas_wait(const unsigned long long* flags, uint32_t n, unsig
 #if RTC_PRECISION != 2 && !RTC_INSTANCES
 hipError_t launch_assemble(const void* gathered, void* image, uint32_t width, uint32_t height, uint32_t shards,
                            uint32_t strip_rows, uint32_t bpp, hipStream_t stream) {
-    (void)hipGetLastError();  // see launch_trace
+    (void)hipGetLastError();  // see launch_kernel
     const uint64_t row_bytes = (uint64_t)width * bpp;
     const bool wide = ((row_bytes | (uintptr_t)gathered | (uintptr_t)image) & 15) == 0;
     const uint64_t per_row = wide ? (row_bytes / 16 + 255) / 256 : 4;  // blocks per row (kernel's two paths)
