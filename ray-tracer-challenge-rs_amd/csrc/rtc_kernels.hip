@@ -2675,44 +2675,66 @@ struct WaveTile {
     uint32_t row0;  // its first row in the shard's strip ...
     uint32_t y0;    // ... and in the image (shard_image_row(row0): a block lies within one tile row)
 };
-template <typename R>
-__device__ inline WaveTile wave_tile(const LaunchParams<R>& P, uint32_t t) {
+// (W: where the launch's words are read, LaunchParams or the iteration's TileHead below)
+template <typename W>
+__device__ inline WaveTile wave_tile(const W& P, uint32_t t) {
     constexpr uint32_t kPerRow = RT_TILE_W / RTC_WAVE_W, kWaveH = 64 / RTC_WAVE_W;
-    const TileAt at = tile_at(P, t);
+    const uint32_t lrow = div_by(t, P.tiles_x, P.tiles_x_magic);
+    const TileAt at = {lrow, t - lrow * P.tiles_x};  // (tile_at)
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x / 64);
     const uint32_t wrow = (wave / kPerRow) * kWaveH;
     return {at.tcol * RT_TILE_W + (wave % kPerRow) * RTC_WAVE_W, at.lrow * RT_TILE_H + wrow,
             shard_tile_image_row(at.lrow, P.shard_count, P.shard_index) + wrow};
 }
-template <typename R>
-__device__ inline bool wave_tile_pixel(const LaunchParams<R>& P, const WaveTile& w, uint32_t lane, uint32_t& x,
-                                       uint32_t& y, uint64_t& out_idx) {
+template <typename W>
+__device__ inline bool wave_tile_pixel(const W& P, const WaveTile& w, uint32_t lane, uint32_t& x, uint32_t& y,
+                                       uint64_t& out_idx) {
     const uint32_t ly = lane / RTC_WAVE_W;
     x = w.x0 + lane % RTC_WAVE_W;
     y = w.y0 + ly;
     out_idx = (uint64_t)((P.image_rows ? w.y0 : w.row0) + ly) * P.width + x;
     return x < P.width && y < P.height;
 }
+// (in two steps for a caller with work to put between the loads and the wait:
+// fetch_pixel_block issues them, hold_pixel_block is where they are waited for)
 template <typename R>
-__device__ inline PixelBlock wave_pixel_block(const LaunchParams<R>& P, const WaveTile& w) {
+constexpr bool kBlockHeights = RTC_LAUNCH_TERMS && sizeof(R) == 4 && jit::kBegin[kNumKinds] <= kPrimaryRectSlots;
+struct PixelBlockWords {
+    uint32_t cols, rows;  // the column's and the row's miss bits, apart: their OR waits for both
+    float head[PixelBlock::kHead];
+};
+template <typename R>
+__device__ inline PixelBlockWords fetch_pixel_block(const LaunchParams<R>& P, const WaveTile& w) {
     constexpr uint32_t kWaveH = 64 / RTC_WAVE_W;
-    PixelBlock block = {0u, {}};
+    PixelBlockWords words = {0u, 0u, {}};
     // the head of this launch's terms, beside the cull words: one wait for both
-    constexpr bool kHeights = RTC_LAUNCH_TERMS && sizeof(R) == 4 && jit::kBegin[kNumKinds] <= kPrimaryRectSlots;
-    if constexpr (kHeights)
-        for (int i = 0; i < PixelBlock::kHead; ++i) block.head[i] = P.terms.head[i];
-    if constexpr (RTC_WAVE_W != kCullCellW || kWaveH != kCullCellH || RT_TILE_H % kCullCellH != 0) return block;
+    if constexpr (kBlockHeights<R>)
+        for (int i = 0; i < PixelBlock::kHead; ++i) words.head[i] = P.terms.head[i];
+    if constexpr (RTC_WAVE_W != kCullCellW || kWaveH != kCullCellH || RT_TILE_H % kCullCellH != 0) return words;
     const uint32_t cx = w.x0 / kCullCellW, cy = w.y0 / kCullCellH;
     // (indices masked into the tables: a block with a pixel on a canvas the
     // tables cover is in range as it is; a canvas beyond them has them all
     // zero, and a ragged tile's blocks past the canvas have no pixels)
     static_assert((kCullCols & (kCullCols - 1)) == 0 && (kCullRows & (kCullRows - 1)) == 0);
-    block.miss = P.cull_cols[cx & (kCullCols - 1)] | P.cull_rows[cy & (kCullRows - 1)];
+    words.cols = P.cull_cols[cx & (kCullCols - 1)];
+    words.rows = P.cull_rows[cy & (kCullRows - 1)];
+    return words;
+}
+template <typename R>
+__device__ inline PixelBlock hold_pixel_block(const PixelBlockWords& words) {
+    constexpr uint32_t kWaveH = 64 / RTC_WAVE_W;
+    PixelBlock block = {words.cols | words.rows, {}};
+    for (int i = 0; i < PixelBlock::kHead; ++i) block.head[i] = words.head[i];
+    if constexpr (RTC_WAVE_W != kCullCellW || kWaveH != kCullCellH || RT_TILE_H % kCullCellH != 0) return block;
     // (held from here on: the compiler would sink each load to its plane's test)
     asm volatile("" : "+s"(block.miss));
-    if constexpr (kHeights)
+    if constexpr (kBlockHeights<R>)
         for (int i = 0; i < PixelBlock::kHead; ++i) asm volatile("" : "+s"(block.head[i]));
     return block;
+}
+template <typename R>
+__device__ inline PixelBlock wave_pixel_block(const LaunchParams<R>& P, const WaveTile& w) {
+    return hold_pixel_block<R>(fetch_pixel_block(P, w));
 }
 #endif
 
@@ -2924,6 +2946,139 @@ __device__ inline const LensParams<R>& kernarg_lens() {
 #ifndef RTC_TILE_DECODE
 #define RTC_TILE_DECODE 1  // (A/B builds: 0 decodes the tile for the pixel and again for the block)
 #endif
+// The head and tail of the per-scene f32 direct kernel's tile loop (A/B
+// builds: -D...=0 turns each off).
+#ifndef RTC_HEAD_CLAUSE
+#define RTC_HEAD_CLAUSE 1  // the iteration's launch words in one load clause (TileHead)
+#endif
+#ifndef RTC_EDGE_CLAMP
+#define RTC_EDGE_CLAMP 1  // lanes past the canvas edge trace the clamped pixel: no exec masks round ray and shading
+#endif
+#if defined(RTC_JIT) && RTC_TILE_DECODE
+// The launch words one iteration of the tile loop reads, in its head (the
+// bound, the decode, the canvas), its tail (the store) and its latch (the grid
+// stride): loaded together at the top of the iteration and held in SGPRs, one
+// wait for all of them, where each load behind the branch that uses it was a
+// scalar-cache round trip of its own on a wave's critical path (a workgroup
+// runs 2-3 tiles).  The camera depends on nothing the decode works out, so it
+// comes in the same clause (f32: camera_ray reads no translation, which is
+// not loaded); the block's cull words, whose addresses the decode forms, and
+// the launch's terms beside them are the iteration's second and last wait
+// (wave_pixel_block).  The fields carry LaunchParams' names, so the decode
+// (wave_tile, wave_tile_pixel) and camera_ray read either.  In the loop, not
+// in front of it: held across iterations the words cost more than they save
+// (DESIGN.md 3.3a).
+template <typename R>
+struct TileHead {
+    void* out;
+    uint32_t out_format, width, height, tiles_x, image_rows, shard_index, shard_count, n_tiles;
+    uint32_t tiles_x_magic;
+    uint32_t stride;    // gridDim.x
+    uint32_t n_lights;  // DevScene::n_lights (the counters)
+    CameraRec<R> cam;
+};
+template <typename R>
+__device__ inline TileHead<R> tile_head(const LaunchParams<R>& P) {
+    static_assert(sizeof(R) == 4);
+    TileHead<R> h = {P.out,         P.out_format,  P.width,   P.height,        P.tiles_x,  P.image_rows,
+                     P.shard_index, P.shard_count, P.n_tiles, P.tiles_x_magic, gridDim.x, (uint32_t)P.scene.n_lights,
+                     {}};
+    const CameraRec<R>& c = P.cam;
+    h.cam = {{c.inv[0], c.inv[1], c.inv[2], 0, c.inv[4], c.inv[5], c.inv[6], 0, c.inv[8], c.inv[9], c.inv[10], 0},
+             {c.origin[0], c.origin[1], c.origin[2]}, c.half_width, c.half_height, c.pixel_size};
+    // (inputs of one empty statement: every load is issued and waited for in front of it)
+    asm volatile("" ::"s"(h.out), "s"(h.out_format), "s"(h.width), "s"(h.height), "s"(h.tiles_x), "s"(h.image_rows),
+                 "s"(h.shard_index), "s"(h.shard_count), "s"(h.n_tiles), "s"(h.tiles_x_magic), "s"(h.stride),
+                 "s"(h.n_lights), "s"(h.cam.inv[0]), "s"(h.cam.inv[1]), "s"(h.cam.inv[2]), "s"(h.cam.inv[4]),
+                 "s"(h.cam.inv[5]), "s"(h.cam.inv[6]), "s"(h.cam.inv[8]), "s"(h.cam.inv[9]), "s"(h.cam.inv[10]),
+                 "s"(h.cam.origin[0]), "s"(h.cam.origin[1]), "s"(h.cam.origin[2]), "s"(h.cam.half_width),
+                 "s"(h.cam.half_height), "s"(h.cam.pixel_size));
+    return h;
+}
+
+// count_events for a wave whose lanes all traced a ray, the lanes of `on`
+// (a ballot) those of pixels on the canvas: the others are counted nowhere.
+// The masks are met as scalars where every lane has arrived.
+template <typename R>
+__device__ inline void count_events_on(Counts& k, unsigned long long on, bool hit, const Shaded<R>& sh, int n_lights) {
+#if RTC_AREA_LIGHTS
+    n_lights += (int)kernarg_params<R>().area_samples;
+#endif
+    auto count = [on](bool p) { return (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(p) & on); };
+    k.c[0] += (uint32_t)__builtin_popcountll(on);
+    const uint32_t shaded = count(hit);
+    k.c[4] += shaded;
+    k.c[1] += shaded * (uint32_t)n_lights;
+    k.c[5] += count(hit & sh.patterned) * (uint32_t)n_lights;
+    k.c[2] += count(hit & sh.refl_child);
+    k.c[3] += count(hit & sh.refr_child);
+    k.c[6] += count(hit & sh.refr_eval);
+    k.c[7] += count(hit & sh.schlick);
+}
+
+// One tile of the per-scene direct kernel: the wave's 16 x 4 block of it.  L:
+// the launch words (TileHead, or P itself in RTC_HEAD_CLAUSE=0 builds).
+//
+// f32, RTC_EDGE_CLAMP: a block with no pixel on the canvas does nothing; in
+// every other block each lane traces pixel (min(x, width-1), min(y, height-1))
+// and `valid` guards only the store and the counters.  The invariant: a
+// clamped lane's pixel is a valid lane's pixel of the same block (the block's
+// first pixel is on the canvas, so width-1 and height-1 lie in the block's
+// columns and rows whenever a lane is clamped to them).  So every wave-level
+// decision (the ballots of the culls, the wave-uniform-hit test, the block's
+// cull words, the shadow rectangles) sees the same set of rays as with the
+// lanes masked off and decides the same way.
+template <typename R, typename W>
+__device__ inline void direct_tile(const W& L, const LaunchParams<R>& P, const DevScene<R>& sc, uint32_t t, Counts& k,
+                                   int n_lights) {
+    constexpr bool kClamp = RTC_EDGE_CLAMP && sizeof(R) == 4;
+    const uint32_t lane = threadIdx.x % 64;
+    const WaveTile wt = wave_tile(L, t);
+    if constexpr (kClamp) {
+        // wave-uniform (the loop holds no barrier).  Both differences wrap to a set top bit exactly
+        // when x0 < width and y0 < height (coordinates and sizes are below 2^31): one test, one branch
+        if ((int32_t)((wt.x0 - L.width) & (wt.y0 - L.height)) >= 0) return;
+    }
+    // (the block's words are on their way while the lanes form their rays)
+    PixelBlockWords words;
+    if constexpr (kClamp) words = fetch_pixel_block(P, wt);
+    uint32_t x, y;
+    uint64_t out_idx;
+    const bool valid = wave_tile_pixel(L, wt, lane, x, y, out_idx);
+    V3<R> o, d;
+    unsigned long long on = 0;
+    if constexpr (kClamp) {
+        // (a ballot per compare: each is the compare's own mask, and `valid` their AND)
+        on = __builtin_amdgcn_ballot_w64(x < L.width) & __builtin_amdgcn_ballot_w64(y < L.height);
+        x = x < L.width - 1 ? x : L.width - 1;
+        y = y < L.height - 1 ? y : L.height - 1;
+        camera_ray(L.cam, x, y, o, d);
+    } else {
+        if (valid) camera_ray(L.cam, x, y, o, d);
+    }
+    // (the origin is the launch's, whatever the lane: a wave-uniform value the compiler keeps in SGPRs)
+    o = {L.cam.origin[0], L.cam.origin[1], L.cam.origin[2]};
+    V3<R> c = {(R)0, (R)0, (R)0};
+    Shaded<R> sh;
+    bool hit = false;
+#if RTC_AREA_LIGHTS
+    sh.ray_id = y * L.width + x;  // (primary_ray_id of the traced pixel)
+#endif
+    PixelBlock block;
+    if constexpr (kClamp) block = hold_pixel_block<R>(words);
+    if (kClamp || valid) {
+        if constexpr (!kClamp) block = wave_pixel_block(P, wt);
+        if (shade_ray<R, false>(sc, o, d, 0, sh, NoPush{}, block)) {
+            hit = true;
+            c = sh.surface;
+        }
+    }
+    if constexpr (kClamp) count_events_on(k, on, hit, sh, n_lights);
+    else count_events(k, valid, hit, sh, n_lights);
+    if (valid) store_pixel(P, out_idx, c);
+}
+#endif
+
 template <typename R, bool kLds>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(sizeof(R) == 4 ? RTC_DIRECT_WAVES : 1))) void trace_direct(
     LaunchParams<R> P, RTC_WORLD_PARAMS(R)) {
@@ -2943,6 +3098,23 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(sizeof(R
     // workgroup, with G = resident workgroups (kSchedStatic) a persistent
     // grid.  Primary-only tiles cost the same, so no queue is needed, and the
     // tile index is an SGPR by construction (loop control stays scalar).
+#if defined(RTC_JIT) && RTC_TILE_DECODE
+    // (camera frames only, rtc_host.cpp launch: one decode of the tile per wave, direct_tile)
+    for (uint32_t t = blockIdx.x;;) {
+        const LaunchParams<R>& P = kernarg_params<R>();
+        const DevScene<R> sc = scene_view<R, kLds>(P, shapes, materials, patterns, lights, smem);
+        if constexpr (RTC_HEAD_CLAUSE && sizeof(R) == 4) {
+            const TileHead<R> L = tile_head(P);
+            if (t >= L.n_tiles) break;
+            direct_tile(L, P, sc, t, k, (int)L.n_lights);
+            t += L.stride;
+        } else {
+            if (t >= P.n_tiles) break;
+            direct_tile(P, P, sc, t, k, sc.n_lights);
+            t += gridDim.x;
+        }
+    }
+#else
     for (uint32_t t = blockIdx.x;; t += gridDim.x) {
         const LaunchParams<R>& P = kernarg_params<R>();
         const DevScene<R> sc = scene_view<R, kLds>(P, shapes, materials, patterns, lights, smem);
@@ -2952,18 +3124,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(sizeof(R
         uint64_t out_idx;
 #ifdef RTC_JIT
         // (camera frames only, rtc_host.cpp launch; RTC_TILE_DECODE=0: the two decodes of load_primary and the block)
-#if RTC_TILE_DECODE
-        const WaveTile wt = wave_tile(P, t);
-        {
-            uint32_t x, y;
-            valid = wave_tile_pixel(P, wt, tid % 64, x, y, out_idx);
-            if (valid) camera_ray(P.cam, x, y, o, d);
-            // (the origin is the launch's, whatever the lane: a wave-uniform value the compiler keeps in SGPRs)
-            o = {P.cam.origin[0], P.cam.origin[1], P.cam.origin[2]};
-        }
-#else
         load_primary<R, true>(P, t, tid, valid, o, d, out_idx);
-#endif
 #else
         load_primary(P, t, tid, valid, o, d, out_idx);
 #endif
@@ -2982,11 +3143,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(sizeof(R
                     c = {h.t * (R)0.01, (R)h.slot, (R)0};
                 }
 #ifdef RTC_JIT  // (camera frames only: load_primary above)
-#if RTC_TILE_DECODE
-            } else if (shade_ray<R, false>(sc, o, d, 0, sh, NoPush{}, wave_pixel_block(P, wt))) {
-#else
             } else if (shade_ray<R, false>(sc, o, d, 0, sh, NoPush{}, wave_pixel_block(P, wave_tile(P, t)))) {
-#endif
 #elif RTC_AREA_LIGHTS  // (the jitter hashes the ray's `remaining`: the primary ray's, though no child is made here)
             } else if (shade_ray<R, false>(sc, o, d, P.max_depth, sh)) {
 #else
@@ -3000,6 +3157,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(sizeof(R
         if (kDiag && P.gen_counts) count_generations(P.gen_counts, valid, hit, P.max_depth);
         if (valid) store_pixel(P, out_idx, c);
     }
+#endif
     if (!(P.flags & RT_FLAG_NO_COUNTERS)) flush_counts(k, P.counters);
     if (kDiag && P.stamps) {
         __syncthreads();
