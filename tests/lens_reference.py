@@ -69,6 +69,35 @@ def lens_rays(cn, w, h, n, aperture, focal, jitter=False, seed=0, x=None, y=None
     return np.stack(origin + [c / mag for c in d], axis=-1)
 
 
+def ordered_mean(cols, h, w, n):
+    """Colours (H W n n, 3) in ray order [y, x, j, i] to the frame: summed j outer and i inner, times 1 / n^2."""
+    cols = np.asarray(cols, dtype=np.float64).reshape(h, w, n, n, 3)
+    acc = np.zeros((h, w, 3), dtype=np.float64)
+    for j in range(n):
+        for i in range(n):
+            acc = acc + cols[:, :, j, i]
+    return acc * (1.0 / (n * n))
+
+
+def traced_lens_frame(trace, tables, cn, w, h, n, aperture, focal, jitter, seed, tolerance, chunk=1024):
+    """The lens frame of a numpy reference (smooth_reference.trace or texture_reference.trace: colours, hits
+    and a decision margin per ray) over the lens rays, `chunk` rays at a time (every ray is traced on its own,
+    so the chunks change no value).  Returns (frame (H, W, 3), sound (H, W): every one of the pixel's n^2 rays
+    has a margin above `tolerance`, counts: the primary rays, the hits and the shadow rays, one per hit and
+    light)."""
+    from concurrent.futures import ThreadPoolExecutor
+    rays = np.ascontiguousarray(lens_rays(cn, w, h, n, aperture, focal, jitter, seed).reshape(-1, 6))
+    cols, margin, hits = np.zeros((len(rays), 3)), np.zeros(len(rays)), 0
+    starts = range(0, len(rays), chunk)
+    with ThreadPoolExecutor(max_workers=8) as pool:  # (numpy releases the interpreter lock in its loops)
+        for a, (rgb, hit, m) in zip(starts, pool.map(lambda a: trace(tables, rays[a:a + chunk]), starts)):
+            cols[a:a + chunk], margin[a:a + chunk] = rgb, m
+            hits += int((hit["shape"] >= 0).sum())
+    sound = (margin.reshape(h, w, n * n) > tolerance).all(axis=2)
+    counts = {"primary": len(rays), "shaded": hits, "shadow": hits * len(tables.lights)}
+    return ordered_mean(cols, h, w, n), sound, counts
+
+
 def lens_frame(oracle, tables, cn, w, h, n, aperture, focal, jitter, seed, depth):
     """The oracle's lens frame: World::color_at over the rays, summed j outer and i inner, times 1 / n^2.
     Returns (frame (H, W, 3) f64, the oracle's stats of the whole ray set)."""

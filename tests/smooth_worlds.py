@@ -187,6 +187,26 @@ def torus_instances(rtc, smooth=True):
     return W.World(lights, [floor], inst).tables(camera())
 
 
+def ico_instances(rtc, smooth=True, extra=()):
+    """Two instances (a translation; a rotation x shear) of the 80-triangle icosphere, opaque, under the light
+    beside the eye and nothing else: a world of triangles only, for which tests/smooth_reference.py speaks
+    (torus_instances and box_instances stand over a plane, and the boxes are glass)."""
+    from rtc_amd import world as W
+    mesh = load(rtc, *icosphere(1))
+    small = W.scaling(0.7, 0.7, 0.7)
+    places = [W.mat_mul(W.translation(-0.8, 0.1, 0.2), small),
+              W.mat_mul(W.translation(0.75, -0.1, 0.5), W.mat_mul(W.mat_mul(W.rotation_y(0.7),
+                                                                            W.shearing(0.3, 0.0, 0.0, 0.2, 0.0, 0.0)), small))]
+    mats = [opaque(), W.Material(color=(0.9, 0.8, 0.1), diffuse=0.7, specular=0.1)]
+    inst = [W.instance(mesh, m, transform=p, smooth=smooth) for m, p in zip(mats, places)]
+    return W.World([eye_light()], list(extra), inst).tables(camera())
+
+
+# The thin lens of the lens tests of these worlds (tests/test_gpu_lens_builds.py): the icosphere's near side is
+# 2.2 from the eye, the focal plane behind it, so that every part of the frame is out of focus.
+LENS_APERTURE, LENS_FOCUS, LENS_SEED = 0.2, 5.0, 1
+
+
 def flat_of(rtc, tables):
     """The same tables without the smooth list: every triangle flat."""
     return rtc.SceneTables(tables.shapes, tables.materials, tables.patterns, tables.lights, tables.camera,
