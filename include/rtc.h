@@ -796,6 +796,92 @@ typedef struct rt_light_info {
 } rt_light_info;
 int rt_scene_light_info(rt_context* ctx, rt_light_info* out);
 
+/* Texture maps: how a hit without texture coordinates gets
+ * its (u, v).  The book's bonus chapter "Texture mapping" is the source; the
+ * reference has no textures, so this text is the contract.
+ *
+ * For a hit without texture coordinates let pp = pattern.inverse *
+ * (shape.inverse * over_point), the point the planar map uses.  All arithmetic
+ * is in the kernel's real type R: plain multiplies and adds, left to right,
+ * the kernel's divisions (IEEE in f64); pi is rounded once to R; atan2, acos
+ * and sqrt are the device math library's for R.  An image pattern has one map:
+ *   RT_MAP_PLANAR       u = pp.x - floor(pp.x), v = pp.z - floor(pp.z)
+ *                       (rt_scene_upload_textured's behaviour, bit for bit)
+ *   RT_MAP_SPHERICAL    theta = atan2(pp.x, pp.z)
+ *                       r = sqrt((pp.x^2 + pp.y^2) + pp.z^2)
+ *                       c = pp.y / r, clamped into [-1, 1] (a rounded r just
+ *                           below |y| would make acos NaN at the poles)
+ *                       phi = acos(c)
+ *                       u = 1 - (theta / (2 pi) + 0.5),  v = 1 - phi / pi
+ *   RT_MAP_CYLINDRICAL  u as in the spherical map,  v = pp.y - floor(pp.y)
+ *   RT_MAP_CUBE         six textures, in the book's order: left 0, front 1,
+ *                       right 2, back 3, up 4, down 5.  With a = max(|x|, |y|,
+ *                       |z|) the face is the first true of a == x: right,
+ *                       a == -x: left, a == y: up, a == -y: down, a == z:
+ *                       front, else back.  With m(c) = c - 2 floor(c / 2):
+ *                           front  u = m(x + 1) / 2   v = m(y + 1) / 2
+ *                           back   u = m(1 - x) / 2   v = m(y + 1) / 2
+ *                           left   u = m(z + 1) / 2   v = m(y + 1) / 2
+ *                           right  u = m(1 - z) / 2   v = m(y + 1) / 2
+ *                           up     u = m(x + 1) / 2   v = m(1 - z) / 2
+ *                           down   u = m(x + 1) / 2   v = m(z + 1) / 2
+ * u = 1 stays 1, as for interpolated coordinates.  Sampling (u, v) under
+ * either filter, the clamp of texel indices, lit_patterned, t, ties, normals,
+ * culls and skips are rt_scene_upload_textured's.  A hit that has texture
+ * coordinates ignores the map and the pattern's inverse and samples the
+ * pattern's sub_a texture.  The pattern's inverse serves every map.
+ *
+ * rt_scene_upload_mapped is rt_scene_upload_lit's argument list plus a sparse
+ * list of maps; with n_maps = 0 it is rt_scene_upload_lit itself, and an image
+ * pattern that no entry names is planar.  A cube map's pattern keeps a valid
+ * sub_a (textured triangles sample it); its faces may repeat.  Two image
+ * patterns are equal iff, beyond rt_scene_upload_textured's rule, their maps
+ * are equal and, for cube maps, the six faces' contents are equal pairwise; a
+ * cube map's brightness bound is the largest channel over its six faces.
+ * RT_ERR_INVALID, each with its own rt_last_error text and checked before the
+ * context is looked at: a null list with a nonzero count, a pattern index out
+ * of range, a named pattern that is not RT_PATTERN_IMAGE, a pattern named
+ * twice, an unknown map, a face index out of range for a cube map, a face
+ * other than -1 for any other map.  Per-scene builds stay refused. */
+#define RT_MAP_PLANAR      0
+#define RT_MAP_SPHERICAL   1
+#define RT_MAP_CYLINDRICAL 2
+#define RT_MAP_CUBE        3
+#define RT_FACE_LEFT  0
+#define RT_FACE_FRONT 1
+#define RT_FACE_RIGHT 2
+#define RT_FACE_BACK  3
+#define RT_FACE_UP    4
+#define RT_FACE_DOWN  5
+typedef struct rt_uv_map_desc {   /* 32 bytes */
+    uint32_t pattern;   /* index of an RT_PATTERN_IMAGE pattern */
+    uint32_t map;       /* RT_MAP_* */
+    int32_t  faces[6];  /* RT_MAP_CUBE: texture indices left, front, right, back, up, down; else all -1 */
+} rt_uv_map_desc;
+int rt_scene_upload_mapped(rt_context* ctx,
+                           const rt_shape_desc* shapes, uint32_t n_shapes,
+                           const rt_mesh_desc* meshes, uint32_t n_meshes,
+                           const rt_instance_desc* instances, uint32_t n_instances,
+                           const rt_smooth_desc* smooth, uint32_t n_smooth,
+                           const rt_uv_desc* uvs, uint32_t n_uvs,
+                           const rt_texture_desc* textures, uint32_t n_textures,
+                           const rt_material_desc* materials, uint32_t n_materials,
+                           const rt_pattern_desc* patterns, uint32_t n_patterns,
+                           const rt_light_desc* lights, uint32_t n_lights,
+                           const rt_area_light_desc* area, uint32_t n_area,
+                           const rt_uv_map_desc* maps, uint32_t n_maps);
+/* The maps of the last upload (zeros after any other upload, and after one
+ * whose entries are all RT_MAP_PLANAR): patterns with a map other than the
+ * planar one, cube maps among them, and whether the last launch ran kernels
+ * that hold the map code. */
+typedef struct rt_map_info {
+    uint32_t mapped_patterns;
+    uint32_t cube_maps;
+    uint32_t ran_mapped;
+    uint32_t reserved;
+} rt_map_info;
+int rt_scene_map_info(rt_context* ctx, rt_map_info* out);
+
 /* Thin-lens camera: depth of field.  The reference has no
  * lens, so this text is the contract.
  *

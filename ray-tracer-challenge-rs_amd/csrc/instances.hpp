@@ -413,14 +413,21 @@ inline bool texture_eq(const rt_texture_desc& a, const rt_texture_desc& b) {
 // their largest channel (scene_brightness).  Rewrites validated patterns in place: an image pattern's sub_a
 // becomes the smallest index of a texture with the same picture, whichever patterns name which textures and in
 // what order, and its color_a and color_b (ignored otherwise) the largest channel / 255.
+//
+// Texture maps (rtc.h rt_scene_upload_mapped; `maps` validated by validate_maps): a pattern with a map other
+// than the planar one gets it into bits 8 and up of `reserved`, beside the filter, so pattern_eq compares it.
+// A cube map's sub_a becomes n_textures + kCubeRecords * s, where s numbers the distinct tuples (renumbered
+// sub_a, six renumbered faces) in the order the patterns meet them, and `records` (cleared first) receives
+// each tuple's kCubeRecords texture indices: the device texture table's records after the textures' own
+// (rtc_internal.hpp TexRec).  Equal sub_a then means equal pictures on every face, and the brightness bound
+// is the largest channel over the seven.
+constexpr uint32_t kCubeRecords = 7;  // the pattern's own texture (a textured triangle samples it), then the faces
 inline void canonical_image_patterns(rt_pattern_desc* pats, uint32_t np, const rt_texture_desc* textures,
-                                     uint32_t n_textures) {
+                                     uint32_t n_textures, const rt_uv_map_desc* maps = nullptr, uint32_t n_maps = 0,
+                                     std::vector<int32_t>* records = nullptr) {
     std::vector<int32_t> first(n_textures, -1);
     std::vector<double> top(n_textures, 0.0);
-    for (uint32_t i = 0; i < np; ++i) {
-        rt_pattern_desc& p = pats[i];
-        if (p.kind != RT_PATTERN_IMAGE) continue;
-        const uint32_t t = (uint32_t)p.sub_a;
+    auto renumber = [&](uint32_t t) {
         if (first[t] < 0) {
             first[t] = (int32_t)t;
             for (uint32_t e = 0; e < t; ++e)  // (every earlier texture, named by a pattern or not)
@@ -431,9 +438,56 @@ inline void canonical_image_patterns(rt_pattern_desc* pats, uint32_t np, const r
             const size_t n = (size_t)textures[t].width * textures[t].height * 3;
             top[t] = (double)*std::max_element(textures[t].rgb, textures[t].rgb + n) / 255.0;
         }
-        p.sub_a = first[t];
-        for (int q = 0; q < 3; ++q) p.color_a[q] = p.color_b[q] = top[t];
+        return first[t];
+    };
+    std::vector<const rt_uv_map_desc*> map_of(n_maps ? np : 0, nullptr);
+    for (uint32_t k = 0; k < n_maps; ++k) map_of[maps[k].pattern] = &maps[k];
+    if (records) records->clear();
+    std::vector<int32_t> sets;  // kCubeRecords indices a distinct tuple
+    for (uint32_t i = 0; i < np; ++i) {
+        rt_pattern_desc& p = pats[i];
+        if (p.kind != RT_PATTERN_IMAGE) continue;
+        const uint32_t t = (uint32_t)p.sub_a;
+        p.sub_a = renumber(t);
+        double bound = top[t];
+        const rt_uv_map_desc* const m = n_maps ? map_of[i] : nullptr;
+        if (m && m->map != RT_MAP_PLANAR) p.reserved |= (int32_t)(m->map << 8);
+        if (m && m->map == RT_MAP_CUBE) {
+            int32_t tuple[kCubeRecords] = {p.sub_a};
+            for (int f = 0; f < 6; ++f) {
+                tuple[1 + f] = renumber((uint32_t)m->faces[f]);
+                bound = std::max(bound, top[(uint32_t)m->faces[f]]);
+            }
+            size_t s = 0;
+            while (s < sets.size() && !std::equal(tuple, tuple + kCubeRecords, sets.begin() + s)) s += kCubeRecords;
+            if (s == sets.size()) sets.insert(sets.end(), tuple, tuple + kCubeRecords);
+            p.sub_a = (int32_t)(n_textures + s);
+        }
+        for (int q = 0; q < 3; ++q) p.color_a[q] = p.color_b[q] = bound;
     }
+    if (records) *records = sets;
+}
+
+// rt_scene_upload_mapped's list against the validated patterns and the texture count; empty: valid.
+inline std::string validate_maps(const rt_uv_map_desc* maps, uint32_t n_maps, const rt_pattern_desc* pats, uint32_t np,
+                                 uint32_t n_textures) {
+    if (n_maps && !maps) return "rt_scene_upload_mapped: null map list with nonzero count";
+    std::vector<char> named(np, 0);
+    for (uint32_t k = 0; k < n_maps; ++k) {
+        const rt_uv_map_desc& m = maps[k];
+        const std::string who = "map " + std::to_string(k);
+        if (m.pattern >= np) return who + ": pattern index out of range";
+        if (pats[m.pattern].kind != RT_PATTERN_IMAGE) return who + ": the pattern is not an image pattern";
+        if (named[m.pattern]) return who + ": pattern named twice";
+        named[m.pattern] = 1;
+        if (m.map > RT_MAP_CUBE) return who + ": unknown map";
+        for (int f = 0; f < 6; ++f) {
+            if (m.map == RT_MAP_CUBE && (m.faces[f] < 0 || (uint32_t)m.faces[f] >= n_textures))
+                return who + ": face texture index out of range";
+            if (m.map != RT_MAP_CUBE && m.faces[f] != -1) return who + ": a face other than -1 for a map that is no cube map";
+        }
+    }
+    return "";
 }
 
 // expanded[k] = 1: instance k has a triangle value-equal to another triangle

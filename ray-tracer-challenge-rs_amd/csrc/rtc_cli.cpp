@@ -23,7 +23,9 @@
 // §3.11; without it the output is what it was), --texture IMAGE.ppm|png with
 // --texture-filter nearest|bilinear (the --obj and --instance meshes' material
 // gets an image pattern and their vt lines are read: rt_scene_upload_textured,
-// DESIGN.md §3.12), --area-light cx,cy,cz:ux,uy,uz:vx,vy,vz:USTEPSxVSTEPS
+// DESIGN.md §3.12), --texture-map planar|spherical|cylindrical (how a face
+// without vt coordinates is mapped) and --cube-map L,F,R,B,U,D (six images in
+// place of --texture: rt_scene_upload_mapped), --area-light cx,cy,cz:ux,uy,uz:vx,vy,vz:USTEPSxVSTEPS
 // [:r,g,b][:jitter[=SEED]] (repeatable: an area light added to the scene's
 // lights, rt_scene_upload_lit), --aperture R --focus D
 // [--lens-jitter[=SEED]] (a thin lens of radius R focused at distance D, both
@@ -47,6 +49,7 @@ static int usage() {
                  "           [--depth D] [--precision f32|f64] [--device N] [--gpus N] [--ppm-binary] [--timings]\n"
                  "           [--samples N] [--obj MESH.obj]... [--instance MESH.obj:tx,ty,tz[:s]]... [--smooth]\n"
                  "           [--texture IMAGE.ppm|png] [--texture-filter nearest|bilinear]\n"
+                 "           [--texture-map planar|spherical|cylindrical] [--cube-map L,F,R,B,U,D]\n"
                  "           [--area-light cx,cy,cz:ux,uy,uz:vx,vy,vz:USTEPSxVSTEPS[:r,g,b][:jitter[=SEED]]]...\n"
                  "           [--aperture R --focus D [--lens-jitter[=SEED]]]\n"
                  "  --obj MESH.obj appends the mesh's triangles (v and f lines; faces fan-triangulated) to the\n"
@@ -58,6 +61,10 @@ static int usage() {
                  "  --texture IMAGE.ppm|png gives the --obj and --instance meshes' material that image as its pattern\n"
                  "  and reads the files' texture coordinates (vt lines, f i/j and i/j/k); a face without them is\n"
                  "  mapped by its x and z.  --texture-filter nearest|bilinear picks the filter (default bilinear).\n"
+                 "  --texture-map planar|spherical|cylindrical maps a face without texture coordinates by its x and z\n"
+                 "  (the default), by longitude and latitude around the origin, or by longitude and height.\n"
+                 "  --cube-map L,F,R,B,U,D takes six image files in place of --texture, the faces left, front, right,\n"
+                 "  back, up and down of the cube |x|, |y|, |z| <= 1; a face with texture coordinates samples F.\n"
                  "  --area-light adds an area light to the scene's lights: the parallelogram from corner c along the\n"
                  "  full edges u and v, USTEPS x VSTEPS samples (1..%d each), intensity r,g,b (default 1,1,1), sampled\n"
                  "  at the cell centres or, with jitter, at hashed positions per ray (seed SEED, default 0); repeatable.\n"
@@ -156,6 +163,9 @@ int main(int argc, char** argv) {
     bool smooth = false;
     const char* texture_path = nullptr;
     int texture_filter = RT_FILTER_BILINEAR;
+    uint32_t texture_map = RT_MAP_PLANAR;
+    bool have_texture_map = false;
+    std::vector<std::string> cube_paths;  // --cube-map: left, front, right, back, up, down
     std::vector<const char*> obj_paths;
     std::vector<Placement> placements;
     std::vector<rt_area_light_desc> area_lights;
@@ -171,6 +181,33 @@ int main(int argc, char** argv) {
             const char* v = next();
             if (!v || (std::strcmp(v, "nearest") && std::strcmp(v, "bilinear"))) return usage();
             texture_filter = std::strcmp(v, "nearest") == 0 ? RT_FILTER_NEAREST : RT_FILTER_BILINEAR;
+        }
+        else if (a == "--texture-map") {
+            const char* v = next();
+            if (!v) return usage();
+            if (std::strcmp(v, "planar") == 0) texture_map = RT_MAP_PLANAR;
+            else if (std::strcmp(v, "spherical") == 0) texture_map = RT_MAP_SPHERICAL;
+            else if (std::strcmp(v, "cylindrical") == 0) texture_map = RT_MAP_CYLINDRICAL;
+            else return usage();
+            have_texture_map = true;
+        }
+        else if (a == "--cube-map") {
+            const char* v = next();
+            if (!v) return usage();
+            const std::string list = v;
+            cube_paths.clear();
+            for (size_t at = 0;;) {
+                const size_t c = list.find(',', at);
+                cube_paths.push_back(list.substr(at, c == std::string::npos ? c : c - at));
+                if (c == std::string::npos) break;
+                at = c + 1;
+            }
+            bool six = cube_paths.size() == 6;
+            for (const std::string& f : cube_paths) six = six && !f.empty();
+            if (!six) {
+                std::fprintf(stderr, "error: --cube-map takes six image files: L,F,R,B,U,D\n");
+                return usage();
+            }
         }
         else if (a == "-r" || a == "--rendering-mode") {
             const char* v = next();
@@ -271,27 +308,57 @@ int main(int argc, char** argv) {
     // --texture: the image, one more pattern after the scene's, and the meshes' texture coordinates
     std::vector<rt_pattern_desc> patterns(v.patterns, v.patterns + v.n_patterns);
     std::vector<rt_uv_desc> uv_list;
-    rt_texture_desc texture = {};
-    uint8_t* texture_rgb = nullptr;
-    if (texture_path && obj_paths.empty() && placements.empty()) {
-        std::fprintf(stderr, "error: --texture needs a mesh to show on: give --obj or --instance\n");
+    // (--texture: one texture; --cube-map: six, the pattern's own being the front face's)
+    std::vector<rt_texture_desc> textures;
+    std::vector<uint8_t*> texture_rgb;
+    std::vector<rt_uv_map_desc> maps;
+    auto free_textures = [&] {
+        for (uint8_t* rgb : texture_rgb) rt_image_free(rgb);
+        texture_rgb.clear();
+    };
+    const bool cube_mapped = !cube_paths.empty();
+    if ((texture_path || cube_mapped) && obj_paths.empty() && placements.empty()) {
+        std::fprintf(stderr, "error: %s needs a mesh to show on: give --obj or --instance\n", texture_path ? "--texture" : "--cube-map");
         return usage();
     }
-    const bool textured = texture_path != nullptr;
+    if (texture_path && cube_mapped) {
+        std::fprintf(stderr, "error: --cube-map takes the place of --texture: give one of them\n");
+        return usage();
+    }
+    if (have_texture_map && cube_mapped) {
+        std::fprintf(stderr, "error: --texture-map applies to --texture's pattern, not to a --cube-map\n");
+        return usage();
+    }
+    if (have_texture_map && !texture_path) {
+        std::fprintf(stderr, "error: --texture-map needs --texture\n");
+        return usage();
+    }
+    const bool textured = texture_path != nullptr || cube_mapped;
     if (textured) {
-        if (rt_image_read(texture_path, &texture_rgb, &texture.width, &texture.height) != RT_OK) {
-            std::fprintf(stderr, "error: %s\n", rt_last_error());
-            return 1;
+        std::vector<std::string> files = cube_paths;
+        if (texture_path) files.assign(1, texture_path);
+        for (const std::string& f : files) {
+            rt_texture_desc t = {};
+            uint8_t* rgb = nullptr;
+            if (rt_image_read(f.c_str(), &rgb, &t.width, &t.height) != RT_OK) {
+                free_textures();
+                std::fprintf(stderr, "error: %s\n", rt_last_error());
+                return 1;
+            }
+            t.rgb = rgb;
+            texture_rgb.push_back(rgb);
+            textures.push_back(t);
+            if (!quiet) std::printf("%s: %u x %u texels\n", f.c_str(), t.width, t.height);
         }
-        texture.rgb = texture_rgb;
         rt_pattern_desc p = {};
         p.kind = RT_PATTERN_IMAGE;
-        p.sub_a = 0;
+        p.sub_a = cube_mapped ? RT_FACE_FRONT : 0;
         p.sub_b = -1;
         p.reserved = texture_filter;
         for (int q = 0; q < 4; ++q) p.inverse[5 * q] = 1.0;
         patterns.push_back(p);
-        if (!quiet) std::printf("%s: %u x %u texels\n", texture_path, texture.width, texture.height);
+        if (cube_mapped) maps.push_back({(uint32_t)patterns.size() - 1, RT_MAP_CUBE, {0, 1, 2, 3, 4, 5}});
+        else if (texture_map != RT_MAP_PLANAR) maps.push_back({(uint32_t)patterns.size() - 1, texture_map, {-1, -1, -1, -1, -1, -1}});
     }
     if (!obj_paths.empty() || !placements.empty()) {
         rt_material_desc m = {};
@@ -397,18 +464,19 @@ int main(int argc, char** argv) {
     const double ctx_ms = ms_since(t_ctx);
     const auto t_up = clk::now();
     if (created != RT_OK ||
-        rt_scene_upload_lit(ctx, shapes.data(), (uint32_t)shapes.size(), meshes.data(), (uint32_t)meshes.size(),
+        rt_scene_upload_mapped(ctx, shapes.data(), (uint32_t)shapes.size(), meshes.data(), (uint32_t)meshes.size(),
                                  instances.data(), (uint32_t)instances.size(), smooth_list.data(),
-                                 (uint32_t)smooth_list.size(), uv_list.data(), (uint32_t)uv_list.size(), &texture,
-                                 textured ? 1u : 0u, materials.data(), (uint32_t)materials.size(), patterns.data(),
+                                 (uint32_t)smooth_list.size(), uv_list.data(), (uint32_t)uv_list.size(), textures.data(),
+                                 (uint32_t)textures.size(), materials.data(), (uint32_t)materials.size(), patterns.data(),
                                  (uint32_t)patterns.size(), v.lights,
                                  v.n_lights, area_lights.data(),
-                                 (uint32_t)area_lights.size()) != RT_OK) {  // (no area light: rt_scene_upload_textured; no texture: rt_scene_upload_smooth; no smooth triangle: rt_scene_upload_instanced; no instances: rt_scene_upload)
-        rt_image_free(texture_rgb);
+                                 (uint32_t)area_lights.size(), maps.data(),
+                                 (uint32_t)maps.size()) != RT_OK) {  // (no map: rt_scene_upload_lit; no area light: rt_scene_upload_textured; no texture: rt_scene_upload_smooth; no smooth triangle: rt_scene_upload_instanced; no instances: rt_scene_upload)
+        free_textures();
         std::fprintf(stderr, "error: %s\n", rt_last_error());
         return 1;
     }
-    rt_image_free(texture_rgb);  // (the upload copied the texels)
+    free_textures();  // (the upload copied the texels)
     // One frame: the default per-scene policy (RT_JIT_AUTO) starts a hipRTC
     // build only at a world's second large frame, so this render never
     // compiles.

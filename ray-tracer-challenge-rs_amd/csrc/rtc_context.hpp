@@ -66,6 +66,7 @@ enum class KernelBuild : uint32_t {
     instanced,  // rtc::instanced::*: the instance level and the smooth triangle's normal (rtc_kernels.hip prepare_hit)
     textured,   // rtc::textured::*: ... plus the texture code, for an image pattern or a coordinate entry
     area,       // rtc::area::*: ... plus the area lights' sample loop
+    mapped,     // rtc::mapped::*: ... plus the spherical, cylindrical and cube maps of an image pattern
 };
 
 // Texel storage of a world (rt_scene_upload_textured): the texture count and the texels of all of them; a
@@ -357,6 +358,7 @@ struct rt_context {
     rtc::TextureCounts tex_counts{};
     rt_texture_info texture_info{};    // rt_scene_texture_info
     rt_light_info light_info{};        // area lights of the uploaded world (rt_scene_light_info)
+    rt_map_info map_info{};            // texture maps of the uploaded world (rt_scene_map_info)
     std::vector<int32_t> world_slot;  // world index -> slot | kind << 24 of the uploaded table
     // ray-pool overflow regions, one per resident workgroup; a ray batch's per-lane LIFOs (launch_rays)
     rtc::DeviceBuffer<unsigned char> d_spill;
@@ -443,6 +445,12 @@ struct WorldLists {
     // the upload came through rt_scene_upload_textured or rt_scene_upload_lit: image patterns are known and
     // checked against `textures` (the older entry points refuse pattern kind 6)
     bool image_patterns = false;
+    const rt_uv_map_desc* maps = nullptr;  // rt_scene_upload_mapped's list
+    uint32_t n_maps = 0;
+    // the device texture table's records after the textures' own (a texture index each: instances.hpp
+    // canonical_image_patterns), filled in by the upload once the maps are validated
+    const int32_t* tex_records = nullptr;
+    uint32_t n_tex_records = 0;
 };
 // Every refusal of rtc.h for these lists, in the entry points' order: the area list, the texture list, the
 // base tables, the mesh and instance lists, the smooth list, the uv list, the lights' total.

@@ -68,6 +68,7 @@ struct SceneHeader {
     rt_texture_info texture_info;
     uint32_t n_area, area_samples;  // area lights (rt_scene_upload_lit): zeros = none
     rt_light_info light_info;
+    rt_map_info map_info;  // texture maps (rt_scene_upload_mapped): zeros = none
 };
 
 // (device pointer, bytes) of every table of a member's world, in one order
@@ -333,7 +334,8 @@ int group_scene_upload(rt_context* ctx, const WorldLists& wl) {
     if (ctx->group.rank == 0) {  // only rank 0's tables are used (rtc.h)
         // a failure here still takes part in the header broadcast, so the
         // other ranks return it instead of waiting in the table broadcast
-        root_rc = validate_scene(wl);
+        // (a world whose image patterns are known was checked and then rewritten by upload_world on every rank)
+        root_rc = wl.image_patterns ? RT_OK : validate_scene(wl);
         if (!root_rc && hipSetDevice(ctx->device) != hipSuccess) root_rc = set_error(RT_ERR_HIP, "hipSetDevice");
         if (!root_rc) root_rc = build_scene(ctx, wl);
         if (root_rc) root_err = rt_last_error();
@@ -350,6 +352,7 @@ int group_scene_upload(rt_context* ctx, const WorldLists& wl) {
         root_h.n_area = ctx->w32.n_area;
         root_h.area_samples = ctx->w32.area_samples;
         root_h.light_info = ctx->light_info;
+        root_h.map_info = ctx->map_info;
         // (the shape table's size: an instanced world's also holds the instances uploaded expanded)
         root_h.ns = root_rc ? wl.n_shapes : (uint32_t)ctx->w32.scene.kind_begin[kNumKinds];
         root_h.nm = wl.n_materials;
@@ -442,6 +445,7 @@ int group_scene_upload(rt_context* ctx, const WorldLists& wl) {
         m->smooth_info = h.smooth_info;
         m->texture_info = h.texture_info;
         m->light_info = h.light_info;
+        m->map_info = h.map_info;
         set_kernel_build(m, h.build);  // (the header's: this rank built nothing)
         m->have_scene = true;
         ++m->scene_gen;

@@ -49,6 +49,7 @@ RTC_KERNEL_LAUNCHERS                          // rtc_kernels*.o: the plain build
 namespace instanced { RTC_KERNEL_LAUNCHERS }  // rtc_kernels_inst*.o: with the instance level, for worlds with mesh instances
 namespace textured { RTC_KERNEL_LAUNCHERS }   // rtc_kernels_tex*.o: the instance build plus the texture code
 namespace area { RTC_KERNEL_LAUNCHERS }       // rtc_kernels_area*.o: the texture build plus the area lights' sample loop
+namespace mapped { RTC_KERNEL_LAUNCHERS }     // rtc_kernels_map*.o: the area build plus the texture maps of an image pattern
 namespace sp { RTC_KERNEL_LAUNCHERS }         // rtc_kernels_sp.o: the f32 frame pool kernel for worlds of spheres and planes only
 #undef RTC_KERNEL_LAUNCHERS
 constexpr uint32_t kKindsSp = (1u << RT_SHAPE_SPHERE) | (1u << RT_SHAPE_PLANE);
@@ -64,7 +65,8 @@ template <typename R>
 constexpr Launchers<R> kLaunchers[] = {{launch_kernel<R>, kernel_occupancy<R>},
                                        {instanced::launch_kernel<R>, instanced::kernel_occupancy<R>},
                                        {textured::launch_kernel<R>, textured::kernel_occupancy<R>},
-                                       {area::launch_kernel<R>, area::kernel_occupancy<R>}};
+                                       {area::launch_kernel<R>, area::kernel_occupancy<R>},
+                                       {mapped::launch_kernel<R>, mapped::kernel_occupancy<R>}};
 template <typename R>
 const Launchers<R>& launchers(const rt_context* ctx) {
     return kLaunchers<R>[(uint32_t)ctx->kernel_build];
@@ -386,7 +388,9 @@ int build_world(rt_context* ctx, DeviceWorld<R>& w, const WorldLists& wl, const 
         for (int q = 0; q < 12; ++q) p.inv[q] = (R)d.inverse[q];
         p.kind = d.kind;
         p.sub_a = d.sub_a;
-        p.sub_b = d.kind == RT_PATTERN_IMAGE ? d.reserved : d.sub_b;  // (an image pattern: its texture and its filter)
+        // (an image pattern: its texture and its filter, and its map from the bits the upload put above the filter)
+        p.sub_b = d.kind == RT_PATTERN_IMAGE ? (d.reserved & 0xFF) : d.sub_b;
+        p.pad = d.kind == RT_PATTERN_IMAGE ? (d.reserved >> 8) : 0;
     }
     std::vector<LightRec<R>> lt(nl);
     for (uint32_t i = 0; i < nl; ++i)
@@ -521,6 +525,7 @@ int validate_scene(const WorldLists& wl) {
     uint64_t total = wl.n_lights;  // the expansion's lights: the point lights and every area light's samples
     for (uint32_t a = 0; why.empty() && a < wl.n_area; ++a) total += wl.area[a].usteps * wl.area[a].vsteps;
     if (why.empty() && total > 0x7fffffffull) why = "table too large";
+    if (why.empty()) why = inst::validate_maps(wl.maps, wl.n_maps, wl.patterns, wl.n_patterns, wl.n_textures);
     return why.empty() ? RT_OK : set_error(RT_ERR_INVALID, why);
 }
 
@@ -1180,6 +1185,7 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
     if (ls.id.pool) ctx->head_set ^= 1;  // (the queue heads' set: see set_queue_heads)
     ctx->smooth_info.ran_smooth = !k.jit && has_smooth(w) ? 1u : 0u;
     ctx->texture_info.ran_textured = !k.jit && has_textures(w) ? 1u : 0u;
+    ctx->map_info.ran_mapped = ctx->texture_info.ran_textured && ctx->kernel_build == KernelBuild::mapped ? 1u : 0u;
     ctx->light_info.ran_area = !k.jit && has_area(w) ? 1u : 0u;
     return RT_OK;
 }
@@ -1248,6 +1254,7 @@ int launch_rays(rt_context* ctx, DeviceWorld<R>& w, const void* d_rays, uint64_t
                                          std::to_string(ls.cap) + " stack entries per lane): " + hipGetErrorString(e));
     ctx->smooth_info.ran_smooth = has_smooth(w) ? 1u : 0u;
     ctx->texture_info.ran_textured = has_textures(w) ? 1u : 0u;
+    ctx->map_info.ran_mapped = ctx->texture_info.ran_textured && ctx->kernel_build == KernelBuild::mapped ? 1u : 0u;
     ctx->light_info.ran_area = has_area(w) ? 1u : 0u;
     return RT_OK;
 }
@@ -1487,10 +1494,13 @@ static int upload_world(rt_context* ctx, const WorldLists& in) {
     WorldLists wl = in;
     // (patterns compare by their textures' contents: a copy with every image pattern's texture renumbered)
     std::vector<rt_pattern_desc> cp;
+    std::vector<int32_t> records;  // (a cube map's faces: more records of the device texture table)
     if (wl.image_patterns) {
         cp.assign(wl.patterns, wl.patterns + wl.n_patterns);
-        inst::canonical_image_patterns(cp.data(), wl.n_patterns, wl.textures, wl.n_textures);
+        inst::canonical_image_patterns(cp.data(), wl.n_patterns, wl.textures, wl.n_textures, wl.maps, wl.n_maps, &records);
         wl.patterns = cp.data();
+        wl.tex_records = records.data();
+        wl.n_tex_records = (uint32_t)records.size();
     }
     if (group) return group_scene_upload(ctx, wl);
     RT_HIP(hipSetDevice(ctx->device));
@@ -1555,6 +1565,19 @@ int rt_scene_upload_lit(rt_context* ctx, const rt_shape_desc* shapes, uint32_t n
                                         smooth, n_smooth, uvs, n_uvs, textures, n_textures, area, n_area, true});
 }
 
+int rt_scene_upload_mapped(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns, const rt_mesh_desc* meshes,
+                           uint32_t n_meshes, const rt_instance_desc* instances, uint32_t n_inst,
+                           const rt_smooth_desc* smooth, uint32_t n_smooth, const rt_uv_desc* uvs, uint32_t n_uvs,
+                           const rt_texture_desc* textures, uint32_t n_textures, const rt_material_desc* mats, uint32_t nm,
+                           const rt_pattern_desc* pats, uint32_t np, const rt_light_desc* lights, uint32_t nl,
+                           const rt_area_light_desc* area, uint32_t n_area, const rt_uv_map_desc* maps, uint32_t n_maps) {
+    WorldLists wl{shapes, ns, mats, nm, pats, np, lights, nl, meshes, n_meshes, instances, n_inst,
+                  smooth, n_smooth, uvs, n_uvs, textures, n_textures, area, n_area, true};
+    wl.maps = maps;
+    wl.n_maps = n_maps;
+    return upload_world(ctx, wl);
+}
+
 int rt_smooth_expand(const rt_shape_desc* shapes, uint32_t ns, const rt_mesh_desc* meshes, uint32_t n_meshes,
                      const rt_instance_desc* instances, uint32_t n_inst, const rt_smooth_desc* smooth, uint32_t n_smooth,
                      rt_smooth_desc* out, uint32_t* n_out) {
@@ -1574,6 +1597,12 @@ int rt_uv_expand(const rt_shape_desc* shapes, uint32_t ns, const rt_mesh_desc* m
 int rt_scene_texture_info(rt_context* ctx, rt_texture_info* out) {
     if (!ctx || !out) return set_error(RT_ERR_INVALID, "null argument");
     *out = ctx->have_scene ? ctx->texture_info : rt_texture_info{};
+    return RT_OK;
+}
+
+int rt_scene_map_info(rt_context* ctx, rt_map_info* out) {
+    if (!ctx || !out) return set_error(RT_ERR_INVALID, "null argument");
+    *out = ctx->have_scene ? ctx->map_info : rt_map_info{};
     return RT_OK;
 }
 
@@ -1987,6 +2016,8 @@ int upload_textures(rt_context* ctx, const WorldLists& wl) {
         table[t] = TexRec{total, textures[t].width, textures[t].height};
         total += (uint64_t)textures[t].width * textures[t].height;
     }
+    // (cube maps: each one's own texture and its six faces as consecutive records, a copy of the texture's each)
+    for (uint32_t r = 0; r < wl.n_tex_records; ++r) table.push_back(table[wl.tex_records[r]]);
     int rc;
     if ((rc = ctx->texels.reserve(std::max<uint64_t>(total, 1))) || (rc = ctx->tex_table.reserve(table.size()))) return rc;
     std::vector<uint32_t> host(std::max<uint64_t>(total, 1), 0u);
@@ -2003,7 +2034,7 @@ int upload_textures(rt_context* ctx, const WorldLists& wl) {
                                        hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync");
     const int rs = hip_status(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");  // (host temporaries)
     if (rc || rs) return rc ? rc : rs;
-    ctx->tex_counts = TextureCounts{n_textures, 1u, total};
+    ctx->tex_counts = TextureCounts{(uint32_t)table.size(), 1u, total};  // (the table's records: a group sizes its copies by them)
     ctx->w32.texels = ctx->w64.texels = ctx->texels.get();
     ctx->w32.tex_table = ctx->w64.tex_table = ctx->tex_table.get();
     return RT_OK;
@@ -2045,6 +2076,7 @@ void clear_lists(rt_context* ctx) {
     ctx->smooth_info = rt_smooth_info{};
     ctx->texture_info = rt_texture_info{};
     ctx->light_info = rt_light_info{};
+    ctx->map_info = rt_map_info{};
     ctx->smooth_shape.clear();
     ctx->tex_counts = TextureCounts{};
     auto clear = [](auto& w) {
@@ -2149,6 +2181,10 @@ int build_general(rt_context* ctx, const WorldLists& wl, bool textured, bool* pl
         ctx->texture_info.textures = wl.n_textures;
         ctx->texture_info.uv_bytes = ctx->w32.uv.bytes() + ctx->w64.uv.bytes();
         ctx->texture_info.texel_bytes = ctx->tex_counts.texels * sizeof(uint32_t) + (uint64_t)wl.n_textures * sizeof(TexRec);
+        for (uint32_t k = 0; k < wl.n_maps; ++k) {
+            ctx->map_info.mapped_patterns += wl.maps[k].map != RT_MAP_PLANAR;
+            ctx->map_info.cube_maps += wl.maps[k].map == RT_MAP_CUBE;
+        }
     }
     if ((rc = upload_instances<float>(ctx, ctx->w32, ip, wl)) || (rc = upload_instances<double>(ctx, ctx->w64, ip, wl)) ||
         (rc = upload_side<inst::SmoothSide>(ctx, ctx->w32, ctx->w32.smooth, ip, ip.normals)) ||
@@ -2214,7 +2250,8 @@ void set_kernel_build(rt_context* ctx, KernelBuild build) {
 
 // Which path an upload takes, and which build of the kernels its world runs, is decided here, by what the
 // validated lists hold:
-//   an area light                             the general path, the area build (with the texture tables);
+//   a map other than the planar one           the general path, the map build (with the texture and area tables);
+//   else an area light                        the general path, the area build (with the texture tables);
 //   else a coordinate entry or image pattern  the general path, the texture build (no other world uploads textures);
 //   else a smooth entry                       the general path, the instance build;
 //   else instances                            the general path and the instance build, unless every instance has a
@@ -2229,7 +2266,8 @@ int build_scene(rt_context* ctx, const WorldLists& wl) {
     bool plain_only = !wl.n_instances && !wl.n_smooth && !textured;
     if (int rc = plain_only ? build_plain_tables(ctx, wl, WorldIndices{}, false) : build_general(ctx, wl, textured, &plain_only))
         return rc;
-    set_kernel_build(ctx, wl.n_area ? KernelBuild::area
+    set_kernel_build(ctx, ctx->map_info.mapped_patterns ? KernelBuild::mapped
+                          : wl.n_area ? KernelBuild::area
                           : textured ? KernelBuild::textured
                           : plain_only ? KernelBuild::plain
                                        : KernelBuild::instanced);

@@ -66,6 +66,16 @@
 // rtc::area::launch_kernel, for worlds uploaded with an area light
 // (rt_scene_upload_lit).  Every line of it sits behind RTC_AREA_LIGHTS, so the
 // other builds compile to what they compiled to before.
+//
+// Map variant: built with -DRTC_INSTANCES=1 -DRTC_TEXTURES=1
+// -DRTC_AREA_LIGHTS=1 -DRTC_UV_MAPS=1 -DRTC_VARIANT=mapped (one TU per
+// precision), the area variant plus the spherical, cylindrical and cube maps of
+// image_color as rtc::mapped::launch_kernel, for worlds uploaded with a map
+// other than the planar one (rt_scene_upload_mapped), with or without an area
+// light.  Inside the texture variant the maps' atan2 and acos cost four f32
+// pool and supersampled kernels 4 to 24 B a lane of scratch beyond the
+// instance variant's, which tests/test_isa_budget_texture.py forbids
+// (DESIGN.md 3.16), so the texture and area variants compile none of it.
 #ifndef RTC_INSTANCES
 #define RTC_INSTANCES 0
 #endif
@@ -74,6 +84,9 @@
 #endif
 #ifndef RTC_TEXTURES
 #define RTC_TEXTURES 0
+#endif
+#ifndef RTC_UV_MAPS
+#define RTC_UV_MAPS 0
 #endif
 #if defined(RTC_VARIANT) && !RTC_INSTANCES
 #define RTC_POOL_ONLY 1  // a kind variant: the f32 pool kernel alone
@@ -1871,19 +1884,78 @@ __device__ inline V3<R> texel_color(uint32_t t) {
     using T = Real<R>;
     return {T::div((R)(t & 0xFFu), (R)255), T::div((R)((t >> 8) & 0xFFu), (R)255), T::div((R)((t >> 16) & 0xFFu), (R)255)};
 }
+//
+// Texture maps (rtc.h rt_scene_upload_mapped; the map build
+// only, RTC_UV_MAPS): a hit without coordinates takes the pattern's map of the
+// pattern-space point, PatternRec::pad (0 planar: the texture build's only
+// one).  A cube map's sub_a names seven consecutive records of the texture
+// table: the pattern's own texture, which a hit with coordinates samples, then
+// the six faces, so the face is an add to the index.  The device math
+// library's atan2, acos and sqrt.
+#if RTC_UV_MAPS
+__device__ inline float map_atan2(float y, float x) { return ::atan2f(y, x); }
+__device__ inline double map_atan2(double y, double x) { return ::atan2(y, x); }
+__device__ inline float map_acos(float c) { return ::acosf(c); }
+__device__ inline double map_acos(double c) { return ::acos(c); }
+__device__ inline float map_sqrt(float a) { return ::sqrtf(a); }
+__device__ inline double map_sqrt(double a) { return ::sqrt(a); }
+template <typename R>
+__device__ inline R map_mod2(R c) {  // m(c) = c - 2 floor(c / 2), halved
+    using T = Real<R>;
+    return T::div(c - (R)2 * T::floor(T::div(c, (R)2)), (R)2);
+}
+#endif
 template <typename R>
 __device__ inline V3<R> image_color(const PatternRec<R>* pr, const uint32_t* texels,
                                                         const TexRec* textures, bool have_uv, R u, R v, V3<R> obj) {
     using T = Real<R>;
+#if RTC_UV_MAPS
+    int record = pr->sub_a;
+#endif
     if (have_uv) {
         if (!(u >= (R)0 && u <= (R)1)) u = u - T::floor(u);
         if (!(v >= (R)0 && v <= (R)1)) v = v - T::floor(v);
     } else {
         const V3<R> pp = xform_point(pr->inv, obj);
+#if !RTC_UV_MAPS
         u = pp.x - T::floor(pp.x);
         v = pp.z - T::floor(pp.z);
+#else
+        const int map = pr->pad;
+        if (map == RT_MAP_PLANAR) {
+            u = pp.x - T::floor(pp.x);
+            v = pp.z - T::floor(pp.z);
+        } else if (map == RT_MAP_CUBE) {
+            const R a = T::fmax(T::fmax(T::fabs(pp.x), T::fabs(pp.y)), T::fabs(pp.z));
+            // left 0, front 1, right 2, back 3, up 4, down 5, after the pattern's own record
+            R cu, cv;
+            if (a == pp.x) record += 1 + RT_FACE_RIGHT, cu = (R)1 - pp.z, cv = pp.y + (R)1;
+            else if (a == -pp.x) record += 1 + RT_FACE_LEFT, cu = pp.z + (R)1, cv = pp.y + (R)1;
+            else if (a == pp.y) record += 1 + RT_FACE_UP, cu = pp.x + (R)1, cv = (R)1 - pp.z;
+            else if (a == -pp.y) record += 1 + RT_FACE_DOWN, cu = pp.x + (R)1, cv = pp.z + (R)1;
+            else if (a == pp.z) record += 1 + RT_FACE_FRONT, cu = pp.x + (R)1, cv = pp.y + (R)1;
+            else record += 1 + RT_FACE_BACK, cu = (R)1 - pp.x, cv = pp.y + (R)1;
+            u = map_mod2<R>(cu);
+            v = map_mod2<R>(cv);
+        } else {
+            constexpr R kPi = (R)3.14159265358979323846264338327950288;
+            const R theta = map_atan2(pp.x, pp.z);
+            u = (R)1 - (T::div(theta, (R)2 * kPi) + (R)0.5);
+            if (map == RT_MAP_SPHERICAL) {
+                const R r = map_sqrt((pp.x * pp.x + pp.y * pp.y) + pp.z * pp.z);
+                const R c = T::fmin(T::fmax(T::div(pp.y, r), (R)-1), (R)1);
+                v = (R)1 - T::div(map_acos(c), kPi);
+            } else {
+                v = pp.y - T::floor(pp.y);
+            }
+        }
+#endif
     }
+#if RTC_UV_MAPS
+    const TexRec tr = textures[record];
+#else
     const TexRec tr = textures[pr->sub_a];
+#endif
     const int w1 = (int)tr.width - 1, h1 = (int)tr.height - 1;
     const uint32_t* const base = texels + tr.offset;
     const R x = u * (R)w1, y = ((R)1 - v) * (R)h1;

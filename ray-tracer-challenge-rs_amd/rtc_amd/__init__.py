@@ -30,7 +30,7 @@ __all__ = [
     "load_obj", "Mesh", "SmoothDesc", "RT_SMOOTH_SHAPES", "RT_OBJ_NORMALS", "RT_NO_NORMAL",
     "AreaLightDesc", "RT_LIGHT_MAX_STEPS", "RT_JITTER_NONE", "RT_JITTER_HASHED", "area_light_sample",
     "LensDesc", "Lens", "lens_ray",
-    "UVDesc", "TextureDesc", "RT_OBJ_TEXCOORDS", "RT_NO_TEXCOORD", "TEXTURE_FILTERS", "read_image",
+    "UVMapDesc", "TEXTURE_MAPS", "UVDesc", "TextureDesc", "RT_OBJ_TEXCOORDS", "RT_NO_TEXCOORD", "TEXTURE_FILTERS", "read_image",
     "RT_DEFAULT_MAX_DEPTH", "RT_TILE_H", "RT_TILE_W",
 ]
 
@@ -55,6 +55,7 @@ RT_NO_NORMAL = 0xFFFFFFFF      # rt_mesh_normals_view.triangle_normals of a flat
 RT_OBJ_TEXCOORDS = 4           # rt_mesh_load_obj_ex: read vt lines and the faces' texture indices
 RT_NO_TEXCOORD = 0xFFFFFFFF    # rt_mesh_texcoords_view.triangle_texcoords of a face without coordinates
 TEXTURE_FILTERS = {"nearest": 0, "bilinear": 1}  # rt_pattern_desc.reserved of an image pattern
+TEXTURE_MAPS = {"planar": 0, "spherical": 1, "cylindrical": 2, "cube": 3}  # rt_uv_map_desc.map
 RT_LIGHT_MAX_STEPS = 16                 # rt_area_light_desc: steps per axis
 RT_JITTER_NONE, RT_JITTER_HASHED = 0, 1  # rt_area_light_desc.jitter
 
@@ -214,6 +215,15 @@ class LightInfo(C.Structure):
                 ("reserved", C.c_uint32), ("area_bytes", C.c_uint64)]
 
 
+class UVMapDesc(C.Structure):
+    _fields_ = [("pattern", C.c_uint32), ("map", C.c_uint32), ("faces", C.c_int32 * 6)]
+
+
+class MapInfo(C.Structure):
+    _fields_ = [("mapped_patterns", C.c_uint32), ("cube_maps", C.c_uint32), ("ran_mapped", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 class MeshTexcoordsView(C.Structure):
     _fields_ = [("texcoords", C.POINTER(C.c_double)), ("n_texcoords", C.c_uint32), ("n_textured", C.c_uint32),
                 ("triangle_texcoords", C.POINTER(C.c_uint32))]
@@ -324,6 +334,12 @@ def _load() -> C.CDLL:
                                           C.c_uint32, P(TextureDesc), C.c_uint32, P(MaterialDesc), C.c_uint32,
                                           P(PatternDesc), C.c_uint32, P(LightDesc), C.c_uint32, P(AreaLightDesc),
                                           C.c_uint32]),
+        "rt_scene_upload_mapped": (C.c_int, [C.c_void_p, P(ShapeDesc), C.c_uint32, P(MeshDesc), C.c_uint32,
+                                             P(InstanceDesc), C.c_uint32, P(SmoothDesc), C.c_uint32, P(UVDesc),
+                                             C.c_uint32, P(TextureDesc), C.c_uint32, P(MaterialDesc), C.c_uint32,
+                                             P(PatternDesc), C.c_uint32, P(LightDesc), C.c_uint32, P(AreaLightDesc),
+                                             C.c_uint32, P(UVMapDesc), C.c_uint32]),
+        "rt_scene_map_info": (C.c_int, [C.c_void_p, P(MapInfo)]),
         "rt_lights_expand": (C.c_int, [P(LightDesc), C.c_uint32, P(AreaLightDesc), C.c_uint32, P(LightDesc),
                                        P(C.c_uint32)]),
         "rt_render_lens": (C.c_int, [C.c_void_p, P(CameraDesc), P(RenderOptions), C.c_uint32, P(LensDesc), C.c_void_p,
@@ -408,6 +424,7 @@ EXPORTED_SYMBOLS = (
     "rt_image_read", "rt_image_free",
     "rt_scene_upload_lit", "rt_lights_expand", "rt_area_light_sample", "rt_scene_light_info",
     "rt_render_lens", "rt_render_lens_device", "rt_lens_ray",
+    "rt_scene_upload_mapped", "rt_scene_map_info",
 )
 
 
@@ -597,6 +614,18 @@ class SceneTables:
     textures: list | None = None
     # Area lights (rtc.h rt_scene_upload_lit): an array of AreaLightDesc; None / empty = none.
     area_lights: C.Array | None = None
+    # Texture maps (rtc.h rt_scene_upload_mapped): an array of UVMapDesc naming image patterns with their map
+    # and a cube map's six textures; None / empty = every image pattern is planar.
+    maps: C.Array | None = None
+
+    @property
+    def mapped(self) -> bool:
+        return self.maps is not None and len(self.maps) > 0
+
+    def mapped_args(self):
+        """rt_scene_upload_mapped's arguments after the context: lit_args() with the map list at the end."""
+        mp = self.maps if self.maps is not None else (UVMapDesc * 0)()
+        return self.lit_args() + (mp, len(mp))
 
     @property
     def lit(self) -> bool:
@@ -684,7 +713,8 @@ class SceneTables:
             if not self.lit:
                 return self
             return SceneTables(self.shapes, self.materials, self.patterns, self.expanded_lights(), self.camera,
-                               self.duplicate_shapes, smooth=self.smooth, uvs=self.uvs, textures=self.textures)
+                               self.duplicate_shapes, smooth=self.smooth, uvs=self.uvs, textures=self.textures,
+                               maps=self.maps)
         md, inst = self.mesh_descs(), self.instances
         total = len(self.shapes) + sum(len(self.meshes[i.mesh]) for i in inst if i.mesh < len(self.meshes))
         out = (ShapeDesc * total)()
@@ -704,7 +734,7 @@ class SceneTables:
             uvs = (UVDesc * n.value)()
             _check(_lib.rt_uv_expand(*a, uvs, C.byref(n)))
         return SceneTables(out, self.materials, self.patterns, self.expanded_lights(), self.camera, smooth=smooth,
-                           uvs=uvs, textures=self.textures)
+                           uvs=uvs, textures=self.textures, maps=self.maps)
 
     @property
     def counts(self):
@@ -980,13 +1010,23 @@ class Context:
         _check(_lib.rt_scene_light_info(self._h, C.byref(t)))
         return {name: getattr(t, name) for name, _ in t._fields_ if name != "reserved"}
 
+    def map_info(self) -> dict:
+        """The uploaded world's texture maps (rtc.h rt_scene_map_info): patterns with a map other than the
+        planar one, cube maps among them, whether the last launch ran the kernels that hold the map code."""
+        t = MapInfo()
+        _check(_lib.rt_scene_map_info(self._h, C.byref(t)))
+        return {name: getattr(t, name) for name, _ in t._fields_ if name != "reserved"}
+
     def upload(self, scene: SceneTables | None) -> None:
         """rt_scene_upload, rt_scene_upload_instanced for tables with instances, rt_scene_upload_smooth for
         tables with smooth triangles, rt_scene_upload_textured for tables with texture coordinates or
-        textures, or rt_scene_upload_lit for tables with area lights; on a non-zero rank of a group, None
+        textures, rt_scene_upload_lit for tables with area lights, or rt_scene_upload_mapped for tables with
+        a texture map entry; on a non-zero rank of a group, None
         (the scene comes from rank 0)."""
         if scene is None:
             _check(_lib.rt_scene_upload(self._h, None, 0, None, 0, None, 0, None, 0))
+        elif scene.mapped:
+            _check(_lib.rt_scene_upload_mapped(self._h, *scene.mapped_args()))
         elif scene.lit:
             _check(_lib.rt_scene_upload_lit(self._h, *scene.lit_args()))
         elif scene.textured:

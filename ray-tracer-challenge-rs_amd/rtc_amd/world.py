@@ -20,7 +20,7 @@ import ctypes as C
 import math
 from dataclasses import dataclass, field
 
-from . import (AreaLightDesc, CameraDesc, InstanceDesc, LightDesc, MaterialDesc, PatternDesc, PATTERN_KINDS, RT_SMOOTH_SHAPES,
+from . import (AreaLightDesc, CameraDesc, InstanceDesc, LightDesc, MaterialDesc, PatternDesc, PATTERN_KINDS, RT_SMOOTH_SHAPES, TEXTURE_MAPS, UVMapDesc,
                SceneTables, ShapeDesc, SHAPE_KINDS, SmoothDesc, TEXTURE_FILTERS, UVDesc, camera_make, matrix_inverse)
 
 F64_MAX = 1.7976931348623157e308
@@ -97,6 +97,10 @@ class Pattern:
     # the filter (TEXTURE_FILTERS); two patterns that hold the same array object share one texture of the upload
     image: object = field(default=None, compare=False)
     filter: int = 0
+    # its texture map (rtc.h rt_scene_upload_mapped, TEXTURE_MAPS) and, for a cube map, the six faces' arrays
+    # in the order left, front, right, back, up, down
+    map: int = 0
+    faces: object = field(default=None, compare=False)
 
     def set_transformation(self, m):
         self.transformation_inverse = inverse(m)
@@ -123,15 +127,30 @@ def complex_pattern(a: Pattern, b: Pattern):
     return Pattern("complex", sub_a=a, sub_b=b)
 
 
-def image_pattern(image, filter="nearest"):
-    """An image texture as a material's pattern (rtc.h rt_scene_upload_textured): `image` is a uint8 array of
-    shape (H, W, 3), row 0 at the top (rtc_amd.read_image); a triangle with texture coordinates samples it at
-    the interpolated (u, v), every other hit through the planar map of the pattern-space point."""
+def _texture_array(image, who):
     import numpy as np
     img = np.ascontiguousarray(image, dtype=np.uint8)
     if img.ndim != 3 or img.shape[2] != 3 or not img.size:
-        raise ValueError("image_pattern takes a uint8 array of shape (H, W, 3)")
-    return Pattern("image", image=img, filter=TEXTURE_FILTERS[filter])
+        raise ValueError(f"{who} takes a uint8 array of shape (H, W, 3)")
+    return img
+
+
+def image_pattern(image, filter="nearest", map="planar"):
+    """An image texture as a material's pattern (rtc.h rt_scene_upload_textured): `image` is a uint8 array of
+    shape (H, W, 3), row 0 at the top (rtc_amd.read_image); a triangle with texture coordinates samples it at
+    the interpolated (u, v), every other hit through `map` of the pattern-space point: "planar", "spherical"
+    or "cylindrical" (rtc.h rt_scene_upload_mapped)."""
+    if map not in ("planar", "spherical", "cylindrical"):
+        raise ValueError("image_pattern: map is 'planar', 'spherical' or 'cylindrical' (cube_map_pattern makes a cube map)")
+    return Pattern("image", image=_texture_array(image, "image_pattern"), filter=TEXTURE_FILTERS[filter],
+                   map=TEXTURE_MAPS[map])
+
+
+def cube_map_pattern(left, front, right, back, up, down, filter="nearest"):
+    """A cube map (rtc.h RT_MAP_CUBE): six images, one per face of the cube |x|, |y|, |z| <= 1 in pattern
+    space.  A triangle with texture coordinates samples `front`."""
+    faces = [_texture_array(f, "cube_map_pattern") for f in (left, front, right, back, up, down)]
+    return Pattern("image", image=faces[1], filter=TEXTURE_FILTERS[filter], map=TEXTURE_MAPS["cube"], faces=faces)
 
 
 def test_pattern():
@@ -395,6 +414,15 @@ class World:
                 e = UVDesc(RT_SMOOTH_SHAPES, i)
                 e.uv_1[:], e.uv_2[:], e.uv_3[:] = [list(map(float, t)) for t in s.uvs]
                 uvs.append(e)
+        maps = []  # UVMapDesc entries: the image patterns whose map is not the planar one
+
+        def texture_index(image) -> int:
+            for j, t in enumerate(textures):
+                if t is image:
+                    return j
+            textures.append(image)
+            return len(textures) - 1
+
         ptab = (PatternDesc * len(pats))()
         for i, p in enumerate(pats):
             d = ptab[i]
@@ -405,14 +433,12 @@ class World:
             d.sub_a = pats.index(p.sub_a) if p.sub_a is not None else -1
             d.sub_b = pats.index(p.sub_b) if p.sub_b is not None else -1
             if p.kind == "image":
-                for j, t in enumerate(textures):
-                    if t is p.image:
-                        d.sub_a = j
-                        break
-                else:
-                    d.sub_a = len(textures)
-                    textures.append(p.image)
+                d.sub_a = texture_index(p.image)
                 d.reserved = int(p.filter)
+                if p.map:
+                    e = UVMapDesc(i, int(p.map))
+                    e.faces[:] = [texture_index(f) for f in p.faces] if p.faces is not None else [-1] * 6
+                    maps.append(e)
         lts = (LightDesc * len(self.lights))()
         for i, lt in enumerate(self.lights):
             lts[i].position[:] = list(map(float, lt.position))
@@ -422,7 +448,8 @@ class World:
                            smooth=(SmoothDesc * len(smooth))(*smooth) if smooth else None,
                            uvs=(UVDesc * len(uvs))(*uvs) if uvs else None, textures=textures or None,
                            area_lights=(AreaLightDesc * len(self.area_lights))(*[a.desc() for a in self.area_lights])
-                           if self.area_lights else None)
+                           if self.area_lights else None,
+                           maps=(UVMapDesc * len(maps))(*maps) if maps else None)
 
 
 def camera(width, height, fov, frm=(0, 0, 0), to=(0, 0, -1), up=(0, 1, 0)) -> CameraDesc:
