@@ -946,6 +946,149 @@ int rt_render_lens_device(rt_context* ctx, const rt_camera_desc* camera,
 int rt_lens_ray(const rt_camera_desc* camera, uint32_t grid, const rt_lens_desc* lens,
                 uint32_t x, uint32_t y, uint32_t i, uint32_t j, double ray[6]);
 
+/* Motion blur: moving shapes and a shutter.  The reference
+ * has no motion, so this text is the contract; what it says can be checked
+ * against the reference all the same, because a ray of time tau in a moving
+ * world is that ray in the static world whose movers are displaced by v tau
+ * (rt_motion_displace), which the reference renders.
+ *
+ * What moves.  A top-level shape or a mesh instance may have a constant
+ * velocity v (world units per unit of time): at time tau it is the shape with
+ * transformation translation(v tau) * T.  Nothing else moves: no light, not
+ * the camera, no triangle inside an rt_mesh_desc run (to move a mesh, place it
+ * as an instance).  The top-level triangle hierarchy stays a static,
+ * world-space structure: a moving top-level triangle goes to the flat run
+ * behind it.
+ *
+ * rt_scene_upload_moving is rt_scene_upload_mapped with a motion list; with
+ * n_motion = 0 it is that call itself.  An entry whose velocity is zero in
+ * every component (+0 or -0) is dropped at upload: that shape is static.  Two
+ * shapes are value-equal (the containers walk's identity classes) iff they
+ * were equal before and their velocities are equal as f64 values.  A moving
+ * instance with a value-equal partner is uploaded expanded, as now, and its
+ * records carry the velocity.  (Two movers that share a transformation and
+ * differ in velocity are two classes at every time, tau = 0 included, where
+ * the displaced static world has them value-equal: the one place the two
+ * differ.)  A moving world is uploaded to one device: a context of a group of
+ * more than one rank refuses it with RT_ERR_INVALID.
+ * RT_ERR_INVALID, each with its own rt_last_error text and checked before the
+ * context is looked at, after the other lists' own checks, in this order: a null list with a nonzero
+ * count, an unknown target, an index out of range, a target named twice, a
+ * component that is not finite, a shape that belongs to a mesh run (a shape
+ * index from n_shapes on that is still a world index of the expansion names a
+ * triangle of an instance's mesh: move the instance instead).
+ *
+ * The displaced point.  All arithmetic in the kernel's real type R; v is
+ * rounded once to R.  For a ray of time tau and a moving shape, every POINT p
+ * that the reference multiplies by shape.inverse is replaced, per component, by
+ * p.x - v.x * tau: multiply, then subtract, no FMA in the f64 kernels.  The
+ * points are the ray origin in Ray::intersect, the world point in normal_at,
+ * the point in pattern_at_shape and over_point in the texture maps.  Vectors
+ * are untouched.  The hit's t, the hit point o + t d, over_point and
+ * under_point are in world space at time tau, as the displaced static world
+ * gives them.  A secondary ray (reflection, refraction, shadow) keeps its
+ * primary ray's tau.  Counters, ties and the u8 quantization are unchanged.
+ *
+ * The shutter.  rt_render_shutter* is rt_render_lens* with one change: sample
+ * (i, j) of pixel (x, y) also has a time.  A NULL lens or aperture == 0 gives
+ * the sample rays of rt_render_supersampled* (camera_ray's arithmetic), else
+ * the lens rays.  Grid range, flags, shards (hashes take whole-image
+ * coordinates), the refusal of groups of more than one rank, the sample order
+ * (j outer, i inner), the weights, the counters, the stream order and the u8
+ * rule are rt_render_lens*'s.  The time, with n = grid, mix and ray_id as
+ * under "Hashed jitter" and uint32_t wraparound:
+ *     RT_JITTER_NONE:    c = j n + i,  jt = 0.5
+ *     RT_JITTER_HASHED:  tk  = mix(seed ^ 0x54494D45)
+ *                        key = mix(tk ^ ray_id),   ray_id = (n y + j)(n W) + n x + i
+ *                        jt  = (key >> 8) * 2^-24
+ *                        r   = mix(tk ^ mix(y W + x)) mod n^2
+ *                        c   = (j n + i + r) mod n^2
+ *     u   = (c + jt) * inv_n2,          inv_n2 = R(1) / R(n^2)
+ *     tau = open_R + span_R * u         (multiply, then add)
+ * open and span = close - open are formed in f64 on the host and each rounded
+ * once to R; y is the whole-image row.  rt_shutter_time (host only) returns
+ * the f64 value for either jitter mode, `camera` being the OUTPUT camera.
+ * A world without moving shapes makes rt_render_shutter* equal rt_render_lens*
+ * after the checks (rt_render_supersampled* when there is no lens): the same
+ * bytes and counters.  RT_ERR_INVALID, each with its own text: a null
+ * shutter, a bound that is not finite, open > close, a jitter other than 0 or
+ * 1; after those whatever rt_render_lens* refuses, with its text.
+ *
+ * Ray batches.  rt_trace_rays_timed* is rt_trace_rays* with a time per ray,
+ * on the device in the precision's own type; times == NULL: every time is 0.
+ * out_hit is the primary ray's closest hit at its time.
+ *
+ * Everything else on a moving world (rt_render*, rt_render_supersampled*,
+ * rt_render_lens*, rt_color_at, rt_trace_rays*) sees the world at tau = 0: the
+ * static world's colours and counters.  Per-scene builds are refused for a
+ * world with a moving shape; rt_jit_status says so in its log.
+ *
+ * rt_motion_displace (host only) writes the static world at time tau: each
+ * moving target's inverse becomes inverse * translation(-v tau), v tau formed
+ * per component in f64 and the product as matrix.rs multiplies (each element
+ * the left fold ((a0 b0 + a1 b1) + a2 b2) + a3 b3).  out_shapes holds
+ * n_shapes entries and out_instances n_instances (either may be NULL when its
+ * count is 0; each may alias its input); at tau = 0, and for a zero velocity,
+ * the inverse is the input's bit for bit.  This is "the world at time tau" of
+ * the tests, and how a still at tau is rendered through the older entry
+ * points, per-scene kernels included. */
+#define RT_MOVE_SHAPE    0
+#define RT_MOVE_INSTANCE 1
+typedef struct rt_motion_desc {   /* 32 bytes */
+    uint32_t target;              /* RT_MOVE_* */
+    uint32_t index;               /* into `shapes` (world order) or `instances` */
+    double   velocity[3];
+} rt_motion_desc;
+int rt_scene_upload_moving(rt_context* ctx,
+                           const rt_shape_desc* shapes, uint32_t n_shapes,
+                           const rt_mesh_desc* meshes, uint32_t n_meshes,
+                           const rt_instance_desc* instances, uint32_t n_instances,
+                           const rt_smooth_desc* smooth, uint32_t n_smooth,
+                           const rt_uv_desc* uvs, uint32_t n_uvs,
+                           const rt_texture_desc* textures, uint32_t n_textures,
+                           const rt_material_desc* materials, uint32_t n_materials,
+                           const rt_pattern_desc* patterns, uint32_t n_patterns,
+                           const rt_light_desc* lights, uint32_t n_lights,
+                           const rt_area_light_desc* area, uint32_t n_area,
+                           const rt_uv_map_desc* maps, uint32_t n_maps,
+                           const rt_motion_desc* motion, uint32_t n_motion);
+typedef struct rt_shutter_desc {  /* 24 bytes */
+    double   open, close;         /* finite, open <= close */
+    uint32_t jitter, seed;        /* RT_JITTER_NONE | RT_JITTER_HASHED */
+} rt_shutter_desc;
+int rt_render_shutter(rt_context* ctx, const rt_camera_desc* camera,
+                      const rt_render_options* options, uint32_t grid,
+                      const rt_lens_desc* lens /* may be NULL */, const rt_shutter_desc* shutter,
+                      void* out_host, rt_stats* stats);
+int rt_render_shutter_device(rt_context* ctx, const rt_camera_desc* camera,
+                             const rt_render_options* options, uint32_t grid,
+                             const rt_lens_desc* lens, const rt_shutter_desc* shutter,
+                             void* out_device, void* hip_stream);
+int rt_shutter_time(const rt_camera_desc* camera, uint32_t grid, const rt_shutter_desc* shutter,
+                    uint32_t x, uint32_t y, uint32_t i, uint32_t j, double* tau);
+int rt_trace_rays_timed(rt_context* ctx, const double* rays, const double* times, uint64_t n_rays,
+                        const rt_ray_options* options, double* out_rgb, rt_ray_hit_f64* out_hit,
+                        rt_stats* stats);
+int rt_trace_rays_timed_device(rt_context* ctx, const void* rays_device, const void* times_device,
+                               uint64_t n_rays, const rt_ray_options* options,
+                               void* out_rgb_device, void* out_hit_device, void* hip_stream);
+int rt_motion_displace(const rt_shape_desc* shapes, uint32_t n_shapes,
+                       const rt_instance_desc* instances, uint32_t n_instances,
+                       const rt_motion_desc* motion, uint32_t n_motion, double tau,
+                       rt_shape_desc* out_shapes, rt_instance_desc* out_instances);
+/* The motion of the last upload (zeros after an upload without a nonzero
+ * velocity): moving shapes and instances, the bytes of the velocity tables of
+ * both precisions, and whether the last launch was a shutter frame or a timed
+ * ray batch of kernels that hold the motion code. */
+typedef struct rt_motion_info {
+    uint32_t moving_shapes;
+    uint32_t moving_instances;
+    uint32_t ran_motion;
+    uint32_t reserved;
+    uint64_t motion_bytes;
+} rt_motion_info;
+int rt_scene_motion_info(rt_context* ctx, rt_motion_info* out);
+
 /* Peer canvas: a frame assembled in place instead of gathered (SURVEY.md
  * §8e; the north star's "gather of framebuffer strips over xGMI" done as the
  * shards' own stores into rank 0's image).  The owner creates a device canvas

@@ -18,6 +18,7 @@ enum class KernelFamily : int {
     supersampled,  // trace_direct_ss, trace_pool_ss
     lens,          // trace_direct_lens, trace_pool_lens
     rays,          // trace_rays (no pool: one ray tree per lane)
+    shutter,       // trace_direct_shutter, trace_pool_shutter (the motion build alone; no per-scene build)
 };
 
 struct KernelId {
@@ -27,14 +28,19 @@ struct KernelId {
     bool dup = false;   // the containers walk by identity class (generic kernels only)
 
     // The supersampled and the lens kernels: a sample loop around the frame kernels' work.
-    constexpr bool sampled() const { return family == KernelFamily::supersampled || family == KernelFamily::lens; }
+    constexpr bool sampled() const {
+        return family == KernelFamily::supersampled || family == KernelFamily::lens || family == KernelFamily::shutter;
+    }
 
     // Slot of the occupancy cache: one per (family, pool, LDS world, precision).  dup has none of its own:
     // occupancy is asked of the dup = false instantiation (rtc_kernels.hip kernel_occupancy).  The ray-batch
     // family comes last and has no pool kernel, so the slots are dense.
     static constexpr int kOccupancySlots = 3 * 8 + 4;
+    // (the shutter family's eight follow them: kOccupancyEntries sizes the cache)
+    static constexpr int kOccupancyEntries = kOccupancySlots + 8;
     constexpr int occupancy_slot(bool f64) const {
-        return (int)family * 8 + (pool ? 4 : 0) + (lds ? 2 : 0) + (f64 ? 1 : 0);
+        const int base = family == KernelFamily::shutter ? kOccupancySlots : (int)family * 8;
+        return base + (pool ? 4 : 0) + (lds ? 2 : 0) + (f64 ? 1 : 0);
     }
 
     // Index of a per-scene build (f32, dup = false, no ray batches): the identity, RT_FLAG_NO_SKIPS and the
@@ -60,6 +66,7 @@ struct KernelId {
                 if (pool) return lds ? "rtc::trace_pool_lens<float, true, false>" : "rtc::trace_pool_lens<float, false, false>";
                 return lds ? "rtc::trace_direct_lens<float, true>" : "rtc::trace_direct_lens<float, false>";
             case KernelFamily::rays: break;
+            case KernelFamily::shutter: break;
         }
         return nullptr;
     }
@@ -70,6 +77,7 @@ struct KernelId {
             case KernelFamily::frame: return pool ? "pool" : "direct";
             case KernelFamily::supersampled: return pool ? "supersampled pool" : "supersampled direct";
             case KernelFamily::lens: return pool ? "lens pool" : "lens direct";
+            case KernelFamily::shutter: return pool ? "shutter pool" : "shutter direct";
             case KernelFamily::rays: break;
         }
         return "ray-batch";

@@ -30,7 +30,10 @@
 // lights, rt_scene_upload_lit), --aperture R --focus D
 // [--lens-jitter[=SEED]] (a thin lens of radius R focused at distance D, both
 // in camera space: rt_render_lens; works with --samples, whose
-// N x N samples leave the cells of an N x N grid on the lens disc).  Pixels are
+// N x N samples leave the cells of an N x N grid on the lens disc), --move
+// I:vx,vy,vz and --instance ...:v=vx,vy,vz with --shutter open,close[:jitter=SEED]
+// (motion blur: rt_scene_upload_moving and rt_render_shutter, DESIGN.md §3.17;
+// each sample also has a time in the shutter's interval).  Pixels are
 // quantized on the device as canvas.rs:117-123 does.
 #include <chrono>
 #include <cstdio>
@@ -47,11 +50,12 @@ static int usage() {
     std::fprintf(stderr,
                  "usage: rtc <SCENE.yaml> <OUT.png|OUT.ppm> [-r serial|parallel|gpu] [-q] [--width W] [--height H]\n"
                  "           [--depth D] [--precision f32|f64] [--device N] [--gpus N] [--ppm-binary] [--timings]\n"
-                 "           [--samples N] [--obj MESH.obj]... [--instance MESH.obj:tx,ty,tz[:s]]... [--smooth]\n"
+                 "           [--samples N] [--obj MESH.obj]... [--instance MESH.obj:tx,ty,tz[:s][:v=vx,vy,vz]]... [--smooth]\n"
                  "           [--texture IMAGE.ppm|png] [--texture-filter nearest|bilinear]\n"
                  "           [--texture-map planar|spherical|cylindrical] [--cube-map L,F,R,B,U,D]\n"
                  "           [--area-light cx,cy,cz:ux,uy,uz:vx,vy,vz:USTEPSxVSTEPS[:r,g,b][:jitter[=SEED]]]...\n"
                  "           [--aperture R --focus D [--lens-jitter[=SEED]]]\n"
+                 "           [--move I:vx,vy,vz]... [--shutter open,close[:jitter=SEED]]\n"
                  "  --obj MESH.obj appends the mesh's triangles (v and f lines; faces fan-triangulated) to the\n"
                  "  scene's shapes, with the default material and no transformation; repeatable.\n"
                  "  --instance MESH.obj:tx,ty,tz[:s] places a copy of the mesh, scaled by s (default 1) and moved by\n"
@@ -73,6 +77,11 @@ static int usage() {
                  "  --aperture R --focus D renders through a thin lens of radius R focused at distance D along the\n"
                  "  view axis (depth of field); each of the N x N samples leaves its own point of the lens, the cell\n"
                  "  centres of a grid on the disc or, with --lens-jitter[=SEED], hashed positions per sample.\n"
+                 "  --move I:vx,vy,vz gives shape I of the scene (file order, from 0) the constant velocity (vx, vy, vz);\n"
+                 "  repeatable.  --instance ...:v=vx,vy,vz gives that copy of the mesh a velocity.  --shutter open,close\n"
+                 "  renders motion blur: each of the N x N samples of --samples N (through the lens of --aperture and\n"
+                 "  --focus where given) sees every mover where it is at the sample's time between open and close,\n"
+                 "  the cell centres of the interval or, with :jitter=SEED, hashed times per sample.\n"
                  "  -r serial|parallel are accepted for the reference's command lines but render on the GPU like\n"
                  "  -r gpu: this build ships no CPU renderer (Camera::render / render_parallel are not in it).\n",
                  RT_LIGHT_MAX_STEPS, RT_MAX_SAMPLE_GRID);
@@ -118,16 +127,69 @@ static bool parse_area_light(const std::string& a, rt_area_light_desc* out) {
     return at == part.size();
 }
 
-// One --instance argument: FILE:tx,ty,tz[:s]
+// Three finite numbers "x,y,z" and nothing else.
+static bool parse_triple(const std::string& v, double t[3]) {
+    char tail = 0;
+    return std::sscanf(v.c_str(), "%lf,%lf,%lf%c", &t[0], &t[1], &t[2], &tail) == 3 && t[0] - t[0] == 0.0 &&
+           t[1] - t[1] == 0.0 && t[2] - t[2] == 0.0;
+}
+
+// One --move argument: I:vx,vy,vz
+struct Move {
+    uint32_t shape;
+    double v[3];
+};
+static bool parse_move(const std::string& a, Move* out) {
+    const size_t c = a.find(':');
+    if (c == std::string::npos || c == 0) return false;
+    char* end = nullptr;
+    const std::string index = a.substr(0, c);
+    const unsigned long i = std::strtoul(index.c_str(), &end, 10);
+    if (index[0] < '0' || index[0] > '9' || *end || i > 0xFFFFFFFFul) return false;
+    out->shape = (uint32_t)i;
+    return parse_triple(a.substr(c + 1), out->v);
+}
+
+// One --shutter argument: open,close[:jitter=SEED]
+static bool parse_shutter(const std::string& a, rt_shutter_desc* out) {
+    const size_t c = a.find(':');
+    const std::string bounds = a.substr(0, c);
+    char tail = 0;
+    *out = rt_shutter_desc{0.0, 0.0, RT_JITTER_NONE, 0};
+    if (std::sscanf(bounds.c_str(), "%lf,%lf%c", &out->open, &out->close, &tail) != 2) return false;
+    if (!(out->open - out->open == 0.0) || !(out->close - out->close == 0.0) || out->open > out->close) return false;
+    if (c == std::string::npos) return true;
+    const std::string j = a.substr(c + 1);
+    if (j.rfind("jitter=", 0) != 0) return false;
+    char* end = nullptr;
+    const unsigned long seed = std::strtoul(j.c_str() + 7, &end, 0);
+    if (j[7] < '0' || j[7] > '9' || *end || seed > 0xFFFFFFFFul) return false;
+    out->jitter = RT_JITTER_HASHED;
+    out->seed = (uint32_t)seed;
+    return true;
+}
+
+// One --instance argument: FILE:tx,ty,tz[:s][:v=vx,vy,vz]
 struct Placement {
     std::string file;
     double t[3], s;
+    double v[3];
+    bool moving;
 };
-static bool parse_placement(const std::string& a, Placement* out) {
+static bool parse_placement(const std::string& whole, Placement* out) {
     auto triple = [](const std::string& v, double t[3]) {
         char tail = 0;
         return std::sscanf(v.c_str(), "%lf,%lf,%lf%c", &t[0], &t[1], &t[2], &tail) == 3;
     };
+    std::string a = whole;
+    out->moving = false;
+    out->v[0] = out->v[1] = out->v[2] = 0.0;
+    const size_t vel = a.rfind(":v=");
+    if (vel != std::string::npos) {  // the trailing velocity, then the placement as it always was
+        if (!parse_triple(a.substr(vel + 3), out->v)) return false;
+        out->moving = true;
+        a = a.substr(0, vel);
+    }
     const size_t last = a.rfind(':');
     if (last == std::string::npos || last == 0) return false;
     out->s = 1.0;
@@ -169,6 +231,9 @@ int main(int argc, char** argv) {
     std::vector<const char*> obj_paths;
     std::vector<Placement> placements;
     std::vector<rt_area_light_desc> area_lights;
+    std::vector<Move> moves;
+    rt_shutter_desc shutter = {0.0, 0.0, RT_JITTER_NONE, 0};
+    bool have_shutter = false;
     for (int i = 3; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> const char* { return i + 1 < argc ? argv[++i] : nullptr; };
@@ -259,10 +324,32 @@ int main(int argc, char** argv) {
             const char* v = next();
             Placement p;
             if (!v || !parse_placement(v, &p)) {
-                std::fprintf(stderr, "error: --instance takes FILE:tx,ty,tz[:s]\n");
+                std::fprintf(stderr, "error: --instance takes FILE:tx,ty,tz[:s][:v=vx,vy,vz]\n");
                 return usage();
             }
             placements.push_back(p);
+        }
+        else if (a == "--move") {
+            const char* v = next();
+            Move m;
+            if (!v || !parse_move(v, &m)) {
+                std::fprintf(stderr, "error: --move takes I:vx,vy,vz, a shape of the scene (file order, from 0) and its velocity\n");
+                return usage();
+            }
+            for (const Move& other : moves)
+                if (other.shape == m.shape) {
+                    std::fprintf(stderr, "error: --move names shape %u twice\n", m.shape);
+                    return usage();
+                }
+            moves.push_back(m);
+        }
+        else if (a == "--shutter") {
+            const char* v = next();
+            if (!v || !parse_shutter(v, &shutter)) {
+                std::fprintf(stderr, "error: --shutter takes open,close[:jitter=SEED], two finite times with open <= close\n");
+                return usage();
+            }
+            have_shutter = true;
         }
         else if (a == "--area-light") {
             const char* v = next();
@@ -288,6 +375,12 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "error: --focus and --lens-jitter describe a lens: give --aperture R\n");
         return usage();
     }
+    bool movers = !moves.empty();
+    for (const Placement& p : placements) movers = movers || p.moving;
+    if (movers && !have_shutter) {
+        std::fprintf(stderr, "error: --move and --instance ...:v= describe motion: give --shutter open,close\n");
+        return usage();
+    }
     if (!quiet) std::printf("Rendering image using scene at %s\n", scene_path);
     using clk = std::chrono::steady_clock;
     auto ms_since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
@@ -299,6 +392,18 @@ int main(int argc, char** argv) {
     }
     rt_scene_view v;
     rt_scene_view_get(scene, &v);
+    // --move: the scene's shapes in file order; --instance ...:v=: the placements in command-line order
+    std::vector<rt_motion_desc> motion;
+    for (const Move& m : moves) {
+        if (m.shape >= v.n_shapes) {
+            std::fprintf(stderr, "error: --move names shape %u, the scene has %u shapes\n", m.shape, v.n_shapes);
+            return 2;
+        }
+        motion.push_back({RT_MOVE_SHAPE, m.shape, {m.v[0], m.v[1], m.v[2]}});
+    }
+    for (size_t k = 0; k < placements.size(); ++k)
+        if (placements[k].moving)
+            motion.push_back({RT_MOVE_INSTANCE, (uint32_t)k, {placements[k].v[0], placements[k].v[1], placements[k].v[2]}});
     rt_camera_desc cam = v.camera;
     if (width || height) rt_camera_resize(&cam, width ? width : cam.width, height ? height : cam.height);
     // --obj: the scene's tables with each mesh's triangles after its shapes, all on one Material::default
@@ -464,14 +569,15 @@ int main(int argc, char** argv) {
     const double ctx_ms = ms_since(t_ctx);
     const auto t_up = clk::now();
     if (created != RT_OK ||
-        rt_scene_upload_mapped(ctx, shapes.data(), (uint32_t)shapes.size(), meshes.data(), (uint32_t)meshes.size(),
+        rt_scene_upload_moving(ctx, shapes.data(), (uint32_t)shapes.size(), meshes.data(), (uint32_t)meshes.size(),
                                  instances.data(), (uint32_t)instances.size(), smooth_list.data(),
                                  (uint32_t)smooth_list.size(), uv_list.data(), (uint32_t)uv_list.size(), textures.data(),
                                  (uint32_t)textures.size(), materials.data(), (uint32_t)materials.size(), patterns.data(),
                                  (uint32_t)patterns.size(), v.lights,
                                  v.n_lights, area_lights.data(),
                                  (uint32_t)area_lights.size(), maps.data(),
-                                 (uint32_t)maps.size()) != RT_OK) {  // (no map: rt_scene_upload_lit; no area light: rt_scene_upload_textured; no texture: rt_scene_upload_smooth; no smooth triangle: rt_scene_upload_instanced; no instances: rt_scene_upload)
+                                 (uint32_t)maps.size(), motion.data(),
+                                 (uint32_t)motion.size()) != RT_OK) {  // (no motion: rt_scene_upload_mapped; no map: rt_scene_upload_lit; no area light: rt_scene_upload_textured; no texture: rt_scene_upload_smooth; no smooth triangle: rt_scene_upload_instanced; no instances: rt_scene_upload)
         free_textures();
         std::fprintf(stderr, "error: %s\n", rt_last_error());
         return 1;
@@ -485,7 +591,8 @@ int main(int argc, char** argv) {
     std::vector<uint8_t> img((size_t)cam.width * cam.height * 3);
     rt_stats st;
     auto t0 = std::chrono::steady_clock::now();
-    if ((have_aperture ? rt_render_lens(ctx, &cam, &o, samples, &lens, img.data(), &st)
+    if ((have_shutter  ? rt_render_shutter(ctx, &cam, &o, samples, have_aperture ? &lens : nullptr, &shutter, img.data(), &st)
+         : have_aperture ? rt_render_lens(ctx, &cam, &o, samples, &lens, img.data(), &st)
          : samples > 1 ? rt_render_supersampled(ctx, &cam, &o, samples, img.data(), &st)
                        : rt_render(ctx, &cam, &o, img.data(), &st)) != RT_OK) {
         std::fprintf(stderr, "error: %s\n", rt_last_error());

@@ -67,6 +67,7 @@ enum class KernelBuild : uint32_t {
     textured,   // rtc::textured::*: ... plus the texture code, for an image pattern or a coordinate entry
     area,       // rtc::area::*: ... plus the area lights' sample loop
     mapped,     // rtc::mapped::*: ... plus the spherical, cylindrical and cube maps of an image pattern
+    moving,     // rtc::moving::*: ... plus a time per ray, the displaced point of a mover and the shutter frame kernels
 };
 
 // Texel storage of a world (rt_scene_upload_textured): the texture count and the texels of all of them; a
@@ -101,6 +102,10 @@ struct DeviceWorld {
     const uint32_t* texels = nullptr;
     const TexRec* tex_table = nullptr;      // non-null: the world runs the texture code
     // Area lights (rt_scene_upload_lit; rtc_internal.hpp AreaLightRec), outside the LDS image
+    // Motion (rt_scene_upload_moving; rtc_internal.hpp MotionArg): the velocity tables, four reals an entry,
+    // one entry per slot of the shape table and one per instance; outside the LDS image
+    DeviceBuffer<R> shape_vel, inst_vel;
+    bool moving = false;                    // the world has a mover: it runs the motion build
     DeviceBuffer<AreaLightRec<R>> area;
     uint32_t n_area = 0;                    // 0: a world without area lights
     uint32_t area_samples = 0;              // the sum of their sample counts
@@ -319,8 +324,8 @@ struct rt_context {
     rtc::KernelBuild kernel_build = rtc::KernelBuild::plain;  // the uploaded world's (set_kernel_build)
     // occupancy cache of kernel_build's kernels, by KernelId::occupancy_slot (kernel_id.hpp): the dynamic LDS
     // size last asked about and the workgroups per CU at it (0: nothing cached)
-    size_t occ_lds[rtc::KernelId::kOccupancySlots] = {};
-    int occ_blocks[rtc::KernelId::kOccupancySlots] = {};
+    size_t occ_lds[rtc::KernelId::kOccupancyEntries] = {};
+    int occ_blocks[rtc::KernelId::kOccupancyEntries] = {};
     Knobs knobs;
     rtc::Stream stream;
     rtc::Event ev_start, ev_stop;
@@ -359,12 +364,14 @@ struct rt_context {
     rt_texture_info texture_info{};    // rt_scene_texture_info
     rt_light_info light_info{};        // area lights of the uploaded world (rt_scene_light_info)
     rt_map_info map_info{};            // texture maps of the uploaded world (rt_scene_map_info)
+    rt_motion_info motion_info{};      // movers of the uploaded world (rt_scene_motion_info)
     std::vector<int32_t> world_slot;  // world index -> slot | kind << 24 of the uploaded table
     // ray-pool overflow regions, one per resident workgroup; a ray batch's per-lane LIFOs (launch_rays)
     rtc::DeviceBuffer<unsigned char> d_spill;
     TileOrder order;
     TileOrder order_ss;  // ... of the supersampled launches (rt_render_supersampled*): costs of n^2 samples per tile
     TileOrder order_lens;  // ... of the lens launches (rt_render_lens*): the lens in the signature
+    TileOrder order_shutter;  // ... of the shutter launches (rt_render_shutter*): the lens and the shutter in the signature
     Jit jit;
     rtc::DeviceBuffer<unsigned char> d_scratch;  // host-buffer renders / color_at staging
     rtc::DeviceBuffer<unsigned long long> d_stamps;  // RT_FLAG_STAMPS diagnostics: two per workgroup
@@ -451,6 +458,8 @@ struct WorldLists {
     // canonical_image_patterns), filled in by the upload once the maps are validated
     const int32_t* tex_records = nullptr;
     uint32_t n_tex_records = 0;
+    const rt_motion_desc* motion = nullptr;  // rt_scene_upload_moving's list (the upload drops its zero velocities)
+    uint32_t n_motion = 0;
 };
 // Every refusal of rtc.h for these lists, in the entry points' order: the area list, the texture list, the
 // base tables, the mesh and instance lists, the smooth list, the uv list, the lights' total.

@@ -50,6 +50,7 @@ namespace instanced { RTC_KERNEL_LAUNCHERS }  // rtc_kernels_inst*.o: with the i
 namespace textured { RTC_KERNEL_LAUNCHERS }   // rtc_kernels_tex*.o: the instance build plus the texture code
 namespace area { RTC_KERNEL_LAUNCHERS }       // rtc_kernels_area*.o: the texture build plus the area lights' sample loop
 namespace mapped { RTC_KERNEL_LAUNCHERS }     // rtc_kernels_map*.o: the area build plus the texture maps of an image pattern
+namespace moving { RTC_KERNEL_LAUNCHERS }     // rtc_kernels_motion*.o: the map build plus a time per ray and the shutter frame kernels; `extra` is a MotionLaunch
 namespace sp { RTC_KERNEL_LAUNCHERS }         // rtc_kernels_sp.o: the f32 frame pool kernel for worlds of spheres and planes only
 #undef RTC_KERNEL_LAUNCHERS
 constexpr uint32_t kKindsSp = (1u << RT_SHAPE_SPHERE) | (1u << RT_SHAPE_PLANE);
@@ -66,7 +67,8 @@ constexpr Launchers<R> kLaunchers[] = {{launch_kernel<R>, kernel_occupancy<R>},
                                        {instanced::launch_kernel<R>, instanced::kernel_occupancy<R>},
                                        {textured::launch_kernel<R>, textured::kernel_occupancy<R>},
                                        {area::launch_kernel<R>, area::kernel_occupancy<R>},
-                                       {mapped::launch_kernel<R>, mapped::kernel_occupancy<R>}};
+                                       {mapped::launch_kernel<R>, mapped::kernel_occupancy<R>},
+                                       {moving::launch_kernel<R>, moving::kernel_occupancy<R>}};
 template <typename R>
 const Launchers<R>& launchers(const rt_context* ctx) {
     return kLaunchers<R>[(uint32_t)ctx->kernel_build];
@@ -238,7 +240,7 @@ struct TrianglePlan {
     double build_ms = 0.0;
 };
 TrianglePlan plan_triangles(const rt_context::Knobs& knobs, const rt_shape_desc* shapes, std::vector<uint32_t>& order,
-                            const std::vector<uint32_t>& cls) {
+                            const std::vector<uint32_t>& cls, ident::Normals velocity = nullptr) {
     TrianglePlan plan;
     if (!knobs.tri_tree || !knobs.cull) return plan;
     const auto t0 = std::chrono::steady_clock::now();
@@ -249,7 +251,8 @@ TrianglePlan plan_triangles(const rt_context::Knobs& knobs, const rt_shape_desc*
     for (size_t j = first; j < order.size(); ++j) {
         double bs[4];
         bounding_sphere(shapes[order[j]], bs);
-        if (bs[3] >= 0.0) {
+        // (a moving triangle stays outside the tree, a static world-space structure: it goes to the flat run)
+        if (bs[3] >= 0.0 && !ident::normals_of(velocity, order[j])) {
             bounded.push_back(order[j]);
             bcls.push_back(cls[order[j]]);
             balls.push_back({{bs[0], bs[1], bs[2]}, bs[3]});
@@ -278,6 +281,7 @@ struct WorldIndices {
     std::vector<int32_t>* slot_of = nullptr;  // out: slot | kind << 24 of list entry i
     ident::Normals normals = nullptr;  // vertex normals of list entry i, null for a flat shape (null: none is smooth)
     ident::Normals uvs = nullptr;      // texture coordinates of list entry i (six doubles), null for a shape without
+    ident::Normals velocity = nullptr;  // the velocity of list entry i (three doubles), null for a static shape (null: none moves)
     uint32_t of(uint32_t i) const { return index ? index[i] : i; }
     uint32_t plain(uint32_t ns) const { return index ? n_plain : ns; }
 };
@@ -345,12 +349,20 @@ int build_world(rt_context* ctx, DeviceWorld<R>& w, const WorldLists& wl, const 
             const bool class_end = next + 1 >= order.size() || cls[order[next + 1]] != cls[i];
             r.flags = (d.closed ? kShapeClosed : 0) | (class_end ? kShapeClassEnd : 0) | (similar ? kShapeSimilar : 0) | (aligned ? kShapeAxisAligned : 0) |
                       (ident::normals_of(wi.normals, i) ? kShapeSmooth : 0) | (ident::normals_of(wi.uvs, i) ? kShapeUV : 0) |
-                      (int32_t)(wi.of(cls[i]) << kShapeClassShift);
+                      (ident::normals_of(wi.velocity, i) ? kShapeMoving : 0) | (int32_t)(wi.of(cls[i]) << kShapeClassShift);
             r.casts_shadow = mats[d.material].casts_shadow ? 1 : 0;
             sh.push_back(r);
         }
     }
     begin[kNumKinds] = (int32_t)sh.size();
+    // the shape velocity table of a moving world (rtc_internal.hpp MotionArg), by slot, each component rounded once to R
+    std::vector<R> vel;
+    if (wi.velocity) {
+        vel.assign(4 * std::max<size_t>(sh.size(), 1), (R)0);
+        for (size_t j = 0; j < order.size(); ++j)
+            if (const double* v = wi.velocity[order[j]])
+                for (int q = 0; q < 3; ++q) vel[4 * j + q] = (R)v[q];
+    }
     // world order -> (slot | kind << 24), padded to whole 16-byte words
     std::vector<int32_t> ws((sh.size() + 3) / 4 * 4, -1);
     for (int k = 0; k < kNumKinds; ++k)
@@ -435,6 +447,17 @@ int build_world(rt_context* ctx, DeviceWorld<R>& w, const WorldLists& wl, const 
         (void)hipStreamSynchronize(ctx->stream);  // the node copy may still read `nodes`
         return rc;
     }
+    if (!vel.empty()) {
+        if ((rc = w.shape_vel.reserve(vel.size()))) {
+            (void)hipStreamSynchronize(ctx->stream);
+            return rc;
+        }
+        if ((rc = hip_status(hipMemcpyAsync(w.shape_vel.get(), vel.data(), vel.size() * sizeof(R), hipMemcpyHostToDevice,
+                                            ctx->stream), "hipMemcpyAsync"))) {
+            (void)hipStreamSynchronize(ctx->stream);
+            return rc;
+        }
+    }
     if (nl && (rc = hip_status(hipMemcpyAsync(w.lights.get(), lt.data(), nl * sizeof(LightRec<R>),
                                               hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync"))) {
         (void)hipStreamSynchronize(ctx->stream);  // the image copy may still read `img`
@@ -467,6 +490,32 @@ static std::string validate_area(const rt_area_light_desc* area, uint32_t n_area
             if (!std::isfinite(d.corner[q]) || !std::isfinite(d.full_uvec[q]) || !std::isfinite(d.full_vvec[q]) ||
                 !std::isfinite(d.intensity[q]))
                 return who + ": a component that is not finite";
+    }
+    return std::string();
+}
+
+// rt_scene_upload_moving's list against the validated shape, mesh and instance lists; empty: valid.  Each
+// refusal has a text of its own (rtc.h "Motion blur"), in the order written there.
+static std::string validate_motion(const WorldLists& wl) {
+    if (wl.n_motion && !wl.motion) return "rt_scene_upload_moving: null motion list with nonzero count";
+    uint64_t world = wl.n_shapes;  // the expansion's shapes: the top-level ones, then every instance's triangles
+    for (uint32_t k = 0; k < wl.n_instances; ++k) world += wl.meshes[wl.instances[k].mesh].n_triangles;
+    std::vector<char> shape_named(wl.n_shapes, 0), inst_named(wl.n_instances, 0);
+    for (uint32_t m = 0; m < wl.n_motion; ++m) {
+        const rt_motion_desc& d = wl.motion[m];
+        const std::string who = "motion " + std::to_string(m);
+        if (d.target != RT_MOVE_SHAPE && d.target != RT_MOVE_INSTANCE) return who + ": unknown target";
+        const bool shape = d.target == RT_MOVE_SHAPE;
+        if (shape ? d.index >= world : d.index >= wl.n_instances) return who + ": index out of range";
+        if (!shape || d.index < wl.n_shapes) {
+            char& named = shape ? shape_named[d.index] : inst_named[d.index];
+            if (named) return who + ": target named twice";
+            named = 1;
+        }
+        for (int q = 0; q < 3; ++q)
+            if (!std::isfinite(d.velocity[q])) return who + ": a velocity component that is not finite";
+        if (shape && d.index >= wl.n_shapes)
+            return who + ": the shape belongs to a mesh run (a triangle of an instance's mesh does not move alone: move the instance)";
     }
     return std::string();
 }
@@ -526,6 +575,7 @@ int validate_scene(const WorldLists& wl) {
     for (uint32_t a = 0; why.empty() && a < wl.n_area; ++a) total += wl.area[a].usteps * wl.area[a].vsteps;
     if (why.empty() && total > 0x7fffffffull) why = "table too large";
     if (why.empty()) why = inst::validate_maps(wl.maps, wl.n_maps, wl.patterns, wl.n_patterns, wl.n_textures);
+    if (why.empty()) why = validate_motion(wl);
     return why.empty() ? RT_OK : set_error(RT_ERR_INVALID, why);
 }
 
@@ -779,7 +829,8 @@ int plan_launch(rt_context* ctx, const DevScene<R>& sc, uint32_t depth, uint32_t
 // lens in the signature beside the camera).
 template <typename R>
 int plan_tile_order(rt_context* ctx, rt_context::TileOrder& to, LaunchParams<R>& P, const rt_camera_desc* cam,
-                    uint32_t depth, uint32_t grid, hipStream_t stream, const rt_lens_desc* lens = nullptr) {
+                    uint32_t depth, uint32_t grid, hipStream_t stream, const rt_lens_desc* lens = nullptr,
+                    const rt_shutter_desc* shutter = nullptr) {
     if (P.n_tiles > kItemTileMask + 1) return RT_OK;  // items carry 20 tile bits: raster order
     uint64_t h = 1469598103934665603ull;  // FNV-1a
     auto mix = [&h](const void* p, size_t n) {
@@ -792,6 +843,7 @@ int plan_tile_order(rt_context* ctx, rt_context::TileOrder& to, LaunchParams<R>&
     const uint64_t geometry = h;
     if (cam) mix(cam, sizeof(*cam));
     if (lens) mix(lens, sizeof(*lens));
+    if (shutter) mix(shutter, sizeof(*shutter));
     bool grew_cost = false, grew_order = false;
     int rc = to.d_cost.reserve(P.n_tiles, &grew_cost);
     // up to 2^kMaxSplitLog2 items per tile, then the item count
@@ -876,6 +928,8 @@ struct LaunchRequest {
     uint32_t samples = 0;  // a supersampled frame's grid (cam = the sample camera, out_w x out_h the output), 0 = plain
     uint32_t out_w = 0, out_h = 0;
     const rt_lens_desc* lens = nullptr;  // with samples (a grid of 1 too): a lens frame (rt_render_lens*), aperture > 0
+    // with samples (a grid of 1 too), of a moving world: a shutter frame (rt_render_shutter*), with or without a lens
+    const rt_shutter_desc* shutter = nullptr;
 };
 
 // Host restatement of the kernels' transforms (rtc_kernels.hip xform_point): the f64 left fold, the f32 fused chain.
@@ -917,6 +971,22 @@ void set_lens_params(const LaunchParams<R>& P, const rt_lens_desc& lens, uint32_
             lens_point<R>(P.cam.inv, o.aperture, o.inv_n, (R)i + (R)0.5, (R)j + (R)0.5, o.points[j * n + i]);
 }
 
+// The launch's shutter (rtc.h "The shutter"): open and span = close - open formed in f64, each rounded once to R.
+template <typename R>
+void set_shutter_params(const rt_shutter_desc& sh, uint32_t n, ShutterParams<R>& o) {
+    o.open = (R)sh.open;
+    o.span = (R)(sh.close - sh.open);
+    o.inv_n2 = (R)1 / (R)(n * n);
+    o.jitter = sh.jitter;
+    o.tk = hash_mix(sh.seed ^ kShutterKey);
+}
+
+// The velocity tables of a moving world as its kernels take them (rtc_internal.hpp MotionArg).
+template <typename R>
+MotionArg motion_arg(const DeviceWorld<R>& w) {
+    return {w.shape_vel.get(), w.inst_counts.instances ? w.inst_vel.get() : nullptr};
+}
+
 // Step 1 of a launch (frames and ray batches alike): the launch's view of the
 // world, its tables, triangle hierarchy, mesh instances (none: no world index
 // reaches inst_world_begin), side tables, textures and area lights.
@@ -948,7 +1018,8 @@ void set_world_params(const rt_context* ctx, const DeviceWorld<R>& w, LaunchPara
 // Step 2: what the launch renders, a camera's canvas (with the lens of a lens
 // frame) or a ray batch, and where its output and counters go.
 template <typename R>
-void set_target_params(rt_context* ctx, const LaunchRequest& q, LaunchParams<R>& P, LensParams<R>& lens_params) {
+void set_target_params(rt_context* ctx, const LaunchRequest& q, LaunchParams<R>& P, ShutterArg<R>& frame_arg) {
+    LensParams<R>& lens_params = frame_arg.lens;
     P.image_rows = q.image_rows ? 1u : 0u;
     if (const rt_camera_desc* cam = q.cam) {
         for (int i = 0; i < 12; ++i) P.cam.inv[i] = (R)cam->inverse[i];
@@ -959,6 +1030,7 @@ void set_target_params(rt_context* ctx, const LaunchRequest& q, LaunchParams<R>&
         // (a supersampled frame: the canvas and its tiles are the output's)
         P.ss_grid = q.samples;
         if (q.lens) set_lens_params(P, *q.lens, q.samples, lens_params);
+        if (q.shutter) set_shutter_params(*q.shutter, q.samples, frame_arg.shutter);  // (no lens: aperture 0, the pinhole's rays)
         P.width = q.samples ? q.out_w : cam->width;
         P.height = q.samples ? q.out_h : cam->height;
         P.tiles_x = (P.width + RT_TILE_W - 1) / RT_TILE_W;
@@ -996,7 +1068,10 @@ int choose_kernel(rt_context* ctx, const DeviceWorld<R>& w, const LaunchRequest&
     int rc;
     LaunchShape& ls = k.ls;
     KernelId id;
-    id.family = q.lens ? KernelFamily::lens : q.samples ? KernelFamily::supersampled : KernelFamily::frame;
+    id.family = q.shutter ? KernelFamily::shutter
+                : q.lens  ? KernelFamily::lens
+                : q.samples ? KernelFamily::supersampled
+                            : KernelFamily::frame;
     // value-equal shapes (rt_scene_upload's identity classes) take the pool
     // kernel whose containers walk aggregates per class
     id.dup = ctx->duplicate_shapes > 0;
@@ -1012,9 +1087,10 @@ int choose_kernel(rt_context* ctx, const DeviceWorld<R>& w, const LaunchRequest&
             RT_FLAG_NO_SHADE | RT_FLAG_NO_TRACE | RT_FLAG_GENERATIONS | (ls.id.pool ? 0u : RT_FLAG_STAMPS);
         // (a world with a triangle hierarchy runs the generic kernels, which walk it)
         const bool instanced = walked_instances(w), smooth = has_smooth(w);
-        const bool tree = w.n_tri_nodes > 0 || instanced || smooth || has_textures(w);
+        const bool tree = w.n_tri_nodes > 0 || instanced || smooth || has_textures(w) || w.moving;
         if (tree && ctx->jit.mode != RT_JIT_OFF && ctx->jit.log.empty())
-            ctx->jit.log = has_area(w) ? "no per-scene build: the world has area lights, which the generic kernels sample"
+            ctx->jit.log = w.moving ? "no per-scene build: the world has moving shapes, whose displaced points the generic kernels form"
+                           : has_area(w) ? "no per-scene build: the world has area lights, which the generic kernels sample"
                            : has_textures(w) ? "no per-scene build: the world has textures, which the generic kernels sample"
                            : smooth ? "no per-scene build: the world has smooth triangles, whose normals the generic kernels interpolate"
                            : instanced
@@ -1064,7 +1140,10 @@ int reserve_spill(rt_context* ctx, const LaunchShape& ls, LaunchParams<R>& P) {
 
 // The tile order a family's launches keep (plan_tile_order).
 inline rt_context::TileOrder& tile_order_of(rt_context* ctx, KernelFamily family) {
-    return family == KernelFamily::lens ? ctx->order_lens : family == KernelFamily::supersampled ? ctx->order_ss : ctx->order;
+    return family == KernelFamily::shutter        ? ctx->order_shutter
+           : family == KernelFamily::lens         ? ctx->order_lens
+           : family == KernelFamily::supersampled ? ctx->order_ss
+                                                  : ctx->order;
 }
 
 // Step 5 (pool launches only: the direct kernel reads no queue heads): the
@@ -1081,7 +1160,7 @@ int set_queue_heads(rt_context* ctx, const LaunchRequest& q, const LaunchShape& 
     P.tile_counter = ctx->d_tile_counter.get() + (ctx->head_set ? set : 0);
     P.next_tile_counter = ctx->d_tile_counter.get() + (ctx->head_set ? 0 : set);
     if (!ctx->knobs.tile_order || !q.cam) return RT_OK;  // frames only: a ray batch's content is not in the signature
-    return plan_tile_order<R>(ctx, tile_order_of(ctx, ls.id.family), P, q.cam, q.depth, ls.grid, q.stream, q.lens);
+    return plan_tile_order<R>(ctx, tile_order_of(ctx, ls.id.family), P, q.cam, q.depth, ls.grid, q.stream, q.lens, q.shutter);
 }
 
 // Step 6 (RT_FLAG_STAMPS): the workgroups' stamps and a pool launch's item log, reserved behind the tile order.
@@ -1129,8 +1208,9 @@ inline void fill_launch_tables(const rt_context* ctx, const DeviceWorld<float>& 
 // Step 8: the launch itself, of the per-scene function or of the generic
 // kernel of the world's build (or of the spheres-and-planes build).
 template <typename R>
-int dispatch(rt_context* ctx, const KernelChoice& k, const LaunchParams<R>& P, const LensParams<R>& lens_params,
-             hipStream_t stream) {
+int dispatch(rt_context* ctx, const DeviceWorld<R>& w, const KernelChoice& k, const LaunchParams<R>& P,
+             const ShutterArg<R>& frame_arg, hipStream_t stream) {
+    const LensParams<R>& lens_params = frame_arg.lens;
     const LaunchShape& ls = k.ls;
     if (k.jit) {
         const ShapeRec<R>* sh = P.scene.shapes;
@@ -1146,7 +1226,11 @@ int dispatch(rt_context* ctx, const KernelChoice& k, const LaunchParams<R>& P, c
     auto launch_kernel = launchers<R>(ctx).launch_kernel;
     if constexpr (sizeof(R) == 4)
         if (k.sp) launch_kernel = sp::launch_kernel<R>;
-    if (hipError_t e = launch_kernel(ls.id, P, &lens_params, ls.grid, ls.lds, stream); e != hipSuccess)
+    // (the lens is the frame argument's first member: the lens kernels read it there, the shutter kernels the whole;
+    // the motion build takes the velocity tables in front of it)
+    const MotionLaunch ml{motion_arg(w), &frame_arg};
+    const void* extra = ctx->kernel_build == KernelBuild::moving ? static_cast<const void*>(&ml) : &frame_arg;
+    if (hipError_t e = launch_kernel(ls.id, P, extra, ls.grid, ls.lds, stream); e != hipSuccess)
         return set_error(RT_ERR_HIP, std::string("launch of the ") + ls.id.describe() + " kernel (grid " +
                                          std::to_string(ls.grid) + ", dynamic LDS " + std::to_string(ls.lds) +
                                          " B, pool " + std::to_string(ls.lcap) + "/" + std::to_string(ls.cap) +
@@ -1158,9 +1242,9 @@ template <typename R>
 int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
     int rc;
     LaunchParams<R> P{};
-    LensParams<R> lens_params{};  // a lens launch's last kernel argument
+    ShutterArg<R> frame_arg{};  // a lens or shutter launch's last kernel argument: the lens, then the shutter
     set_world_params(ctx, w, P);
-    set_target_params(ctx, q, P, lens_params);
+    set_target_params(ctx, q, P, frame_arg);
     if (P.n_tiles == 0) return RT_OK;
     if ((rc = order_after_last(ctx, q.stream))) return rc;
     KernelChoice k;
@@ -1181,12 +1265,13 @@ int launch(rt_context* ctx, DeviceWorld<R>& w, const LaunchRequest& q) {
     if (q.flags & RT_FLAG_FAIL_LAUNCH) return set_error(RT_ERR_HIP, "launch refused (RT_FLAG_FAIL_LAUNCH)");
     if constexpr (sizeof(R) == 4)
         if (reads_launch_tables(ctx, w, q, k)) fill_launch_tables(ctx, w, P);
-    if ((rc = dispatch(ctx, k, P, lens_params, q.stream))) return rc;
+    if ((rc = dispatch(ctx, w, k, P, frame_arg, q.stream))) return rc;
     if (ls.id.pool) ctx->head_set ^= 1;  // (the queue heads' set: see set_queue_heads)
     ctx->smooth_info.ran_smooth = !k.jit && has_smooth(w) ? 1u : 0u;
     ctx->texture_info.ran_textured = !k.jit && has_textures(w) ? 1u : 0u;
     ctx->map_info.ran_mapped = ctx->texture_info.ran_textured && ctx->kernel_build == KernelBuild::mapped ? 1u : 0u;
     ctx->light_info.ran_area = !k.jit && has_area(w) ? 1u : 0u;
+    ctx->motion_info.ran_motion = ls.id.family == KernelFamily::shutter ? 1u : 0u;
     return RT_OK;
 }
 
@@ -1216,8 +1301,8 @@ int plan_rays(rt_context* ctx, const DevScene<R>& sc, uint32_t depth, uint32_t n
 // and, if d_hits, the primary hits, on `stream`.  No range check of the
 // world and none of the directions: trace_rays sums per lane in plain R.
 template <typename R>
-int launch_rays(rt_context* ctx, DeviceWorld<R>& w, const void* d_rays, uint64_t n, const rt_ray_options* o,
-                void* d_rgb, void* d_hits, hipStream_t stream) {
+int launch_rays(rt_context* ctx, DeviceWorld<R>& w, const void* d_rays, const void* d_times, uint64_t n,
+                const rt_ray_options* o, void* d_rgb, void* d_hits, hipStream_t stream) {
     int rc;
     LaunchParams<R> P{};
     set_world_params(ctx, w, P);
@@ -1247,8 +1332,11 @@ int launch_rays(rt_context* ctx, DeviceWorld<R>& w, const void* d_rays, uint64_t
     }
     ctx->jit.used = false;
     if (o->flags & RT_FLAG_FAIL_LAUNCH) return set_error(RT_ERR_HIP, "launch refused (RT_FLAG_FAIL_LAUNCH)");
-    const RayBatchArg batch{d_rays, d_rgb, d_hits};
-    if (hipError_t e = launchers<R>(ctx).launch_kernel(ls.id, P, &batch, ls.grid, ls.lds, stream); e != hipSuccess)
+    // (a static world has no mover for a time to displace: its batch runs as it always did, whatever the times)
+    const RayBatchTimedArg batch{{d_rays, d_rgb, d_hits}, d_times};
+    const MotionLaunch ml{motion_arg(w), &batch};
+    const void* extra = ctx->kernel_build == KernelBuild::moving ? static_cast<const void*>(&ml) : &batch.batch;
+    if (hipError_t e = launchers<R>(ctx).launch_kernel(ls.id, P, extra, ls.grid, ls.lds, stream); e != hipSuccess)
         return set_error(RT_ERR_HIP, std::string("launch of the ") + ls.id.describe() + " kernel (grid " +
                                          std::to_string(ls.grid) + ", dynamic LDS " + std::to_string(ls.lds) + " B, " +
                                          std::to_string(ls.cap) + " stack entries per lane): " + hipGetErrorString(e));
@@ -1256,6 +1344,7 @@ int launch_rays(rt_context* ctx, DeviceWorld<R>& w, const void* d_rays, uint64_t
     ctx->texture_info.ran_textured = has_textures(w) ? 1u : 0u;
     ctx->map_info.ran_mapped = ctx->texture_info.ran_textured && ctx->kernel_build == KernelBuild::mapped ? 1u : 0u;
     ctx->light_info.ran_area = has_area(w) ? 1u : 0u;
+    ctx->motion_info.ran_motion = d_times && w.moving ? 1u : 0u;
     return RT_OK;
 }
 
@@ -1268,10 +1357,11 @@ int check_ray_options(const rt_ray_options* o) {
     return RT_OK;
 }
 
-int launch_rays_precision(rt_context* ctx, const void* d_rays, uint64_t n, const rt_ray_options* o, void* d_rgb,
-                          void* d_hits, hipStream_t stream) {
-    return o->precision == RT_PRECISION_F32 ? launch_rays<float>(ctx, ctx->w32, d_rays, n, o, d_rgb, d_hits, stream)
-                                            : launch_rays<double>(ctx, ctx->w64, d_rays, n, o, d_rgb, d_hits, stream);
+int launch_rays_precision(rt_context* ctx, const void* d_rays, const void* d_times, uint64_t n, const rt_ray_options* o,
+                          void* d_rgb, void* d_hits, hipStream_t stream) {
+    return o->precision == RT_PRECISION_F32
+               ? launch_rays<float>(ctx, ctx->w32, d_rays, d_times, n, o, d_rgb, d_hits, stream)
+               : launch_rays<double>(ctx, ctx->w64, d_rays, d_times, n, o, d_rgb, d_hits, stream);
 }
 
 InitTrace::InitTrace(const char* what) : what_(what), on_(debug_knob("trace_init", nullptr)) {
@@ -1492,6 +1582,16 @@ static int upload_world(rt_context* ctx, const WorldLists& in) {
         if (int rc = validate_scene(in)) return rc;
     if (!ctx) return set_error(RT_ERR_INVALID, "null context");
     WorldLists wl = in;
+    // (a velocity of zero in every component, +0 or -0, is no motion: that shape is static)
+    std::vector<rt_motion_desc> movers;
+    for (uint32_t m = 0; m < in.n_motion && in.motion; ++m)
+        if (in.motion[m].velocity[0] != 0.0 || in.motion[m].velocity[1] != 0.0 || in.motion[m].velocity[2] != 0.0)
+            movers.push_back(in.motion[m]);
+    wl.motion = movers.data();
+    wl.n_motion = (uint32_t)movers.size();
+    if (group && wl.n_motion && ctx->group.n_ranks > 1)
+        return set_error(RT_ERR_INVALID, "a moving world is uploaded to one device: a group of " +
+                                             std::to_string(ctx->group.n_ranks) + " ranks shares no velocity tables");
     // (patterns compare by their textures' contents: a copy with every image pattern's texture renumbered)
     std::vector<rt_pattern_desc> cp;
     std::vector<int32_t> records;  // (a cube map's faces: more records of the device texture table)
@@ -1576,6 +1676,63 @@ int rt_scene_upload_mapped(rt_context* ctx, const rt_shape_desc* shapes, uint32_
     wl.maps = maps;
     wl.n_maps = n_maps;
     return upload_world(ctx, wl);
+}
+
+int rt_scene_upload_moving(rt_context* ctx, const rt_shape_desc* shapes, uint32_t ns, const rt_mesh_desc* meshes,
+                           uint32_t n_meshes, const rt_instance_desc* instances, uint32_t n_inst,
+                           const rt_smooth_desc* smooth, uint32_t n_smooth, const rt_uv_desc* uvs, uint32_t n_uvs,
+                           const rt_texture_desc* textures, uint32_t n_textures, const rt_material_desc* mats, uint32_t nm,
+                           const rt_pattern_desc* pats, uint32_t np, const rt_light_desc* lights, uint32_t nl,
+                           const rt_area_light_desc* area, uint32_t n_area, const rt_uv_map_desc* maps, uint32_t n_maps,
+                           const rt_motion_desc* motion, uint32_t n_motion) {
+    WorldLists wl{shapes, ns, mats, nm, pats, np, lights, nl, meshes, n_meshes, instances, n_inst,
+                  smooth, n_smooth, uvs, n_uvs, textures, n_textures, area, n_area, true};
+    wl.maps = maps;
+    wl.n_maps = n_maps;
+    wl.motion = motion;
+    wl.n_motion = n_motion;
+    return upload_world(ctx, wl);
+}
+
+int rt_scene_motion_info(rt_context* ctx, rt_motion_info* out) {
+    if (!ctx || !out) return set_error(RT_ERR_INVALID, "null argument");
+    *out = ctx->have_scene ? ctx->motion_info : rt_motion_info{};
+    return RT_OK;
+}
+
+int rt_motion_displace(const rt_shape_desc* shapes, uint32_t ns, const rt_instance_desc* instances, uint32_t n_inst,
+                       const rt_motion_desc* motion, uint32_t n_motion, double tau, rt_shape_desc* out_shapes,
+                       rt_instance_desc* out_instances) {
+    if ((ns && (!shapes || !out_shapes)) || (n_inst && (!instances || !out_instances)) || (n_motion && !motion))
+        return set_error(RT_ERR_INVALID, "rt_motion_displace: null list with nonzero count");
+    if (!std::isfinite(tau)) return set_error(RT_ERR_INVALID, "rt_motion_displace: a time that is not finite");
+    for (uint32_t m = 0; m < n_motion; ++m) {
+        if (motion[m].target != RT_MOVE_SHAPE && motion[m].target != RT_MOVE_INSTANCE)
+            return set_error(RT_ERR_INVALID, "motion " + std::to_string(m) + ": unknown target");
+        if (motion[m].index >= (motion[m].target == RT_MOVE_SHAPE ? ns : n_inst))
+            return set_error(RT_ERR_INVALID, "motion " + std::to_string(m) + ": index out of range");
+    }
+    for (uint32_t i = 0; i < ns; ++i)
+        if (out_shapes + i != shapes + i) out_shapes[i] = shapes[i];
+    for (uint32_t k = 0; k < n_inst; ++k)
+        if (out_instances + k != instances + k) out_instances[k] = instances[k];
+    for (uint32_t m = 0; m < n_motion; ++m) {
+        const rt_motion_desc& d = motion[m];
+        // (a static target, and every target at tau = 0, keeps the input's inverse bit for bit)
+        if ((d.velocity[0] == 0.0 && d.velocity[1] == 0.0 && d.velocity[2] == 0.0) || tau == 0.0) continue;
+        double* inv = d.target == RT_MOVE_SHAPE ? out_shapes[d.index].inverse : out_instances[d.index].inverse;
+        // inverse * translation(-v tau) as matrix.rs multiplies: each element the left fold over the row and the
+        // column; only the translation's last column differs from the identity's
+        const double t[3] = {-(d.velocity[0] * tau), -(d.velocity[1] * tau), -(d.velocity[2] * tau)};
+        hm::M4 a, b = hm::identity();
+        for (int r = 0; r < 4; ++r)
+            for (int c = 0; c < 4; ++c) a.m[r][c] = inv[4 * r + c];
+        for (int r = 0; r < 3; ++r) b.m[r][3] = t[r];
+        const hm::M4 p = hm::mul(a, b);
+        for (int r = 0; r < 4; ++r)
+            for (int c = 0; c < 4; ++c) inv[4 * r + c] = p.m[r][c];
+    }
+    return RT_OK;
 }
 
 int rt_smooth_expand(const rt_shape_desc* shapes, uint32_t ns, const rt_mesh_desc* meshes, uint32_t n_meshes,
@@ -1815,7 +1972,7 @@ int build_plain_tables(rt_context* ctx, const WorldLists& wl, const WorldIndices
     const rt_shape_desc* shapes = wl.shapes;
     const uint32_t ns = wl.n_shapes;
     PlainPlan pp;
-    ctx->duplicate_shapes = ident::shape_classes(shapes, ns, wl.materials, wl.patterns, pp.cls, wi.normals, wi.uvs);
+    ctx->duplicate_shapes = ident::shape_classes(shapes, ns, wl.materials, wl.patterns, pp.cls, wi.normals, wi.uvs, wi.velocity);
     pp.order = table_order(shapes, ns, pp.cls);
     // A world the per-scene builds take whole (their records: up to
     // kJitRecordsMaxShapes shapes) keeps the flat triangle run and with it
@@ -1823,7 +1980,7 @@ int build_plain_tables(rt_context* ctx, const WorldLists& wl, const WorldIndices
     // size than the generic kernels with a tree (a tree inside
     // per-scene builds is future work).  RTC_DEBUG=tri_min=N overrides.
     const bool per_scene_world = (int64_t)ns <= (int64_t)kJitRecordsMaxShapes && !ctx->knobs.tri_min && !generic_only;
-    if (!per_scene_world) pp.triangles = plan_triangles(ctx->knobs, shapes, pp.order, pp.cls);
+    if (!per_scene_world) pp.triangles = plan_triangles(ctx->knobs, shapes, pp.order, pp.cls, wi.velocity);
     const TrianglePlan& plan = pp.triangles;
     ctx->tree_info = rt_tree_info{};
     if (!plan.tree.nodes.empty()) {
@@ -1865,6 +2022,7 @@ struct InstancePlan {
     std::vector<uint32_t> list_begin;               // by instance: its first entry of the plain list (expanded ones)
     InstanceCounts counts;
     SideList normals, uvs;                          // the smooth list and the uv list
+    std::vector<const double*> velocity;            // by instance: its velocity, null for a static one (empty: none moves)
 };
 
 // A side list of `wl` in the build's terms, before the expanded instances' entries are appended to `list`.
@@ -1934,6 +2092,7 @@ int upload_instances(rt_context* ctx, DeviceWorld<R>& w, const InstancePlan& ip,
         r.casts_shadow = wl.materials[d.material].casts_shadow ? 1 : 0;
         r.material = d.material;
         r.n_triangles = (int32_t)meshes[m].n_triangles;
+        r.moving = !ip.velocity.empty() && ip.velocity[k] ? 1 : 0;
         if (ip.expanded[k]) {
             r.expanded = 1;
             r.pos_begin = (int32_t)ip.expanded_pos[k];
@@ -1957,7 +2116,17 @@ int upload_instances(rt_context* ctx, DeviceWorld<R>& w, const InstancePlan& ip,
         return bytes ? hip_status(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync")
                      : RT_OK;
     };
+    // the instance velocity table of a moving world (rtc_internal.hpp MotionArg), each component rounded once to R
+    std::vector<R> vel;
+    if (!ip.velocity.empty()) {
+        vel.assign(4 * (size_t)n_inst, (R)0);
+        for (uint32_t k = 0; k < n_inst; ++k)
+            if (ip.velocity[k])
+                for (int q = 0; q < 3; ++q) vel[4 * (size_t)k + q] = (R)ip.velocity[k][q];
+        if ((rc = w.inst_vel.reserve(vel.size()))) return rc;
+    }
     rc = put(w.inst.get(), ir.data(), ir.size() * sizeof(ir[0]));
+    if (!rc) rc = put(w.inst_vel.get(), vel.data(), vel.size() * sizeof(R));
     if (!rc) rc = put(w.inst_shapes.get(), recs.data(), recs.size() * sizeof(recs[0]));
     if (!rc) rc = put(w.inst_nodes.get(), nodes.data(), nodes.size() * sizeof(nodes[0]));
     if (!rc) rc = put(w.inst_pos.get(), pos.data(), pos.size() * sizeof(pos[0]));
@@ -2077,6 +2246,7 @@ void clear_lists(rt_context* ctx) {
     ctx->texture_info = rt_texture_info{};
     ctx->light_info = rt_light_info{};
     ctx->map_info = rt_map_info{};
+    ctx->motion_info = rt_motion_info{};
     ctx->smooth_shape.clear();
     ctx->tex_counts = TextureCounts{};
     auto clear = [](auto& w) {
@@ -2085,6 +2255,7 @@ void clear_lists(rt_context* ctx) {
         w.texels = nullptr;
         w.tex_table = nullptr;
         w.n_area = w.area_samples = 0;
+        w.moving = false;
     };
     clear(ctx->w32);
     clear(ctx->w64);
@@ -2107,6 +2278,11 @@ int build_general(rt_context* ctx, const WorldLists& wl, bool textured, bool* pl
     ip.expanded = inst::decide_expanded(wl.shapes, ns, meshes, n_meshes, instances, n_inst, wl.materials, wl.patterns,
                                         wl.n_smooth ? &ip.normals.index : nullptr);
     ip.bases = inst::world_bases(ns, meshes, instances, n_inst);
+    // the movers (rt_scene_upload_moving): the velocity of each top-level shape and of each instance, null for a static one
+    std::vector<const double*> shape_velocity(wl.n_motion ? ns : 0, nullptr), inst_velocity(wl.n_motion ? n_inst : 0, nullptr);
+    for (uint32_t m = 0; m < wl.n_motion; ++m)
+        (wl.motion[m].target == RT_MOVE_SHAPE ? shape_velocity : inst_velocity)[wl.motion[m].index] = wl.motion[m].velocity;
+    std::vector<const double*> velocity = shape_velocity;  // by entry of the plain list
     std::vector<rt_shape_desc> list(wl.shapes, wl.shapes + ns);
     std::vector<uint32_t> index(ns);
     for (uint32_t i = 0; i < ns; ++i) index[i] = i;
@@ -2129,12 +2305,13 @@ int build_general(rt_context* ctx, const WorldLists& wl, bool textured, bool* pl
             index.push_back(ip.bases[k] + j);
             ip.normals.list.push_back(ident::normals_of(ip.normals.index.of_mesh(instances[k].mesh), j));
             ip.uvs.list.push_back(ident::normals_of(ip.uvs.index.of_mesh(instances[k].mesh), j));
+            if (wl.n_motion) velocity.push_back(inst_velocity[k]);  // (an expanded instance's records carry its velocity)
         }
     }
     WorldLists plain = wl;  // (build_plain_tables reads the base tables alone)
     plain.shapes = list.data();
     plain.n_shapes = (uint32_t)list.size();
-    *plain_only = n_expanded == n_inst && !wl.n_smooth && !textured;
+    *plain_only = n_expanded == n_inst && !wl.n_smooth && !textured && !wl.n_motion;
     if (*plain_only) {
         if ((rc = build_plain_tables(ctx, plain, WorldIndices{}, false))) return rc;
         ctx->instance_info.meshes = n_meshes;
@@ -2172,7 +2349,17 @@ int build_general(rt_context* ctx, const WorldLists& wl, bool textured, bool* pl
     wi.slot_of = &ip.slot_of;
     wi.normals = wl.n_smooth ? ip.normals.list.data() : nullptr;
     wi.uvs = wl.n_uvs ? ip.uvs.list.data() : nullptr;
+    wi.velocity = wl.n_motion ? velocity.data() : nullptr;
     if ((rc = build_plain_tables(ctx, plain, wi, true))) return rc;
+    if (wl.n_motion) {
+        ip.velocity = inst_velocity;
+        ctx->w32.moving = ctx->w64.moving = true;
+        ctx->motion_info.moving_shapes = (uint32_t)std::count_if(shape_velocity.begin(), shape_velocity.end(), [](const double* v) { return v != nullptr; });
+        ctx->motion_info.moving_instances = wl.n_motion - ctx->motion_info.moving_shapes;
+        // (four reals an entry in both precisions: one per slot of the shape table, one per instance)
+        ctx->motion_info.motion_bytes =
+            ((uint64_t)std::max<size_t>(list.size(), 1) + n_inst) * 4 * (sizeof(float) + sizeof(double));
+    }
     if (textured) {
         if ((rc = upload_side<inst::UVSide>(ctx, ctx->w32, ctx->w32.uv, ip, ip.uvs)) ||
             (rc = upload_side<inst::UVSide>(ctx, ctx->w64, ctx->w64.uv, ip, ip.uvs)) || (rc = upload_textures(ctx, wl)))
@@ -2250,7 +2437,8 @@ void set_kernel_build(rt_context* ctx, KernelBuild build) {
 
 // Which path an upload takes, and which build of the kernels its world runs, is decided here, by what the
 // validated lists hold:
-//   a map other than the planar one           the general path, the map build (with the texture and area tables);
+//   a nonzero velocity                        the general path, the motion build (with whatever else the world holds);
+//   else a map other than the planar one      the general path, the map build (with the texture and area tables);
 //   else an area light                        the general path, the area build (with the texture tables);
 //   else a coordinate entry or image pattern  the general path, the texture build (no other world uploads textures);
 //   else a smooth entry                       the general path, the instance build;
@@ -2263,10 +2451,11 @@ int build_scene(rt_context* ctx, const WorldLists& wl) {
     bool images = false;
     for (uint32_t i = 0; i < wl.n_patterns; ++i) images = images || wl.patterns[i].kind == RT_PATTERN_IMAGE;
     const bool textured = wl.n_area || wl.n_uvs || images;
-    bool plain_only = !wl.n_instances && !wl.n_smooth && !textured;
+    bool plain_only = !wl.n_instances && !wl.n_smooth && !textured && !wl.n_motion;
     if (int rc = plain_only ? build_plain_tables(ctx, wl, WorldIndices{}, false) : build_general(ctx, wl, textured, &plain_only))
         return rc;
-    set_kernel_build(ctx, ctx->map_info.mapped_patterns ? KernelBuild::mapped
+    set_kernel_build(ctx, wl.n_motion ? KernelBuild::moving
+                          : ctx->map_info.mapped_patterns ? KernelBuild::mapped
                           : wl.n_area ? KernelBuild::area
                           : textured ? KernelBuild::textured
                           : plain_only ? KernelBuild::plain
@@ -2572,20 +2761,22 @@ int check_lens(const rt_lens_desc* lens) {
 // lens: the same frame through a lens of positive aperture (null: none); a
 // grid of 1 is then one lens ray per pixel.
 int launch_frame_ss(rt_context* ctx, const rt_camera_desc* cam, const rt_camera_desc* cn, const rt_render_options* o,
-                    uint32_t samples, void* out_device, hipStream_t s, const rt_lens_desc* lens = nullptr) {
-    if (samples == 1 && !lens) return launch_frame(ctx, cam, o, o->shard_index, o->shard_count, out_device, s);
+                    uint32_t samples, void* out_device, hipStream_t s, const rt_lens_desc* lens = nullptr,
+                    const rt_shutter_desc* shutter = nullptr) {
+    if (samples == 1 && !lens && !shutter) return launch_frame(ctx, cam, o, o->shard_index, o->shard_count, out_device, s);
     RT_HIP(hipSetDevice(ctx->device));
     return launch_precision(ctx, o->precision,
                             {.cam = cn, .depth = o->max_depth, .out_format = o->out_format,
                              .shard_index = o->shard_index, .shard_count = o->shard_count, .out_device = out_device,
                              .stream = s, .flags = o->flags, .samples = samples, .out_w = cam->width,
-                             .out_h = cam->height, .lens = lens});
+                             .out_h = cam->height, .lens = lens, .shutter = shutter});
 }
 
 // rt_render's frame into a host buffer; samples != 0: rt_render_supersampled's
 // (cn = the sample camera), with a lens rt_render_lens's.
 int render_to_host(rt_context* ctx, const rt_camera_desc* cam, const rt_render_options* o, void* out_host,
-                   rt_stats* stats, uint32_t samples, const rt_camera_desc* cn, const rt_lens_desc* lens = nullptr) {
+                   rt_stats* stats, uint32_t samples, const rt_camera_desc* cn, const rt_lens_desc* lens = nullptr,
+                   const rt_shutter_desc* shutter = nullptr) {
     int rc;
     if (!out_host) return set_error(RT_ERR_INVALID, "null output");
     RT_HIP(hipSetDevice(ctx->device));
@@ -2615,7 +2806,7 @@ int render_to_host(rt_context* ctx, const rt_camera_desc* cam, const rt_render_o
     if (o->shard_count > 1) RT_HIP(hipMemsetAsync(ctx->d_scratch.get(), 0, bytes, s));  // strip rows past the canvas
     RT_HIP(hipEventRecord(ctx->ev_start, s));
     tr.step("enqueue before launch");
-    if ((rc = samples ? launch_frame_ss(ctx, cam, cn, o, samples, ctx->d_scratch.get(), s, lens)
+    if ((rc = samples ? launch_frame_ss(ctx, cam, cn, o, samples, ctx->d_scratch.get(), s, lens, shutter)
                       : launch_frame(ctx, cam, o, o->shard_index, o->shard_count, ctx->d_scratch.get(), s)))
         return rc;
     tr.step("launch");
@@ -2690,6 +2881,66 @@ int rt_render_lens_device(rt_context* ctx, const rt_camera_desc* cam, const rt_r
     if (cam->width == 0 || cam->height == 0) return RT_OK;  // empty canvas, as rt_render_device
     return launch_frame_ss(ctx, cam, &cn, o, samples, out_device, static_cast<hipStream_t>(hip_stream),
                            lens->aperture == 0.0 ? nullptr : lens);
+}
+
+}  // extern "C"
+
+namespace {
+// What a shutter is (rtc.h "The shutter"), checked before the context is looked at.
+int check_shutter(const rt_shutter_desc* sh) {
+    if (!sh) return set_error(RT_ERR_INVALID, "null shutter");
+    if (!std::isfinite(sh->open) || !std::isfinite(sh->close))
+        return set_error(RT_ERR_INVALID, "shutter bound that is not finite");
+    if (sh->open > sh->close) return set_error(RT_ERR_INVALID, "shutter opens after it closes (open > close)");
+    if (sh->jitter != RT_JITTER_NONE && sh->jitter != RT_JITTER_HASHED)
+        return set_error(RT_ERR_INVALID, "shutter jitter " + std::to_string(sh->jitter) +
+                                             " is neither RT_JITTER_NONE nor RT_JITTER_HASHED");
+    return RT_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int rt_render_shutter(rt_context* ctx, const rt_camera_desc* cam, const rt_render_options* o, uint32_t samples,
+                      const rt_lens_desc* lens, const rt_shutter_desc* shutter, void* out_host, rt_stats* stats) {
+    if (int rc = check_shutter(shutter)) return rc;
+    if (lens)
+        if (int rc = check_lens(lens)) return rc;
+    rt_camera_desc cn;
+    if (int rc = check_supersampled(ctx, cam, o, samples, &cn)) return rc;
+    // (aperture 0: the pinhole's sample rays; a world without movers: the lens frame, or the supersampled one)
+    if (lens && lens->aperture == 0.0) lens = nullptr;
+    return render_to_host(ctx, cam, o, out_host, stats, samples, &cn, lens, ctx->w32.moving ? shutter : nullptr);
+}
+
+int rt_render_shutter_device(rt_context* ctx, const rt_camera_desc* cam, const rt_render_options* o, uint32_t samples,
+                             const rt_lens_desc* lens, const rt_shutter_desc* shutter, void* out_device, void* hip_stream) {
+    if (int rc = check_shutter(shutter)) return rc;
+    if (lens)
+        if (int rc = check_lens(lens)) return rc;
+    rt_camera_desc cn;
+    if (int rc = check_supersampled(ctx, cam, o, samples, &cn)) return rc;
+    if (!out_device) return set_error(RT_ERR_INVALID, "null camera or output");
+    if (cam->width == 0 || cam->height == 0) return RT_OK;  // empty canvas, as rt_render_device
+    if (lens && lens->aperture == 0.0) lens = nullptr;
+    return launch_frame_ss(ctx, cam, &cn, o, samples, out_device, static_cast<hipStream_t>(hip_stream), lens,
+                           ctx->w32.moving ? shutter : nullptr);
+}
+
+int rt_shutter_time(const rt_camera_desc* cam, uint32_t n, const rt_shutter_desc* shutter, uint32_t x, uint32_t y,
+                    uint32_t i, uint32_t j, double* tau) {
+    if (int rc = check_shutter(shutter)) return rc;
+    if (!cam || !tau) return set_error(RT_ERR_INVALID, "null argument");
+    if (n < 1 || n > RT_MAX_SAMPLE_GRID || (uint64_t)n * cam->width > 0xFFFFFFFFull ||
+        (uint64_t)n * cam->height > 0xFFFFFFFFull)
+        return set_error(RT_ERR_INVALID, "sample grid " + std::to_string(n) + " outside 1.." +
+                                             std::to_string(RT_MAX_SAMPLE_GRID));
+    if (x >= cam->width || y >= cam->height || i >= n || j >= n)
+        return set_error(RT_ERR_INVALID, "rt_shutter_time: pixel or sample out of range");
+    ShutterParams<double> sp;  // the kernels' arithmetic in R = double (rtc_internal.hpp shutter_time)
+    set_shutter_params(*shutter, n, sp);
+    *tau = shutter_time(sp, n, cam->width, x, y, i, j);
+    return RT_OK;
 }
 
 int rt_lens_ray(const rt_camera_desc* cam, uint32_t n, const rt_lens_desc* lens, uint32_t x, uint32_t y, uint32_t i,
@@ -2786,6 +3037,11 @@ int rt_color_at(rt_context* ctx, const double* rays, uint64_t n, uint32_t depth,
 
 int rt_trace_rays_device(rt_context* ctx, const void* rays_device, uint64_t n_rays, const rt_ray_options* o,
                          void* out_rgb_device, void* out_hit_device, void* hip_stream) {
+    return rt_trace_rays_timed_device(ctx, rays_device, nullptr, n_rays, o, out_rgb_device, out_hit_device, hip_stream);
+}
+
+int rt_trace_rays_timed_device(rt_context* ctx, const void* rays_device, const void* times_device, uint64_t n_rays,
+                               const rt_ray_options* o, void* out_rgb_device, void* out_hit_device, void* hip_stream) {
     if (!ctx) return set_error(RT_ERR_INVALID, "null context");
     if (!rays_device || !out_rgb_device) return set_error(RT_ERR_INVALID, "null rays or output");
     int rc = check_ray_options(o);
@@ -2794,13 +3050,17 @@ int rt_trace_rays_device(rt_context* ctx, const void* rays_device, uint64_t n_ra
     if ((rc = check_ready(ctx))) return rc;
     if (n_rays == 0) return RT_OK;
     RT_HIP(hipSetDevice(ctx->device));
-    return launch_rays_precision(ctx, rays_device, n_rays, o, out_rgb_device, out_hit_device,
+    return launch_rays_precision(ctx, rays_device, times_device, n_rays, o, out_rgb_device, out_hit_device,
                                  static_cast<hipStream_t>(hip_stream));
 }
 
 int rt_trace_rays(rt_context* ctx, const double* rays, uint64_t n, const rt_ray_options* o, double* out,
                   void* out_hit_f64, rt_stats* stats) {
-    rt_ray_hit_f64* out_hit = static_cast<rt_ray_hit_f64*>(out_hit_f64);
+    return rt_trace_rays_timed(ctx, rays, nullptr, n, o, out, static_cast<rt_ray_hit_f64*>(out_hit_f64), stats);
+}
+
+int rt_trace_rays_timed(rt_context* ctx, const double* rays, const double* times, uint64_t n, const rt_ray_options* o,
+                        double* out, rt_ray_hit_f64* out_hit, rt_stats* stats) {
     if (!ctx) return set_error(RT_ERR_INVALID, "null context");
     if (!rays || !out) return set_error(RT_ERR_INVALID, "null rays or output");
     int rc = check_ray_options(o);
@@ -2812,17 +3072,26 @@ int rt_trace_rays(rt_context* ctx, const double* rays, uint64_t n, const rt_ray_
         return RT_OK;
     }
     RT_HIP(hipSetDevice(ctx->device));
-    // staging in the kernel's own real type: [rays][rgb][hits], each 16-byte aligned
+    // staging in the kernel's own real type: [rays][rgb][hits][times], each 16-byte aligned
     const bool f32 = o->precision == RT_PRECISION_F32;
     const size_t real = f32 ? sizeof(float) : sizeof(double);
     auto align16 = [](size_t b) { return (b + 15) / 16 * 16; };
     const size_t in_bytes = n * 6 * real, rgb_bytes = n * 3 * real;
     const size_t hit_bytes = out_hit ? n * (f32 ? sizeof(rt_ray_hit_f32) : sizeof(rt_ray_hit_f64)) : 0;
     const size_t rgb_at = align16(in_bytes), hit_at = rgb_at + align16(rgb_bytes);
-    if ((rc = ctx->d_scratch.reserve(hit_at + hit_bytes))) return rc;
+    const size_t times_at = hit_at + align16(hit_bytes), times_bytes = times ? n * real : 0;
+    if ((rc = ctx->d_scratch.reserve(times_at + times_bytes))) return rc;
     unsigned char* d_rays = ctx->d_scratch.get();
     unsigned char* d_rgb = d_rays + rgb_at;
     unsigned char* d_hit = out_hit ? d_rays + hit_at : nullptr;
+    unsigned char* d_times = times ? d_rays + times_at : nullptr;
+    if (times && f32) {
+        std::vector<float> tmp(n);
+        for (uint64_t i = 0; i < n; ++i) tmp[i] = (float)times[i];
+        RT_HIP(hipMemcpy(d_times, tmp.data(), times_bytes, hipMemcpyHostToDevice));
+    } else if (times) {
+        RT_HIP(hipMemcpy(d_times, times, times_bytes, hipMemcpyHostToDevice));
+    }
     if (f32) {
         std::vector<float> tmp(n * 6);
         for (uint64_t i = 0; i < n * 6; ++i) tmp[i] = (float)rays[i];
@@ -2833,7 +3102,7 @@ int rt_trace_rays(rt_context* ctx, const double* rays, uint64_t n, const rt_ray_
     unsigned long long before[kNumCounters], after[kNumCounters];
     if ((rc = read_counters(ctx, before))) return rc;
     RT_HIP(hipEventRecord(ctx->ev_start, ctx->stream));
-    if ((rc = launch_rays_precision(ctx, d_rays, n, o, d_rgb, d_hit, ctx->stream))) return rc;
+    if ((rc = launch_rays_precision(ctx, d_rays, d_times, n, o, d_rgb, d_hit, ctx->stream))) return rc;
     RT_HIP(hipEventRecord(ctx->ev_stop, ctx->stream));
     RT_HIP(hipStreamSynchronize(ctx->stream));
     float ms = 0.f;
@@ -2918,7 +3187,7 @@ int rt_context_set_frames_in_flight(rt_context* ctx, uint32_t frames) {
         const double split = frames > 1 ? 1.5 : 1.0;
         if (!split_knob && m->knobs.split_factor != split) {
             m->knobs.split_factor = split;
-            m->order.valid = m->order_ss.valid = m->order_lens.valid = false;  // the next launches rebuild the tile order with it
+            m->order.valid = m->order_ss.valid = m->order_lens.valid = m->order_shutter.valid = false;  // the next launches rebuild the tile order with it
         }
     }
     return RT_OK;

@@ -309,6 +309,14 @@ constexpr int kSmoothReals = 9;  // n1, n2, n3
 // normal tables.  Only the texture build's prepare_hit reads the bit.
 constexpr int32_t kShapeUV = 32;
 constexpr int kUVReals = 6;  // t1, t2, t3
+// A moving shape (rtc.h rt_scene_upload_moving): its velocity is entry `slot`
+// of the launch's shape velocity table (MotionArg::shape_vel).  A moving mesh
+// instance carries the same fact in InstRec::moving and its velocity at entry
+// `instance` of MotionArg::inst_vel; the virtual records for_instances hands
+// out carry the bit and the velocity itself in `bound[0..2]`, their cull being
+// done.  Only the motion build (RTC_MOTION) reads the bit; a static shape in a
+// moving world pays its wave-uniform test and nothing more.
+constexpr int32_t kShapeMoving = 64;
 // One texture of the upload: its first texel in LaunchParams::texels (one
 // packed dword per texel, R | G << 8 | B << 16, row 0 at the top) and its size.
 struct alignas(16) TexRec {
@@ -427,7 +435,7 @@ struct alignas(16) InstRec {
     int32_t rec_end;
     int32_t pos_begin;  // local index j -> inst_pos[pos_begin + j]: the local record (or, expanded: slot | kind << 24)
     int32_t expanded;   // 1: uploaded as plain records, the walk passes it by
-    int32_t pad;
+    int32_t moving;     // 1: the instance has a velocity (kShapeMoving); zero in every world without motion
 };
 static_assert(sizeof(InstRec<float>) % 16 == 0 && sizeof(InstRec<double>) % 16 == 0);
 
@@ -595,6 +603,64 @@ RTC_HD inline void lens_hashed_cell(uint32_t lk, uint32_t ray_id, uint32_t pixel
     const uint32_t cj = k / n, ci = k - cj * n;
     fu = (R)ci + ju;
     fv = (R)cj + jv;
+}
+
+// Motion (rtc.h "Motion blur"; the motion build only, RTC_MOTION).
+// The velocity tables of a moving world, four reals an entry (x, y, z, 0), each
+// rounded once to R: one entry per slot of the shape table, one per instance.
+// Every kernel of the motion build takes them as one more argument behind the
+// four table pointers, in front of the family's own (MotionLaunch below):
+// LaunchParams stays as it is.
+struct MotionArg {
+    const void* shape_vel;  // kind_begin[kNumKinds] x 4 of R; a static shape's entry is zero and never read
+    const void* inst_vel;   // n_instances x 4 of R, or null
+};
+// What the host hands the motion build's launch_kernel as `extra`: the tables
+// and the family's own argument (a RayBatchTimedArg, a LensParams<R>, a
+// ShutterArg<R>, or null).
+struct MotionLaunch {
+    MotionArg motion;
+    const void* extra;
+};
+// A timed ray batch (rt_trace_rays_timed*): the batch and a time per ray in R, null = every time 0.
+struct RayBatchTimedArg {
+    RayBatchArg batch;
+    const void* times;
+};
+// The shutter of a shutter frame in the kernel's real type: `open` and
+// `span` = close - open formed in f64 and rounded once, inv_n2 = R(1) / R(n^2),
+// `tk` = mix(seed ^ 0x54494D45) hashed once on the host.
+constexpr uint32_t kShutterKey = 0x54494D45u;
+template <typename R>
+struct ShutterParams {
+    R open, span, inv_n2;
+    uint32_t jitter, tk;
+};
+// A shutter frame's argument: the lens (aperture 0: the pinhole's sample rays, camera_ray's arithmetic) and the shutter.
+template <typename R>
+struct ShutterArg {
+    LensParams<R> lens;
+    ShutterParams<R> shutter;
+};
+// The time of sample (i, j) of pixel (x, y), y the whole-image row, W the
+// image's width, n the grid.  One definition for the kernels and
+// rt_shutter_time (R = double).
+template <typename R>
+RTC_HD inline R shutter_time(const ShutterParams<R>& S, uint32_t n, uint32_t W, uint32_t x, uint32_t y, uint32_t i,
+                             uint32_t j) {
+    const uint32_t n2 = n * n;
+    uint32_t c = j * n + i;
+    R jt = (R)0.5;
+    if (S.jitter == RT_JITTER_HASHED) {
+        const uint32_t ray_id = (n * y + j) * (n * W) + n * x + i;
+        const uint32_t key = hash_mix(S.tk ^ ray_id);
+        jt = (R)(key >> 8) * (R)0x1p-24;
+        const uint32_t r = hash_mix(S.tk ^ hash_mix(y * W + x)) % n2;
+        c = (c + r) % n2;
+    }
+    const R u = ((R)c + jt) * S.inv_n2;
+    const R su = S.span * u;  // multiply, then add
+    return S.open + su;
 }
 
 // One launch of the tracer.

@@ -76,6 +76,25 @@
 // pool and supersampled kernels 4 to 24 B a lane of scratch beyond the
 // instance variant's, which tests/test_isa_budget_texture.py forbids
 // (DESIGN.md 3.16), so the texture and area variants compile none of it.
+//
+// Motion variant: built with the map variant's defines plus -DRTC_MOTION=1
+// -DRTC_VARIANT=moving (one TU per precision) as rtc::moving::launch_kernel,
+// for worlds uploaded with a moving shape or instance (rt_scene_upload_moving,
+// DESIGN.md 3.17).  A ray carries a time tau (Shaded::tau, the lane's own), and
+// every use of a moving shape's inverse on a point sees the point less
+// v * tau; the kernels take the velocity tables as one more argument
+// (MotionArg).  Adds the shutter frame kernels (trace_direct_shutter,
+// trace_pool_shutter) and a time per ray to trace_rays.  Every line of it sits
+// behind RTC_MOTION (RTC_IF_MOTION where it is part of a line), so the other
+// builds compile to what they compiled to before.
+#ifndef RTC_MOTION
+#define RTC_MOTION 0
+#endif
+#if RTC_MOTION
+#define RTC_IF_MOTION(...) __VA_ARGS__
+#else
+#define RTC_IF_MOTION(...)
+#endif
 #ifndef RTC_INSTANCES
 #define RTC_INSTANCES 0
 #endif
@@ -623,6 +642,41 @@ __device__ inline T ld_const(const T* p) {
     }
     return out;
 }
+#if RTC_MOTION
+// The velocity tables of a moving world (rtc_internal.hpp MotionArg), re-read
+// from the kernarg segment like the launch's parameters: the argument behind
+// the four table pointers.
+template <typename R>
+struct alignas(16) Velocity {
+    R v[4];
+};
+template <typename R>
+constexpr size_t kMotionArgOffset = sizeof(LaunchParams<R>) + 4 * sizeof(void*);
+template <typename R>
+__device__ inline const MotionArg& kernarg_motion() {
+    auto k = __builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(k));
+    return *(const MotionArg*)((const char*)k + kMotionArgOffset<R>);
+}
+// The point a moving record's inverse sees for the world point p of a ray of
+// time tau: p - v tau per component, multiply, then subtract (rtc.h "The
+// displaced point").  The record and its bit are wave-uniform: a static record
+// returns p after one scalar test.  A plain record's velocity is its slot's
+// entry of the table, one scalar load; a virtual record of a mesh instance
+// (slot < 0) brings it in bound[0..2] (for_instances).  The lanes' times
+// differ, so what a wave decides from the displaced point (the ball culls,
+// the plane and cube skips) is the OR over its lanes' own tests, as before.
+template <typename R>
+__device__ inline V3<R> moved_point(const ShapeRec<R>& s, int slot, V3<R> p, R tau) {
+    if (!(s.flags & kShapeMoving)) return p;
+    V3<R> v = {s.bound[0], s.bound[1], s.bound[2]};
+    if (slot >= 0) {
+        const Velocity<R> q = ld_const(&static_cast<const Velocity<R>*>(kernarg_motion<R>().shape_vel)[slot]);
+        v = {q.v[0], q.v[1], q.v[2]};
+    }
+    return {p.x - v.x * tau, p.y - v.y * tau, p.z - v.z * tau};
+}
+#endif
 // The instance level of the triangle step (rt_scene_upload_instanced; generic
 // builds only): the world's virtual triangles, instance by instance in world
 // order.  Wave-uniform like for_triangles: the instance index, its record
@@ -640,7 +694,7 @@ __device__ inline T ld_const(const T* p) {
 // done.  The callback's own inv o and inv d of the same scalar matrix are the
 // values formed here.
 template <typename R, bool kHalfLine, typename F>
-__device__ inline void for_instances(V3<R> o, V3<R> d, R dd, F&& f) {
+__device__ inline void for_instances(V3<R> o, V3<R> d, R dd RTC_IF_MOTION(, R tau), F&& f) {
     typedef R Ball4 __attribute__((ext_vector_type(4)));
     typedef int32_t Link4 __attribute__((ext_vector_type(4)));
     const LaunchParams<R>& P = kernarg_params<R>();
@@ -651,6 +705,15 @@ __device__ inline void for_instances(V3<R> o, V3<R> d, R dd, F&& f) {
     for (int k = 0; k < n_inst; ++k) {
         const InstRec<R> I = ld_const(&inst[k]);
         if (I.expanded) continue;
+#if RTC_MOTION
+        // A moving instance: the lane's origin less v tau goes through the ball test and the inverse, so the
+        // mesh's hierarchy and local records are the static ones; its records carry the velocity to the callback.
+        const V3<R> o_world = o;
+        Velocity<R> vel = {};
+        if (I.moving) vel = ld_const(&static_cast<const Velocity<R>*>(kernarg_motion<R>().inst_vel)[k]);  // wave-uniform
+        V3<R> o = o_world;
+        if (I.moving) o = {o_world.x - vel.v[0] * tau, o_world.y - vel.v[1] * tau, o_world.z - vel.v[2] * tau};
+#endif
         if (I.ball[3] >= (R)0 && !wave_ball_may_hit<R, kHalfLine>(I.ball[0], I.ball[1], I.ball[2], I.ball[3], o, d, dd))
             continue;
         const V3<R> lo = xform_point(I.inv, o);
@@ -686,6 +749,12 @@ __device__ inline void for_instances(V3<R> o, V3<R> d, R dd, F&& f) {
                 s.material = I.material;
                 s.casts_shadow = I.casts_shadow;
                 s.flags = kShapeClassEnd | (int32_t)((uint32_t)s.world_index << kShapeClassShift);
+#if RTC_MOTION
+                if (I.moving) {
+                    s.flags |= kShapeMoving;
+                    for (int q = 0; q < 3; ++q) s.bound[q] = vel.v[q];
+                }
+#endif
                 f(s, -1);
             }
         }
@@ -693,7 +762,7 @@ __device__ inline void for_instances(V3<R> o, V3<R> d, R dd, F&& f) {
 }
 #endif
 template <typename R, bool kHalfLine, typename F>
-__device__ inline void for_triangles(const DevScene<R>& sc, V3<R> o, V3<R> d, R dd, F&& f) {
+__device__ inline void for_triangles(const DevScene<R>& sc, V3<R> o, V3<R> d, R dd RTC_IF_MOTION(, R tau), F&& f) {
 #ifdef RTC_JIT
     (void)o;
     (void)d;
@@ -734,7 +803,7 @@ __device__ inline void for_triangles(const DevScene<R>& sc, V3<R> o, V3<R> d, R 
         }
     }
 #if RTC_INSTANCES
-    if (P.n_instances) for_instances<R, kHalfLine>(o, d, dd, f);  // wave-uniform (launch parameters)
+    if (P.n_instances) for_instances<R, kHalfLine>(o, d, dd RTC_IF_MOTION(, tau), f);  // wave-uniform (launch parameters)
 #endif
 #endif
 }
@@ -742,7 +811,7 @@ __device__ inline void for_triangles(const DevScene<R>& sc, V3<R> o, V3<R> d, R 
 // Every kind in table order; the triangle step may walk the hierarchy for the
 // wave's rays.
 template <typename R, bool kHalfLine, typename F>
-__device__ inline void for_all_kinds(const DevScene<R>& sc, V3<R> o, V3<R> d, R dd, F&& f) {
+__device__ inline void for_all_kinds(const DevScene<R>& sc, V3<R> o, V3<R> d, R dd RTC_IF_MOTION(, R tau), F&& f) {
     for_kind_if<R, RT_SHAPE_SPHERE>(sc, [&](const ShapeRec<R>& s, int i) { f.template operator()<RT_SHAPE_SPHERE>(s, i); });
     for_kind_if<R, RT_SHAPE_PLANE>(sc, [&](const ShapeRec<R>& s, int i) { f.template operator()<RT_SHAPE_PLANE>(s, i); });
     for_kind_if<R, RT_SHAPE_CUBE>(sc, [&](const ShapeRec<R>& s, int i) { f.template operator()<RT_SHAPE_CUBE>(s, i); });
@@ -750,7 +819,7 @@ __device__ inline void for_all_kinds(const DevScene<R>& sc, V3<R> o, V3<R> d, R 
                                    [&](const ShapeRec<R>& s, int i) { f.template operator()<RT_SHAPE_CYLINDER>(s, i); });
     for_kind_if<R, RT_SHAPE_CONE>(sc, [&](const ShapeRec<R>& s, int i) { f.template operator()<RT_SHAPE_CONE>(s, i); });
     if constexpr ((RTC_KINDS >> RT_SHAPE_TRIANGLE) & 1)
-        for_triangles<R, kHalfLine>(sc, o, d, dd,
+        for_triangles<R, kHalfLine>(sc, o, d, dd RTC_IF_MOTION(, tau),
                                     [&](const ShapeRec<R>& s, int i) { f.template operator()<RT_SHAPE_TRIANGLE>(s, i); });
 }
 
@@ -1029,7 +1098,8 @@ struct NoSkip {
     }
 };
 template <typename R, bool kHalfLine, bool kBall = true, typename F, typename S = NoSkip>
-__device__ inline void for_all_culled(const DevScene<R>& sc, V3<R>& o, V3<R>& d, R dd, F&& f, S&& skip = S{}) {
+__device__ inline void for_all_culled(const DevScene<R>& sc, V3<R>& o, V3<R>& d, R dd RTC_IF_MOTION(, R tau), F&& f,
+                                      S&& skip = S{}) {
 #ifdef RTC_JIT
     if constexpr (sizeof(R) == 4 && jit::kNumClusters > 0) {
         jit_unclustered<0>(f);
@@ -1038,7 +1108,7 @@ __device__ inline void for_all_culled(const DevScene<R>& sc, V3<R>& o, V3<R>& d,
     }
 #endif
     (void)skip;
-    for_all_kinds<R, kHalfLine>(sc, o, d, dd, f);
+    for_all_kinds<R, kHalfLine>(sc, o, d, dd RTC_IF_MOTION(, tau), f);
 }
 
 template <typename R>
@@ -1222,7 +1292,7 @@ struct PixelBlock {
 };
 
 template <typename R, typename B = NoBlock>
-__device__ inline Hit<R> closest_hit(const DevScene<R>& sc, V3<R> o, V3<R> d, B blk = B{}) {
+__device__ inline Hit<R> closest_hit(const DevScene<R>& sc, V3<R> o, V3<R> d RTC_IF_MOTION(, R tau), B blk = B{}) {
     Nearest<R> best;
 #if defined(RTC_JIT) && !defined(RTC_NO_SKIPS) && RTC_PRIMARY_RECTS
     constexpr bool kRects = B::kOn && sizeof(R) == 4 && jit::kBegin[kNumKinds] <= kPrimaryRectSlots;
@@ -1248,7 +1318,11 @@ __device__ inline Hit<R> closest_hit(const DevScene<R>& sc, V3<R> o, V3<R> d, B 
         rdd0 = recip(dd0);
         rd0 = recip3(d);
     }
-    for_all_culled<R, true>(sc, o, d, dd0, [&]<int K>(const ShapeRec<R>& s, int slot) {
+    for_all_culled<R, true>(sc, o, d, dd0 RTC_IF_MOTION(, tau), [&]<int K>(const ShapeRec<R>& s, int slot) {
+#if RTC_MOTION
+        const V3<R>& o_world = o;  // (from here on `o` is the origin this record sees: the cull, the world-space paths, the inverse)
+        V3<R> o = moved_point(s, slot, o_world, tau);
+#endif
         if constexpr (kTerms) jit_fence_dir(d, slot);
         else jit_fence(o, d, slot);
         if constexpr (kRects && (K != RT_SHAPE_PLANE || RTC_PLANE_RECTS))
@@ -1378,7 +1452,8 @@ struct ShadowBits {
 // direct kernel (its per-scene build culls from the light's side).  sb: the
 // wave's shadow-rectangle bits for this light and the plane it hit.
 template <typename R, bool kDirect = false, typename SB = NoShadowBits>
-__device__ inline bool any_hit(const DevScene<R>& sc, V3<R> o, V3<R> d, R dist, V3<R> lpos, SB sb = SB{}) {
+__device__ inline bool any_hit(const DevScene<R>& sc, V3<R> o, V3<R> d, R dist, V3<R> lpos RTC_IF_MOTION(, R tau),
+                               SB sb = SB{}) {
     Blocker<R> b;
 #if defined(RTC_JIT) && !defined(RTC_NO_SKIPS) && RTC_SHADOW_LIGHT_CULL
     // the per-scene f32 direct build culls from the light's side (wave_ball_may_hit_from)
@@ -1416,8 +1491,14 @@ __device__ inline bool any_hit(const DevScene<R>& sc, V3<R> o, V3<R> d, R dist, 
         if constexpr (kLight) return !ball_may_hit(cx, cy, cz, r2);  // (stands in for for_all_culled's test)
         return false;
     };
-    for_all_culled<R, true, !kLight>(sc, o, d, dd0, [&]<int K>(const ShapeRec<R>& s, int slot) {
+    for_all_culled<R, true, !kLight>(sc, o, d, dd0 RTC_IF_MOTION(, tau), [&]<int K>(const ShapeRec<R>& s, int slot) {
         if (!s.casts_shadow) return;  // wave-uniform
+#if RTC_MOTION
+        // (both ends of the segment as this record sees them: the cube-face and plane-side skips read the light's point too)
+        const V3<R>&o_world = o, &lpos_world = lpos;
+        V3<R> o = moved_point(s, slot, o_world, tau);
+        const V3<R> lpos = moved_point(s, slot, lpos_world, tau);
+#endif
         if constexpr (SB::kOn)
             if (sb.skips(slot)) return;  // wave-uniform, SALU
         jit_fence(o, d, slot);
@@ -1496,8 +1577,8 @@ __device__ inline bool any_hit(const DevScene<R>& sc, V3<R> o, V3<R> d, R dist, 
 // Same-box A/B, per-class walk in every world vs this split: reflect_refract
 // +3.5%, refraction +2.2% kernel time.
 template <typename R, bool kDup>
-__device__ inline void refractive_indices(const DevScene<R>& sc, V3<R> o, V3<R> d, const Hit<R>& h, int hit_mat,
-                                          R& n1, R& n2) {
+__device__ inline void refractive_indices(const DevScene<R>& sc, V3<R> o, V3<R> d RTC_IF_MOTION(, R tau), const Hit<R>& h,
+                                          int hit_mat, R& n1, R& n2) {
     struct Key {
         R t;
         int w, e;
@@ -1533,7 +1614,11 @@ __device__ inline void refractive_indices(const DevScene<R>& sc, V3<R> o, V3<R> 
         }
     };
     // entries of one shape before the hit: their count and the latest
-    auto scan = [&]<int K>(const ShapeRec<R>& s, int& count, Key& last) {
+    auto scan = [&]<int K>(const ShapeRec<R>& s, int& count, Key& last RTC_IF_MOTION(, int slot)) {
+#if RTC_MOTION
+        const V3<R>& o_world = o;
+        V3<R> o = moved_point(s, slot, o_world, tau);
+#endif
         jit_fence(o, d);
         const int w = s.world_index;
         int e = 0;
@@ -1573,8 +1658,8 @@ __device__ inline void refractive_indices(const DevScene<R>& sc, V3<R> o, V3<R> 
             (RTC_INSTANCES && (h.kind >> 8)) ? (uint32_t)h.world : (uint32_t)sc.lshapes[h.slot].flags >> kShapeClassShift;
         int count = 0;  // over the current class's records
         Key last{};
-        for_all_kinds<R, false>(sc, o, d, dd, [&]<int K>(const ShapeRec<R>& s, int slot) {
-            if (!kWalkCull || wave_line_may_hit<R, K>(s, o, d, dd)) scan.template operator()<K>(s, count, last);
+        for_all_kinds<R, false>(sc, o, d, dd RTC_IF_MOTION(, tau), [&]<int K>(const ShapeRec<R>& s, int slot) {
+            if (!kWalkCull || wave_line_may_hit<R, K>(s, o, d, dd)) scan.template operator()<K>(s, count, last RTC_IF_MOTION(, slot));
             if (!(s.flags & kShapeClassEnd)) return;  // wave-uniform: more members follow
             settle(count, last, s, (uint32_t)s.flags >> kShapeClassShift == hit_class);
             count = 0;
@@ -1605,7 +1690,7 @@ __device__ inline void refractive_indices(const DevScene<R>& sc, V3<R> o, V3<R> 
                               Real<R>::madd(h.t, d.z, o.z - cz)};
             return wave_any(dot(pc, pc) * kKeep <= r2);
         };
-        for_all_culled<R, false>(sc, o, d, dd, [&]<int K>(const ShapeRec<R>& s, int slot) {
+        for_all_culled<R, false>(sc, o, d, dd RTC_IF_MOTION(, tau), [&]<int K>(const ShapeRec<R>& s, int slot) {
             if (points && (K == RT_SHAPE_SPHERE || K == RT_SHAPE_CUBE)) {
                 if (!holds(s.bound[0], s.bound[1], s.bound[2], s.bound[3]) && !wave_any(slot == h.slot)) return;
             } else if (!wave_line_may_hit<R, K>(s, o, d, dd)) {
@@ -1613,7 +1698,7 @@ __device__ inline void refractive_indices(const DevScene<R>& sc, V3<R> o, V3<R> 
             }
             int count = 0;
             Key last{};
-            scan.template operator()<K>(s, count, last);
+            scan.template operator()<K>(s, count, last RTC_IF_MOTION(, slot));
             settle(count, last, s, slot == h.slot);
         }, [&](R cx, R cy, R cz, R r2, bool convex) {
             // a cluster of spheres and cubes whose ball holds no lane's p (a
@@ -1622,10 +1707,10 @@ __device__ inline void refractive_indices(const DevScene<R>& sc, V3<R> o, V3<R> 
         });
     } else {
         // ("is the hit's shape" by world index: a virtual triangle of a mesh instance has no slot)
-        for_all_kinds<R, false>(sc, o, d, dd, [&]<int K>(const ShapeRec<R>& s, int) {
+        for_all_kinds<R, false>(sc, o, d, dd RTC_IF_MOTION(, tau), [&]<int K>(const ShapeRec<R>& s, int RTC_IF_MOTION(slot)) {
             int count = 0;
             Key last{};
-            scan.template operator()<K>(s, count, last);
+            scan.template operator()<K>(s, count, last RTC_IF_MOTION(, slot));
             settle(count, last, s, s.world_index == h.world);
         });
     }
@@ -2003,6 +2088,9 @@ struct Shaded {
 #if RTC_AREA_LIGHTS
     uint32_t ray_id = 0;     // in: the primary ray this ray descends from (rtc.h "Hashed jitter")
 #endif
+#if RTC_MOTION
+    R tau = (R)0;            // in: the ray's time, its primary ray's (rtc.h "Motion blur"); 0: the world as uploaded
+#endif
 };
 
 // Children are handed to push(origin, direction, weight) where they are
@@ -2146,8 +2234,8 @@ __device__ inline void prepare_hit_const(const DevScene<float>& sc, V3<float> o,
 #endif
 
 template <typename R>
-__device__ inline const MaterialRec<R>& prepare_hit(const DevScene<R>& sc, V3<R> o, V3<R> d, const Hit<R>& h,
-                                                     Prepared<R>& q, bool& patterned) {
+__device__ inline const MaterialRec<R>& prepare_hit(const DevScene<R>& sc, V3<R> o, V3<R> d RTC_IF_MOTION(, R tau),
+                                                     const Hit<R>& h, Prepared<R>& q, bool& patterned) {
 #ifdef RTC_JIT
     if constexpr (kJitRecords && sizeof(R) == 4) {
         q.p = along(o, d, h.t);
@@ -2191,6 +2279,21 @@ __device__ inline const MaterialRec<R>& prepare_hit(const DevScene<R>& sc, V3<R>
         const int kind = h.kind & 0xFF;
         q.p = along(o, d, h.t);
         V3<R> ln;
+#if RTC_MOTION
+        // A hit on a moving shape or instance: the ray's origin, the hit point and over_point go through the
+        // inverse less v tau (RTC_MOVED); the hit point itself, the offset and over_point stay the world's at
+        // tau.  Per lane: the velocity is two gathers, for the lanes that hit a mover.
+        V3<R> shift = {(R)0, (R)0, (R)0};
+        if (virt ? I->moving != 0 : (g->flags & kShapeMoving) != 0) {
+            const MotionArg& M = kernarg_motion<R>();
+            const R* const v = virt ? static_cast<const R*>(M.inst_vel) + 4 * (size_t)((h.kind >> 8) - 1)
+                                    : static_cast<const R*>(M.shape_vel) + 4 * (size_t)h.slot;
+            shift = {v[0] * tau, v[1] * tau, v[2] * tau};
+        }
+#define RTC_MOVED(p) vsub(p, shift)
+#else
+#define RTC_MOVED(p) p
+#endif
 #if RTC_TEXTURES
         R tu = (R)0, tv = (R)0;  // a textured triangle's interpolated coordinates (below)
         bool have_uv = false;
@@ -2202,7 +2305,7 @@ __device__ inline const MaterialRec<R>& prepare_hit(const DevScene<R>& sc, V3<R>
             // per component, left to right.  Six per-lane loads.
             const R* const tt = virt ? P.uv_inst + (size_t)h.slot * kUVReals
                                      : P.uv_plain + (size_t)(h.slot - sc.kind_begin[RT_SHAPE_TRIANGLE]) * kUVReals;
-            const TriangleTest<R> b = triangle_test(*g, xform_point(inv, o), xform_vector(inv, d));
+            const TriangleTest<R> b = triangle_test(*g, xform_point(inv, RTC_MOVED(o)), xform_vector(inv, d));
             const R w = ((R)1 - b.u) - b.v;
             tu = (tt[2] * b.u + tt[4] * b.v) + tt[0] * w;
             tv = (tt[3] * b.u + tt[5] * b.v) + tt[1] * w;
@@ -2213,7 +2316,7 @@ __device__ inline const MaterialRec<R>& prepare_hit(const DevScene<R>& sc, V3<R>
                 ln = {(nn[3] * b.u + nn[6] * b.v) + nn[0] * w, (nn[4] * b.u + nn[7] * b.v) + nn[1] * w,
                       (nn[5] * b.u + nn[8] * b.v) + nn[2] * w};
             } else {
-                ln = local_normal(*g, kind, xform_point(inv, q.p));
+                ln = local_normal(*g, kind, xform_point(inv, RTC_MOVED(q.p)));
             }
         } else
 #endif
@@ -2225,12 +2328,12 @@ __device__ inline const MaterialRec<R>& prepare_hit(const DevScene<R>& sc, V3<R>
             // multiplies and adds.  Nine per-lane loads, once per shaded hit.
             const R* const nn = virt ? P.smooth_inst + (size_t)h.slot * kSmoothReals
                                      : P.smooth_plain + (size_t)(h.slot - sc.kind_begin[RT_SHAPE_TRIANGLE]) * kSmoothReals;
-            const TriangleTest<R> b = triangle_test(*g, xform_point(inv, o), xform_vector(inv, d));
+            const TriangleTest<R> b = triangle_test(*g, xform_point(inv, RTC_MOVED(o)), xform_vector(inv, d));
             const R w = ((R)1 - b.u) - b.v;
             ln = {(nn[3] * b.u + nn[6] * b.v) + nn[0] * w, (nn[4] * b.u + nn[7] * b.v) + nn[1] * w,
                   (nn[5] * b.u + nn[8] * b.v) + nn[2] * w};
         } else {
-            ln = local_normal(*g, kind, xform_point(inv, q.p));
+            ln = local_normal(*g, kind, xform_point(inv, RTC_MOVED(q.p)));
         }
         q.n = normalized(xform_normal(inv, ln));  // normal_at
         q.eye = vneg(d);
@@ -2246,13 +2349,14 @@ __device__ inline const MaterialRec<R>& prepare_hit(const DevScene<R>& sc, V3<R>
             // (an image pattern exists in textured worlds only; its fetch stays out of line of every other path)
             const PatternRec<R>* const pr = &sc.lpats[m.pattern];
             if (P.textures && pr->kind == RT_PATTERN_IMAGE)
-                q.base = image_color<R>(pr, P.texels, P.textures, have_uv, tu, tv, xform_point(inv, q.over));
+                q.base = image_color<R>(pr, P.texels, P.textures, have_uv, tu, tv, xform_point(inv, RTC_MOVED(q.over)));
             else
-                q.base = pattern_color_obj(sc, m.pattern, xform_point(inv, q.over));  // pattern_color
+                q.base = pattern_color_obj(sc, m.pattern, xform_point(inv, RTC_MOVED(q.over)));  // pattern_color
         }
 #else
-        if (patterned) q.base = pattern_color_obj(sc, m.pattern, xform_point(inv, q.over));  // pattern_color
+        if (patterned) q.base = pattern_color_obj(sc, m.pattern, xform_point(inv, RTC_MOVED(q.over)));  // pattern_color
 #endif
+#undef RTC_MOVED
         return m;
     }
 #endif
@@ -2335,7 +2439,8 @@ struct LightSide {
 };
 template <typename R, bool kDirect, typename SB = NoShadowBits>
 __device__ __attribute__((always_inline)) inline LightSide<R> light_side(const DevScene<R>& sc, const LightRec<R>& L,
-                                                                         V3<R> over, V3<R> n, SB sb = SB{}) {
+                                                                         V3<R> over, V3<R> n RTC_IF_MOTION(, R tau),
+                                                                         SB sb = SB{}) {
     const V3<R> lpos = {L.position[0], L.position[1], L.position[2]};
     const V3<R> to_light = vsub(lpos, over);
     const R dist = magnitude(to_light);
@@ -2347,7 +2452,7 @@ __device__ __attribute__((always_inline)) inline LightSide<R> light_side(const D
     // counters still count one shadow ray per light.
     const R ldn = dot(ld, n);
     bool shadowed = false;
-    if (!(ldn < (R)0) || !skips_on(sc)) shadowed = any_hit<R, kDirect, SB>(sc, over, ld, dist, lpos, sb);
+    if (!(ldn < (R)0) || !skips_on(sc)) shadowed = any_hit<R, kDirect, SB>(sc, over, ld, dist, lpos RTC_IF_MOTION(, tau), sb);
     return {ld, ldn, shadowed};
 }
 
@@ -2399,6 +2504,9 @@ __device__ inline unsigned long long area_pass_mask(const DevScene<R>& sc, const
         const ShapeRec<R>* s = &sc.shapes[slot];  // wave-uniform: the ball alone is loaded
         const R r2 = s->bound[3];
         if (!(r2 >= (R)0) || !(r2 < Real<R>::kInf)) continue;  // a plane or an unbounded record
+#if RTC_MOTION
+        if (s->flags & kShapeMoving) continue;  // a mover's ball is elsewhere at the lanes' times: it keeps its per-sample culls
+#endif
         const R reach = Real<R>::sqrt(r2) + lr;
         const V3<R> v = {s->bound[0] - over.x, s->bound[1] - over.y, s->bound[2] - over.z};
         const R vv = dot(v, v);
@@ -2419,7 +2527,7 @@ __device__ inline unsigned long long area_pass_mask(const DevScene<R>& sc, const
 template <typename R, bool kDirect>
 __device__ inline V3<R> area_light_term(const DevScene<R>& sc, const AreaLightRec<R>& A, uint32_t area_index,
                                         uint32_t ray_id, uint32_t remaining, const MaterialRec<R>& m, V3<R> base,
-                                        V3<R> n, V3<R> eye, V3<R> over) {
+                                        V3<R> n, V3<R> eye, V3<R> over RTC_IF_MOTION(, R tau)) {
     // (the host refuses counts outside 1..RT_LIGHT_MAX_STEPS; the clamp bounds the loop whatever the record holds)
     const uint32_t us = A.usteps < (uint32_t)RT_LIGHT_MAX_STEPS ? A.usteps : (uint32_t)RT_LIGHT_MAX_STEPS;
     const uint32_t vs = A.vsteps < (uint32_t)RT_LIGHT_MAX_STEPS ? A.vsteps : (uint32_t)RT_LIGHT_MAX_STEPS;
@@ -2445,7 +2553,7 @@ __device__ inline V3<R> area_light_term(const DevScene<R>& sc, const AreaLightRe
                 L.position[q] = (A.corner[q] + A.uvec[q] * fu) + A.vvec[q] * fv;
                 L.intensity[q] = A.intensity[q];
             }
-            const LightSide<R> s = light_side<R, kDirect, AreaPassBits>(sc, L, over, n, sb);
+            const LightSide<R> s = light_side<R, kDirect, AreaPassBits>(sc, L, over, n RTC_IF_MOTION(, tau), sb);
             if (!s.shadowed && !(s.ldn < (R)0)) {
                 V3<R> c = {kd.x * s.ldn, kd.y * s.ldn, kd.z * s.ldn};
                 if (m.specular != (R)0) {
@@ -2519,7 +2627,8 @@ template <typename R, bool kChildren, bool kDup = false, typename Push = NoPush,
 __device__ inline bool shade_ray(const DevScene<R>& sc, V3<R> o, V3<R> d, uint32_t remaining, Shaded<R>& out,
                                  Push&& push = Push{}, B blk = B{}) {
     using T = Real<R>;
-    const Hit<R> h = closest_hit(sc, o, d, blk);
+    RTC_IF_MOTION(const R tau = out.tau;)
+    const Hit<R> h = closest_hit(sc, o, d RTC_IF_MOTION(, tau), blk);
     if (h.slot < 0) return false;  // world.rs:85: miss -> BLACK
 #ifdef RTC_JIT
     if constexpr (kJitConstMaterials && !kChildren && sizeof(R) == 4) {
@@ -2540,12 +2649,12 @@ __device__ inline bool shade_ray(const DevScene<R>& sc, V3<R> o, V3<R> d, uint32
     }
 #endif
     Prepared<R> q;
-    const MaterialRec<R>& m = prepare_hit(sc, o, d, h, q, out.patterned);
+    const MaterialRec<R>& m = prepare_hit(sc, o, d RTC_IF_MOTION(, tau), h, q, out.patterned);
     const V3<R> p = q.p, n = q.n, eye = q.eye, over = q.over, base = q.base;
     const R off = q.off;
     V3<R> surface = {(R)0, (R)0, (R)0};
     for_lights(sc, [&](const LightRec<R>& L) {
-        const LightSide<R> s = light_side<R, B::kOn>(sc, L, over, n);
+        const LightSide<R> s = light_side<R, B::kOn>(sc, L, over, n RTC_IF_MOTION(, tau));
         const V3<R> c = lighting_term(L, m, base, n, eye, s.ld, s.ldn, s.shadowed);
         surface = {surface.x + c.x, surface.y + c.y, surface.z + c.z};
     });
@@ -2556,7 +2665,7 @@ __device__ inline bool shade_ray(const DevScene<R>& sc, V3<R> o, V3<R> d, uint32
         const uint32_t n_area = AP.area ? AP.n_area : 0u;  // wave-uniform (launch parameters)
         for (uint32_t ai = 0; ai < n_area; ++ai) {
             const AreaLightRec<R> A = ld_const(&AP.area[ai]);  // wave-uniform: scalar loads, as ld_uniform(&sc.lights[li])
-            const V3<R> c = area_light_term<R, B::kOn>(sc, A, ai, out.ray_id, remaining, m, base, n, eye, over);
+            const V3<R> c = area_light_term<R, B::kOn>(sc, A, ai, out.ray_id, remaining, m, base, n, eye, over RTC_IF_MOTION(, tau));
             surface = {surface.x + c.x, surface.y + c.y, surface.z + c.z};
         }
     }
@@ -2580,7 +2689,7 @@ __device__ inline bool shade_ray(const DevScene<R>& sc, V3<R> o, V3<R> d, uint32
         // glass tree, so this skips most walks: DESIGN.md §3.2.
         R n1 = (R)1, n2 = (R)1;
         if (kTransparent && m.transparency != (R)0 && remaining > 0)
-            refractive_indices<R, kDup>(sc, o, d, h, q.mat, n1, n2);
+            refractive_indices<R, kDup>(sc, o, d RTC_IF_MOTION(, tau), h, q.mat, n1, n2);
         // Schlick mixing only when both (world.rs:59-66)
         R fr = (R)1, ft = (R)1;
         if (reflective && transparent) {  // computed_hit.rs:50-68
@@ -2986,12 +3095,12 @@ template <typename R>
 __device__ inline const LensParams<R>& kernarg_lens() {
     auto k = __builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(k));
-    return *(const LensParams<R>*)((const char*)k + kLensArgOffset<R>);
+    return *(const LensParams<R>*)((const char*)k + kLensArgOffset<R> RTC_IF_MOTION(+sizeof(MotionArg)));
 }
 
 #define RTC_WORLD_PARAMS(R)                                                                                  \
     const ShapeRec<R>* __restrict__ shapes, const MaterialRec<R>* __restrict__ materials,                   \
-        const PatternRec<R>* __restrict__ patterns, const LightRec<R>* __restrict__ lights
+        const PatternRec<R>* __restrict__ patterns, const LightRec<R>* __restrict__ lights RTC_IF_MOTION(, MotionArg motion)
 
 // --------------------------------------------------------------- kernels
 // Waves per SIMD the f32 direct kernel is register-limited to (VGPRs <= 512 /
@@ -3211,7 +3320,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(sizeof(R
                 if (P.flags & RT_FLAG_NO_TRACE) {
                     c = d;
                 } else {
-                    const Hit<R> h = closest_hit(sc, o, d);
+                    const Hit<R> h = closest_hit(sc, o, d RTC_IF_MOTION(, (R)0));
                     c = {h.t * (R)0.01, (R)h.slot, (R)0};
                 }
 #ifdef RTC_JIT  // (camera frames only: load_primary above)
@@ -3614,6 +3723,31 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(sizeof(R
 #undef RTC_SS_DIRECT
 #undef RTC_SS_POOL
 #undef RTC_SS_LENS
+#if RTC_MOTION
+// ... and a third time with a time per sample (rt_render_shutter*): the lens kernels' text
+// with the sample's tau worked out where its ray is (the direct kernel) and where its ray_id is (the pool
+// kernel), and camera_ray's arithmetic for a lens of aperture 0.
+static_assert(kLensArgOffset<float> + sizeof(MotionArg) + sizeof(ShutterArg<float>) <= 4096 &&
+              kLensArgOffset<double> + sizeof(MotionArg) + sizeof(ShutterArg<double>) <= 4096);
+static_assert(offsetof(ShutterArg<float>, lens) == 0 && offsetof(ShutterArg<double>, lens) == 0);
+template <typename R>
+__device__ inline const ShutterParams<R>& kernarg_shutter() {
+    auto k = __builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(k));
+    return *(const ShutterParams<R>*)((const char*)k + kLensArgOffset<R> + sizeof(MotionArg) + offsetof(ShutterArg<R>, shutter));
+}
+#define RTC_SS_DIRECT trace_direct_shutter
+#define RTC_SS_POOL trace_pool_shutter
+#define RTC_SS_LENS 1
+#undef RTC_SS_SHUTTER
+#define RTC_SS_SHUTTER 1
+#include "rtc_ss_frames.inc"
+#undef RTC_SS_DIRECT
+#undef RTC_SS_POOL
+#undef RTC_SS_LENS
+#undef RTC_SS_SHUTTER
+#define RTC_SS_SHUTTER 0
+#endif
 
 #ifndef RTC_JIT  // ray batches run the generic build only: per-scene sources stop here
 // Waves per SIMD the f32 ray-batch kernel is register-limited to.  Left to
@@ -3632,6 +3766,9 @@ struct RayBatch {
     const R* rays;  // n_rays x {o, d}
     R* rgb;         // n_rays x 3
     void* hits;     // n_rays x rt_ray_hit_f32 / rt_ray_hit_f64, or null
+#if RTC_MOTION
+    const R* times;  // n_rays times (rt_trace_rays_timed*), or null: every ray at time 0
+#endif
 };
 
 // trace_rays: one ray tree per lane, walked depth first.
@@ -3670,9 +3807,13 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(sizeof(R
             o = {q[0], q[1], q[2]};
             d = {q[3], q[4], q[5]};
         }
+#if RTC_MOTION
+        // the ray's time: the lane's own, kept through its whole tree (a child keeps its primary ray's time)
+        const R tau = valid && B.times ? B.times[r] : (R)0;
+#endif
         if (B.hits) {  // the primary ray's closest hit: t and the shape's world index
             if (valid) {
-                const Hit<R> h = closest_hit(sc, o, d);
+                const Hit<R> h = closest_hit(sc, o, d RTC_IF_MOTION(, tau));
                 const int32_t shape = h.slot < 0 ? -1 : (int32_t)h.world;
                 const R ht = h.slot < 0 ? Real<R>::kInf : h.t;
                 if constexpr (sizeof(R) == 4) {
@@ -3701,6 +3842,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(sizeof(R
             };
 #if RTC_AREA_LIGHTS
             sh.ray_id = (uint32_t)r;  // the ray's index in the batch, modulo 2^32; its children keep it
+#endif
+#if RTC_MOTION
+            sh.tau = tau;
 #endif
             if (active) hit = shade_ray<R, true, kDup>(sc, o, d, rem, sh, push);
             count_events(k, primary, hit, sh, sc.n_lights);
@@ -3980,6 +4124,11 @@ const void* kernel_of(KernelId id) {
         case KernelFamily::frame: return id.pool ? RTC_POOL_OF(trace_pool) : RTC_DIRECT_OF(trace_direct);
         case KernelFamily::supersampled: return id.pool ? RTC_POOL_OF(trace_pool_ss) : RTC_DIRECT_OF(trace_direct_ss);
         case KernelFamily::lens: return id.pool ? RTC_POOL_OF(trace_pool_lens) : RTC_DIRECT_OF(trace_direct_lens);
+#if RTC_MOTION
+        case KernelFamily::shutter: return id.pool ? RTC_POOL_OF(trace_pool_shutter) : RTC_DIRECT_OF(trace_direct_shutter);
+#else
+        case KernelFamily::shutter: return nullptr;  // (the motion build's)
+#endif
         case KernelFamily::rays: return id.pool ? nullptr : RTC_POOL_OF(trace_rays);
     }
     return nullptr;
@@ -3992,8 +4141,13 @@ const void* kernel_of(KernelId id) {
 // One launch of kernel `id`.  `extra`: the kernel's argument behind the four
 // table pointers, the RayBatchArg of a ray batch (RayBatch<R>'s bytes) or the
 // LensParams<R> of a lens frame; the other kernels have none and read none.
-static_assert(sizeof(RayBatchArg) == sizeof(RayBatch<float>) && sizeof(RayBatchArg) == sizeof(RayBatch<double>) &&
-              offsetof(RayBatchArg, rgb) == offsetof(RayBatch<float>, rgb) && offsetof(RayBatchArg, hits) == offsetof(RayBatch<double>, hits));
+#if RTC_MOTION  // (`extra` is a MotionLaunch: the tables, then the family's own argument, a ray batch's with its times)
+static_assert(sizeof(RayBatchTimedArg) == sizeof(RayBatch<float>) && sizeof(RayBatchTimedArg) == sizeof(RayBatch<double>) &&
+              offsetof(RayBatchTimedArg, times) == offsetof(RayBatch<float>, times));
+#else
+static_assert(sizeof(RayBatchArg) == sizeof(RayBatch<float>) && sizeof(RayBatchArg) == sizeof(RayBatch<double>));
+#endif
+static_assert(offsetof(RayBatchArg, rgb) == offsetof(RayBatch<float>, rgb) && offsetof(RayBatchArg, hits) == offsetof(RayBatch<double>, hits));
 template <typename R>
 hipError_t launch_kernel(KernelId id, const LaunchParams<R>& P, const void* extra, uint32_t grid, size_t dyn_lds,
                          hipStream_t stream) {
@@ -4006,7 +4160,13 @@ hipError_t launch_kernel(KernelId id, const LaunchParams<R>& P, const void* extr
     const MaterialRec<R>* materials = P.scene.materials;
     const PatternRec<R>* patterns = P.scene.patterns;
     const LightRec<R>* lights = P.scene.lights;
+#if RTC_MOTION
+    const MotionLaunch& ml = *static_cast<const MotionLaunch*>(extra);
+    void* args[] = {const_cast<LaunchParams<R>*>(&P), &shapes, &materials, &patterns, &lights,
+                    const_cast<MotionArg*>(&ml.motion), const_cast<void*>(ml.extra)};
+#else
     void* args[] = {const_cast<LaunchParams<R>*>(&P), &shapes, &materials, &patterns, &lights, const_cast<void*>(extra)};
+#endif
     (void)hipLaunchKernel(kernel, dim3(grid), dim3(kBlock), args, dyn_lds, stream);
     return hipGetLastError();
 }

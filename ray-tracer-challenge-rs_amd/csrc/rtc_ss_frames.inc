@@ -12,9 +12,18 @@
 // (rt_render_lens*, DESIGN.md §3.14): sample (i, j) is lens_ray's ray.  Nothing
 // else changes: shade_ray runs with NoBlock and no launch terms here, so
 // nothing downstream assumes that the primary rays share an origin.
+// RTC_SS_SHUTTER (with RTC_SS_LENS; the motion build's trace_direct_shutter and
+// trace_pool_shutter, rt_render_shutter*, DESIGN.md §3.17): the argument is a
+// ShutterArg, the lens and the shutter; the sample also has a time
+// (shutter_time), and a lens of aperture 0 (wave-uniform) takes camera_ray.
+#ifndef RTC_SS_SHUTTER
+#define RTC_SS_SHUTTER 0
+#endif
 template <typename R, bool kLds>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(sizeof(R) == 4 ? RTC_DIRECT_SS_WAVES : 1))) void RTC_SS_DIRECT(
-#if RTC_SS_LENS
+#if RTC_SS_SHUTTER
+    LaunchParams<R> P, RTC_WORLD_PARAMS(R), ShutterArg<R> sa) {
+#elif RTC_SS_LENS
     LaunchParams<R> P, RTC_WORLD_PARAMS(R), LensParams<R> lens) {
 #else
     LaunchParams<R> P, RTC_WORLD_PARAMS(R)) {
@@ -38,7 +47,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(sizeof(R
                 bool hit = false;
                 if (valid) {
                     V3<R> o, d;
-#if RTC_SS_LENS
+#if RTC_SS_SHUTTER
+                    if (kernarg_lens<R>().aperture == (R)0) camera_ray(P.cam, n * x + i, n * y + j, o, d);
+                    else lens_ray(P, kernarg_lens<R>(), n, x, y, i, j, o, d);
+                    sh.tau = shutter_time(kernarg_shutter<R>(), n, P.width, x, y, i, j);
+#elif RTC_SS_LENS
                     lens_ray(P, kernarg_lens<R>(), n, x, y, i, j, o, d);  // (re-read where it is used, as P is)
 #else
                     camera_ray(P.cam, n * x + i, n * y + j, o, d);
@@ -79,7 +92,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(sizeof(R
 // unchanged.
 template <typename R, bool kLds, bool kDup>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(sizeof(R) == 4 ? RTC_POOL_WAVES : 1))) void RTC_SS_POOL(
-#if RTC_SS_LENS
+#if RTC_SS_SHUTTER
+    LaunchParams<R> P, RTC_WORLD_PARAMS(R), ShutterArg<R> sa) {
+#elif RTC_SS_LENS
     LaunchParams<R> P, RTC_WORLD_PARAMS(R), LensParams<R> lens) {
 #else
     LaunchParams<R> P, RTC_WORLD_PARAMS(R)) {
@@ -169,7 +184,12 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(sizeof(R
                 const bool valid = pixel(x, y, out_idx);
 #endif
                 V3<R> o, d;
-#if RTC_SS_LENS
+#if RTC_SS_SHUTTER
+                if (valid) {
+                    if (sa.lens.aperture == (R)0) camera_ray(P.cam, n * x + i, n * y + j, o, d);
+                    else lens_ray(P, sa.lens, n, x, y, i, j, o, d);
+                }
+#elif RTC_SS_LENS
                 if (valid) lens_ray(P, lens, n, x, y, i, j, o, d);
 #else
                 if (valid) camera_ray(P.cam, n * x + i, n * y + j, o, d);
@@ -204,6 +224,14 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(sizeof(R
 #if RTC_AREA_LIGHTS
                 // (one sample's rays at a time in the pool: the sample is the loop's, the pixel the entry's)
                 sh.ray_id = sample_ray_id(P, t, pix, n, sample - (sample / n) * n, sample / n);
+#endif
+#if RTC_SS_SHUTTER
+                {  // the entry's time from its pixel and the loop's sample, where its ray_id is: the pool's entries stay as they are
+                    uint32_t sx, sy;
+                    uint64_t so;
+                    (void)tile_pixel(P, t, pix, sx, sy, so);
+                    sh.tau = shutter_time(kernarg_shutter<R>(), n, P.width, sx, sy, sample - (sample / n) * n, sample / n);
+                }
 #endif
                 if (active) hit = shade_ray<R, true, kDup>(sc, ro, rd, meta >> 8, sh, push);
                 count_events(k, false, hit, sh, sc.n_lights);

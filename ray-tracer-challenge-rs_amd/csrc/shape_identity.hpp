@@ -80,13 +80,24 @@ inline bool uvs_eq(const double* a, const double* b) {
     return reals_eq(a, b, 6);
 }
 
+// A velocity (rtc.h rt_scene_upload_moving) is three more values of a shape,
+// given like the normals: per shape its three doubles or null for a static
+// one (a zero velocity is dropped at upload, so a given one is nonzero).  Two
+// shapes are equal iff they were equal before and their velocities are equal
+// as f64 values: two static ones, or two movers with equal components.
+inline bool velocity_eq(const double* a, const double* b) {
+    if (!a || !b) return !a && !b;
+    return reals_eq(a, b, 3);
+}
+
 // dyn Shape equality (shape.rs:34-38): same kind, then the derived field-wise
 // equality of that kind.  A triangle's vertex_2/vertex_3 are not in the
 // descriptor; they are compared through vertex_1 + edges.
 inline bool shape_eq(const rt_shape_desc* S, const rt_material_desc* M, const rt_pattern_desc* P, uint32_t a,
-                     uint32_t b, Normals N = nullptr, Normals UV = nullptr) {
+                     uint32_t b, Normals N = nullptr, Normals UV = nullptr, Normals V = nullptr) {
     if (a == b) return true;
     const rt_shape_desc &x = S[a], &y = S[b];
+    if (!velocity_eq(normals_of(V, a), normals_of(V, b))) return false;
     if (!normals_eq(normals_of(N, a), normals_of(N, b))) return false;
     if (!uvs_eq(normals_of(UV, a), normals_of(UV, b))) return false;
     if (x.kind != y.kind || !reals_eq(x.inverse, y.inverse, 16)) return false;
@@ -134,7 +145,7 @@ inline uint64_t geometry_hash(const rt_shape_desc& s, const double* normals = nu
 // equal an earlier one.
 inline uint32_t shape_classes(const rt_shape_desc* S, uint32_t n, const rt_material_desc* M,
                               const rt_pattern_desc* P, std::vector<uint32_t>& cls, Normals N = nullptr,
-                              Normals UV = nullptr) {
+                              Normals UV = nullptr, Normals V = nullptr) {
     cls.resize(n);
     std::unordered_map<uint64_t, std::vector<uint32_t>> buckets;  // hash -> class representatives
     uint32_t dups = 0;
@@ -142,7 +153,7 @@ inline uint32_t shape_classes(const rt_shape_desc* S, uint32_t n, const rt_mater
         cls[i] = i;
         auto& reps = buckets[geometry_hash(S[i], normals_of(N, i), normals_of(UV, i))];
         for (uint32_t r : reps)
-            if (shape_eq(S, M, P, r, i, N, UV)) {
+            if (shape_eq(S, M, P, r, i, N, UV, V)) {
                 cls[i] = r;
                 ++dups;
                 break;

@@ -224,6 +224,22 @@ class MapInfo(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+class MotionDesc(C.Structure):
+    _fields_ = [("target", C.c_uint32), ("index", C.c_uint32), ("velocity", C.c_double * 3)]
+
+
+class ShutterDesc(C.Structure):
+    _fields_ = [("open", C.c_double), ("close", C.c_double), ("jitter", C.c_uint32), ("seed", C.c_uint32)]
+
+
+class MotionInfo(C.Structure):
+    _fields_ = [("moving_shapes", C.c_uint32), ("moving_instances", C.c_uint32), ("ran_motion", C.c_uint32),
+                ("reserved", C.c_uint32), ("motion_bytes", C.c_uint64)]
+
+
+RT_MOVE_SHAPE, RT_MOVE_INSTANCE = 0, 1
+
+
 class MeshTexcoordsView(C.Structure):
     _fields_ = [("texcoords", C.POINTER(C.c_double)), ("n_texcoords", C.c_uint32), ("n_textured", C.c_uint32),
                 ("triangle_texcoords", C.POINTER(C.c_uint32))]
@@ -340,6 +356,24 @@ def _load() -> C.CDLL:
                                              P(PatternDesc), C.c_uint32, P(LightDesc), C.c_uint32, P(AreaLightDesc),
                                              C.c_uint32, P(UVMapDesc), C.c_uint32]),
         "rt_scene_map_info": (C.c_int, [C.c_void_p, P(MapInfo)]),
+        "rt_scene_upload_moving": (C.c_int, [C.c_void_p, P(ShapeDesc), C.c_uint32, P(MeshDesc), C.c_uint32,
+                                             P(InstanceDesc), C.c_uint32, P(SmoothDesc), C.c_uint32, P(UVDesc),
+                                             C.c_uint32, P(TextureDesc), C.c_uint32, P(MaterialDesc), C.c_uint32,
+                                             P(PatternDesc), C.c_uint32, P(LightDesc), C.c_uint32, P(AreaLightDesc),
+                                             C.c_uint32, P(UVMapDesc), C.c_uint32, P(MotionDesc), C.c_uint32]),
+        "rt_scene_motion_info": (C.c_int, [C.c_void_p, P(MotionInfo)]),
+        "rt_motion_displace": (C.c_int, [P(ShapeDesc), C.c_uint32, P(InstanceDesc), C.c_uint32, P(MotionDesc),
+                                         C.c_uint32, C.c_double, P(ShapeDesc), P(InstanceDesc)]),
+        "rt_render_shutter": (C.c_int, [C.c_void_p, P(CameraDesc), P(RenderOptions), C.c_uint32, P(LensDesc),
+                                        P(ShutterDesc), C.c_void_p, P(Stats)]),
+        "rt_render_shutter_device": (C.c_int, [C.c_void_p, P(CameraDesc), P(RenderOptions), C.c_uint32, P(LensDesc),
+                                               P(ShutterDesc), C.c_void_p, C.c_void_p]),
+        "rt_shutter_time": (C.c_int, [P(CameraDesc), C.c_uint32, P(ShutterDesc), C.c_uint32, C.c_uint32, C.c_uint32,
+                                      C.c_uint32, P(C.c_double)]),
+        "rt_trace_rays_timed": (C.c_int, [C.c_void_p, P(C.c_double), P(C.c_double), C.c_uint64, P(RayOptions),
+                                          P(C.c_double), C.c_void_p, P(Stats)]),
+        "rt_trace_rays_timed_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, P(RayOptions),
+                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
         "rt_lights_expand": (C.c_int, [P(LightDesc), C.c_uint32, P(AreaLightDesc), C.c_uint32, P(LightDesc),
                                        P(C.c_uint32)]),
         "rt_render_lens": (C.c_int, [C.c_void_p, P(CameraDesc), P(RenderOptions), C.c_uint32, P(LensDesc), C.c_void_p,
@@ -425,6 +459,8 @@ EXPORTED_SYMBOLS = (
     "rt_scene_upload_lit", "rt_lights_expand", "rt_area_light_sample", "rt_scene_light_info",
     "rt_render_lens", "rt_render_lens_device", "rt_lens_ray",
     "rt_scene_upload_mapped", "rt_scene_map_info",
+    "rt_scene_upload_moving", "rt_scene_motion_info", "rt_motion_displace", "rt_render_shutter",
+    "rt_render_shutter_device", "rt_shutter_time", "rt_trace_rays_timed", "rt_trace_rays_timed_device",
 )
 
 
@@ -553,6 +589,22 @@ def lens_ray(camera: "CameraDesc", grid: int, lens: "LensDesc", x: int, y: int, 
     return np.array(ray[:], dtype=np.float64)
 
 
+def Shutter(open: float, close: float, jitter: bool = False, seed: int = 0) -> "ShutterDesc":
+    """A shutter (rtc.h rt_shutter_desc): the interval of time a frame's samples spread over; jitter False =
+    cell centres (RT_JITTER_NONE), True = hashed per sample with `seed`."""
+    return ShutterDesc(float(open), float(close), RT_JITTER_HASHED if jitter else RT_JITTER_NONE,
+                       int(seed) & 0xFFFFFFFF)
+
+
+def shutter_time(camera: "CameraDesc", grid: int, shutter: "ShutterDesc", x: int, y: int, i: int, j: int) -> float:
+    """rt_shutter_time: the f64 time of sample (i, j) of pixel (x, y) of a shutter frame of the output camera
+    `camera`, for either jitter mode."""
+    tau = C.c_double(0.0)
+    _check(_lib.rt_shutter_time(C.byref(camera), grid, None if shutter is None else C.byref(shutter), x, y, i, j,
+                                C.byref(tau)))
+    return tau.value
+
+
 def area_light_sample(desc: "AreaLightDesc", area_index: int, ray_id: int, remaining: int, k: int) -> np.ndarray:
     """rt_area_light_sample: the f64 position of sample k of an area light, for either jitter mode."""
     pos = (C.c_double * 3)()
@@ -617,6 +669,34 @@ class SceneTables:
     # Texture maps (rtc.h rt_scene_upload_mapped): an array of UVMapDesc naming image patterns with their map
     # and a cube map's six textures; None / empty = every image pattern is planar.
     maps: C.Array | None = None
+    # Motion (rtc.h rt_scene_upload_moving): an array of MotionDesc naming shapes of `shapes` (RT_MOVE_SHAPE)
+    # or instances (RT_MOVE_INSTANCE) with their velocities; None / empty = nothing moves.
+    motion: C.Array | None = None
+
+    @property
+    def moving(self) -> bool:
+        return self.motion is not None and len(self.motion) > 0
+
+    def moving_args(self):
+        """rt_scene_upload_moving's arguments after the context: mapped_args() with the motion list at the end."""
+        mo = self.motion if self.motion is not None else (MotionDesc * 0)()
+        return self.mapped_args() + (mo, len(mo))
+
+    def at_time(self, tau: float) -> "SceneTables":
+        """The static world at time tau (rt_motion_displace): every moving shape's and instance's inverse
+        becomes inverse * translation(-v tau); the other tables are shared and the result has no motion list.
+        A world without one: itself."""
+        if not self.moving:
+            return self
+        inst = self.instances if self.instances is not None else (InstanceDesc * 0)()
+        shapes = (ShapeDesc * len(self.shapes))()
+        out_inst = (InstanceDesc * len(inst))()
+        _check(_lib.rt_motion_displace(self.shapes, len(self.shapes), inst, len(inst), self.motion, len(self.motion),
+                                       float(tau), shapes, out_inst))
+        return SceneTables(shapes, self.materials, self.patterns, self.lights, self.camera, self.duplicate_shapes,
+                           meshes=self.meshes, instances=out_inst if len(inst) else self.instances,
+                           smooth=self.smooth, uvs=self.uvs, textures=self.textures, area_lights=self.area_lights,
+                           maps=self.maps)
 
     @property
     def mapped(self) -> bool:
@@ -1017,14 +1097,23 @@ class Context:
         _check(_lib.rt_scene_map_info(self._h, C.byref(t)))
         return {name: getattr(t, name) for name, _ in t._fields_ if name != "reserved"}
 
+    def motion_info(self) -> dict:
+        """The uploaded world's motion (rtc.h rt_scene_motion_info): moving shapes and instances, the device
+        bytes of the velocity tables, whether the last launch was a shutter frame or a timed ray batch."""
+        t = MotionInfo()
+        _check(_lib.rt_scene_motion_info(self._h, C.byref(t)))
+        return {name: getattr(t, name) for name, _ in t._fields_ if name != "reserved"}
+
     def upload(self, scene: SceneTables | None) -> None:
-        """rt_scene_upload, rt_scene_upload_instanced for tables with instances, rt_scene_upload_smooth for
+        """rt_scene_upload_moving for tables with a motion list; else rt_scene_upload, rt_scene_upload_instanced for tables with instances, rt_scene_upload_smooth for
         tables with smooth triangles, rt_scene_upload_textured for tables with texture coordinates or
         textures, rt_scene_upload_lit for tables with area lights, or rt_scene_upload_mapped for tables with
         a texture map entry; on a non-zero rank of a group, None
         (the scene comes from rank 0)."""
         if scene is None:
             _check(_lib.rt_scene_upload(self._h, None, 0, None, 0, None, 0, None, 0))
+        elif scene.moving:
+            _check(_lib.rt_scene_upload_moving(self._h, *scene.moving_args()))
         elif scene.mapped:
             _check(_lib.rt_scene_upload_mapped(self._h, *scene.mapped_args()))
         elif scene.lit:
@@ -1140,6 +1229,41 @@ class Context:
                                           None if lens is None else C.byref(lens), C.c_void_p(out_ptr or 0),
                                           C.c_void_p(stream_ptr or 0)))
 
+    def render_shutter(self, camera: CameraDesc, grid: int, shutter: "ShutterDesc", lens: "LensDesc | None" = None,
+                       depth: int = RT_DEFAULT_MAX_DEPTH, precision: str = "f32", out_format: str = "real",
+                       shard=(0, 1), out: np.ndarray | None = None, flags: int = 0):
+        """render_lens() with a time per sample (rtc.h rt_render_shutter): sample (i, j) of a pixel sees every
+        moving shape where it is at the sample's time in [shutter.open, shutter.close].  lens None (or an
+        aperture of 0) takes render_supersampled()'s sample rays.  In a world without movers it is
+        render_lens() / render_supersampled()."""
+        opts = self.options(depth, precision, out_format, shard, flags)
+        rows = camera.height if shard[1] == 1 else shard_rows(camera.height, shard[1])
+        dtype = np.uint8 if out_format == "u8" else (np.float32 if precision == "f32" else np.float64)
+        if out is not None:
+            if out.shape != (rows, camera.width, 3) or out.dtype != dtype or not out.flags.c_contiguous:
+                raise ValueError(f"out must be a C-contiguous {dtype.__name__} array of shape {(rows, camera.width, 3)}")
+            img = out
+        else:
+            img = np.zeros((rows, camera.width, 3), dtype=dtype)
+        st = Stats()
+        _check(_lib.rt_render_shutter(self._h, C.byref(camera), C.byref(opts), grid,
+                                      None if lens is None else C.byref(lens),
+                                      None if shutter is None else C.byref(shutter),
+                                      img.ctypes.data_as(C.c_void_p), C.byref(st)))
+        return img, st.as_dict()
+
+    def render_shutter_device(self, camera: CameraDesc, grid: int, shutter: "ShutterDesc", out_ptr: int,
+                              lens: "LensDesc | None" = None, stream_ptr: int | None = None,
+                              depth: int = RT_DEFAULT_MAX_DEPTH, precision: str = "f32", out_format: str = "real",
+                              shard=(0, 1), flags: int = 0) -> None:
+        """render_lens_device() with a time per sample (rtc.h rt_render_shutter_device): the W x H x 3 buffer of
+        the output camera, asynchronous on the stream."""
+        opts = self.options(depth, precision, out_format, shard, flags)
+        _check(_lib.rt_render_shutter_device(self._h, C.byref(camera), C.byref(opts), grid,
+                                             None if lens is None else C.byref(lens),
+                                             None if shutter is None else C.byref(shutter),
+                                             C.c_void_p(out_ptr or 0), C.c_void_p(stream_ptr or 0)))
+
     def color_at(self, rays, depth: int = RT_DEFAULT_MAX_DEPTH, precision: str = "f32"):
         """Batched World::color_at: rays (n, 6) = origin, direction -> colours (n, 3) f64.  In a world with
         reflective or transparent materials the directions must be unit length (rtc.h rt_color_at)."""
@@ -1151,7 +1275,7 @@ class Context:
         return out, st.as_dict()
 
     def trace_rays(self, rays, depth: int = RT_DEFAULT_MAX_DEPTH, precision: str | None = None, hits: bool = False,
-                   flags: int = 0):
+                   flags: int = 0, times=None):
         """World::color_at for any rays in any uploaded world (rtc.h rt_trace_rays*): no unit-length rule, no
         brightness bound.  rays (n, 6) = origin, direction, float32 or float64, C-contiguous; the dtype is the
         precision (a tensor's must agree with `precision` if given; a numpy batch travels as f64 and
@@ -1160,8 +1284,18 @@ class Context:
             no host copy; returns colours (n, 3), with hits=True (colours, t (n,), shape (n,) int32);
           - a numpy array: rt_trace_rays; returns (colours f64, stats), with hits=True (colours, t, shape, stats).
         shape is the primary hit's index in the uploaded shape table, -1 on a miss (t = inf).
+        times: a time per ray (rtc.h rt_trace_rays_timed*), shape (n,), of the rays' own kind (a tensor of their
+        dtype on their device, or a numpy array); None = every ray at time 0.
         Raises ValueError for anything else before the library is called."""
         kind, prec = _ray_batch_kind(rays, precision, self.device)
+        if times is not None:
+            if kind == "numpy":
+                times = np.ascontiguousarray(times, dtype=np.float64)
+            elif type(times) is not type(rays) or times.dtype != rays.dtype or times.device != rays.device or \
+                    not times.is_contiguous():
+                raise ValueError("times must be a contiguous tensor of the rays' dtype on their device")
+            if times.ndim != 1 or times.shape[0] != rays.shape[0]:
+                raise ValueError(f"times must have shape ({int(rays.shape[0])},), not {tuple(times.shape)}")
         opts = RayOptions(int(depth), PRECISIONS[prec], int(flags), 0)
         n = int(rays.shape[0])
         if kind == "torch":
@@ -1172,8 +1306,9 @@ class Context:
                               device=rays.device) if hits else None
             if n:
                 stream = torch.cuda.current_stream(rays.device).cuda_stream
-                _check(_lib.rt_trace_rays_device(self._h, C.c_void_p(rays.data_ptr()), n, C.byref(opts),
-                                                 C.c_void_p(rgb.data_ptr()),
+                _check(_lib.rt_trace_rays_timed_device(self._h, C.c_void_p(rays.data_ptr()),
+                                                 None if times is None else C.c_void_p(times.data_ptr()), n,
+                                                 C.byref(opts), C.c_void_p(rgb.data_ptr()),
                                                  C.c_void_p(rec.data_ptr()) if hits else None, C.c_void_p(stream or 0)))
             if not hits:
                 return rgb
@@ -1184,8 +1319,9 @@ class Context:
         out = np.zeros((n, 3), dtype=np.float64)
         rec = np.zeros(n, dtype=RAY_HIT_F64) if hits else None
         st = Stats()
-        _check(_lib.rt_trace_rays(self._h, r.ctypes.data_as(C.POINTER(C.c_double)), n, C.byref(opts),
-                                  out.ctypes.data_as(C.POINTER(C.c_double)),
+        _check(_lib.rt_trace_rays_timed(self._h, r.ctypes.data_as(C.POINTER(C.c_double)),
+                                  None if times is None else times.ctypes.data_as(C.POINTER(C.c_double)), n,
+                                  C.byref(opts), out.ctypes.data_as(C.POINTER(C.c_double)),
                                   rec.ctypes.data_as(C.c_void_p) if hits else None, C.byref(st)))
         if not hits:
             return out, st.as_dict()

@@ -79,14 +79,15 @@ def scene_to_bytes(scene) -> bytes:
     hdr["n"] = scene.counts
     hdr["duplicate_shapes"] = scene.duplicate_shapes
     parts = [hdr.tobytes()] + [bytes(t) for t in (scene.shapes, scene.materials, scene.patterns, scene.lights)]
-    return b"".join(parts) + bytes(scene.camera)
+    # (a motion list, rt_scene_upload_moving's, follows the camera: a world without one gives the bytes it always gave)
+    return b"".join(parts) + bytes(scene.camera) + (bytes(scene.motion) if scene.moving else b"")
 
 
 def scene_from_bytes(data: bytes):
     """Inverse of scene_to_bytes (bit-exact: the f64 fields are copied raw)."""
     import ctypes as C
 
-    from . import RT_ABI_VERSION, CameraDesc, LightDesc, MaterialDesc, PatternDesc, SceneTables, ShapeDesc
+    from . import RT_ABI_VERSION, CameraDesc, LightDesc, MaterialDesc, MotionDesc, PatternDesc, SceneTables, ShapeDesc
     hdr = np.frombuffer(data[:_HEADER.itemsize], dtype=_HEADER)[0]
     if hdr["magic"] != _MAGIC or hdr["version"] != RT_ABI_VERSION:
         raise ValueError("not a scene broadcast of this ABI version")
@@ -99,9 +100,20 @@ def scene_from_bytes(data: bytes):
         tables.append(arr)
         off += size
     cam = CameraDesc.from_buffer_copy(data[off:off + C.sizeof(CameraDesc)])
-    if off + C.sizeof(CameraDesc) != len(data):
+    off += C.sizeof(CameraDesc)
+    if (len(data) - off) % C.sizeof(MotionDesc) != 0 or len(data) < off:
         raise ValueError("scene broadcast has the wrong length")
-    return SceneTables(*tables, cam, int(hdr["duplicate_shapes"]))
+    motion = None
+    if len(data) > off:  # what follows the camera is the motion list
+        motion = (MotionDesc * ((len(data) - off) // C.sizeof(MotionDesc)))()
+        C.memmove(motion, data[off:], len(data) - off)
+        # (no count says that a list follows: every entry must be one, so that a garbled or truncated
+        # broadcast whose tail happens to be a multiple of an entry's size is still refused)
+        for m in motion:
+            ok = m.target in (0, 1) and all(v == v and abs(v) != float("inf") for v in m.velocity)
+            if not ok or (m.target == 0 and m.index >= int(hdr["n"][0])):
+                raise ValueError("scene broadcast has the wrong length or a motion entry that is none")
+    return SceneTables(*tables, cam, int(hdr["duplicate_shapes"]), motion=motion)
 
 
 def broadcast_scene(scene, rank: int, device, src: int = 0):

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import json
 
-from . import CameraDesc, LightDesc, MaterialDesc, PatternDesc, SceneTables, ShapeDesc
+from . import CameraDesc, LightDesc, MaterialDesc, MotionDesc, PatternDesc, SceneTables, ShapeDesc
 
 
 def _struct_to_dict(s) -> dict:
@@ -34,6 +34,14 @@ def _dict_to_struct(cls, d: dict):
 
 
 def tables_to_dict(scene: SceneTables) -> dict:
+    """(a motion list, rt_scene_upload_moving's, is one more key; a world without one writes what it always wrote)"""
+    d = _base_dict(scene)
+    if scene.moving:
+        d["motion"] = [_struct_to_dict(x) for x in scene.motion]
+    return d
+
+
+def _base_dict(scene: SceneTables) -> dict:
     return {
         "shapes": [_struct_to_dict(x) for x in scene.shapes],
         "materials": [_struct_to_dict(x) for x in scene.materials],
@@ -52,7 +60,8 @@ def tables_from_dict(d: dict) -> SceneTables:
         return a
     return SceneTables(arr(ShapeDesc, d["shapes"]), arr(MaterialDesc, d["materials"]),
                        arr(PatternDesc, d["patterns"]), arr(LightDesc, d["lights"]),
-                       _dict_to_struct(CameraDesc, d["camera"]), d.get("duplicate_shapes", 0))
+                       _dict_to_struct(CameraDesc, d["camera"]), d.get("duplicate_shapes", 0),
+                       motion=arr(MotionDesc, d["motion"]) if d.get("motion") else None)
 
 
 def save(scene: SceneTables, path: str, source: str = "") -> None:

@@ -20,7 +20,7 @@ import ctypes as C
 import math
 from dataclasses import dataclass, field
 
-from . import (AreaLightDesc, CameraDesc, InstanceDesc, LightDesc, MaterialDesc, PatternDesc, PATTERN_KINDS, RT_SMOOTH_SHAPES, TEXTURE_MAPS, UVMapDesc,
+from . import (AreaLightDesc, CameraDesc, InstanceDesc, LightDesc, MaterialDesc, MotionDesc, RT_MOVE_INSTANCE, RT_MOVE_SHAPE, PatternDesc, PATTERN_KINDS, RT_SMOOTH_SHAPES, TEXTURE_MAPS, UVMapDesc,
                SceneTables, ShapeDesc, SHAPE_KINDS, SmoothDesc, TEXTURE_FILTERS, UVDesc, camera_make, matrix_inverse)
 
 F64_MAX = 1.7976931348623157e308
@@ -187,6 +187,7 @@ class Shape:
     triangle: tuple | None = None  # (v1, e1, e2, normal)
     normals: tuple | None = None   # a smooth triangle's (n1, n2, n3), used as given; None: flat
     uvs: tuple | None = None       # a triangle's texture coordinates (t1, t2, t3) of p1, p2, p3; None: none
+    velocity: tuple | None = None  # world units per unit of time (rtc.h rt_scene_upload_moving); None: static
 
     def set_transformation(self, m):
         self.transformation_inverse = inverse(m)
@@ -291,6 +292,7 @@ class Instance:
     transformation_inverse: list = field(default_factory=lambda: [row[:] for row in IDENTITY])
     smooth: bool = False  # the mesh's faces with three normals are smooth triangles (another mesh than its flat use)
     textured: bool = False  # the mesh's faces with three texture coordinates carry them (another mesh again)
+    velocity: tuple | None = None  # the placement's velocity (rtc.h rt_scene_upload_moving); None: static
 
 
 def instance(m, material=None, transform=None, smooth=False, textured=False):
@@ -439,6 +441,13 @@ class World:
                     e = UVMapDesc(i, int(p.map))
                     e.faces[:] = [texture_index(f) for f in p.faces] if p.faces is not None else [-1] * 6
                     maps.append(e)
+        motion = []  # MotionDesc entries: the moving shapes in world order, then the moving instances
+        for target, things in ((RT_MOVE_SHAPE, self.shapes), (RT_MOVE_INSTANCE, self.instances)):
+            for i, s in enumerate(things):
+                if s.velocity is not None:
+                    e = MotionDesc(target, i)
+                    e.velocity[:] = list(map(float, s.velocity))
+                    motion.append(e)
         lts = (LightDesc * len(self.lights))()
         for i, lt in enumerate(self.lights):
             lts[i].position[:] = list(map(float, lt.position))
@@ -449,7 +458,8 @@ class World:
                            uvs=(UVDesc * len(uvs))(*uvs) if uvs else None, textures=textures or None,
                            area_lights=(AreaLightDesc * len(self.area_lights))(*[a.desc() for a in self.area_lights])
                            if self.area_lights else None,
-                           maps=(UVMapDesc * len(maps))(*maps) if maps else None)
+                           maps=(UVMapDesc * len(maps))(*maps) if maps else None,
+                           motion=(MotionDesc * len(motion))(*motion) if motion else None)
 
 
 def camera(width, height, fov, frm=(0, 0, 0), to=(0, 0, -1), up=(0, 1, 0)) -> CameraDesc:
