@@ -66,6 +66,25 @@ def trace(oracle, scene, rays, times, depth):
     return out, total
 
 
+def trace_at_times(reference_trace, scene, rays, times):
+    """A numpy restatement (smooth_reference.trace, texture_reference.trace: colours, the primary hits and a
+    decision margin per ray) over (ray, time) pairs, where the oracle has nothing to say: ray k in
+    scene.at_time(times[k]).expanded(), grouped by time as trace() groups them.  Returns (colours (n, 3),
+    {"t", "shape"} of the primary hits, margins (n,))."""
+    rays = np.asarray(rays, dtype=np.float64).reshape(-1, 6)
+    times = np.asarray(times, dtype=np.float64).reshape(-1)
+    assert rays.shape[0] == times.shape[0]
+    n = rays.shape[0]
+    out, margin = np.zeros((n, 3)), np.zeros(n)
+    hit = {"t": np.full(n, np.inf), "shape": np.full(n, -1, dtype=np.int64)}
+    for tau in np.unique(times):
+        at = times == tau
+        cols, h, m = reference_trace(scene.at_time(float(tau)).expanded(), rays[at])
+        out[at], margin[at] = cols, m
+        hit["t"][at], hit["shape"][at] = h["t"], h["shape"]
+    return out, hit, margin
+
+
 def frame(oracle, scene, cam, rtc, w, h, n, shutter, depth, lens=None):
     """The frame rt_render_shutter means: the ordered mean over the n^2 oracle colours of every pixel.
     shutter = (open, close, jitter, seed)."""

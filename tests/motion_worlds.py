@@ -14,6 +14,10 @@ position (the position at tau = 0) instead of the displaced one:
                  oracle samples no images, so the map's texture is the 2 x 1 texture [a b] under the nearest
                  filter, which coincides with the oracle's stripe_pattern(a, b) away from the plane x = 0
                  (tests/uv_map_worlds.py tie()): pattern(mapped=False) is the oracle's world;
+  maps()         a unit cylinder under the cylindrical map and a unit cube under a cube map, both scaled, turned
+                 about y and moving: the maps' points travel with their shapes too.  The textures are
+                 tests/uv_map_worlds.py tie()'s, which coincide with the oracle's stripe_pattern(a, b) away from
+                 the planes x = 0 and x = +-1 of the shape's own space; maps(mapped=False) is the oracle's world;
   area()         a mover under an area light: the light-level caster cull;
   tree()         72 static top-level triangles, enough for a triangle hierarchy, with a moving triangle that
                  must stay outside it, and two instances of one mesh with one placement and one material (a
@@ -192,6 +196,47 @@ def pattern(mapped=True):
                             _still((0.0, 0.0, 0.6), 1.5)]
 
 
+ONE_A, ONE_B = np.array([[A]], dtype=np.uint8), np.array([[B]], dtype=np.uint8)
+TWO_BA = np.array([[B, A]], dtype=np.uint8)
+MAPS_CYLINDER = ((-1.2, 1.0, 0.5), (-0.24, 0.2, 1.1))  # its centre at tau = 0 and its velocity
+MAPS_CUBE = ((1.3, 0.9, 0.8), (-0.9, 0.3, -0.4))
+
+
+def maps(mapped=True, shift=None):
+    """A closed unit cylinder under the cylindrical map with the 2 x 1 texture [a b] and a unit cube under a cube
+    map of [a b] textures and their mirror images (tests/uv_map_worlds.py tie_pattern(): left a and right b
+    alone, where the over point lies beyond the stripes' edge), nearest filter, both scaled and turned about y.
+    mapped=False: the oracle's world, stripe_pattern(a, b) in both places; with `shift` the probe of
+    tests/test_motion_random_cpu.py: the cylinder's stripes moved by it along x, the cube's twice as wide and
+    moved by it (their edge is x = 0 alone: the cube's left and right faces lie 8e-8 beyond x = +-1 on purpose).
+
+    The two patterns differ on the cylinder's lines x = +-1, where the over point's offset carries x past the
+    stripes' edge.  The cylinder's x axis is turned square to the line from the eye to its centre and its
+    velocity runs along that line (and along y), so both lines stay just behind its outline for every eye of the
+    batches (within 0.2 of EYE, against a radius of 0.5) and of the lens frames, at every time."""
+    world = W.World([_light()], [_floor()])
+    a1, b1 = tuple(c / 255.0 for c in A), tuple(c / 255.0 for c in B)
+    def stripes(wide=False):
+        p = W.stripe_pattern(a1, b1)
+        if shift is None:
+            return p
+        t = W.translation(shift, 0.0, 0.0)
+        return p.set_transformation(W.mat_mul(t, W.scaling(2.0, 1.0, 1.0)) if wide else t)
+    (cc, cv), (bc, bv) = MAPS_CYLINDER, MAPS_CUBE
+    assert abs(cv[0] * (cc[2] - EYE[2]) - cv[2] * (cc[0] - EYE[0])) < 1e-12  # the velocity along the line of sight
+    turn = -np.arctan2(-(cc[0] - EYE[0]), cc[2] - EYE[2])  # rotation_y(turn) (1, 0, 0) is square to that line
+    tube = W.cylinder(-1.0, 1.0, True, W.Material(pattern=W.image_pattern(TWO_AB, "nearest", "cylindrical") if mapped else stripes(),
+                                                  specular=0.2),
+                      W.mat_mul(W.translation(*cc), W.mat_mul(W.rotation_y(turn), W.scaling(0.5, 0.45, 0.5))))
+    tube.velocity = cv
+    faces = W.cube_map_pattern(ONE_A, TWO_BA, ONE_B, TWO_AB, TWO_BA, TWO_BA, filter="nearest") if mapped else stripes(wide=True)
+    box = W.cube(W.Material(pattern=faces, specular=0.2),
+                 W.mat_mul(W.translation(*bc), W.mat_mul(W.rotation_y(0.5), W.scaling(0.45, 0.4, 0.5))))
+    box.velocity = bv
+    world.shapes += [tube, box]
+    return _tables(world), [_moving(cc, cv, 0.2), _moving(bc, bv, 0.18), _still((0.0, 0.0, 0.6), 1.5)]
+
+
 def area():
     """The far sphere's slower cousin under an area light of 2 x 2 samples (cell centres)."""
     world = W.World([], [_floor()])
@@ -227,7 +272,7 @@ def tree():
 
 WORLDS = {**{f"far_{k}": functools.partial(far, k) for k in FAR_KINDS},
           "shadow": shadow, "plane": plane, "glass": glass, "glass_single": functools.partial(glass, False),
-          "pattern": pattern, "area": area, "tree": tree}
+          "pattern": pattern, "area": area, "tree": tree, "maps": maps}
 DEPTH = {"glass": 5, "glass_single": 5}
 POOL = ("glass", "glass_single")  # worlds with secondary rays: the pool kernel
 
@@ -239,8 +284,8 @@ def world(name):
 
 @functools.lru_cache(maxsize=None)
 def oracle_scene(name):
-    """The tables the oracle traces for `name`: the world's own, but for pattern()'s stripes."""
-    return pattern(mapped=False)[0] if name == "pattern" else world(name)[0]
+    """The tables the oracle traces for `name`: the world's own, but for pattern()'s and maps()'s stripes."""
+    return {"pattern": pattern, "maps": maps}[name](mapped=False)[0] if name in ("pattern", "maps") else world(name)[0]
 
 
 def depth(name):
